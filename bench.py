@@ -77,6 +77,38 @@ def make_streams(torch, dev, ids, n_frames, n_unique, snr_db, iq):
     return np.asarray(cfos), [ens[gid % n_unique] for gid in ids]
 
 
+DUMP_LIMIT = 64 << 20                      # --dump-outputs: bytes written in all
+
+
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array
+    (float32 for the integer outputs, which it holds exactly; float64 as computed otherwise).  `arrays` is a list of
+    (name, 2-D tensor or array, byte budget).  One over its budget is written as a fixed, seeded sample of its rows, in
+    row order, with the row numbers in DIR/<name>_rows.npy (float64).  The sample depends only on the name and the
+    shape, and the same arguments give the same inputs, so two builds can be compared output for output."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a, budget in arrays:
+        rows, cols = a.shape
+        dtype = np.float64 if a.dtype in (torch.float64, np.float64) else np.float32
+        row_bytes = cols * np.dtype(dtype).itemsize
+        if rows * row_bytes <= budget:
+            sel = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        else:
+            k = max(1, budget // row_bytes)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(rows, k, replace=False))
+            sel = a[torch.as_tensor(idx, device=a.device)].cpu().numpy() if torch.is_tensor(a) else np.asarray(a)[idx]
+            written[name + "_rows"] = idx.astype(np.float64)
+        written[name] = sel.astype(dtype)
+    total = sum(v.nbytes for v in written.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for name, v in written.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return sorted(written)
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -146,9 +178,14 @@ def parse_args(argv=None):
                     help="what dabgpu_alloc_frame_buffers is asked for: two hipMallocs, or placement by HBM domain (<= 1.5 x the "
                          "pair held for ~0.1 s at set-up; the library itself ends in a plain pair on any failure and on a box "
                          "whose chunks share one domain -- config.buffer_placement is its report)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's outputs; "
+                         "<= 64 MiB in all, a fixed seeded sample of rows where an output is larger; see dump_outputs)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -343,6 +380,17 @@ def main():
         dist.destroy_process_group()
 
     if rank == 0:
+        if args.dump_outputs:
+            # the last timed step's outputs, before any leg reuses the buffers: soft bits (a row per OFDM symbol), FIBs and
+            # their CRC flags, the sub-channel's logical frames, and the frequency offset each stream's loop now holds
+            MiB = 1 << 20
+            names = dump_outputs(torch, args.dump_outputs, [
+                ("soft_bits", soft.view(-1, dabgpu.NB_CARRIERS * 2), 40 * MiB),
+                ("fib", fib.view(-1, 32), 8 * MiB),
+                ("fib_crc_ok", crc, 2 * MiB),
+                ("msc", msc.view(-1, msc.shape[-1]), 12 * MiB),
+                ("net_freq_offset", np.array([[ctx.get_stats(s).net_freq_offset] for s in range(E)], np.float32), MiB)])
+            print("bench.py: outputs of the last timed step in %s: %s" % (args.dump_outputs, ", ".join(names)), file=sys.stderr)
         value = frames_total / elapsed
         # HBM bytes per launch cannot be counted inside this run (PMC counters need rocprofv3 around the process, in
         # passes of their own): the figure is the one the tracked PMC run of this same command measured, and the line

@@ -199,8 +199,15 @@ void simd_ofdm_demod_frame(const float *iq, float freq_offset, int8_t *soft)
                 const float ar = fabsf(r), ai = fabsf(i);
                 const float m = ar > ai ? ar : ai;
                 const float sc = m > 0.0f ? -127.0f / m : 0.0f;
-                o[n] = (int8_t)(r * sc);
-                o[DAB_NB_CARRIERS + n] = (int8_t)(i * sc);
+                /* the larger component is exactly -127 sign(c), as the oracle's -127 (c / max) gives it: c times a rounded
+                   (under -ffast-math, approximate) reciprocal can land just short of 127 and truncate to 126.  Selects,
+                   not branches, so that the loop stays vectorised (sign 0 covers the all-zero carrier) */
+                const float er = r > 0.0f ? -127.0f : (r < 0.0f ? 127.0f : 0.0f);
+                const float ei = i > 0.0f ? -127.0f : (i < 0.0f ? 127.0f : 0.0f);
+                const float qr = ar == m ? er : r * sc;
+                const float qi = ai == m ? ei : i * sc;
+                o[n] = (int8_t)qr;
+                o[DAB_NB_CARRIERS + n] = (int8_t)qi;
             }
         }
         memcpy(ws->prev_re, ws->b_re, sizeof(float) * N);
