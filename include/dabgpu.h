@@ -696,6 +696,69 @@ int dabgpu_decode_stream_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft
 int dabgpu_decode_stream_reset(dabgpu_ctx *ctx);
 
 /* ------------------------------------------------------------------------ */
+/* Reception quality ("Reception quality"): two figures from   */
+/* what the front end and the decoder already left on the device, for every    */
+/* front-end entry point and every decoder.                                     */
+/*                                                                            */
+/* MER  of the quantised differential constellation, per frame, equal-weighted  */
+/*      over carriers: with a = |soft[n]|, b = |soft[1536 + n]| of carrier n of  */
+/*      a data symbol, signal = sum (a+b)^2, error = sum (a-b)^2 over the       */
+/*      carriers whose pair is not (0, 0) (erased).  MER in dB =                */
+/*      10 log10(signal / error) (+inf when error is 0).  Not channel SNR: the   */
+/*      phase error of the differential symbol, which saturates at high SNR      */
+/*      through the quantiser's truncation.                                      */
+/* BER  before the Viterbi decoder, per codeword: the decoded bits are          */
+/*      scrambled and encoded again, punctured as the profile says and compared  */
+/*      with the hard decisions of the soft bits the decoder read; erased bits   */
+/*      are not counted.  A codeword the decoder got wrong re-encodes to other   */
+/*      bits than were sent, and its count is then too low (the FIB CRC shows    */
+/*      it for the FIC).                                                         */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_mer {      /* per frame, 24 bytes */
+    uint64_t signal;             /* sum (|re|+|im|)^2 over counted carriers           */
+    uint64_t error;              /* sum (|re|-|im|)^2                                  */
+    int32_t  carriers;           /* carriers counted (not erased)                      */
+    int32_t  reserved;
+} dabgpu_mer;
+
+typedef struct dabgpu_ber_count {  /* per codeword */
+    uint32_t errors;             /* kept mother bits whose soft bit has the wrong sign */
+    uint32_t bits;               /* kept mother bits with a soft bit != 0              */
+} dabgpu_ber_count;
+
+/* MER of data symbols [first_symbol, first_symbol + n_symbols) (within 0..74) of n_frames frames (frame f's soft bits
+ * at d_soft + f*soft_stride, as the front end wrote them) -> d_out[n_frames].  d_soft and soft_stride multiples of 16
+ * bytes, d_out of 8.  Symbols 0..2 (the FIC) are the cheap figure of a monitor; with a soft-bit selection
+ * (dabgpu_ofdm_set_soft_selection) only selected symbols hold what the front end wrote. */
+int dabgpu_mer_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_frames, int first_symbol, int n_symbols,
+                   dabgpu_mer *d_out, void *stream);
+
+/* Channel BER of a decode call that has been enqueued before it on the same stream (dabgpu_decode_frames_dev,
+ * dabgpu_fic_decode_dev, dabgpu_msc_decode_dev / _multi_dev): the same soft bits, frame shape, sub-channels and history_in.
+ *   d_fib     that call's FIBs, or NULL: no FIC count;  d_fic [n_streams*frames_per_stream][4], one per FIC codeword
+ *             (3 FIBs)
+ *   d_out[i]  sub-channel i's decoded bytes;  d_msc[i] [n_streams][frames_per_stream*4], aligned with d_out: entry t
+ *             counts logical frame t - 15, whose bits lie in CIFs t-15..t (with d_history_in NULL the first 15 entries
+ *             of a stream count only the bits of this call's CIFs)
+ * Pointer arrays are HOST arrays of DEVICE pointers (d_history_in may be NULL, and so may its entries); sub-channels must
+ * not overlap.  One launch for the FIC and up to 16 sub-channels. */
+int dabgpu_channel_ber_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream,
+                           const uint8_t *d_fib, dabgpu_ber_count *d_fic, const dabgpu_subchannel *sc, int n_subchannels,
+                           const int8_t *const *d_history_in, const uint8_t *const *d_out, dabgpu_ber_count *const *d_msc,
+                           void *stream);
+
+/* dabgpu_decode_stream_frames with the quality of the same frames, in the same batch of downloads and behind the same
+ * synchronisation (the de-interleaver rings this call reads live inside the context: a caller could not count the
+ * sub-channels' BER afterwards).  HOST outputs, each NULL = not computed:
+ *   fic_ber     [n_frames][4]
+ *   msc_ber[i]  [n_frames*4] for sub-channel i (the array NULL, or single entries NULL)
+ *   mer         [n_frames], all 75 data symbols (the whole frame is uploaded then, not only the ranges the decode reads)
+ * With every quality output NULL this IS dabgpu_decode_stream_frames. */
+int dabgpu_decode_stream_frames_quality(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_frames, uint8_t *fib,
+                                        uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out,
+                                        dabgpu_ber_count *fic_ber, dabgpu_ber_count *const *msc_ber, dabgpu_mer *mer);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

@@ -487,10 +487,18 @@ int dabgpu_decode_stream_reset(dabgpu_ctx *ctx) {
 }
 
 static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_frames, uint8_t *fib,
-                                     uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out);
+                                     uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out,
+                                     dabgpu_ber_count *fic_ber, dabgpu_ber_count *const *msc_ber, dabgpu_mer *mer);
 
 int dabgpu_decode_stream_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_frames, uint8_t *fib,
                                 uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out) {
+    return dabgpu_decode_stream_frames_quality(ctx, soft, soft_stride, n_frames, fib, crc_ok, sc, n_subchannels, out, nullptr,
+                                               nullptr, nullptr);
+}
+
+int dabgpu_decode_stream_frames_quality(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_frames, uint8_t *fib,
+                                        uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out,
+                                        dabgpu_ber_count *fic_ber, dabgpu_ber_count *const *msc_ber, dabgpu_mer *mer) {
     if (!ctx || !soft || !fib || !crc_ok || n_frames < 0 || n_subchannels < 0) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_subchannels > 0 && (!sc || !out)) return DABGPU_ERR_ARG;
@@ -504,7 +512,9 @@ int dabgpu_decode_stream_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft
         if (!out[i]) return DABGPU_ERR_ARG;
     }
     if (!subchannels_disjoint(sc, n_subchannels)) return DABGPU_ERR_ARG;
-    const int rc = decode_stream_frames_body(ctx, soft, soft_stride, n_frames, fib, crc_ok, sc, n_subchannels, out);
+    if (mer && n_frames > 1 && (soft_stride & 15)) return DABGPU_ERR_ARG;          // (the MER kernel's 16-byte loads)
+    const int rc = decode_stream_frames_body(ctx, soft, soft_stride, n_frames, fib, crc_ok, sc, n_subchannels, out, fic_ber,
+                                             msc_ber, mer);
     if (rc != DABGPU_OK) {
         // A call that failed part-way leaves rings that have missed this frame (and `live` marks on some of them): no
         // ring continues the stream any more.  All of them go; the next call starts every sub-channel from erasures.
@@ -517,7 +527,8 @@ int dabgpu_decode_stream_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft
 }
 
 static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_frames, uint8_t *fib,
-                                     uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out) {
+                                     uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels, uint8_t *const *out,
+                                     dabgpu_ber_count *fic_ber, dabgpu_ber_count *const *msc_ber, dabgpu_mer *mer) {
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t nb_fib = size_t(n_frames) * NB_FIBS * 32, nb_crc = size_t(n_frames) * NB_FIBS;
     std::vector<size_t> out_off(n_subchannels), out_bytes(n_subchannels);
@@ -554,6 +565,15 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
         p_hi[i] = h.ring[h.cur];
         p_ho[i] = h.ring[h.cur ^ 1];
     }
+    // the quality outputs land behind the decoder's results, in the same area and the same download
+    const size_t nb_ber = size_t(n_frames) * NB_CIFS * sizeof(dabgpu_ber_count), nb_mer = size_t(n_frames) * sizeof(dabgpu_mer);
+    const size_t off_fic_ber = res_total;
+    if (fic_ber) res_total += al(nb_ber);
+    std::vector<size_t> off_msc_ber(n_subchannels, 0);
+    for (int i = 0; i < n_subchannels; i++)
+        if (msc_ber && msc_ber[i]) { off_msc_ber[i] = res_total; res_total += al(nb_ber); }
+    const size_t off_mer = res_total;
+    if (mer) res_total += al(nb_mer);
     const size_t nb_soft = size_t(n_frames - 1) * soft_stride + NB_FRAME_BITS;
     void *d_soft, *d_res;
     int rc;
@@ -570,7 +590,7 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
     void *soft_alias = (nb_soft & 15) ? nullptr : device_alias_of_pinned(soft);
     if (soft_alias && !(reinterpret_cast<uintptr_t>(soft_alias) & 15)) {
         std::vector<dabk::CopyPiece> up;
-        if (n_frames == 1 && 1 + NB_CIFS * n_subchannels <= dabk::copy_pieces_max()) {
+        if (n_frames == 1 && !mer && 1 + NB_CIFS * n_subchannels <= dabk::copy_pieces_max()) {
             char *d = static_cast<char *>(d_soft);
             const char *h = static_cast<const char *>(soft_alias);
             up.push_back(dabk::CopyPiece{d, h, size_t(NB_FIC_BITS)});
@@ -597,6 +617,29 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
                                   n_subchannels ? p_hi.data() : nullptr, n_subchannels ? p_ho.data() : nullptr,
                                   n_subchannels ? p_out.data() : nullptr, s);
     if (rc) return rc;
+    {   // quality of the same frames from the same soft bits and rings (one more launch for the BER, one for the MER)
+        std::vector<dabgpu_subchannel> q_sc;
+        std::vector<const int8_t *> q_hi;
+        std::vector<const uint8_t *> q_out;
+        std::vector<dabgpu_ber_count *> q_ber;
+        for (int i = 0; i < n_subchannels; i++)
+            if (msc_ber && msc_ber[i]) {
+                q_sc.push_back(sc[i]);
+                q_hi.push_back(p_hi[i]);
+                q_out.push_back(p_out[i]);
+                q_ber.push_back(reinterpret_cast<dabgpu_ber_count *>(res + off_msc_ber[i]));
+            }
+        if (fic_ber || !q_sc.empty()) {
+            rc = dabgpu_channel_ber_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, 1, n_frames,
+                                        fic_ber ? reinterpret_cast<const uint8_t *>(res) : nullptr,
+                                        reinterpret_cast<dabgpu_ber_count *>(res + off_fic_ber), q_sc.data(), int(q_sc.size()),
+                                        q_hi.data(), q_out.data(), q_ber.data(), s);
+            if (rc) return rc;
+        }
+        if (mer && (rc = dabgpu_mer_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, n_frames, 0, NB_DATA_SYMBOLS,
+                                        reinterpret_cast<dabgpu_mer *>(res + off_mer), s)))
+            return rc;
+    }
     {   // one synchronisation: the word behind the landing area's payload
         const size_t off_flag = ctx->h_bounce_bytes - 64;
         if ((rc = wait_for_signal(s, reinterpret_cast<volatile unsigned long long *>(static_cast<char *>(ctx->h_bounce) + off_flag),
@@ -608,8 +651,11 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
     std::memcpy(crc_ok, hb + al(nb_fib), nb_crc);
     for (int i = 0; i < n_subchannels; i++) {
         std::memcpy(out[i], hb + out_off[i], out_bytes[i]);
+        if (msc_ber && msc_ber[i]) std::memcpy(msc_ber[i], hb + off_msc_ber[i], nb_ber);
         ctx->sub_history[size_t(hist_index[i])].cur ^= 1;
     }
+    if (fic_ber) std::memcpy(fic_ber, hb + off_fic_ber, nb_ber);
+    if (mer) std::memcpy(mer, hb + off_mer, nb_mer);
     // a sub-channel left out of this call has missed a frame: its ring no longer continues the stream, and a later
     // call starts it from erasures again (this also bounds the list over any number of reconfigurations)
     size_t kept = 0;
@@ -618,6 +664,76 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
         else { (void)hipFree(h.ring[0]); (void)hipFree(h.ring[1]); }
     }
     ctx->sub_history.resize(kept);
+    return DABGPU_OK;
+}
+
+// ---------------------------------------------------------------------------- reception quality
+static_assert(sizeof(dabgpu_mer) == sizeof(dabk::MerSums), "ABI struct mirrors the kernel's");
+static_assert(sizeof(dabgpu_ber_count) == 8, "{errors, bits}: one uint2 per codeword");
+
+int dabgpu_mer_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_frames, int first_symbol, int n_symbols,
+                   dabgpu_mer *d_out, void *stream) {
+    if (!ctx || !d_soft || !d_out || n_frames < 0) return DABGPU_ERR_ARG;
+    if (first_symbol < 0 || n_symbols < 1 || first_symbol + n_symbols > NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    const size_t stride = n_frames > 1 ? soft_stride : 0;     // (one frame: the stride is never used)
+    if (n_frames > 1 && stride < size_t(first_symbol + n_symbols) * NB_SYM_BITS) return DABGPU_ERR_ARG;
+    if (((reinterpret_cast<uintptr_t>(d_soft) | stride) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return DABGPU_ERR_ARG;
+    if (n_frames == 0) return DABGPU_OK;
+    HIP_TRY(dabk::launch_mer(d_soft, stride, n_frames, first_symbol, n_symbols, reinterpret_cast<dabk::MerSums *>(d_out),
+                             pick_stream(ctx, stream)));
+    return DABGPU_OK;
+}
+
+int dabgpu_channel_ber_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream,
+                           const uint8_t *d_fib, dabgpu_ber_count *d_fic, const dabgpu_subchannel *sc, int n_subchannels,
+                           const int8_t *const *d_history_in, const uint8_t *const *d_out, dabgpu_ber_count *const *d_msc,
+                           void *stream) {
+    if (!ctx || !d_soft || n_streams < 0 || frames_per_stream < 0 || n_subchannels < 0) return DABGPU_ERR_ARG;
+    if (d_fib && (!d_fic || (reinterpret_cast<uintptr_t>(d_fic) & 7))) return DABGPU_ERR_ARG;
+    if (n_subchannels > 0 && (!sc || !d_out || !d_msc)) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    const size_t nframes = size_t(n_streams) * frames_per_stream;
+    if (nframes > 1 && soft_stride < size_t(n_subchannels > 0 ? NB_FRAME_BITS : NB_FIC_BITS)) return DABGPU_ERR_ARG;
+    // validate everything before enqueueing anything: profiles, bounds, no overlap inside the CIF (as the decode calls)
+    std::vector<dabk::BerItem> items;
+    if (d_fib) {
+        dabk::BerItem it{};
+        it.nsteps = ctx->fic.prof.nsteps;
+        it.prbs_bytes = ctx->fic.d_prbs;
+        it.punct_idx = ctx->fic.d_punct_idx;
+        it.args.soft = d_soft;
+        it.args.soft_stride = soft_stride;
+        it.args.n_streams = n_streams;
+        it.args.frames_per_stream = frames_per_stream;
+        it.args.out = const_cast<uint8_t *>(d_fib);       // (read only)
+        it.is_fic = true;
+        it.counts = reinterpret_cast<uint32_t *>(d_fic);
+        items.push_back(it);
+    }
+    for (int i = 0; i < n_subchannels; i++) {
+        DeviceCode *dc = nullptr;
+        const int rc = lookup_code(ctx, &sc[i], &dc);
+        if (rc) return rc;
+        if (!d_out[i] || !d_msc[i] || (reinterpret_cast<uintptr_t>(d_msc[i]) & 7)) return DABGPU_ERR_ARG;
+        dabk::BerItem it{};
+        it.nsteps = dc->prof.nsteps;
+        it.prbs_bytes = dc->d_prbs;
+        it.punct_idx = dc->d_punct_idx;
+        it.args.soft = d_soft;
+        it.args.soft_stride = soft_stride;
+        it.args.n_streams = n_streams;
+        it.args.frames_per_stream = frames_per_stream;
+        it.args.start_bit = sc[i].start_address * CU_BITS;
+        it.args.nbits = sc[i].length * CU_BITS;
+        it.args.hist_in = d_history_in ? d_history_in[i] : nullptr;
+        it.args.out = const_cast<uint8_t *>(d_out[i]);    // (read only)
+        it.counts = reinterpret_cast<uint32_t *>(d_msc[i]);
+        items.push_back(it);
+    }
+    if (!subchannels_disjoint(sc, n_subchannels)) return DABGPU_ERR_ARG;
+    if (nframes == 0 || items.empty()) return DABGPU_OK;
+    HIP_TRY(dabk::launch_channel_ber(items.data(), int(items.size()), pick_stream(ctx, stream)));
     return DABGPU_OK;
 }
 

@@ -409,6 +409,33 @@ size_t balanced_lds_bytes(unsigned grid, size_t lds, unsigned o_cap);
 // history ring update alone (used by both MSC variants)
 hipError_t launch_msc_history(const MscArgs &a, hipStream_t s);
 
+// ---- reception quality (quality_kernels.hip) ----------------------------------
+// MER of the differential constellation from the soft bits, per frame: data symbols [first_symbol, first_symbol + n_symbols)
+// of frame f (at soft + f*stride); out[f] = {sum (a+b)^2, sum (a-b)^2, carriers counted, 0} with a = |soft[n]|,
+// b = |soft[1536 + n]| of a symbol's carrier n, carriers whose pair is (0, 0) (erased) left out (== dabgpu_mer)
+struct MerSums {
+    uint64_t signal, error;
+    int32_t carriers, reserved;
+};
+hipError_t launch_mer(const int8_t *soft, size_t stride, int n_frames, int first_symbol, int n_symbols, MerSums *out,
+                      hipStream_t s);
+// Channel bit errors by re-encoding: per codeword the decoded bytes (args.out for a sub-channel, the FIBs for the FIC) are
+// scrambled again, run through the mother code and compared with the hard decisions of the soft bytes the decoder read
+// (soft_source.hpp) for every mother bit the profile keeps; counts[g] = {errors, bits} (bits: soft byte != 0).  Sub-channel
+// items take args.soft / soft_stride / n_streams / frames_per_stream / start_bit / nbits / hist_in / out; the FIC item
+// args.soft / soft_stride / n_streams / frames_per_stream / out (= FIBs).  Up to ber_group_max() items per launch (longer
+// lists are chunked).
+struct BerItem {
+    int nsteps;
+    const uint8_t *prbs_bytes;
+    const int32_t *punct_idx;  // LaneTables::punct_idx of the profile
+    MscArgs args;
+    bool is_fic;
+    uint32_t *counts;          // [n_codewords][2]
+};
+hipError_t launch_channel_ber(const BerItem *items, int n, hipStream_t s);
+int ber_group_max();
+
 // Let every kernel that takes dynamic LDS use the whole 160 KB of a CU: set once per context creation (on the
 // context's device) instead of per launch.
 hipError_t init_viterbi_kernel_attributes();

@@ -28,6 +28,7 @@
 #include "mem_stream.hpp"
 #include "kernels.hpp"
 #include "dab_tables.hpp"
+#include "soft_source.hpp"
 
 namespace dabk {
 
@@ -81,41 +82,7 @@ __host__ __device__ constexpr int rotl6c(int v, int r) { return r == 0 ? v : (((
 // sign pattern of the branch (state n reached from its older-bit-0 predecessor): bit0 <-> (s0+s3), bit1 <-> s1, bit2 <-> s2
 __host__ __device__ constexpr int sig_of(int n) { return par7(n & 109) | (par7(n & 79) << 1) | (par7(n & 83) << 2); }
 
-// ---- where a codeword's punctured soft bits come from ----
-// row(g): first punctured byte of codeword g.  PRE = how many earlier codewords a codeword draws from (the time
-// de-interleaver reads CIFs t-15..t of its own stream; consecutive codeword indices are consecutive CIFs).
-struct LSrcFic {
-    static constexpr int PRE = 0;
-    const int8_t *soft;
-    size_t stride;
-    __device__ __forceinline__ const int8_t *row(int g) const {
-        return soft + size_t(g >> 2) * stride + size_t(g & 3) * NB_FIC_GROUP_BITS;
-    }
-};
-struct LSrcPlain {
-    static constexpr int PRE = 0;
-    const int8_t *punct;
-    int n_punct;
-    __device__ __forceinline__ const int8_t *row(int g) const { return punct + size_t(g) * n_punct; }
-};
-struct LSrcMsc {
-    static constexpr int PRE = 15;
-    const int8_t *soft;
-    size_t stride;
-    const int8_t *hist;
-    int cifs_per_stream;
-    int base_off;             // first byte of the codeword's part in CIF 0 of a frame (FIC: 0; MSC: 9216 + 64*start CU)
-    int per_cif;              // distance between the four codewords of a frame (FIC group: 2304; CIF: 55296)
-    int nbits;
-    int d_force;              // -1: time de-interleaver delays from the descriptor table; 15: no interleaving (FIC)
-    __device__ __forceinline__ const int8_t *row(int g) const {
-        return soft + size_t(g >> 2) * stride + base_off + size_t(g & 3) * per_cif;
-    }
-};
-__host__ __device__ inline LSrcMsc make_msc_src(const MscArgs &a) {
-    return LSrcMsc{a.soft, a.soft_stride, a.hist_in, a.frames_per_stream * NB_CIFS, NB_FIC_BITS + a.start_bit, NB_CIF_BITS,
-                   a.nbits, -1};
-}
+// ---- where a codeword's punctured soft bits come from: LSrcFic / LSrcPlain / LSrcMsc (soft_source.hpp) ----
 // A descriptor is (delay * FPITCH + column) | column << 16: the low half is the window offset of a time-interleaved
 // bit, the high half the column alone for sources without interleaving (delay 0: FIC / plain codewords) or with a
 // forced delay (the FIC riding in a grouped launch: d_force = 15, its own row).  desc_shift / desc_extra pick the
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *
             if (idx < 0) continue;
             unsigned v;
             if constexpr (Src::PRE > 0) {
-                const int d = int(__brev(unsigned(idx) & 15u) >> 28);
+                const int d = tdi_delay(idx);
                 if (t_in_stream + d >= 15) {
                     v = win[(r_eff + d) * PREP_PITCH + (idx - lo_al)];
                 } else {                                      // before the stream's first CIF: carried history
@@ -839,10 +806,9 @@ hipError_t launch_lane_group(const LaneGroupItem *items, int n, const LaneScratc
             LaneEntry &e = pack.e[i];
             e.n_codewords = int(item_codewords(it));
             if (it.is_fic) {
-                // the FIC as one more entry: four 2304-bit groups per frame, no interleaving (every bit "delay 15" =
-                // the codeword's own row), never a history row
+                // the FIC as one more entry (make_fic_src: no interleaving, never a history row)
                 if (!aligned16(a.soft, a.soft_stride) || (reinterpret_cast<uintptr_t>(a.out) & 3)) return hipErrorInvalidValue;
-                e.src = LSrcMsc{a.soft, a.soft_stride, nullptr, e.n_codewords + 128, 0, NB_FIC_GROUP_BITS, NB_FIC_GROUP_BITS, 15};
+                e.src = make_fic_src(a.soft, a.soft_stride, e.n_codewords);
             } else {
                 if (!lane_group_fusable(a)) return hipErrorInvalidValue;
                 e.src = make_msc_src(a);
@@ -895,7 +861,7 @@ void build_lane_fused_tables(const uint8_t *mask, int nsteps, std::vector<int32_
         tiles[2 * tile + 1] = (hi - lo_al + 15) / 16;           // <= FCOLS by construction
         for (int p = p0; p < p1; p++) {
             if (idx[p] < 0) continue;
-            unsigned i = unsigned(idx[p]) & 15u, d = ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3);
+            const int d = tdi_delay(idx[p]);
             const int col = idx[p] - lo_al;
             desc[p] = (int(d) * FPITCH + col) | (col << 16);
         }

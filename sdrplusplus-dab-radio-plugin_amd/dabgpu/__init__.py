@@ -45,6 +45,7 @@ EXPORTS = [
     "dabgpu_mover_frames_dev", "dabgpu_pipe_open", "dabgpu_pipe_submit", "dabgpu_pipe_wait", "dabgpu_pipe_reset", "dabgpu_pipe_close",
     "dabgpu_set_stream_loop", "dabgpu_set_loop_gate", "dabgpu_track_default_cfg", "dabgpu_track_start_dev", "dabgpu_ofdm_demod_tracked_dev",
     "dabgpu_ofdm_demod_stream_frame", "dabgpu_ofdm_demod_frames_dd_dev", "dabgpu_test_fail_frame_call",
+    "dabgpu_mer_dev", "dabgpu_channel_ber_dev", "dabgpu_decode_stream_frames_quality",
 ]
 
 ABI_VERSION = 6
@@ -101,6 +102,29 @@ STREAM_STATE_DTYPE = np.dtype([("fine_freq_offset", np.float32), ("coarse_freq_o
                                ("loop_gated", np.int32), ("dd_branch", np.int32), ("dd_pending", np.int32),
                                ("reserved", np.int32)])     # 64 bytes, device-resident
 assert STREAM_STATE_DTYPE.itemsize == 64
+
+# reception quality (include/dabgpu.h: dabgpu_mer per frame, dabgpu_ber_count per codeword)
+MER_DTYPE = np.dtype([("signal", np.uint64), ("error", np.uint64), ("carriers", np.int32), ("reserved", np.int32)])
+assert MER_DTYPE.itemsize == 24
+BER_DTYPE = np.dtype([("errors", np.uint32), ("bits", np.uint32)])
+assert BER_DTYPE.itemsize == 8
+
+
+def mer_db(rec):
+    """MER in dB of MER_DTYPE record(s): 10 log10(signal / error); +inf where error == 0, nan where no carrier counted."""
+    rec = np.asarray(rec)
+    sig = rec["signal"].astype(np.float64)
+    err = rec["error"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        db = 10.0 * np.log10(sig / err)
+    return np.where(rec["carriers"] > 0, db, np.nan)
+
+
+def ber(counts):
+    """Bit-error rate of BER_DTYPE counts, summed over all of them (nan when no bit was counted)."""
+    counts = np.asarray(counts)
+    bits = int(counts["bits"].sum(dtype=np.uint64))
+    return float(counts["errors"].sum(dtype=np.uint64)) / bits if bits else float("nan")
 
 
 class SyncResult(C.Structure):
@@ -257,6 +281,9 @@ def load_library(path):
     L.dabgpu_ofdm_demod_stream_frame.argtypes = [vp, i, vp, i, C.POINTER(TrackCfg), vp, vp, C.POINTER(FrameResult)]
     L.dabgpu_get_prs_reference.argtypes = [i, vp, i]
     L.dabgpu_get_mapper_reference.argtypes = [vp, i, i]
+    L.dabgpu_mer_dev.argtypes = [vp, vp, sz, i, i, i, vp, vp]
+    L.dabgpu_channel_ber_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, i, vp, vp, vp, vp]
+    L.dabgpu_decode_stream_frames_quality.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp, vp, vp, vp]
     return L
 
 
@@ -610,8 +637,10 @@ class Context:
                                           ptrs(hos), ptrs(outs)), "dabgpu_decode_frames")
         return fib, ok, outs, (hos if want_history else None)
 
-    def decode_stream_frames(self, soft, scs):
-        """Consecutive frames of one stream; the de-interleaver state stays in the context.  -> fib, crc_ok, [out_i]"""
+    def decode_stream_frames(self, soft, scs, quality=False):
+        """Consecutive frames of one stream; the de-interleaver state stays in the context.  -> fib, crc_ok, [out_i]
+        quality=True (dabgpu_decode_stream_frames_quality): -> fib, crc_ok, [out_i], fic_ber [n_frames][4],
+        [msc_ber_i [n_frames*4]] (BER_DTYPE), mer [n_frames] (MER_DTYPE, all 75 symbols)"""
         soft = np.ascontiguousarray(soft, np.int8)
         n_frames, stride = soft.shape
         n = len(scs)
@@ -624,9 +653,17 @@ class Context:
             _check(min(nb, 0), "dabgpu_subchannel_bytes")
             outs.append(np.zeros((1, n_frames * 4, nb), np.uint8))
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs]) if n else None
-        _check(self._lib.dabgpu_decode_stream_frames(self._h, _p(soft), stride, n_frames, _p(fib), _p(ok), arr, n, ptrs),
-               "dabgpu_decode_stream_frames")
-        return fib, ok, outs
+        if not quality:
+            _check(self._lib.dabgpu_decode_stream_frames(self._h, _p(soft), stride, n_frames, _p(fib), _p(ok), arr, n, ptrs),
+                   "dabgpu_decode_stream_frames")
+            return fib, ok, outs
+        fic_ber = np.zeros((n_frames, 4), BER_DTYPE)
+        msc_ber = [np.zeros(n_frames * 4, BER_DTYPE) for _ in range(n)]
+        mer = np.zeros(n_frames, MER_DTYPE)
+        bptrs = (C.c_void_p * n)(*[a.ctypes.data for a in msc_ber]) if n else None
+        _check(self._lib.dabgpu_decode_stream_frames_quality(self._h, _p(soft), stride, n_frames, _p(fib), _p(ok), arr, n, ptrs,
+                                                             _p(fic_ber), bptrs, _p(mer)), "dabgpu_decode_stream_frames_quality")
+        return fib, ok, outs, fic_ber, msc_ber, mer
 
     def decode_stream_reset(self):
         _check(self._lib.dabgpu_decode_stream_reset(self._h), "dabgpu_decode_stream_reset")
@@ -785,6 +822,25 @@ class Context:
         _check(self._lib.dabgpu_decode_frames_dev(self._h, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok,
                                               arr, n, ptrs(d_hist_in), ptrs(d_hist_out), ptrs(d_out), stream),
                "dabgpu_decode_frames_dev")
+
+    def mer_dev(self, d_soft, soft_stride, n_frames, d_out, first_symbol=0, n_symbols=75, stream=None):
+        """MER sums of data symbols [first_symbol, first_symbol + n_symbols) per frame -> d_out [n_frames] (MER_DTYPE)."""
+        _check(self._lib.dabgpu_mer_dev(self._h, d_soft, soft_stride, n_frames, first_symbol, n_symbols, d_out, stream),
+               "dabgpu_mer_dev")
+
+    def channel_ber_dev(self, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_fic, scs=(), d_hist_in=None, d_out=None,
+                        d_msc=None, stream=None):
+        """Channel BER counts (BER_DTYPE) of a decode enqueued before: d_fib / d_fic [n_frames][4] for the FIC (None: not
+        counted), per sub-channel d_out[i] (decoded bytes) -> d_msc[i] [n_streams][frames_per_stream*4]; d_hist_in as the
+        decode had it (lists of device addresses as msc_decode_multi_dev)."""
+        n = len(scs)
+        arr = (Subchannel * max(n, 1))(*scs)
+        def ptrs(lst):
+            if lst is None or n == 0:
+                return None
+            return (C.c_void_p * n)(*[C.c_void_p(x) if x else None for x in lst])
+        _check(self._lib.dabgpu_channel_ber_dev(self._h, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_fic, arr, n,
+                                                ptrs(d_hist_in), ptrs(d_out), ptrs(d_msc), stream), "dabgpu_channel_ber_dev")
 
     def msc_decode_dev(self, sc, d_soft, soft_stride, n_streams, frames_per_stream, d_hist_in, d_hist_out, d_out,
                        stream=None):
