@@ -155,7 +155,8 @@ void dabgpu_host_free(void *p);
  * (the two Process calls run on threads nobody can throw to). */
 int dabgpu_test_fail_frame_call(dabgpu_ctx *ctx, int nth);
 
-/* Device buffers for a batch user's IQ samples ([n_frames][frame_stride] cf32, frame_stride >= 196608 samples) and
+/* Device buffers for a batch user's IQ samples ([n_frames][frame_stride] cf32, frame_stride >= 196608 samples; buffers of
+ * integer samples, dabgpu_set_iq_format, are plain device allocations of the caller's) and
  * soft bits ([n_frames][230400] int8).  Any device buffer is accepted by the _dev entry points; this call exists for
  * callers that own their buffers and want them placed for the front end.
  *   placement  DABGPU_PLACE_PLAIN    two hipMallocs.
@@ -226,8 +227,37 @@ int dabgpu_free_frame_buffers(dabgpu_ctx *ctx, void *d_iq, int8_t *d_soft);
  * one wavefront per run of symbols cut exactly as dabgpu_ofdm_demod_frames_dev cuts the same batch, streaming
  * accesses, the same LDS footprint (occupancy) -- and no arithmetic.  Overwrites d_soft with meaningless bytes.
  * Time it with events on `stream`; bench.py reports it as roofline.mover_same_geometry_ms. */
+/* (cf32 only: DABGPU_ERR_ARG on a context set to another sample format, dabgpu_set_iq_format.) */
 int dabgpu_mover_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames, int8_t *d_soft,
                             int with_prefixes, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Sample formats of the device-pointer calls (per context; cf32 by default). */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_IQ_CF32 0  /* interleaved float32 I,Q -- the default, what every call reads unless told otherwise */
+#define DABGPU_IQ_CS16 1  /* interleaved int16 I,Q                                                             */
+#define DABGPU_IQ_CS8  2  /* interleaved int8 I,Q (HackRF)                                                     */
+#define DABGPU_IQ_CU8  3  /* interleaved uint8 I,Q, value = u - 127.5 (rtl_sdr)                                */
+/* Sets the format the context's device-pointer calls read their d_iq in; DABGPU_ERR_ARG for an unknown value, or while
+ * the context has an open ring (dabgpu_pipe_open sizes its staging slots for the format it finds).
+ * The value contract: the kernels convert right after the load, before any arithmetic and without scaling, to
+ *   float(i), float(q)            (cs16, cs8)
+ *   float(u) - 127.5f             (cu8; exact)
+ * so every output -- soft bits, cyclic-prefix correlations, decision-directed sums, stream states, sync results, acquired
+ * frames and counts, decoded bytes -- is bit for bit what the cf32 path gives on a cf32 buffer holding the same values.
+ * The quantiser and every threshold are relative, so no scale is needed; signal_average (stream states, dabgpu_get_stats)
+ * is then in the format's units.  Strides, starts and offsets stay in complex samples.  d_iq needs one complex sample of
+ * alignment (4 bytes cs16, 2 bytes cs8 / cu8) and frame_stride may be odd (frames at odd sample offsets are read sample by
+ * sample).
+ * Reading the format: dabgpu_ofdm_demod_frames_dev, dabgpu_ofdm_demod_frames_dd_dev, dabgpu_ofdm_demod_streams_dev (both
+ * loops), dabgpu_sync_prs_dev, dabgpu_acquire_dev, dabgpu_ofdm_demod_acquired_dev, dabgpu_ofdm_demod_tracked_dev (auto_acquire
+ * included) and the ring (dabgpu_pipe_*), with or without a soft-bit selection and a d_cyc buffer.
+ * Refusing any format but cf32 with DABGPU_ERR_ARG, nothing enqueued: the host-pointer calls (their `const float *` is cf32),
+ * dabgpu_ofdm_demod_stream_frame, dabgpu_fft_symbols[_dev], dabgpu_mover_frames_dev, and any call given d_dqpsk != NULL.
+ * dabgpu_alloc_frame_buffers sizes cf32 buffers: integer IQ buffers are plain device allocations.
+ * dabgpu_get_iq_format returns the context's format (DABGPU_ERR_ARG for a NULL context). */
+int dabgpu_set_iq_format(dabgpu_ctx *ctx, int format);
+int dabgpu_get_iq_format(const dabgpu_ctx *ctx);
 
 /* ------------------------------------------------------------------------ */
 /* A2..A6: OFDM front end on time-aligned frames.                             */
@@ -238,7 +268,9 @@ int dabgpu_mover_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stri
 /* iq           cf32; frame f starts (first PRS sample, i.e. after the null    */
 /*              symbol) at iq + f*frame_stride complex samples; 76*2552        */
 /*              samples are read per frame.  Must be 16-byte aligned and        */
-/*              frame_stride even.                                              */
+/*              frame_stride even.  The _dev call reads the context's sample    */
+/*              format (dabgpu_set_iq_format: then one sample of alignment, any */
+/*              stride, no dqpsk); the host call cf32 only.                     */
 /* freq_offset  [n_frames] correction in cycles/sample applied as               */
 /*              x[n]*exp(+j*2*pi*f*n) (the sum the reference shows as           */
 /*              GetNetFrequencyOffset(), src/render_radio_block.cpp:204).       */
@@ -348,6 +380,7 @@ dabgpu_stream_state *dabgpu_stream_states(dabgpu_ctx *ctx);
 /* host-side setter (synchronises the context stream): NULL = leave that offset as it is.  The host mirror stores the
  * coarse offset found at acquisition here (is_coarse_freq_correction, src/render_radio_block.cpp:215). */
 int dabgpu_set_stream_offsets(dabgpu_ctx *ctx, int stream_index, const float *fine, const float *coarse);
+/* (Reads d_iq in the context's sample format, dabgpu_set_iq_format; d_dqpsk needs cf32.  The host call: cf32 only.) */
 int dabgpu_ofdm_demod_streams_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_streams,
                                   int frames_per_stream, float fine_freq_update_beta, int8_t *d_soft, void *d_cyc,
                                   void *d_dqpsk, void *stream);
@@ -408,6 +441,7 @@ int dabgpu_soft_selection(const struct dabgpu_subchannel *subchannels, int n_sub
  * FFT of the useful part of each of the 76 symbols.  Replaces the FFTW3f plan the
  * reference links (/root/reference/CMakeLists.txt:55-64).
  * spectra  [n_frames][76][2048] cf32, unnormalised, natural bin order. */
+/* (cf32 only: DABGPU_ERR_ARG on a context set to another sample format, dabgpu_set_iq_format.) */
 int dabgpu_fft_symbols_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames,
                            const float *d_freq_offset, void *d_spectra, void *stream);
 int dabgpu_fft_symbols(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_frames,
@@ -440,6 +474,7 @@ typedef struct dabgpu_sync_result {
     float coarse_peak_to_mean;
 } dabgpu_sync_result;
 
+/* (Reads d_iq in the context's sample format, dabgpu_set_iq_format.  The host call: cf32 only.) */
 int dabgpu_sync_prs_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames,
                         const float *d_freq_offset, int max_coarse, dabgpu_sync_result *d_out, void *stream);
 int dabgpu_sync_prs(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_frames, const float *freq_offset,
@@ -502,6 +537,8 @@ typedef struct dabgpu_acquired_frame {
 } dabgpu_acquired_frame;
 
 void dabgpu_acquire_default_cfg(dabgpu_acquire_cfg *cfg);
+/* (dabgpu_acquire_dev and dabgpu_ofdm_demod_acquired_dev read d_iq in the context's sample format, dabgpu_set_iq_format;
+ * d_dqpsk needs cf32.  The host call dabgpu_acquire: cf32 only.) */
 int dabgpu_acquire_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams, int64_t n_samples,
                        const dabgpu_acquire_cfg *cfg, int max_frames, dabgpu_acquired_frame *d_out, int32_t *d_counts,
                        void *stream);
@@ -574,6 +611,7 @@ void dabgpu_track_default_cfg(dabgpu_track_cfg *cfg);
 /* only_lost != 0: streams that are tracking keep their state (re-acquisition of the lost ones beside them) */
 int dabgpu_track_start_dev(dabgpu_ctx *ctx, const dabgpu_acquired_frame *d_frames, const int32_t *d_counts, int n_streams,
                            int max_frames, int64_t advance, int only_lost, void *stream);
+/* (Reads d_iq in the context's sample format, dabgpu_set_iq_format, auto_acquire included; d_dqpsk needs cf32.) */
 int dabgpu_ofdm_demod_tracked_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams,
                                   int64_t n_samples, int max_frames, int64_t advance, const dabgpu_track_cfg *cfg,
                                   int8_t *d_soft, void *d_cyc, void *d_dqpsk, dabgpu_acquired_frame *d_frames,
@@ -602,6 +640,7 @@ typedef struct dabgpu_frame_result {
     int32_t reserved;
     dabgpu_stats stats;
 } dabgpu_frame_result;
+/* (cf32 only: DABGPU_ERR_ARG on a context set to another sample format, dabgpu_set_iq_format.) */
 int dabgpu_ofdm_demod_stream_frame(dabgpu_ctx *ctx, int stream_index, const float *iq, int acquiring,
                                    const dabgpu_track_cfg *cfg, int8_t *soft, float *dqpsk, dabgpu_frame_result *result);
 
@@ -769,9 +808,10 @@ int dabgpu_decode_stream_frames_quality(dabgpu_ctx *ctx, const int8_t *soft, siz
 /*                                                                            */
 /* dabgpu_pipe_open   slots 2..8 (3 keeps all three engines busy); max_frames =   */
 /*            the largest n_streams * frames_per_stream a submit will carry;       */
-/*            frame_stride of the host IQ ([n][frame_stride] cf32, frame f's first  */
-/*            PRS sample at iq + f*frame_stride, 76*2552 samples read).  One ring    */
-/*            per context.                                                         */
+/*            frame_stride of the host IQ ([n][frame_stride] complex samples of the */
+/*            context's format, dabgpu_set_iq_format, which the ring records and    */
+/*            sizes its staging slots for; frame f's first PRS sample at            */
+/*            iq + f*frame_stride, 76*2552 samples read).  One ring per context.    */
 /* dabgpu_pipe_submit enqueues ONE batch and returns at once: the samples go up,    */
 /*            are demodulated -- with freq_offset[n_frames] as                       */
 /*            dabgpu_ofdm_demod_frames does, or (freq_offset == NULL) closed loop on   */
@@ -794,7 +834,7 @@ int dabgpu_decode_stream_frames_quality(dabgpu_ctx *ctx, const int8_t *soft, siz
 /* stay ordered with the ring (and wait behind it).                                                   */
 /* ------------------------------------------------------------------------ */
 int dabgpu_pipe_open(dabgpu_ctx *ctx, int slots, int max_frames, size_t frame_stride);
-int dabgpu_pipe_submit(dabgpu_ctx *ctx, const float *iq, int n_streams, int frames_per_stream, const float *freq_offset,
+int dabgpu_pipe_submit(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
                        float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft,
                        uint8_t *fib, uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket);
 int dabgpu_pipe_wait(dabgpu_ctx *ctx, int64_t ticket);

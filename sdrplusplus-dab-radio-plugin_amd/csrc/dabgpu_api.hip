@@ -433,10 +433,32 @@ int dabgpu_mean_kernel_ms(dabgpu_ctx *ctx, int which, float *mean_ms, int *launc
     return DABGPU_OK;
 }
 
+// ---------------------------------------------------------------------------- sample formats
+int dabgpu_set_iq_format(dabgpu_ctx *ctx, int format) {
+    if (!ctx || !dabk::iq_format_valid(format)) return DABGPU_ERR_ARG;
+    if (ctx->pipe) return DABGPU_ERR_ARG;                       // the ring's staging slots are sized for the format it opened with
+    ctx->iq_format = format;
+    return DABGPU_OK;
+}
+
+int dabgpu_get_iq_format(const dabgpu_ctx *ctx) { return ctx ? ctx->iq_format : DABGPU_ERR_ARG; }
+
+// the calls that read cf32 only (host-pointer calls, the FFT stage, the mover, a constellation output)
+static bool cf32_only(const dabgpu_ctx *ctx) { return ctx->iq_format != dabk::IQ_CF32; }
+// a device IQ pointer must hold one complex sample of the context's format at its alignment
+static bool iq_misaligned(const dabgpu_ctx *ctx, const void *d_iq) {
+    return (reinterpret_cast<uintptr_t>(d_iq) & (dabk::iq_sample_bytes(ctx->iq_format) - 1)) != 0;
+}
+
 // ---------------------------------------------------------------------------- OFDM
-static int check_iq(const void *d_iq, size_t frame_stride, int n_frames) {
+static int check_iq(const dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames) {
     if (!d_iq || n_frames < 0) return DABGPU_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) || (frame_stride & 1u)) return DABGPU_ERR_ARG;
+    if (ctx->iq_format != dabk::IQ_CF32) {
+        // integer samples: one sample of alignment, any stride (frames at odd sample offsets take the per-sample loads)
+        if (iq_misaligned(ctx, d_iq)) return DABGPU_ERR_ARG;
+    } else if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) || (frame_stride & 1u)) {
+        return DABGPU_ERR_ARG;
+    }
     if (n_frames > 1 && frame_stride < size_t(NB_FRAME_SYMBOLS) * NB_SYM_PERIOD) return DABGPU_ERR_ARG;
     return DABGPU_OK;
 }
@@ -444,9 +466,9 @@ static int check_iq(const void *d_iq, size_t frame_stride, int n_frames) {
 int dabgpu_ofdm_demod_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames,
                                  const float *d_freq_offset, int8_t *d_soft, void *d_cyc, void *d_dqpsk,
                                  void *stream) {
-    if (!ctx || !d_soft) return DABGPU_ERR_ARG;
+    if (!ctx || !d_soft || (d_dqpsk && cf32_only(ctx))) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    int rc = check_iq(d_iq, frame_stride, n_frames);
+    int rc = check_iq(ctx, d_iq, frame_stride, n_frames);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(d_soft) & 15u) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
@@ -464,7 +486,7 @@ int dabgpu_ofdm_demod_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame
     ScopedTimer tm(ctx, 0, s);
     const RunPlan plan = plan_runs(ctx, n_frames, NB_DATA_SYMBOLS);
     a.uncut_frames = plan.uncut_frames;
-    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s));
+    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
     return DABGPU_OK;
 }
 
@@ -472,7 +494,7 @@ int dabgpu_ofdm_demod_frames_dd_dev(dabgpu_ctx *ctx, const void *d_iq, size_t fr
                                     const float *d_freq_offset, int8_t *d_soft, void *d_dd4, void *stream) {
     if (!ctx || !d_soft || !d_dd4) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    int rc = check_iq(d_iq, frame_stride, n_frames);
+    int rc = check_iq(ctx, d_iq, frame_stride, n_frames);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(d_soft) & 15u) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
@@ -489,15 +511,15 @@ int dabgpu_ofdm_demod_frames_dd_dev(dabgpu_ctx *ctx, const void *d_iq, size_t fr
     ScopedTimer tm(ctx, 0, s);
     const RunPlan plan = plan_runs(ctx, n_frames, NB_DATA_SYMBOLS);
     a.uncut_frames = plan.uncut_frames;
-    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s));
+    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
     return DABGPU_OK;
 }
 
 int dabgpu_mover_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames, int8_t *d_soft,
                             int with_prefixes, void *stream) {
-    if (!ctx || !d_soft) return DABGPU_ERR_ARG;
+    if (!ctx || !d_soft || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    int rc = check_iq(d_iq, frame_stride, n_frames);
+    int rc = check_iq(ctx, d_iq, frame_stride, n_frames);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(d_soft) & 15u) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
@@ -553,9 +575,9 @@ int dabgpu_ofdm_set_soft_selection(dabgpu_ctx *ctx, const dabgpu_bit_range *rang
 
 int dabgpu_fft_symbols_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_frames,
                            const float *d_freq_offset, void *d_spectra, void *stream) {
-    if (!ctx || !d_spectra) return DABGPU_ERR_ARG;
+    if (!ctx || !d_spectra || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    int rc = check_iq(d_iq, frame_stride, n_frames);
+    int rc = check_iq(ctx, d_iq, frame_stride, n_frames);
     if (rc) return rc;
     if (n_frames == 0) return DABGPU_OK;
     hipStream_t s = pick_stream(ctx, stream);
@@ -580,6 +602,7 @@ static size_t iq_span(size_t frame_stride, int n_frames) {
 
 int dabgpu_ofdm_demod_frames(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_frames,
                              const float *freq_offset, int8_t *soft, float *cyc, float *dqpsk) {
+    if (ctx && cf32_only(ctx)) return DABGPU_ERR_ARG;
     if (!ctx || !iq || !soft || n_frames < 0) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_frames == 0) return DABGPU_OK;
@@ -761,13 +784,13 @@ int dabgpu_set_loop_gate(dabgpu_ctx *ctx, float dd_gate) {
 int dabgpu_ofdm_demod_streams_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_streams,
                                   int frames_per_stream, float fine_freq_update_beta, int8_t *d_soft, void *d_cyc,
                                   void *d_dqpsk, void *stream) {
-    if (!ctx || !d_soft || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;
+    if (!ctx || !d_soft || n_streams < 0 || frames_per_stream < 0 || (d_dqpsk && cf32_only(ctx))) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_streams > ctx->n_states) return DABGPU_ERR_CAPACITY;   // dabgpu_streams_reset first
     if (!(fine_freq_update_beta >= 0.f && fine_freq_update_beta <= 1.f)) return DABGPU_ERR_ARG;
     if (size_t(n_streams) * size_t(frames_per_stream) > size_t(0x7fffffff) / NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
     const int n_frames = n_streams * frames_per_stream;
-    int rc = check_iq(d_iq, frame_stride, n_frames);
+    int rc = check_iq(ctx, d_iq, frame_stride, n_frames);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(d_soft) & 15u) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
@@ -795,18 +818,18 @@ int dabgpu_ofdm_demod_streams_dev(dabgpu_ctx *ctx, const void *d_iq, size_t fram
         ScopedTimer tm(ctx, 0, s);
         const RunPlan plan = plan_runs(ctx, n_frames, NB_DATA_SYMBOLS);
         a.uncut_frames = plan.uncut_frames;
-        HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s));
+        HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
     }
     HIP_TRY(dabk::launch_stream_update(ctx->d_states, dd ? a.dd4 : a.cyc, a.iq, frame_stride, n_streams, frames_per_stream,
                                        fine_freq_update_beta, ctx->thr_null_start, ctx->signal_beta, dd ? 1 : 0, ctx->dd_gate,
-                                       256 * ((a.keep && !a.dqpsk) ? ctx->keep_symbols : NB_DATA_SYMBOLS), s));
+                                       256 * ((a.keep && !a.dqpsk) ? ctx->keep_symbols : NB_DATA_SYMBOLS), s, ctx->iq_format));
     return note_state_use(ctx, s);
 }
 
 int dabgpu_ofdm_demod_streams(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_streams,
                               int frames_per_stream, float fine_freq_update_beta, int8_t *soft, float *cyc,
                               float *dqpsk) {
-    if (!ctx || !iq || !soft || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;
+    if (!ctx || !iq || !soft || n_streams < 0 || frames_per_stream < 0 || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (size_t(n_streams) * size_t(frames_per_stream) > size_t(0x7fffffff) / NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
     const int n_frames = n_streams * frames_per_stream;
@@ -841,7 +864,7 @@ int dabgpu_ofdm_demod_streams(dabgpu_ctx *ctx, const float *iq, size_t frame_str
 
 int dabgpu_fft_symbols(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_frames,
                        const float *freq_offset, float *spectra) {
-    if (!ctx || !iq || !spectra || n_frames < 0) return DABGPU_ERR_ARG;
+    if (!ctx || !iq || !spectra || n_frames < 0 || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_frames == 0) return DABGPU_OK;
     void *d_iq, *d_fo = nullptr, *d_sp;
@@ -868,19 +891,20 @@ int dabgpu_sync_prs_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, 
                         const float *d_freq_offset, int max_coarse, dabgpu_sync_result *d_out, void *stream) {
     if (!ctx || !d_iq || !d_out || n_frames < 0 || max_coarse < 0 || max_coarse > 1023) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) || (frame_stride & 1u)) return DABGPU_ERR_ARG;
+    if (ctx->iq_format != dabk::IQ_CF32 ? iq_misaligned(ctx, d_iq) : ((reinterpret_cast<uintptr_t>(d_iq) & 15u) || (frame_stride & 1u)))
+        return DABGPU_ERR_ARG;
     if (n_frames > 1 && frame_stride < size_t(NB_SYM_PERIOD)) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
     hipStream_t s = pick_stream(ctx, stream);
     dabk::SyncTables tab{ctx->d_twiddle, ctx->d_prs_qt, ctx->d_sync_pairs, ctx->n_sync_pairs, ctx->d_sync_fs};
     HIP_TRY(dabk::launch_prs_sync(tab, static_cast<const float2 *>(d_iq), frame_stride, n_frames, d_freq_offset,
-                                  max_coarse, reinterpret_cast<dabk::SyncResult *>(d_out), s));
+                                  max_coarse, reinterpret_cast<dabk::SyncResult *>(d_out), s, ctx->iq_format));
     return DABGPU_OK;
 }
 
 int dabgpu_sync_prs(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, int n_frames, const float *freq_offset,
                     int max_coarse, dabgpu_sync_result *out) {
-    if (!ctx || !iq || !out || n_frames < 0) return DABGPU_ERR_ARG;
+    if (!ctx || !iq || !out || n_frames < 0 || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_frames == 0) return DABGPU_OK;
     void *d_iq, *d_fo = nullptr, *d_out;
@@ -961,7 +985,7 @@ int dabgpu_acquire_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, 
     static_assert(sizeof(dabgpu_acquired_frame) == 32 && sizeof(dabk::AcquiredFrame) == 32, "acquired-frame layout");
     if (!ctx || !d_iq || !d_out || !d_counts || n_streams < 0 || max_frames <= 0 || n_samples < 0) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    if (reinterpret_cast<uintptr_t>(d_iq) & 7u) return DABGPU_ERR_ARG;
+    if (iq_misaligned(ctx, d_iq)) return DABGPU_ERR_ARG;
     if (n_streams > 1 && stream_stride < size_t(n_samples)) return DABGPU_ERR_ARG;
     dabgpu_acquire_cfg c;
     if (cfg) c = *cfg; else dabgpu_acquire_default_cfg(&c);
@@ -982,13 +1006,13 @@ int dabgpu_acquire_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, 
     dabk::AcquireArgs a{};
     if ((rc2 = acquire_args(ctx, d_iq, stream_stride, n_streams, n_samples, c, max_frames, d_out, d_counts, s, a))) return rc2;
     dabk::SyncTables tab{ctx->d_twiddle, ctx->d_prs_qt, ctx->d_sync_pairs, ctx->n_sync_pairs, ctx->d_sync_fs};
-    HIP_TRY(dabk::launch_acquire(tab, a, s));
+    HIP_TRY(dabk::launch_acquire(tab, a, s, ctx->iq_format));
     return DABGPU_OK;
 }
 
 int dabgpu_acquire(dabgpu_ctx *ctx, const float *iq, size_t stream_stride, int n_streams, int64_t n_samples,
                    const dabgpu_acquire_cfg *cfg, int max_frames, dabgpu_acquired_frame *out, int32_t *counts) {
-    if (!ctx || !iq || !out || !counts || n_streams < 0 || max_frames <= 0 || n_samples < 0) return DABGPU_ERR_ARG;
+    if (!ctx || !iq || !out || !counts || n_streams < 0 || max_frames <= 0 || n_samples < 0 || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_streams == 0) return DABGPU_OK;
     if (n_streams > 1 && stream_stride < size_t(n_samples)) return DABGPU_ERR_ARG;
@@ -1018,9 +1042,9 @@ int dabgpu_acquire(dabgpu_ctx *ctx, const float *iq, size_t stream_stride, int n
 int dabgpu_ofdm_demod_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams,
                                    int max_frames, const dabgpu_acquired_frame *d_frames, int8_t *d_soft, void *d_cyc,
                                    void *d_dqpsk, void *stream) {
-    if (!ctx || !d_iq || !d_frames || !d_soft || n_streams < 0 || max_frames <= 0) return DABGPU_ERR_ARG;
+    if (!ctx || !d_iq || !d_frames || !d_soft || n_streams < 0 || max_frames <= 0 || (d_dqpsk && cf32_only(ctx))) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 7u) || (reinterpret_cast<uintptr_t>(d_soft) & 15u)) return DABGPU_ERR_ARG;
+    if (iq_misaligned(ctx, d_iq) || (reinterpret_cast<uintptr_t>(d_soft) & 15u)) return DABGPU_ERR_ARG;
     if (n_streams == 0) return DABGPU_OK;
     if (size_t(n_streams) * size_t(max_frames) > size_t(0x7fffffff) / NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
     hipStream_t s = pick_stream(ctx, stream);
@@ -1038,7 +1062,7 @@ int dabgpu_ofdm_demod_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t str
     ScopedTimer tm(ctx, 0, s);
     const RunPlan plan = plan_runs(ctx, a.n_frames, NB_DATA_SYMBOLS);
     a.uncut_frames = plan.uncut_frames;
-    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s));
+    HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
     return DABGPU_OK;
 }
 
@@ -1159,9 +1183,9 @@ static int tracked_launches(dabgpu_ctx *ctx, const TrackedCall &k, const dabgpu_
         t.copy_src = static_cast<const uint4 *>(k.upload_from);
         t.copy_n16 = unsigned(k.upload_bytes >> 4);
     }
-    HIP_TRY(dabk::launch_track_sync(stab, t, s));
+    HIP_TRY(dabk::launch_track_sync(stab, t, s, ctx->iq_format));
     // streams that are not tracking: acquired here (their rows of d_frames / d_counts; the pass above left them empty)
-    if (auto_acq) HIP_TRY(dabk::launch_acquire(stab, *auto_acq, s));
+    if (auto_acq) HIP_TRY(dabk::launch_acquire(stab, *auto_acq, s, ctx->iq_format));
     dabk::OfdmTables tab{ctx->d_twiddle, ctx->d_bin_of_n, ctx->d_n_of_vj};
     dabk::OfdmArgs a{};
     a.iq = static_cast<const float2 *>(d_iq);
@@ -1178,7 +1202,7 @@ static int tracked_launches(dabgpu_ctx *ctx, const TrackedCall &k, const dabgpu_
         ScopedTimer tm(ctx, 0, s);
         const RunPlan plan = plan_runs(ctx, a.n_frames, NB_DATA_SYMBOLS);
         a.uncut_frames = plan.uncut_frames;
-        HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s));
+        HIP_TRY(dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
     }
     dabk::TrackUpdateArgs u{};
     u.state = states;
@@ -1204,7 +1228,7 @@ static int tracked_launches(dabgpu_ctx *ctx, const TrackedCall &k, const dabgpu_
     // ... and their tracking starts from what the acquisition found (marked 2; the update launch makes it 1)
     if (auto_acq)
         HIP_TRY(dabk::launch_track_start(states, t.out, d_counts, n_streams, max_frames, advance, 1, s));
-    HIP_TRY(dabk::launch_track_update(u, s));
+    HIP_TRY(dabk::launch_track_update(u, s, ctx->iq_format));
     return k.note_states ? note_state_use(ctx, s) : DABGPU_OK;
 }
 
@@ -1212,10 +1236,11 @@ int dabgpu_ofdm_demod_tracked_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stre
                                   int64_t n_samples, int max_frames, int64_t advance, const dabgpu_track_cfg *cfg,
                                   int8_t *d_soft, void *d_cyc, void *d_dqpsk, dabgpu_acquired_frame *d_frames,
                                   int32_t *d_counts, void *stream) {
-    if (!ctx || !d_iq || !d_soft || !d_frames || !d_counts || n_streams < 0 || max_frames <= 0 || n_samples < 0 || advance < 0)
+    if (!ctx || !d_iq || !d_soft || !d_frames || !d_counts || n_streams < 0 || max_frames <= 0 || n_samples < 0 || advance < 0 ||
+        (d_dqpsk && cf32_only(ctx)))
         return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 7u) || (reinterpret_cast<uintptr_t>(d_soft) & 15u)) return DABGPU_ERR_ARG;
+    if (iq_misaligned(ctx, d_iq) || (reinterpret_cast<uintptr_t>(d_soft) & 15u)) return DABGPU_ERR_ARG;
     if (n_streams > 1 && stream_stride < size_t(n_samples)) return DABGPU_ERR_ARG;
     if (n_streams > ctx->n_states) return DABGPU_ERR_CAPACITY;   // dabgpu_streams_reset first
     if (size_t(n_streams) * size_t(max_frames) > size_t(0x7fffffff) / NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
@@ -1262,7 +1287,7 @@ int dabgpu_ofdm_demod_tracked_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stre
 
 int dabgpu_ofdm_demod_stream_frame(dabgpu_ctx *ctx, int stream_index, const float *iq, int acquiring,
                                    const dabgpu_track_cfg *cfg, int8_t *soft, float *dqpsk, dabgpu_frame_result *result) {
-    if (!ctx || !iq || !soft || !result || stream_index < 0 || stream_index >= ctx->n_states) return DABGPU_ERR_ARG;
+    if (!ctx || !iq || !soft || !result || stream_index < 0 || stream_index >= ctx->n_states || cf32_only(ctx)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     dabgpu_track_cfg c;
     int rc = track_cfg(cfg, c);

@@ -13,6 +13,7 @@
 
 #include "dab_tables.hpp"
 #include "kernels.hpp"
+#include "iq_load.hpp"
 
 namespace dabapi {
 
@@ -121,6 +122,7 @@ struct dabgpu_ctx {
     unsigned long long signal_seq = 0;   // number of the last one-frame call that ended through wait_for_signal
     dabapi::Arena arena;                 // dabgpu_alloc_frame_buffers(DABGPU_PLACE_DOMAINS)
     dabapi::Pipeline *pipe = nullptr;    // dabgpu_pipe_open
+    int iq_format = 0;                   // DABGPU_IQ_* of the samples the device-pointer calls read (dabgpu_set_iq_format)
 };
 
 namespace dabapi {

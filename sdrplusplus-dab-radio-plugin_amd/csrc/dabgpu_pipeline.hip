@@ -29,6 +29,7 @@ struct Pipeline {
     hipStream_t s_up = nullptr, s_down = nullptr;
     int max_frames = 0;
     size_t frame_stride = 0;
+    int iq_format = 0;                               // the context's sample format when the ring opened (DABGPU_IQ_*)
     int64_t next_ticket = 0;
     // de-interleaver rings of the sub-channels the ring decodes, on the device, double-buffered: [n_streams][15][bits]
     struct Ring {
@@ -82,12 +83,13 @@ int dabgpu_pipe_open(dabgpu_ctx *ctx, int slots, int max_frames, size_t frame_st
     ctx->pipe = p;
     p->max_frames = max_frames;
     p->frame_stride = frame_stride;
+    p->iq_format = ctx->iq_format;
     p->slots.resize(size_t(slots));
     int rc = DABGPU_OK;
     if (hipStreamCreateWithFlags(&p->s_up, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&p->s_down, hipStreamNonBlocking) != hipSuccess)
         rc = DABGPU_ERR_HIP;
-    const size_t nb_iq = size_t(max_frames) * frame_stride * sizeof(float2);
+    const size_t nb_iq = size_t(max_frames) * frame_stride * dabk::iq_sample_bytes(p->iq_format);
     for (auto &s : p->slots) {
         if (rc) break;
         if (hipMalloc(&s.d_iq, nb_iq) != hipSuccess || hipMalloc(&s.d_soft, size_t(max_frames) * NB_FRAME_BITS) != hipSuccess ||
@@ -115,11 +117,11 @@ int dabgpu_pipe_reset(dabgpu_ctx *ctx) {
     return DABGPU_OK;
 }
 
-static int submit_body(dabgpu_ctx *ctx, const float *iq, int n_streams, int frames_per_stream, const float *freq_offset,
+static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
                        float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
                        uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket);
 
-int dabgpu_pipe_submit(dabgpu_ctx *ctx, const float *iq, int n_streams, int frames_per_stream, const float *freq_offset,
+int dabgpu_pipe_submit(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
                        float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
                        uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket) {
     if (!ctx || !ctx->pipe || !iq || !fib || !crc_ok || !ticket || n_streams <= 0 || frames_per_stream <= 0 || n_subchannels < 0)
@@ -155,7 +157,7 @@ int dabgpu_pipe_submit(dabgpu_ctx *ctx, const float *iq, int n_streams, int fram
     return rc;
 }
 
-static int submit_body(dabgpu_ctx *ctx, const float *iq, int n_streams, int frames_per_stream, const float *freq_offset,
+static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
                        float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
                        uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket) {
     Pipeline *p = ctx->pipe;
@@ -214,7 +216,7 @@ static int submit_body(dabgpu_ctx *ctx, const float *iq, int n_streams, int fram
         p_out[size_t(i)] = static_cast<uint8_t *>(s.d_res) + out_off[size_t(i)];
     }
     // ---- upload (copy stream) ----
-    const size_t nb_iq = (size_t(n_frames - 1) * p->frame_stride + size_t(NB_FRAME_SYMBOLS) * NB_SYM_PERIOD) * sizeof(float2);
+    const size_t nb_iq = (size_t(n_frames - 1) * p->frame_stride + size_t(NB_FRAME_SYMBOLS) * NB_SYM_PERIOD) * dabk::iq_sample_bytes(p->iq_format);
     HIP_TRY(hipMemcpyAsync(s.d_iq, iq, nb_iq, hipMemcpyHostToDevice, p->s_up));
     if (freq_offset) HIP_TRY(hipMemcpyAsync(s.d_fo, freq_offset, sizeof(float) * size_t(n_frames), hipMemcpyHostToDevice, p->s_up));
     HIP_TRY(hipEventRecord(s.up, p->s_up));

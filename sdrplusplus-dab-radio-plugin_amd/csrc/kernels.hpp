@@ -70,7 +70,11 @@ struct OfdmArgs {
 
 // fused A2..A6.  Frames behind the first a.uncut_frames are cut into `parts` contiguous runs of data symbols (1..75);
 // a run re-reads the symbol before it as differential reference.
-hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s);
+//
+// iq_format (IQ_*, iq_load.hpp; every launcher that reads samples takes it): a.iq / the iq pointers then hold the caller's
+// integer samples; strides and starts stay in complex samples.  The integer formats take the fused kernel without a
+// constellation output only, and the tracking pass in batch mode without a riding upload (hipErrorInvalidValue otherwise).
+hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s, int iq_format = 0);
 // A2+A3 only; parts in 1..76.
 hipError_t launch_fft_symbols(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s);
 // Fine-frequency loop and counters of the stream call, after the demodulation launch on the same stream:
@@ -103,7 +107,7 @@ hipError_t launch_geometry_mover(const float2 *iq, size_t frame_stride, int n_fr
 // (dd_gate, dd_terms_per_frame: see dd_loop_error / TrackUpdateArgs)
 hipError_t launch_stream_update(StreamState *state, const float2 *cyc, const float2 *iq, size_t frame_stride,
                                 int n_streams, int frames_per_stream, float beta, float thr_null_start, float signal_beta,
-                                int dd, float dd_gate, int dd_terms_per_frame, hipStream_t s);
+                                int dd, float dd_gate, int dd_terms_per_frame, hipStream_t s, int iq_format = 0);
 
 // ---- synchronisation on the PRS (sync_kernels.hip) -----------------------------
 struct SyncTables {
@@ -120,7 +124,7 @@ struct SyncResult {            // == dabgpu_sync_result
     float coarse_peak_to_mean;
 };
 hipError_t launch_prs_sync(const SyncTables &t, const float2 *iq, size_t frame_stride, int n_frames,
-                           const float *freq_offset, int max_coarse, SyncResult *out, hipStream_t s);
+                           const float *freq_offset, int max_coarse, SyncResult *out, hipStream_t s, int iq_format = 0);
 
 // Which tap of the channel impulse response a frame is aligned to (impulse_peak_distance_probability,
 // /root/reference/src/render_radio_block.cpp:225):
@@ -168,7 +172,7 @@ struct AcquireArgs {
     const StreamState *skip_tracked = nullptr;
 };
 size_t acquire_scratch_bytes(int n_streams, int64_t n_samples, int max_out);
-hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t s);
+hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t s, int iq_format = 0);
 
 // ---- per-stream timing tracking (sync_kernels.hip) -------------------------------
 // Batch mode (fixed_start = 0): frame slot i of stream s is predicted from the stream's state at
@@ -207,7 +211,7 @@ struct TrackArgs {
     unsigned copy_n16 = 0;
     int copy_blocks = 0;                 // set by the launcher
 };
-hipError_t launch_track_sync(const SyncTables &t, const TrackArgs &a, hipStream_t s);
+hipError_t launch_track_sync(const SyncTables &t, const TrackArgs &a, hipStream_t s, int iq_format = 0);
 
 // After the demodulation of those frames, one workgroup per stream:
 //   fine loop   fine -= beta * mean(arg cyc) / (2 pi 2048) over the locked frames, wrapped to +-half a carrier
@@ -286,7 +290,7 @@ struct TrackUpdateArgs {
     StreamState *state_out = nullptr;
     int copy_blocks = 0;       // set by the launcher
 };
-hipError_t launch_track_update(const TrackUpdateArgs &a, hipStream_t s);
+hipError_t launch_track_update(const TrackUpdateArgs &a, hipStream_t s, int iq_format = 0);
 // Start tracking from an acquisition result (dabgpu_acquire_dev on the same capture): per stream, a least-squares line
 // through the starts of the locked frames against their frame number round((start - first)/196608) gives the drift
 // (0 with fewer than 4 locked frames); next_frame_start = start_last + 196608 + drift - advance; fine offset = mean of

@@ -31,6 +31,7 @@
 #include "dab_tables.hpp"
 #include "fft_common.hpp"
 #include "mem_stream.hpp"
+#include "iq_load.hpp"
 
 namespace dabk {
 
@@ -134,8 +135,11 @@ __device__ __forceinline__ uint32_t frame_dphi(const OfdmArgs &a, int frame) {
 // NCO: a frequency correction is applied (the launch has a freq_offset array, stream states or acquired frames).  A
 // compile-time switch, not a per-frame branch: the branch cost 31 register moves per symbol where its two paths
 // re-joined.
-template <bool FFT_ONLY, bool WITH_DQPSK, bool SELECT = false, bool NCO = true>
+// FMT: sample format (IQ_*, iq_load.hpp); the integer ones are converted to float right after their loads.  (A compile-time
+// switch as well: with the cs8 / cu8 difference as a kernel argument the cf32 instantiations' code would not stay as it is.)
+template <bool FFT_ONLY, bool WITH_DQPSK, bool SELECT = false, bool NCO = true, int FMT = IQ_CF32>
 __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab, OfdmArgs a, int parts, int n_items) {
+    constexpr int FAM = iq_family(FMT);
     __shared__ WaveLds sm;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -170,7 +174,8 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
     } else {
         parts = 1;
     }
-    const float2 *fiq = a.iq + size_t(frame) * a.frame_stride;
+    const IqSrc<FAM> iq0 = iq_src<FAM>(a.iq, FMT);
+    IqSrc<FAM> fiq = iq0 + size_t(frame) * a.frame_stride;
     // fused: data symbols (l_first, l_last]; l_first is only the differential reference
     const int l_first = FFT_ONLY ? (NB_FRAME_SYMBOLS * part) / parts : (NB_DATA_SYMBOLS * part) / parts;
     const int l_last = FFT_ONLY ? (NB_FRAME_SYMBOLS * (part + 1)) / parts - 1 : (NB_DATA_SYMBOLS * (part + 1)) / parts;
@@ -186,10 +191,12 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
             }
             return;
         }
-        fiq = a.iq + size_t(frame / a.acq_per_stream) * a.frame_stride + m.start;
+        fiq = iq0 + size_t(frame / a.acq_per_stream) * a.frame_stride + m.start;
         dphi_acq = uint32_t(__double2ll_rn(double(m.freq_offset) * 4294967296.0));
     }
-    const bool aligned16 = (reinterpret_cast<uintptr_t>(fiq) & 15u) == 0;
+    bool aligned16;                                             // (integer formats: every load pair aligned to its width)
+    if constexpr (FAM == IQF_F32) aligned16 = (reinterpret_cast<uintptr_t>(fiq) & 15u) == 0;
+    else aligned16 = fiq.pair_aligned();
     const uint32_t dphi = a.acq ? dphi_acq : frame_dphi(a, frame);
     float2 *ex = sm.ex[wave];
     const float2 *tw = sm.tw;
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
     };
 
     for (int l = l_first; l <= l_last; l++) {
-        const float2 *sym = fiq + size_t(l) * NB_SYM_PERIOD;
+        const IqSrc<FAM> sym = fiq + size_t(l) * NB_SYM_PERIOD;
         const bool emit = FFT_ONLY || (l > l_first) || (l == 0);
         // Lane roles, derived per iteration from an opaque copy of the lane number: every LDS address below is one or
         // two VALU ops from these, which is cheaper than letting LICM park ~60 loop-invariant addresses in VGPRs (spills).
@@ -257,13 +264,31 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
             if (!need) {
                 if ((a.cyc && emit) || (dd && l == 0)) {
                     float2 acc = make_float2(0.f, 0.f);
-                    const float2 *cp = sym + 2 * (lane - 4);
-                    const float2 *tail = sym + NB_CP + 128 * 12 + 2 * lane;
+                    const IqSrc<FAM> cp = sym + 2 * (lane - 4);
+                    const IqSrc<FAM> tail = sym + NB_CP + 128 * 12 + 2 * lane;
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
                         if (i > 0 || lane >= 4) {
-                            const float2 c0 = ld_stream(cp + 128 * i), c1 = ld_stream(cp + 128 * i + 1);
-                            const float2 u0 = ld_stream(tail + 128 * i), u1 = ld_stream(tail + 128 * i + 1);
+                            float2 c0, c1, u0, u1;
+                            if constexpr (FAM == IQF_F32) {
+                                c0 = ld_stream(cp + 128 * i); c1 = ld_stream(cp + 128 * i + 1);
+                                u0 = ld_stream(tail + 128 * i); u1 = ld_stream(tail + 128 * i + 1);
+                            } else {
+                                if (aligned16) {
+                                    cp.ld2(128 * i, c0, c1);
+                                    tail.ld2(128 * i, u0, u1);
+                                } else {
+                                    c0 = cp.ld(128 * i); c1 = cp.ld(128 * i + 1);
+                                    u0 = tail.ld(128 * i); u1 = tail.ld(128 * i + 1);
+                                }
+                                // the cf32 instantiations' rounding (iq_load.hpp, mul_rn): real part four rounded products
+                                // added in order, imaginary part one product and three fused steps
+                                const float sx = add_rn(add_rn(add_rn(mul_rn(c0.x, u0.x), mul_rn(c0.y, u0.y)), mul_rn(c1.x, u1.x)),
+                                                        mul_rn(c1.y, u1.y));
+                                const float sy = fmaf(-c1.y, u1.x, fmaf(c1.x, u1.y, fmaf(-c0.y, u0.x, mul_rn(c0.x, u0.y))));
+                                acc = make_float2(add_rn(acc.x, sx), add_rn(acc.y, sy));
+                                continue;
+                            }
                             acc.x += c0.x * u0.x + c0.y * u0.y + c1.x * u1.x + c1.y * u1.y;      // conj(c) * u
                             acc.y += c0.x * u0.y - c0.y * u0.x + c1.x * u1.y - c1.y * u1.x;
                         }
@@ -284,7 +309,19 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
         __builtin_amdgcn_sched_barrier(0);
         // ---- loads: 16 x 16 B per lane, row n1 = samples 128*n1 + 2*lane, +1 ----
         float2 x0[16], x1[16];
-        if (aligned16) {
+        if constexpr (FAM != IQF_F32) {
+            // one 8-byte (cs16) or 4-byte (cs8/cu8) load per lane and row: 512 / 256 contiguous bytes per wave instruction
+            if (aligned16) {
+#pragma unroll
+                for (int n1 = 0; n1 < 16; n1++) sym.ld2(NB_CP + 128 * n1 + 2 * lane, x0[n1], x1[n1]);
+            } else {                                          // odd sample offset: one load per sample
+#pragma unroll
+                for (int n1 = 0; n1 < 16; n1++) {
+                    x0[n1] = sym.ld(NB_CP + 128 * n1 + 2 * lane);
+                    x1[n1] = sym.ld(NB_CP + 128 * n1 + 2 * lane + 1);
+                }
+            }
+        } else if (aligned16) {
             const float4 *rows = reinterpret_cast<const float4 *>(sym + NB_CP) + lane;
 #pragma unroll
             for (int n1 = 0; n1 < 16; n1++) {
@@ -305,18 +342,30 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
         // (decision-directed mode: of the PRS only -- its angle picks the branch of the fourth-power estimate, 4.1)
         if ((a.cyc && emit) || (dd && l == 0)) {
             float2 acc = make_float2(0.f, 0.f);
-            const float2 *cp = sym + 2 * (lane - 4);
+            const IqSrc<FAM> cp = sym + 2 * (lane - 4);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 if (i > 0 || lane >= 4) {
                     float4 c;
-                    if (aligned16) {
+                    if constexpr (FAM != IQF_F32) {
+                        float2 c0, c1;
+                        if (aligned16) cp.ld2(128 * i, c0, c1);
+                        else { c0 = cp.ld(128 * i); c1 = cp.ld(128 * i + 1); }
+                        c = make_float4(c0.x, c0.y, c1.x, c1.y);
+                    } else if (aligned16) {
                         c = ld_stream(reinterpret_cast<const float4 *>(cp + 128 * i));
                     } else {
                         const float2 c0 = ld_stream(cp + 128 * i), c1 = ld_stream(cp + 128 * i + 1);
                         c = make_float4(c0.x, c0.y, c1.x, c1.y);
                     }
                     const float2 u0 = x0[12 + i], u1 = x1[12 + i];
+                    if constexpr (FAM != IQF_F32) {
+                        // the cf32 instantiations' rounding (iq_load.hpp, mul_rn): one rounded product, three fused steps
+                        const float sx = fmaf(c.w, u1.y, fmaf(c.z, u1.x, fmaf(c.x, u0.x, mul_rn(c.y, u0.y))));
+                        const float sy = fmaf(-c.w, u1.x, fmaf(c.z, u1.y, fmaf(c.x, u0.y, -mul_rn(c.y, u0.x))));
+                        acc = make_float2(add_rn(acc.x, sx), add_rn(acc.y, sy));
+                        continue;
+                    }
                     acc.x += c.x * u0.x + c.y * u0.y + c.z * u1.x + c.w * u1.y;      // conj(c) * u
                     acc.y += c.x * u0.y - c.y * u0.x + c.z * u1.y - c.w * u1.x;
                 }
@@ -518,6 +567,7 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
 
 // One 1024-thread workgroup per stream.  Restated by oracle.py stream_update() for the parity test.
 constexpr int SU_THREADS = 1024;
+template <int FMT = IQ_CF32>
 __global__ __launch_bounds__(SU_THREADS) void stream_update_kernel(StreamState *state, const float2 *cyc, const float2 *iq,
                                                                    size_t frame_stride, int frames_per_stream, float beta,
                                                                    float thr_null_start, float signal_beta, int dd, float dd_gate,
@@ -530,10 +580,19 @@ __global__ __launch_bounds__(SU_THREADS) void stream_update_kernel(StreamState *
     float acc = 0.f;
     double sx = 0.0, sy = 0.0;
     // level of the stream's most recent frame: first 4096 samples (PRS and the start of the first data symbol); read first
-    const float4 *x = reinterpret_cast<const float4 *>(iq + (size_t(s) * frames_per_stream + (frames_per_stream - 1)) * frame_stride);
     float4 lv[2048 / SU_THREADS];
+    if constexpr (FMT == IQ_CF32) {
+        const float4 *x = reinterpret_cast<const float4 *>(iq + (size_t(s) * frames_per_stream + (frames_per_stream - 1)) * frame_stride);
 #pragma unroll
-    for (int k = 0; k < 2048 / SU_THREADS; k++) lv[k] = x[tid + k * SU_THREADS];
+        for (int k = 0; k < 2048 / SU_THREADS; k++) lv[k] = x[tid + k * SU_THREADS];
+    } else {                                                    // (the same pairs of samples, any alignment)
+        const IqSrc<iq_family(FMT)> x = iq_src<iq_family(FMT)>(iq, FMT) + (size_t(s) * frames_per_stream + (frames_per_stream - 1)) * frame_stride;
+#pragma unroll
+        for (int k = 0; k < 2048 / SU_THREADS; k++) {
+            const float2 u = x[2 * (tid + k * SU_THREADS)], v = x[2 * (tid + k * SU_THREADS) + 1];
+            lv[k] = make_float4(u.x, u.y, v.x, v.y);
+        }
+    }
     // (eight entries in flight per thread; each thread still adds its entries in ascending order)
     constexpr int SU_BATCH = 8;
     if (dd) {
@@ -775,14 +834,23 @@ hipError_t launch_fill_noise(void *p, size_t bytes, hipStream_t s) {
 
 hipError_t launch_stream_update(StreamState *state, const float2 *cyc, const float2 *iq, size_t frame_stride,
                                 int n_streams, int frames_per_stream, float beta, float thr_null_start, float signal_beta,
-                                int dd, float dd_gate, int dd_terms_per_frame, hipStream_t s) {
+                                int dd, float dd_gate, int dd_terms_per_frame, hipStream_t s, int iq_format) {
     if (n_streams <= 0 || frames_per_stream <= 0) return hipSuccess;
-    hipLaunchKernelGGL(stream_update_kernel, dim3(unsigned(n_streams)), dim3(SU_THREADS), 0, s, state, cyc, iq, frame_stride,
-                       frames_per_stream, beta, thr_null_start, signal_beta, dd, dd_gate, dd_terms_per_frame);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(n_streams)), dim3(SU_THREADS), 0, s, state, cyc, iq, frame_stride,
+                           frames_per_stream, beta, thr_null_start, signal_beta, dd, dd_gate, dd_terms_per_frame);
+    };
+    switch (iq_format) {
+    case IQ_CF32: go(stream_update_kernel<IQ_CF32>); break;
+    case IQ_CS16: go(stream_update_kernel<IQ_CS16>); break;
+    case IQ_CS8: go(stream_update_kernel<IQ_CS8>); break;
+    case IQ_CU8: go(stream_update_kernel<IQ_CU8>); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s) {
+hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s, int iq_format) {
     if (a.n_frames <= 0) return hipSuccess;
     if (parts <= 0 || parts > NB_DATA_SYMBOLS) return hipErrorInvalidValue;
     if (a.state && a.frames_per_stream <= 0) return hipErrorInvalidValue;
@@ -792,6 +860,20 @@ hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, 
     const dim3 grid(unsigned((items + WAVES - 1) / WAVES)), block(64 * WAVES);
     OfdmArgs b = a;
     if (a.dqpsk) b.keep = nullptr;      // the constellation output covers every symbol: a selection is ignored there
+    if (iq_format != IQ_CF32) {
+        // integer samples: the fused kernel with or without a selection, with or without the NCO (no constellation output)
+        if (b.dqpsk || !iq_format_valid(iq_format)) return hipErrorInvalidValue;
+#define DABK_INT_FE(SEL, NCO_)                                                                                          \
+        do {                                                                                                               \
+            if (iq_format == IQ_CS16) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS16>), grid, block, 0, s, t, b, parts, items); \
+            else if (iq_format == IQ_CS8) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS8>), grid, block, 0, s, t, b, parts, items); \
+            else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CU8>), grid, block, 0, s, t, b, parts, items);     \
+        } while (0)
+        if (b.keep) { if (nco) DABK_INT_FE(true, true); else DABK_INT_FE(true, false); }
+        else { if (nco) DABK_INT_FE(false, true); else DABK_INT_FE(false, false); }
+#undef DABK_INT_FE
+        return hipGetLastError();
+    }
     if (b.dqpsk) {
         if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, true>), grid, block, 0, s, t, b, parts, items);
         else hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, false>), grid, block, 0, s, t, b, parts, items);

@@ -18,6 +18,7 @@
 #include "dab_tables.hpp"
 #include "fft_common.hpp"
 #include "mem_stream.hpp"
+#include "iq_load.hpp"
 
 namespace dabk {
 
@@ -93,10 +94,17 @@ __device__ __forceinline__ void block_argmax_sum(Lds &sm, int tid, float m, int 
 // Fractional frequency error from the cyclic prefix of the PRS: products first .. first+375 of the candidate's prefix
 // against the samples 2048 later (inside the prefix for any candidate within +-64 samples of first - 64 early);
 // -angle / (2 pi 2048) cycles per sample.  Block-wide; ends with a barrier.
-__device__ __forceinline__ float cp_fine_offset(SyncLds &sm, const float2 *sym, int first, int tid) {
+template <class Src>
+__device__ __forceinline__ float cp_fine_offset(SyncLds &sm, const Src sym, int first, int tid) {
     double cr = 0.0, ci = 0.0;
     for (int i = first + tid; i < first + 376; i += WG) {
         const float2 a = sym[i], b = sym[i + NB_FFT];
+        if constexpr (!std::is_same<Src, const float2 *>::value) {
+            // integer samples: the rounding the cf32 instantiations are compiled to (iq_load.hpp, mul_rn)
+            cr += double(fmaf(a.x, b.x, mul_rn(a.y, b.y)));
+            ci += double(fmaf(a.x, b.y, -mul_rn(a.y, b.x)));
+            continue;
+        }
         cr += double(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)));      // conj(a) * b
         ci += double(__fsub_rn(__fmul_rn(a.x, b.y), __fmul_rn(a.y, b.x)));
     }
@@ -141,7 +149,8 @@ struct Predictor {
 // geometry of an upload riding in a synchronisation launch (see the kernel's head): measured over eight streams of a process,
 // 256 x 2: 81-92 us per frame call, 128 x 4: 70-80, 64 x 8 / 48 x 8 / 32 x 16: 68-70 on every stream
 constexpr int RIDE_BLOCKS = 64, RIDE_UNROLL = 8;
-template <int MODE, bool LITE = false>
+// FMT: sample format of the stream (IQ_*); the integer ones are read through iq_load.hpp, everything after the loads is the same.
+template <int MODE, bool LITE = false, int FMT = IQ_CF32>
 __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const float2 *iq, size_t frame_stride,
                                                       const float *freq_offset, int max_coarse_arg, SyncResult *out,
                                                       AcquireArgs acq, TrackArgs trk, int n_total) {
@@ -175,7 +184,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
     // is served behind all of them (measured: the launch took upload + synchronisation, 55 us instead of 37).
     float2 pre[8];
     bool prefetched = false;
-    if constexpr (MODE == MODE_TRACK && !LITE) {
+    if constexpr (MODE == MODE_TRACK && !LITE && FMT == IQ_CF32) {
         if (trk.copy_n16 != 0 && trk.sync_iq != nullptr) {
             prefetched = true;
 #pragma unroll
@@ -209,7 +218,8 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
     __syncthreads();
     for (int frame = blockIdx.x; frame < n_total; frame += n_sync_blocks) {
     int max_coarse = max_coarse_arg;
-    const float2 *sym;
+    constexpr int FAM = iq_family(FMT);
+    IqSrc<FAM> sym;
     uint32_t dphi;
     int64_t cand = 0;
     float fine = 0.0f, coarse = 0.0f;
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
             continue;
         }
         cand = acq.cands[frame];
-        sym = acq.iq + size_t(st) * acq.stream_stride + cand;
+        sym = iq_src<FAM>(acq.iq, FMT) + size_t(st) * acq.stream_stride + cand;
         fine = cp_fine_offset(sm, sym, 64, tid);
         dphi = uint32_t(__double2ll_rn(double(fine) * 4294967296.0));
         max_coarse = acq.max_coarse;
@@ -244,7 +254,8 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
             }
             continue;
         }
-        sym = (trk.sync_iq ? trk.sync_iq : trk.iq) + size_t(st) * trk.stream_stride + cand;
+        if constexpr (FMT == IQ_CF32) sym = (trk.sync_iq ? trk.sync_iq : trk.iq) + size_t(st) * trk.stream_stride + cand;
+        else sym = iq_src<FAM>(trk.iq, FMT) + size_t(st) * trk.stream_stride + cand;
         fine = ss.fine_freq_offset;
         // first frame after a null-symbol detection: the fine offset starts from this PRS's own cyclic prefix, so that
         // the frame is already demodulated with it (the loop then refines it)
@@ -256,7 +267,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
         do_coarse = max_coarse > 0;
         rule = trk.rule;
     } else {
-        sym = iq + size_t(frame) * frame_stride;
+        sym = iq_src<FAM>(iq, FMT) + size_t(frame) * frame_stride;
         dphi = dphi_of(freq_offset, frame);
     }
     // ---- X = FFT(nco * window) ----
@@ -266,6 +277,14 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
         for (int r = 0; r < 8; r++) {
             const int n = tid + r * WG;
             v[r] = prefetched ? pre[r] : sym[NB_CP + n];
+            if constexpr (FMT != IQ_CF32) {
+                // integer samples: the rounding the cf32 instantiations are compiled to (iq_load.hpp, mul_rn)
+                if (dphi != 0u) {
+                    const float2 w = nco(uint32_t(n), dphi), x = v[r];
+                    v[r] = make_float2(fmaf(w.x, x.x, -mul_rn(w.y, x.y)), fmaf(w.y, x.x, mul_rn(w.x, x.y)));
+                }
+                continue;
+            }
             if (dphi != 0u) v[r] = cmul(v[r], nco(uint32_t(n), dphi));
         }
         block_fft2048(v, sm.t1, sm.x, tw, twc8, twc64, tid);
@@ -415,6 +434,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
 
 // ---- timing tracking: state update after the demodulation of the tracked frames (TrackUpdateArgs) ----
 constexpr int TU = 1024;          // threads per stream: the kernel is one workgroup per stream and lives on loads in flight
+template <int FMT = IQ_CF32>
 __global__ __launch_bounds__(TU) void track_update_kernel(TrackUpdateArgs a) {
     __shared__ double red[7][TU];
     __shared__ int red_last[TU];
@@ -518,8 +538,8 @@ __global__ __launch_bounds__(TU) void track_update_kernel(TrackUpdateArgs a) {
     // level of the last locked frame: its first 4096 samples
     float l1 = 0.f;
     if (last >= 0) {
-        const float2 *x = a.iq + size_t(s) * a.stream_stride + fr[last].start;
-        for (int i = tid; i < 4096; i += TU) l1 += fabsf(x[i].x) + fabsf(x[i].y);
+        const IqSrc<iq_family(FMT)> x = iq_src<iq_family(FMT)>(a.iq, FMT) + size_t(s) * a.stream_stride + fr[last].start;
+        for (int i = tid; i < 4096; i += TU) { const float2 v = x[i]; l1 += fabsf(v.x) + fabsf(v.y); }
     }
     // ... and, for the decision-directed loop, the angles of the locked frames' PRS cyclic-prefix correlations (entry 0)
     double ang0 = 0.0;
@@ -645,6 +665,7 @@ __global__ __launch_bounds__(64) void track_start_kernel(StreamState *state, con
 // owns 32 consecutive blocks (16 KB of samples, four trips' loads in flight at a time) and writes their norms as ONE
 // 128-byte store: two dwords per wave, as a first version did, are partial cache lines that eight XCDs' L2s each
 // hold a piece of.
+template <int FMT = IQ_CF32>
 __global__ __launch_bounds__(256) void null_l1_kernel(const float2 *iq, size_t stream_stride, int64_t nb, float *l1,
                                                       const StreamState *skip_tracked) {
     const int st = blockIdx.y;
@@ -652,7 +673,7 @@ __global__ __launch_bounds__(256) void null_l1_kernel(const float2 *iq, size_t s
     const int lane = threadIdx.x & 63;
     const int64_t wave = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
     const int64_t n_waves = int64_t(gridDim.x) * 4;
-    const float2 *x = iq + size_t(st) * stream_stride;
+    const IqSrc<iq_family(FMT)> x = iq_src<iq_family(FMT)>(iq, FMT) + size_t(st) * stream_stride;
     float *o = l1 + size_t(st) * nb;
     const int64_t n_chunks = (nb + 31) / 32;
     for (int64_t chunk = wave; chunk < n_chunks; chunk += n_waves) {
@@ -665,9 +686,14 @@ __global__ __launch_bounds__(256) void null_l1_kernel(const float2 *iq, size_t s
             for (int u = 0; u < 4; u++) {
                 // (a block past the end re-reads the last one: no branch between the loads, the store is predicated)
                 const int64_t blk = min(b0 + 2 * (j0 + u) + (lane >> 5), nb - 1);
-                const float2 *p = x + blk * 64 + 2 * (lane & 31);
-                s0[u] = ld_stream(p);
-                s1[u] = ld_stream(p + 1);
+                const IqSrc<iq_family(FMT)> p = x + blk * 64 + 2 * (lane & 31);
+                if constexpr (FMT == IQ_CF32) {
+                    s0[u] = ld_stream(p);
+                    s1[u] = ld_stream(p + 1);
+                } else {
+                    s0[u] = p.ld(0);
+                    s1[u] = p.ld(1);
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -883,19 +909,51 @@ __global__ __launch_bounds__(64) void null_stitch_kernel(AcquireArgs a, int n_se
 // stride, keeps the tail short and loads the tables once per eight candidates
 static unsigned sync_grid(int n) { return unsigned(std::max(1, std::min(n, 4096))); }
 
+// f(std::integral_constant<int, FMT>{}) for a sample format known at run time
+template <class F>
+static hipError_t with_iq_format(int fmt, F &&f) {
+    switch (fmt) {
+    case IQ_CF32: f(std::integral_constant<int, IQ_CF32>{}); break;
+    case IQ_CS16: f(std::integral_constant<int, IQ_CS16>{}); break;
+    case IQ_CS8: f(std::integral_constant<int, IQ_CS8>{}); break;
+    case IQ_CU8: f(std::integral_constant<int, IQ_CU8>{}); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_prs_sync(const SyncTables &t, const float2 *iq, size_t frame_stride, int n_frames,
-                           const float *freq_offset, int max_coarse, SyncResult *out, hipStream_t s) {
+                           const float *freq_offset, int max_coarse, SyncResult *out, hipStream_t s, int iq_format) {
     if (n_frames <= 0) return hipSuccess;
     if (max_coarse < 0 || max_coarse > 1023) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(prs_sync_kernel<MODE_PLAIN>, dim3(sync_grid(n_frames)), dim3(WG), 0, s, t, iq, frame_stride,
-                       freq_offset, max_coarse, out, AcquireArgs{}, TrackArgs{}, n_frames);
+    const hipError_t e = with_iq_format(iq_format, [&](auto fmt) {
+        hipLaunchKernelGGL((prs_sync_kernel<MODE_PLAIN, false, decltype(fmt)::value>), dim3(sync_grid(n_frames)), dim3(WG), 0, s, t, iq,
+                           frame_stride, freq_offset, max_coarse, out, AcquireArgs{}, TrackArgs{}, n_frames);
+    });
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
-hipError_t launch_track_sync(const SyncTables &t, const TrackArgs &a, hipStream_t s) {
+hipError_t launch_track_sync(const SyncTables &t, const TrackArgs &a, hipStream_t s, int iq_format) {
     if (a.n_streams <= 0 || a.max_out <= 0) return hipSuccess;
     if (a.max_coarse < 0 || a.max_coarse > 1023 || (a.fixed_start && a.max_out != 1)) return hipErrorInvalidValue;
     TrackArgs b = a;
+    if (iq_format != IQ_CF32) {
+        // integer samples: batch tracking (the lite synchronisation, no whole-carrier search, no upload riding along)
+        if (a.fixed_start || a.max_coarse != 0 || a.copy_n16 != 0) return hipErrorInvalidValue;
+        b.rule.expected = a.margin;
+        b.copy_blocks = 0;
+        b.copy_dst = nullptr;
+        b.copy_src = nullptr;
+        b.sync_iq = nullptr;
+        const hipError_t e = with_iq_format(iq_format, [&](auto fmt) {
+            hipLaunchKernelGGL((prs_sync_kernel<MODE_TRACK, true, decltype(fmt)::value>), dim3(sync_grid(a.n_streams * a.max_out)), dim3(WG),
+                               0, s, t, static_cast<const float2 *>(nullptr), size_t(0), static_cast<const float *>(nullptr), 0,
+                               static_cast<SyncResult *>(nullptr), AcquireArgs{}, b, a.n_streams * a.max_out);
+        });
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
     b.rule.expected = a.margin;
     b.copy_blocks = 0;
     if (a.copy_n16) {
@@ -921,7 +979,7 @@ hipError_t launch_track_sync(const SyncTables &t, const TrackArgs &a, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_track_update(const TrackUpdateArgs &a, hipStream_t s) {
+hipError_t launch_track_update(const TrackUpdateArgs &a, hipStream_t s, int iq_format) {
     if (a.n_streams <= 0 || a.max_out <= 0) return hipSuccess;
     TrackUpdateArgs b = a;
     unsigned words = 0;
@@ -930,7 +988,10 @@ hipError_t launch_track_update(const TrackUpdateArgs &a, hipStream_t s) {
         words += unsigned(c.bytes >> 4);
     }
     b.copy_blocks = int((words + TU - 1) / TU);
-    hipLaunchKernelGGL(track_update_kernel, dim3(unsigned(a.n_streams + b.copy_blocks)), dim3(TU), 0, s, b);
+    const hipError_t e = with_iq_format(iq_format, [&](auto fmt) {
+        hipLaunchKernelGGL(track_update_kernel<decltype(fmt)::value>, dim3(unsigned(a.n_streams + b.copy_blocks)), dim3(TU), 0, s, b);
+    });
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
@@ -952,7 +1013,7 @@ size_t acquire_scratch_bytes(int n_streams, int64_t n_samples, int max_out) {
            al256(size_t(n_streams) * n_seg * max_out * sizeof(int64_t)) + al256(size_t(n_streams) * (nb / 64 + 1) * sizeof(double));
 }
 
-hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t s) {
+hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t s, int iq_format) {
     if (a.n_streams <= 0 || a.max_out <= 0) return hipSuccess;
     const int64_t nb = a.n_samples / 64;
     if (nb <= 0 || a.max_coarse < 0 || a.max_coarse > 1023) return hipErrorInvalidValue;
@@ -960,7 +1021,11 @@ hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t
     // launch whose streams are all skipped (auto-acquisition beside tracked streams) then costs microseconds
     const int64_t per_stream = std::max<int64_t>(16, 8192 / std::max(1, a.n_streams));
     const unsigned gx = unsigned(std::min<int64_t>(((nb + 31) / 32 + 3) / 4, std::min<int64_t>(per_stream, 4096)));
-    hipLaunchKernelGGL(null_l1_kernel, dim3(gx, unsigned(a.n_streams)), dim3(256), 0, s, a.iq, a.stream_stride, nb, a.l1, a.skip_tracked);
+    if (!iq_format_valid(iq_format)) return hipErrorInvalidValue;
+    (void)with_iq_format(iq_format, [&](auto fmt) {
+        hipLaunchKernelGGL(null_l1_kernel<decltype(fmt)::value>, dim3(gx, unsigned(a.n_streams)), dim3(256), 0, s, a.iq, a.stream_stride, nb,
+                           a.l1, a.skip_tracked);
+    });
     // the rest of the scratch buffer follows the candidate lists (acquire_scratch_bytes)
     const int n_seg = int(dip_segments(nb));
     char *p = reinterpret_cast<char *>(a.cands) + al256(size_t(a.n_streams) * a.max_out * sizeof(int64_t));
@@ -984,9 +1049,11 @@ hipError_t launch_acquire(const SyncTables &t, const AcquireArgs &a, hipStream_t
     hipLaunchKernelGGL(null_segment_kernel, dim3(unsigned(n_seg), unsigned(a.n_streams)), dim3(64), 0, s, b, nb, n_seg, avg, segs,
                        seg_cands);
     hipLaunchKernelGGL(null_stitch_kernel, dim3(unsigned(a.n_streams)), dim3(64), 0, s, b, n_seg, segs, seg_cands);
-    hipLaunchKernelGGL(prs_sync_kernel<MODE_ACQ>, dim3(sync_grid(a.n_streams * a.max_out)), dim3(WG), 0, s, t,
-                       static_cast<const float2 *>(nullptr), size_t(0), static_cast<const float *>(nullptr), 0,
-                       static_cast<SyncResult *>(nullptr), b, TrackArgs{}, a.n_streams * a.max_out);
+    (void)with_iq_format(iq_format, [&](auto fmt) {
+        hipLaunchKernelGGL((prs_sync_kernel<MODE_ACQ, false, decltype(fmt)::value>), dim3(sync_grid(a.n_streams * a.max_out)), dim3(WG), 0, s,
+                           t, static_cast<const float2 *>(nullptr), size_t(0), static_cast<const float *>(nullptr), 0,
+                           static_cast<SyncResult *>(nullptr), b, TrackArgs{}, a.n_streams * a.max_out);
+    });
     return hipGetLastError();
 }
 

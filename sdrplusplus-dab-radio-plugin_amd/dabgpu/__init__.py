@@ -46,6 +46,7 @@ EXPORTS = [
     "dabgpu_set_stream_loop", "dabgpu_set_loop_gate", "dabgpu_track_default_cfg", "dabgpu_track_start_dev", "dabgpu_ofdm_demod_tracked_dev",
     "dabgpu_ofdm_demod_stream_frame", "dabgpu_ofdm_demod_frames_dd_dev", "dabgpu_test_fail_frame_call",
     "dabgpu_mer_dev", "dabgpu_channel_ber_dev", "dabgpu_decode_stream_frames_quality",
+    "dabgpu_set_iq_format", "dabgpu_get_iq_format",
 ]
 
 ABI_VERSION = 6
@@ -60,6 +61,10 @@ FLAG_VITERBI_WAVE = 1 << 0
 FLAG_VITERBI_LANE = 1 << 1
 FLAG_LANE_UNFUSED = 1 << 2
 FLAG_TEST_ONE_DOMAIN = 1 << 30          # test hook: the allocator's check of a placed pair reads 1.00
+#: sample formats of the device-pointer calls and the ring (Context.set_iq_format); cu8's value is u - 127.5
+IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
+#: numpy dtype of one I or Q value per format
+IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype(np.int16), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
 
 
 class DabGpuError(RuntimeError):
@@ -274,6 +279,8 @@ def load_library(path):
     L.dabgpu_pipe_close.argtypes = [vp]
     L.dabgpu_set_stream_loop.argtypes = [vp, C.c_float, C.c_float, i]
     L.dabgpu_set_loop_gate.argtypes = [vp, C.c_float]
+    L.dabgpu_set_iq_format.argtypes = [vp, i]
+    L.dabgpu_get_iq_format.argtypes = [vp]
     L.dabgpu_track_default_cfg.restype = None
     L.dabgpu_track_default_cfg.argtypes = [C.POINTER(TrackCfg)]
     L.dabgpu_track_start_dev.argtypes = [vp, vp, vp, i, i, C.c_int64, i, vp]
@@ -515,7 +522,13 @@ class Context:
     def pipe_submit(self, iq, n_streams, frames_per_stream, freq_offset, scs, soft, fib, crc_ok, outs, beta=0.9):
         """Enqueue one batch (dabgpu_pipe_submit).  Every array argument is a numpy array (or None for freq_offset / soft)
         that the CALLER keeps alive and untouched until pipe_wait(ticket); page-locked ones (PinnedArray.array) move at the
-        link rate.  -> ticket"""
+        link rate.  A ring of integer samples (set_iq_format before pipe_open) takes int16 / int8 / uint8 arrays of shape
+        [n, frame_stride, 2] of exactly its format's dtype.  -> ticket"""
+        fmt = self.iq_format
+        if fmt != IQ_CF32 and (iq.dtype != IQ_DTYPES[fmt] or iq.ndim != 3 or iq.shape[-1] != 2):
+            raise ValueError("the ring reads %s samples as [n, frame_stride, 2]; got %s %s" % (IQ_DTYPES[fmt], iq.dtype, iq.shape))
+        if fmt == IQ_CF32 and iq.dtype.kind in "iu":
+            raise ValueError("the ring reads cf32 samples; set_iq_format before pipe_open for %s" % iq.dtype)
         n = len(scs)
         arr = (Subchannel * max(n, 1))(*scs)
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs]) if n else None
@@ -567,6 +580,16 @@ class Context:
         t = device_tensor(torch, self.stream_states_ptr, (n_streams * 64,), torch.uint8, torch.device("cuda", self._device))
         torch.cuda.synchronize()
         return t.cpu().numpy().view(STREAM_STATE_DTYPE).copy()
+
+    def set_iq_format(self, fmt):
+        """Sample format the device-pointer calls and a ring opened after this read (IQ_CF32 / IQ_CS16 / IQ_CS8 / IQ_CU8;
+        dabgpu_set_iq_format).  The outputs are bit for bit the cf32 path's on float32 copies of the same values (cu8:
+        u - 127.5).  Refused (DabGpuError, ERR_ARG) for an unknown value or while a ring is open."""
+        _check(self._lib.dabgpu_set_iq_format(self._h, int(fmt)), "dabgpu_set_iq_format")
+
+    @property
+    def iq_format(self):
+        return self._lib.dabgpu_get_iq_format(self._h)
 
     def set_loop_gate(self, dd_gate):
         _check(self._lib.dabgpu_set_loop_gate(self._h, dd_gate), "dabgpu_set_loop_gate")
