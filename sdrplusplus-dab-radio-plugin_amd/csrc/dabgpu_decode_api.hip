@@ -760,8 +760,9 @@ int dabgpu_dabplus_superframes(dabgpu_ctx *ctx, const uint8_t *in, size_t in_str
     if (!ctx || !in || !out || !status || n_superframes < 0) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (bitrate_kbps < 8 || bitrate_kbps % 8 || bitrate_kbps > 512) return DABGPU_ERR_PROFILE;
-    if (n_superframes == 0) return DABGPU_OK;
     const int s = bitrate_kbps / 8;
+    if (n_superframes > 1 && in_stride < size_t(120) * s) return DABGPU_ERR_ARG;   // (before any byte of `in` is read)
+    if (n_superframes == 0) return DABGPU_OK;
     const size_t nb_in = size_t(n_superframes - 1) * in_stride + size_t(120) * s;
     const size_t nb_out = size_t(n_superframes) * 110 * s;
     // A few super-frames in page-locked buffers (the host mirror's channels hand over ONE, ~1-2 kB in, ~1 kB out): the kernel

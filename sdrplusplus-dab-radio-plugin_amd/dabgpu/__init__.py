@@ -113,6 +113,11 @@ MER_DTYPE = np.dtype([("signal", np.uint64), ("error", np.uint64), ("carriers", 
 assert MER_DTYPE.itemsize == 24
 BER_DTYPE = np.dtype([("errors", np.uint32), ("bits", np.uint32)])
 assert BER_DTYPE.itemsize == 8
+#: dabgpu_superframe_status: one DAB+ super-frame's checks (include/dabgpu.h)
+SUPERFRAME_STATUS_DTYPE = np.dtype([("firecode_ok", np.int32), ("rs_corrected", np.int32), ("rs_uncorrectable", np.int32),
+                                    ("num_aus", np.int32), ("au_crc_mask", np.int32), ("au_start", np.int32, (8,)),
+                                    ("reserved", np.int32, (3,))])
+assert SUPERFRAME_STATUS_DTYPE.itemsize == 64
 
 
 def mer_db(rec):
@@ -751,18 +756,29 @@ class Context:
         _check(self._lib.dabgpu_ofdm_demod_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, d_soft,
                                                     d_cyc, d_dqpsk, stream), "dabgpu_ofdm_demod_acquired_dev")
 
-    def dabplus_superframes(self, sfs, bitrate_kbps):
-        """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status structured array)."""
+    def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
+        """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).
+        out / status: the caller's own arrays of those shapes (page-locked ones take the library's page-locked path)."""
         sfs = np.ascontiguousarray(sfs, np.uint8)
         n, stride = sfs.shape
         s = bitrate_kbps // 8
-        out = np.zeros((n, 110 * s), np.uint8)
-        st = np.zeros(n, dtype=[("firecode_ok", np.int32), ("rs_corrected", np.int32), ("rs_uncorrectable", np.int32),
-                                ("num_aus", np.int32), ("au_crc_mask", np.int32), ("au_start", np.int32, (8,)),
-                                ("reserved", np.int32, (3,))])
-        _check(self._lib.dabgpu_dabplus_superframes(self._h, _p(sfs), stride, n, bitrate_kbps, _p(out), _p(st)),
+        if out is None:
+            out = np.zeros((n, 110 * s), np.uint8)
+        if status is None:
+            status = np.zeros(n, SUPERFRAME_STATUS_DTYPE)
+        if out.dtype != np.uint8 or out.shape != (n, 110 * s) or not out.flags.c_contiguous:
+            raise ValueError("out must be contiguous uint8 [%d][%d]" % (n, 110 * s))
+        if status.dtype != SUPERFRAME_STATUS_DTYPE or status.shape != (n,) or not status.flags.c_contiguous:
+            raise ValueError("status must be contiguous SUPERFRAME_STATUS_DTYPE [%d]" % n)
+        _check(self._lib.dabgpu_dabplus_superframes(self._h, _p(sfs), stride, n, bitrate_kbps, _p(out), _p(status)),
                "dabgpu_dabplus_superframes")
-        return out, st
+        return out, status
+
+    def dabplus_superframes_dev(self, d_in, in_stride, n, bitrate_kbps, d_out, d_status, stream=None):
+        """Device pointers: super-frame f at d_in + f * in_stride (120*s bytes) -> d_out [n][110*s], d_status [n]
+        (SUPERFRAME_STATUS_DTYPE)."""
+        _check(self._lib.dabgpu_dabplus_superframes_dev(self._h, d_in, in_stride, n, bitrate_kbps, d_out, d_status, stream),
+               "dabgpu_dabplus_superframes_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""
