@@ -798,6 +798,83 @@ int dabgpu_decode_stream_frames_quality(dabgpu_ctx *ctx, const int8_t *soft, siz
                                         dabgpu_ber_count *fic_ber, dabgpu_ber_count *const *msc_ber, dabgpu_mer *mer);
 
 /* ------------------------------------------------------------------------ */
+/* Transmitter identification (TII, EN 300 401 section 14.8, Mode I): which   */
+/* transmitters of a single-frequency network are received, and how strongly,  */
+/* from the combs they put into the null symbol.  Comb c (sub-identifier,       */
+/* 0..23) and position b (0..7) own the carrier pairs k = B + 2c + 48b, k + 1   */
+/* for B in {-768, -384, 1, 385}; pattern p (main identifier, 0..69) switches  */
+/* on four of the eight positions (dabgpu_tii_pattern: bit 7 - b = position b). */
+/*                                                                            */
+/* Per frame the 2048 samples [-2352, -304) before the first sample of the PRS  */
+/* prefix are corrected in frequency and transformed; with P(k) = |X_k|^2:      */
+/*   cell[c][b]  sum of P over the 8 carriers of (c, b)                         */
+/*   floor       mean P over the noise bins 776 <= |k| <= 927                   */
+/* The calls ADD each stream's frames, in frame order, to d_acc[stream] (zero   */
+/* it to start; no atomics: the sums repeat bit for bit).  d_frame, when not    */
+/* NULL, receives every frame's own record ([n_streams][frames_per_stream],     */
+/* frames = 1, or 0 for a skipped slot, whose sums are 0).  d_iq is read in the */
+/* context's sample format (dabgpu_set_iq_format); the records are the same    */
+/* for every format holding the same values.                                    */
+/*                                                                            */
+/* dabgpu_tii_frames_dev    frame (s, f) as the front end has it: its PRS      */
+/*            prefix at d_iq + (s*frames_per_stream + f)*frame_stride (>= 2656  */
+/*            when there is more than one frame); the caller guarantees the      */
+/*            2656 samples before every frame are readable.  d_freq_offset       */
+/*            [n_frames] cycles/sample as dabgpu_ofdm_demod_frames_dev takes it,  */
+/*            or NULL: each stream's fine + coarse offset from the context's      */
+/*            stream states, what dabgpu_ofdm_demod_streams_dev would apply if    */
+/*            enqueued next (DABGPU_ERR_ARG without stream states,                */
+/*            DABGPU_ERR_CAPACITY for more streams than there are states).        */
+/* dabgpu_tii_acquired_dev  the slots dabgpu_acquire_dev / _tracked_dev wrote    */
+/*            ([n_streams][max_frames]) with their start and freq_offset; the    */
+/*            PRS prefix is at start + timing_margin (the margin the slots were   */
+/*            found with, 0..504).  Counted: flags == 3 and the window inside the  */
+/*            capture (start + timing_margin >= 2352); other slots add nothing.   */
+/* dabgpu_tii_decode        host only (no context, no device): level(c, b) =    */
+/*            cell / (8 floor) - 1, the estimated SNR of a TII carrier; a cell is */
+/*            on at level >= 10^(min_level_db / 10).  A pattern whose four cells  */
+/*            are on is an entry {p, c, 10 log10(mean of its four levels),        */
+/*            AMBIGUOUS when its comb has more than four cells on}.  Entries by    */
+/*            level descending (ties: sub_id, then main_id ascending).  Returns    */
+/*            how many there are (none for frames == 0 or floor <= 0; nothing      */
+/*            written beyond max_out), DABGPU_ERR_ARG for a NULL acc, a NULL out   */
+/*            with max_out > 0, max_out < 0 or a min_level_db that is not finite. */
+/*            cfg NULL = the defaults.                                           */
+/* Refusals (DABGPU_ERR_ARG / _CAPACITY) enqueue nothing and leave the outputs   */
+/* untouched.  The tables restate the standard from memory: the pattern bit     */
+/* order and the bases are not checked against it.   */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_tii_acc {   /* DEVICE memory, 784 bytes: a stream's sums, or one frame's record */
+    float cell[24][8];            /* sum over frames of the cell energies                             */
+    float floor;                  /* sum over frames of the mean noise-bin power                      */
+    int32_t frames;               /* frames added                                                     */
+    int32_t reserved[2];          /* left as they are by the calls; 0 in per-frame records            */
+} dabgpu_tii_acc;
+
+typedef struct dabgpu_tii_cfg {
+    float min_level_db;           /* a cell is on at this TII-carrier SNR or more (3.0) */
+    int32_t reserved;             /* 0 */
+} dabgpu_tii_cfg;
+
+#define DABGPU_TII_AMBIGUOUS 1    /* the comb has more than four cells on (e.g. two transmitters share the sub-identifier) */
+typedef struct dabgpu_tii_entry {
+    int32_t main_id;              /* pattern p, 0..69     */
+    int32_t sub_id;               /* comb c, 0..23        */
+    float level_db;               /* 10 log10(mean level) */
+    int32_t flags;                /* DABGPU_TII_*         */
+} dabgpu_tii_entry;
+
+void dabgpu_tii_default_cfg(dabgpu_tii_cfg *cfg);
+/* the 8-bit mask of pattern p (bit 7 - b = position b), -1 outside 0..69 */
+int dabgpu_tii_pattern(int p);
+int dabgpu_tii_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_streams, int frames_per_stream,
+                          const float *d_freq_offset, dabgpu_tii_acc *d_frame, dabgpu_tii_acc *d_acc, void *stream);
+int dabgpu_tii_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams, int max_frames,
+                            const dabgpu_acquired_frame *d_frames, int timing_margin, dabgpu_tii_acc *d_frame,
+                            dabgpu_tii_acc *d_acc, void *stream);
+int dabgpu_tii_decode(const dabgpu_tii_acc *acc, const dabgpu_tii_cfg *cfg, dabgpu_tii_entry *out, int max_out);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

@@ -1386,3 +1386,108 @@ int dabgpu_ofdm_demod_stream_frame(dabgpu_ctx *ctx, int stream_index, const floa
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------- transmitter identification
+static_assert(sizeof(dabgpu_tii_acc) == sizeof(dabk::TiiRecord), "ABI struct mirrors the kernel's");
+static_assert(offsetof(dabgpu_tii_acc, floor) == offsetof(dabk::TiiRecord, floor) &&
+              offsetof(dabgpu_tii_acc, frames) == offsetof(dabk::TiiRecord, frames), "ABI struct mirrors the kernel's");
+
+namespace {
+// both calls: checks, the per-frame records (the caller's or slot 7), the launches
+int tii_launch(dabgpu_ctx *ctx, dabk::TiiArgs &a, dabgpu_tii_acc *d_frame, dabgpu_tii_acc *d_acc, void *stream) {
+    if ((reinterpret_cast<uintptr_t>(d_acc) & 3u) || (reinterpret_cast<uintptr_t>(d_frame) & 3u)) return DABGPU_ERR_ARG;
+    const size_t n_frames = size_t(a.n_streams) * size_t(a.frames_per_stream);
+    if (n_frames > size_t(0x7fffffff)) return DABGPU_ERR_ARG;
+    if (n_frames == 0) return DABGPU_OK;
+    int rc;
+    void *rec = d_frame;
+    if (!rec && (rc = stage(ctx, 7, n_frames * sizeof(dabk::TiiRecord), &rec))) return rc;
+    a.frame = static_cast<dabk::TiiRecord *>(rec);
+    a.acc = reinterpret_cast<dabk::TiiRecord *>(d_acc);
+    hipStream_t s = pick_stream(ctx, stream);
+    HIP_TRY(dabk::launch_tii(ctx->d_twiddle, a, s, ctx->iq_format));
+    return a.state ? note_state_use(ctx, s) : DABGPU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void dabgpu_tii_default_cfg(dabgpu_tii_cfg *cfg) {
+    if (!cfg) return;
+    cfg->min_level_db = 3.0f;
+    cfg->reserved = 0;
+}
+
+int dabgpu_tii_pattern(int p) { return p >= 0 && p < dabk::TII_PATTERNS ? dabk::tii_pattern_mask(p) : -1; }
+
+int dabgpu_tii_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_streams, int frames_per_stream,
+                          const float *d_freq_offset, dabgpu_tii_acc *d_frame, dabgpu_tii_acc *d_acc, void *stream) {
+    if (!ctx || !d_iq || !d_acc || n_streams < 0 || frames_per_stream < 0 || iq_misaligned(ctx, d_iq)) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    if (size_t(n_streams) * size_t(frames_per_stream) > 1 && frame_stride < size_t(NB_NULL_PERIOD)) return DABGPU_ERR_ARG;
+    if (!d_freq_offset && n_streams > 0 && frames_per_stream > 0) {
+        if (!ctx->d_states) return DABGPU_ERR_ARG;                 // dabgpu_streams_reset first
+        if (n_streams > ctx->n_states) return DABGPU_ERR_CAPACITY;
+    }
+    dabk::TiiArgs a{};
+    a.iq = static_cast<const float2 *>(d_iq);
+    a.stride = frame_stride;
+    a.n_streams = n_streams;
+    a.frames_per_stream = frames_per_stream;
+    a.freq_offset = d_freq_offset;
+    a.state = d_freq_offset ? nullptr : ctx->d_states;
+    return tii_launch(ctx, a, d_frame, d_acc, stream);
+}
+
+int dabgpu_tii_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams, int max_frames,
+                            const dabgpu_acquired_frame *d_frames, int timing_margin, dabgpu_tii_acc *d_frame,
+                            dabgpu_tii_acc *d_acc, void *stream) {
+    if (!ctx || !d_iq || !d_frames || !d_acc || n_streams < 0 || max_frames <= 0 || iq_misaligned(ctx, d_iq)) return DABGPU_ERR_ARG;
+    if (timing_margin < 0 || timing_margin > NB_CP || (reinterpret_cast<uintptr_t>(d_frames) & 7u)) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    dabk::TiiArgs a{};
+    a.iq = static_cast<const float2 *>(d_iq);
+    a.stride = stream_stride;
+    a.n_streams = n_streams;
+    a.frames_per_stream = max_frames;
+    a.acq = reinterpret_cast<const dabk::AcquiredFrame *>(d_frames);
+    a.timing_margin = timing_margin;
+    return tii_launch(ctx, a, d_frame, d_acc, stream);
+}
+
+int dabgpu_tii_decode(const dabgpu_tii_acc *acc, const dabgpu_tii_cfg *cfg, dabgpu_tii_entry *out, int max_out) {
+    dabgpu_tii_cfg def;
+    dabgpu_tii_default_cfg(&def);
+    if (!cfg) cfg = &def;
+    if (!acc || max_out < 0 || (max_out > 0 && !out) || !std::isfinite(cfg->min_level_db)) return DABGPU_ERR_ARG;
+    if (acc->frames == 0 || !(acc->floor > 0.0f)) return 0;
+    const double thr = std::pow(10.0, double(cfg->min_level_db) / 10.0);
+    const double noise = 8.0 * double(acc->floor);
+    std::vector<dabgpu_tii_entry> found;
+    for (int c = 0; c < dabk::TII_COMBS; c++) {
+        double level[dabk::TII_POSITIONS];
+        int on = 0, n_on = 0;
+        for (int b = 0; b < dabk::TII_POSITIONS; b++) {
+            level[b] = double(acc->cell[c][b]) / noise - 1.0;
+            if (level[b] >= thr) {
+                on |= 0x80 >> b;
+                n_on++;
+            }
+        }
+        for (int p = 0; p < dabk::TII_PATTERNS; p++) {
+            const int m = dabk::tii_pattern_mask(p);
+            if ((on & m) != m) continue;
+            double sum = 0.0;
+            for (int b = 0; b < dabk::TII_POSITIONS; b++)
+                if (m & (0x80 >> b)) sum += level[b];
+            found.push_back(dabgpu_tii_entry{p, c, float(10.0 * std::log10(sum / 4.0)), n_on > 4 ? DABGPU_TII_AMBIGUOUS : 0});
+        }
+    }
+    std::stable_sort(found.begin(), found.end(), [](const dabgpu_tii_entry &x, const dabgpu_tii_entry &y) {
+        return x.level_db > y.level_db;                             // (found in sub_id, main_id order: ties keep it)
+    });
+    for (size_t i = 0; i < found.size() && i < size_t(max_out); i++) out[i] = found[i];
+    return int(found.size());
+}
+
+}  // extern "C"

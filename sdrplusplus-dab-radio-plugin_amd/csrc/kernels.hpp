@@ -440,6 +440,41 @@ struct BerItem {
 hipError_t launch_channel_ber(const BerItem *items, int n, hipStream_t s);
 int ber_group_max();
 
+// ---- transmitter identification from the null symbol (tii_kernels.hip) --------
+// EN 300 401 section 14.8, Mode I.  Comb c (sub-identifier, 0..23) and position b (0..7) own the carrier pairs
+// k = B + 2c + 48b, k + 1 for the four bases B; pattern p (main identifier, 0..69) switches on four of the eight positions.
+// The carrier bases and which bit of a pattern is b = 0 are the two conventions the tests cannot pin against the standard:
+// both live here, and only here (tests/tii_reference.py restates them).
+constexpr int TII_COMBS = 24, TII_POSITIONS = 8, TII_CELLS = TII_COMBS * TII_POSITIONS, TII_PATTERNS = 70;
+__host__ __device__ constexpr int tii_base(int q) { return q < 2 ? -768 + 384 * q : 384 * q - 767; }   // -768 -384 1 385
+// pattern p = the p-th 8-bit value with four bits set, ascending; bit 7 - b is position b
+__host__ __device__ constexpr int tii_pattern_mask(int p) {
+    for (int v = 0, i = 0; v < 256; v++)
+        if (__builtin_popcount(unsigned(v)) == 4 && i++ == p) return v;
+    return -1;
+}
+// The window: 2048 samples centred in the null symbol, [-2352, -304) relative to the first sample of the PRS prefix; the
+// noise floor: mean power of the bins 776 <= |k| <= 927 (outside the ensemble, inside the guard band to the next block).
+constexpr int TII_WIN_BEGIN = 2352, TII_FLOOR_LO = 776, TII_FLOOR_HI = 927;
+struct TiiRecord {             // == dabgpu_tii_acc (784 bytes): per frame, or a stream's running sums
+    float cell[TII_CELLS];     // [c][b]: power of the cell's 8 carriers
+    float floor;               // mean power of a noise bin
+    int32_t frames;
+    int32_t reserved[2];
+};
+struct TiiArgs {
+    const float2 *iq;          // context's sample format
+    size_t stride;             // frame (frame calls) or stream (acquired calls) stride, complex samples
+    int n_streams, frames_per_stream;
+    const float *freq_offset;  // frame calls: [n_frames] cycles/sample, or nullptr: the stream states
+    const struct StreamState *state;
+    const AcquiredFrame *acq;  // acquired calls: [n_streams][frames_per_stream]
+    int timing_margin;         // acquired calls: PRS prefix = start + timing_margin
+    TiiRecord *frame;          // [n_frames] per-frame records
+    TiiRecord *acc;            // [n_streams] += the stream's frames, in frame order
+};
+hipError_t launch_tii(const float2 *twiddle, const TiiArgs &a, hipStream_t s, int iq_format);
+
 // Let every kernel that takes dynamic LDS use the whole 160 KB of a CU: set once per context creation (on the
 // context's device) instead of per launch.
 hipError_t init_viterbi_kernel_attributes();

@@ -47,6 +47,7 @@ EXPORTS = [
     "dabgpu_ofdm_demod_stream_frame", "dabgpu_ofdm_demod_frames_dd_dev", "dabgpu_test_fail_frame_call",
     "dabgpu_mer_dev", "dabgpu_channel_ber_dev", "dabgpu_decode_stream_frames_quality",
     "dabgpu_set_iq_format", "dabgpu_get_iq_format",
+    "dabgpu_tii_default_cfg", "dabgpu_tii_pattern", "dabgpu_tii_frames_dev", "dabgpu_tii_acquired_dev", "dabgpu_tii_decode",
 ]
 
 ABI_VERSION = 6
@@ -118,6 +119,13 @@ SUPERFRAME_STATUS_DTYPE = np.dtype([("firecode_ok", np.int32), ("rs_corrected", 
                                     ("num_aus", np.int32), ("au_crc_mask", np.int32), ("au_start", np.int32, (8,)),
                                     ("reserved", np.int32, (3,))])
 assert SUPERFRAME_STATUS_DTYPE.itemsize == 64
+#: dabgpu_tii_acc: a stream's transmitter-identification sums (device memory; zero it to start), or one frame's record
+TII_ACC_DTYPE = np.dtype([("cell", np.float32, (24, 8)), ("floor", np.float32), ("frames", np.int32), ("reserved", np.int32, (2,))])
+assert TII_ACC_DTYPE.itemsize == 784
+#: dabgpu_tii_entry: one transmitter found by tii_decode
+TII_ENTRY_DTYPE = np.dtype([("main_id", np.int32), ("sub_id", np.int32), ("level_db", np.float32), ("flags", np.int32)])
+assert TII_ENTRY_DTYPE.itemsize == 16
+TII_AMBIGUOUS = 1
 
 
 def mer_db(rec):
@@ -172,6 +180,29 @@ class FrameResult(C.Structure):
 ACQUIRED_FRAME_DTYPE = np.dtype([("start", np.int64), ("freq_offset", np.float32), ("coarse_carriers", np.int32),
                                  ("fine_offset", np.float32), ("peak_to_mean", np.float32),
                                  ("coarse_peak_to_mean", np.float32), ("flags", np.int32)])     # 32 bytes
+
+
+class TiiCfg(C.Structure):
+    _fields_ = [("min_level_db", C.c_float), ("reserved", C.c_int32)]
+
+
+def tii_pattern(p):
+    """8-bit mask of TII pattern p (main identifier 0..69; bit 7 - b = position b), -1 outside the table: the library's own."""
+    return int(lib().dabgpu_tii_pattern(int(p)))
+
+
+def tii_decode(acc, min_level_db=3.0, max_out=24 * 70):
+    """Transmitters in one TII_ACC_DTYPE accumulator (a host copy) -> TII_ENTRY_DTYPE array, strongest first
+    (dabgpu_tii_decode: host only, no GPU)."""
+    acc = np.ascontiguousarray(np.asarray(acc, TII_ACC_DTYPE).reshape(()))
+    cfg = TiiCfg()
+    lib().dabgpu_tii_default_cfg(C.byref(cfg))
+    cfg.min_level_db = min_level_db
+    out = np.zeros(max_out, TII_ENTRY_DTYPE)
+    n = lib().dabgpu_tii_decode(_p(acc), C.byref(cfg), _p(out), max_out)
+    if n < 0:
+        raise DabGpuError(n, "dabgpu_tii_decode")
+    return out[:min(n, max_out)].copy()
 
 
 def soft_selection(subchannels, with_fic=True):
@@ -296,6 +327,12 @@ def load_library(path):
     L.dabgpu_mer_dev.argtypes = [vp, vp, sz, i, i, i, vp, vp]
     L.dabgpu_channel_ber_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, i, vp, vp, vp, vp]
     L.dabgpu_decode_stream_frames_quality.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp, vp, vp, vp]
+    L.dabgpu_tii_default_cfg.restype = None
+    L.dabgpu_tii_default_cfg.argtypes = [C.POINTER(TiiCfg)]
+    L.dabgpu_tii_pattern.argtypes = [i]
+    L.dabgpu_tii_frames_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp]
+    L.dabgpu_tii_acquired_dev.argtypes = [vp, vp, sz, i, i, vp, i, vp, vp, vp]
+    L.dabgpu_tii_decode.argtypes = [vp, C.POINTER(TiiCfg), vp, i]
     return L
 
 
@@ -755,6 +792,21 @@ class Context:
                                 d_dqpsk=None, stream=None):
         _check(self._lib.dabgpu_ofdm_demod_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, d_soft,
                                                     d_cyc, d_dqpsk, stream), "dabgpu_ofdm_demod_acquired_dev")
+
+    def tii_frames_dev(self, d_iq, frame_stride, n_streams, frames_per_stream, d_acc, d_freq_offset=None, d_frame=None,
+                       stream=None):
+        """Transmitter identification of frames (s, f) at d_iq + (s*frames_per_stream + f)*frame_stride (PRS prefix; the 2656
+        samples before are read): d_acc [n_streams] (TII_ACC_DTYPE) += the streams' frames; d_frame, if given, every frame's
+        record.  d_freq_offset None = the stream states' fine + coarse offsets."""
+        _check(self._lib.dabgpu_tii_frames_dev(self._h, d_iq, frame_stride, n_streams, frames_per_stream, d_freq_offset,
+                                               d_frame, d_acc, stream), "dabgpu_tii_frames_dev")
+
+    def tii_acquired_dev(self, d_iq, stream_stride, n_streams, max_frames, d_frames, d_acc, timing_margin=64, d_frame=None,
+                         stream=None):
+        """Transmitter identification of the locked, whole frames of acquire_dev / ofdm_demod_tracked_dev slots
+        (PRS prefix at start + timing_margin) whose null window lies inside the capture."""
+        _check(self._lib.dabgpu_tii_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, timing_margin,
+                                                 d_frame, d_acc, stream), "dabgpu_tii_acquired_dev")
 
     def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
         """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).

@@ -295,11 +295,54 @@ def _tables():
     return _CAR, _PRS
 
 
-def modulate_frame(bits):
-    """230400 bits -> complex64[196608] (null + PRS + 75 symbols), unit average symbol power."""
+#: transmitter identification (EN 300 401 section 14.8): the carrier bases of the four pair groups
+TII_BASES = (-768, -384, 1, 385)
+
+
+def tii_null(tii):
+    """The null symbol [2656] complex64 of the transmitters `tii` = [(c, p) or (c, p, gain), ...]: comb c (sub-identifier),
+    pattern p (main identifier, the p-th 8-bit value with four bits set, bit 7 - b = position b), complex amplitude gain
+    (default 1).  Each switched-on pair k = B + 2c + 48b, k + 1 carries a data carrier's amplitude with the PRS phase of
+    its carrier; the 2048-sample symbol is extended cyclically over the whole null period (a 608-sample prefix)."""
+    _, prs = _tables()
+    patterns = [v for v in range(256) if bin(v).count("1") == 4]
+    spec = np.zeros(NB_FFT, np.complex128)
+    for t in tii:
+        c, p = int(t[0]), int(t[1])
+        g = t[2] if len(t) > 2 else 1.0
+        for b in range(8):
+            if patterns[p] >> (7 - b) & 1:
+                for base in TII_BASES:
+                    for k in (base + 2 * c + 48 * b, base + 2 * c + 48 * b + 1):
+                        spec[k % NB_FFT] += g * prs[k + 768]
+    t = np.fft.ifft(spec) * (NB_FFT / np.sqrt(NB_CARRIERS))
+    return t[(np.arange(NB_NULL) - (NB_NULL - NB_FFT)) % NB_FFT].astype(np.complex64)
+
+
+def sfn(frame_bits, transmitters):
+    """A single-frequency network: every transmitter sends the same frames (frame_bits [n][230400]) with its own TII.
+    transmitters = [(c, p, delay in samples, gain in dB), ...] -> the sum as received, complex64 [n * 196608]
+    (a delayed transmitter's first samples are zeros)."""
+    frame_bits = np.asarray(frame_bits, np.uint8).reshape(-1, NB_FRAME_BITS)
+    base = np.concatenate([modulate_frame(b) for b in frame_bits]).astype(np.complex128)
+    out = np.zeros_like(base)
+    for c, p, delay, gain_db in transmitters:
+        x = base.copy()
+        for f in range(frame_bits.shape[0]):
+            x[f * NB_FRAME_SAMPLES:f * NB_FRAME_SAMPLES + NB_NULL] = tii_null([(c, p)])
+        d = int(delay)
+        out[d:] += 10.0 ** (gain_db / 20.0) * x[:x.size - d]
+    return out.astype(np.complex64)
+
+
+def modulate_frame(bits, tii=None):
+    """230400 bits -> complex64[196608] (null + PRS + 75 symbols), unit average symbol power.  tii: the transmitters whose
+    identification the null symbol carries (tii_null); None = a null symbol of zeros."""
     car, prs = _tables()
     bits = np.asarray(bits, np.uint8).reshape(75, NB_SYM_BITS)
     out = np.zeros(NB_FRAME_SAMPLES, np.complex64)
+    if tii is not None:
+        out[:NB_NULL] = tii_null(tii)
     z = prs.copy()                       # indexed k+768
     pos = NB_NULL
     scale = NB_FFT / np.sqrt(NB_CARRIERS)
