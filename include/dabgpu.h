@@ -28,7 +28,10 @@
  *     them (or two contexts, as the host mirror uses: one for OFDM_Demod, one for
  *     BasicRadio).
  *   - soft bits are int8: +127 = logical 1, -127 = logical 0, 0 = erased
- *     (`viterbi_bit_t`, /root/reference/src/radio_block.h:19).
+ *     (`viterbi_bit_t`, /root/reference/src/radio_block.h:19).  They are
+ *     level-free: scaling cf32 samples of unit mean power by 2^k leaves every
+ *     soft bit unchanged for -52 <= k <= 56 (measured; the quantiser's 1e-30
+ *     floor and float32's range end it).
  *   - the library REQUIRES a gfx950 device for everything except the table
  *     getters; there is no CPU fallback.
  */
@@ -274,6 +277,13 @@ int dabgpu_get_iq_format(const dabgpu_ctx *ctx);
 /* freq_offset  [n_frames] correction in cycles/sample applied as               */
 /*              x[n]*exp(+j*2*pi*f*n) (the sum the reference shows as           */
 /*              GetNetFrequencyOffset(), src/render_radio_block.cpp:204).       */
+/*              Exactly: f is quantised to a 32-bit phase step                  */
+/*              dphi = llrint(f*2^32) mod 2^32 (ties to even), and sample n,    */
+/*              counted from the frame's first sample (n = 0 at the PRS         */
+/*              prefix, prefixes included), is multiplied by                    */
+/*              exp(+j*2*pi*frac(n*dphi/2^32)).  The same holds for the stream  */
+/*              states' fine + coarse offset (added in float32) and an acquired */
+/*              frame's freq_offset.                                            */
 /*              NULL = no correction.                                           */
 /* soft         [n_frames][230400] int8 (frame bits in transmission order)      */
 /* cyc          optional [n_frames][76] cf32: cyclic-prefix correlations        */
