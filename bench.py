@@ -22,9 +22,13 @@ The IQ / soft-bit buffers are what the library gives any caller: ONE dabgpu_allo
 (`config.buffer_placement` = its report).  `decoder.roofline` = the channel decoder against its own bounds (forward pass:
 VALU issue; traceback: HBM), from the library's HIP events between its kernels during the timed steps.
 
-Everything measured AFTER the timed region -- that leg, the sustained leg, the FFT stage, BASELINE configs 2 and 3 (one
-ensemble), the host-fed figures, unaligned captures, the CPU baseline -- lives in bench_legs.py and runs on rank 0 of a
-one-GPU run (`--legs all` forces it elsewhere, `--legs none` skips it).
+A plain run does what `value` needs and nothing else: set-up (buffers, input, acquisition, the fine loop settled), the
+warm-up steps, the timed steps, `--dump-outputs` if given, the line.  Everything else runs only with `--full`: the mover
+ceiling (roofline.mover_*, a run of its own before acquisition), the fine loop's residual against the channel's offsets,
+the check of the timed step's FIBs and sub-channel bytes against the transmitted multiplexes (fic_bit_exact /
+msc_bit_exact), and the legs measured AFTER the timed region -- that leg, the sustained leg, the FFT stage, BASELINE
+configs 2 and 3 (one ensemble), the host-fed figures, unaligned captures, the CPU baseline -- which live in bench_legs.py
+and run on rank 0 of a one-GPU run (`--legs all` forces them elsewhere, `--legs none` skips them).
 
 Ensembles shard across GPUs with no data-path collective (weak scaling: 64 per rank; global ensemble ids
 `id % world == rank`).  Prints ONE JSON line on rank 0.
@@ -154,12 +158,15 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=256, help="consecutive frames per ensemble per step (multiple of 4)")
     ap.add_argument("--unique", type=int, default=8, help="distinct synthetic multiplexes generated on the host")
     ap.add_argument("--snr", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not only what `value` needs: the mover ceiling, the fine loop's residual, "
+                         "the timed outputs against the transmitted multiplexes, and the legs (--legs); off: a plain run")
     ap.add_argument("--legs", choices=["auto", "all", "none"], default="auto",
-                    help="the measurements after the timed region (bench_legs.py): auto = all of them on a one-GPU run, none of "
-                         "them when world > 1 (ranks 1..N-1 would idle in a barrier while rank 0 works for ~30 s)")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU baseline budget, both implementations together (0 = skip)")
+                    help="with --full, the measurements after the timed region (bench_legs.py): auto = all of them on a one-GPU "
+                         "run, none of them when world > 1 (ranks 1..N-1 would idle in a barrier while rank 0 works for ~30 s)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU baseline budget (--full), both implementations together (0 = skip)")
     ap.add_argument("--sustained-seconds", type=float, default=3.0,
-                    help="length of the `sustained` leg: the same step repeated for this long, so that the package's "
+                    help="length of the `sustained` leg (--full): the same step repeated for this long, so that the package's "
                          "power-limited steady state is in the record (0 = skip)")
     for leg, what in (("fft-stage", "the unfused FFT-stage measurement"), ("selective", "the selective-soft-output measurement"),
                       ("closed-loop", "the unaligned-capture / tracking measurement"), ("sustained", "the sustained leg"),
@@ -169,7 +176,7 @@ def parse_args(argv=None):
                       ("host-mirror", "the C++ host mirror end to end (dab_host_demo over three DAB+ services)"),
                       ("traffic", "measuring roofline.traffic now (two rocprofv3 --pmc child processes, ~20 s); the tracked figure "
                                   "of profiles/pmc_traffic.json is reported instead")):
-        ap.add_argument("--no-" + leg, action="store_true", help="skip " + what)
+        ap.add_argument("--no-" + leg, action="store_true", help="with --full, skip " + what)
     ap.add_argument("--decoder", choices=["auto", "lane", "wave"], default="auto",
                     help="which kernels decode (dabgpu_cfg.flags; results are identical): auto = by batch size, the library's default "
                          "(codeword-per-lane from 24 576 codewords per launch: the default shape); lane / wave pin one (tests: "
@@ -186,6 +193,8 @@ def parse_args(argv=None):
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.legs == "all" and not args.full:
+        raise SystemExit("--legs all needs --full (a plain run measures the timed step alone)")
     return args
 
 
@@ -236,7 +245,7 @@ def main():
     dist_world = dist.get_world_size() if dist is not None else 1
     if dist_world != world:
         raise SystemExit("process group has %d ranks, WORLD_SIZE says %d" % (dist_world, world))
-    run_legs = args.legs == "all" or (args.legs == "auto" and world == 1)
+    run_legs = args.full and (args.legs == "all" or (args.legs == "auto" and world == 1))
 
     E, F = args.ensembles, args.frames
     n_frames = E * F
@@ -278,17 +287,19 @@ def main():
 
     # ---- the ceiling the front end is held against: a pure data mover of its own geometry on these very buffers (the
     # same runs, loads, stores and occupancy, no arithmetic; it leaves meaningless bytes in `soft`, which every later call
-    # overwrites).  Untimed set-up.
-    mover_ev = []
-    for i in range(2 + 5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ctx.mover_frames_dev(d_iq, L, n_frames, soft.data_ptr(), True, stream)      # with_prefixes: what the timed launch reads
-        e1.record()
-        if i >= 2:
-            mover_ev.append((e0, e1))
-    torch.cuda.synchronize()
-    mover_ms = float(np.mean([a.elapsed_time(b) for a, b in mover_ev]))
+    # overwrites).  Untimed set-up, --full only.
+    mover_ms = None
+    if args.full:
+        mover_ev = []
+        for i in range(2 + 5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ctx.mover_frames_dev(d_iq, L, n_frames, soft.data_ptr(), True, stream)      # with_prefixes: what the timed launch reads
+            e1.record()
+            if i >= 2:
+                mover_ev.append((e0, e1))
+        torch.cuda.synchronize()
+        mover_ms = float(np.mean([a.elapsed_time(b) for a, b in mover_ev]))
 
     # ---- acquisition, untimed: whole-carrier offset of every stream from its first PRS, then the fine loop settles
     ctx.streams_reset(E)
@@ -317,8 +328,9 @@ def main():
     for k in range(4):
         ctx.ofdm_demod_streams_dev(d_iq, L, E, F, BETA, soft.data_ptr(), None, None, stream)
     torch.cuda.synchronize()
-    net = np.array([ctx.get_stats(s).net_freq_offset for s in range(E)])
-    loop_residual = float(np.abs(net + cfo_true).max() * 2048.0)            # carriers; reported, not used
+    if args.full:
+        net = np.array([ctx.get_stats(s).net_freq_offset for s in range(E)])
+        loop_residual = float(np.abs(net + cfo_true).max() * 2048.0)        # carriers; reported, not used
 
     def barrier():
         torch.cuda.synchronize()
@@ -338,21 +350,23 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
 
-    # ---- correctness of what was just timed (outside the timed region) ----
-    fib_h, crc_h, msc_h = fib.cpu().numpy(), crc.cpu().numpy(), msc.cpu().numpy()
-    fic_ok = bool(crc_h.all())
-    msc_ok = True
-    for s in range(E):
-        e = ens[s]
-        for f in range(F):
-            fic_ok &= bool((fib_h[s * F + f] == e.fibs[f % 4]).all())
-        # logical frame finished by CIF t was transmitted from CIF t-15 (cyclic 16-CIF multiplex);
-        # with warm history every entry is valid
-        for t in range(0 if args.warmup + args.steps >= 2 else 15, F * 4):
-            msc_ok &= bool((msc_h[s, t] == e.msc_bytes[(t - 15) % 16]).all())
+    # ---- correctness of what was just timed (outside the timed region; --full) ----
+    checks = []
+    if args.full:
+        fib_h, crc_h, msc_h = fib.cpu().numpy(), crc.cpu().numpy(), msc.cpu().numpy()
+        fic_ok = bool(crc_h.all())
+        msc_ok = True
+        for s in range(E):
+            e = ens[s]
+            for f in range(F):
+                fic_ok &= bool((fib_h[s * F + f] == e.fibs[f % 4]).all())
+            # logical frame finished by CIF t was transmitted from CIF t-15 (cyclic 16-CIF multiplex);
+            # with warm history every entry is valid
+            for t in range(0 if args.warmup + args.steps >= 2 else 15, F * 4):
+                msc_ok &= bool((msc_h[s, t] == e.msc_bytes[(t - 15) % 16]).all())
+        checks = [fic_ok, msc_ok]
     elapsed_rank = elapsed
-    elapsed, frames_total, (fic_ok, msc_ok) = reduce_report(dist, red_dev, elapsed, n_frames * args.steps,
-                                                            [fic_ok, msc_ok])
+    elapsed, frames_total, checks = reduce_report(dist, red_dev, elapsed, n_frames * args.steps, checks)
 
     ofdm_call_ms = float(np.mean([a.elapsed_time(b) for a, b in ofdm_ev]))     # front-end call: kernel + state update
     # every timed step's own device time (front-end call + decode call), so that the spread inside a run -- and, over the
@@ -367,10 +381,11 @@ def main():
     ctx.set_timing(False)
     achieved = A_OFDM * n_frames / (ofdm_ms * 1e-3) / 1e9
     # one row per rank, so that an imbalance between the GPUs of a node is visible in the line
-    # (+ what the allocator gave this rank and the mover's time on it: a slow rank of an 8-GPU node explains itself)
+    # (+ what the allocator gave this rank and, with --full, the mover's time on it: a slow rank of an 8-GPU node explains
+    # itself)
     per_rank = gather_per_rank(dist, red_dev, [n_frames * args.steps / elapsed_rank, ofdm_ms, dec_ms, dev_index,
-                                               achieved / HBM_PEAK_GBS, mover_ms, rep.method, rep.fallback_reason,
-                                               rep.pair_over_same_domain, rep.n_domains])
+                                               achieved / HBM_PEAK_GBS, rep.method, rep.fallback_reason,
+                                               rep.pair_over_same_domain, rep.n_domains] + ([mover_ms] if args.full else []))
     collective = "none (one rank)"
     if dist is not None:
         collective = "nccl (RCCL)" if backend == "nccl" else backend + " (test ranks sharing a GPU: NOT RCCL)"
@@ -378,6 +393,18 @@ def main():
         # away BEFORE anything long runs on rank 0, so that no rank sits in a collective while another works
         dist.barrier()
         dist.destroy_process_group()
+
+    def rank_row(i, r):
+        row = {"rank": i, "frames_per_s": r[0], "front_end_kernel_ms": r[1], "decoder_ms": r[2], "device": int(r[3]),
+               "roofline_frac": r[4]}
+        if args.full:
+            row.update({"mover_same_geometry_ms": r[9],
+                        "mover_source": "dabgpu_mover_frames_dev on this rank's timed buffers, mean of 5 launches after 2 (set-up, untimed)",
+                        "kernel_over_mover": r[1] / r[9] if r[9] > 0 else None})
+        row["buffer_placement"] = {"method": "domain-aware pair" if int(r[5]) == 1 else "plain hipMalloc pair",
+                                   "fallback_reason": None if int(r[5]) == 1 else dabgpu.PLAIN_REASONS.get(int(r[6]), str(int(r[6]))),
+                                   "pair_over_same_domain": round(r[7], 3), "domains_seen": int(r[8])}
+        return row
 
     if rank == 0:
         if args.dump_outputs:
@@ -409,14 +436,7 @@ def main():
         out = {
             "metric": "DAB Mode-I frames/sec (OFDM+Viterbi)", "value": value, "unit": "frames/s",
             "n_gpus": world, "world": dist_world, "collective_backend": collective,
-            "per_rank": [{"rank": i, "frames_per_s": r[0], "front_end_kernel_ms": r[1], "decoder_ms": r[2], "device": int(r[3]),
-                          "roofline_frac": r[4], "mover_same_geometry_ms": r[5],
-                          "mover_source": "dabgpu_mover_frames_dev on this rank's timed buffers, mean of 5 launches after 2 (set-up, untimed)",
-                          "kernel_over_mover": r[1] / r[5] if r[5] > 0 else None,
-                          "buffer_placement": {"method": "domain-aware pair" if int(r[6]) == 1 else "plain hipMalloc pair",
-                                               "fallback_reason": None if int(r[6]) == 1 else dabgpu.PLAIN_REASONS.get(int(r[7]), str(int(r[7]))),
-                                               "pair_over_same_domain": round(r[8], 3), "domains_seen": int(r[9])}}
-                         for i, r in enumerate(per_rank)],
+            "per_rank": [rank_row(i, r) for i, r in enumerate(per_rank)],
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "step_ms": {"min": float(step_dev_ms.min()), "median": float(np.median(step_dev_ms)), "max": float(step_dev_ms.max()),
@@ -435,8 +455,7 @@ def main():
                        "sharding": "independent ensembles per rank (global id % world == rank), no data-path collective",
                        "buffer_placement": placement},
             "x_realtime": value / REALTIME_FPS,
-            "fic_bit_exact": fic_ok, "msc_bit_exact": msc_ok,
-            "fine_loop_residual_carriers": loop_residual,
+            "full": args.full,
             "value_own_estimator": None,
             "roofline": {"bound": "hbm", "kernel": "dabk::ofdm_wave_kernel<false,false,false,true> (fused A2..A6, cyclic-prefix correlations out)",
                          "achieved": achieved,
@@ -448,13 +467,6 @@ def main():
                                                    "SURVEY 8(d)'s A_ofdm (1 803 264 B: + the null symbol, which is never read) the same "
                                                    "launch would read achieved_on_survey_bytes",
                          "achieved_on_survey_bytes": A_OFDM_SURVEY * n_frames / (ofdm_ms * 1e-3) / 1e9,
-                         # the practical ceiling: dabgpu_mover_frames_dev on the timed buffers -- the kernel's loads, stores,
-                         # runs and occupancy without its arithmetic
-                         "mover_same_geometry_ms": mover_ms,
-                         "mover_same_geometry_GBps": A_OFDM * n_frames / (mover_ms * 1e-3) / 1e9,
-                         # this box's ceiling for this read / write mix, on the same scale as `frac`
-                         "box_mover_frac": A_OFDM * n_frames / (mover_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_over_mover": ofdm_ms / mover_ms,
                          "frac_own_estimator": None},
             # the channel decoder is integer add-compare-select work, not bandwidth: report ACS/s
             "decoder": {"fic_and_msc_ms": dec_ms, "acs_per_s": (ACS_FIC + ACS_MSC64) * n_frames / (dec_ms * 1e-3),
@@ -465,6 +477,16 @@ def main():
                         "roofline": None},
             "cpu_baseline": None,
         }
+        if args.full:
+            out.update({"fic_bit_exact": checks[0], "msc_bit_exact": checks[1], "fine_loop_residual_carriers": loop_residual})
+            out["roofline"].update({
+                # the practical ceiling: dabgpu_mover_frames_dev on the timed buffers -- the kernel's loads, stores,
+                # runs and occupancy without its arithmetic
+                "mover_same_geometry_ms": mover_ms,
+                "mover_same_geometry_GBps": A_OFDM * n_frames / (mover_ms * 1e-3) / 1e9,
+                # this box's ceiling for this read / write mix, on the same scale as `frac`
+                "box_mover_frac": A_OFDM * n_frames / (mover_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "kernel_over_mover": ofdm_ms / mover_ms})
         import bench_legs
         if dec_parts is not None:
             dr = bench_legs.decoder_roofline(dec_parts, n_frames, [(4 * n_frames, 774), (4 * n_frames, 1542)])
@@ -485,6 +507,8 @@ def main():
                                 cfo_true=cfo_true, fib_h=fib_h, crc_h=crc_h, msc_h=msc_h, ms_per_step=elapsed / args.steps * 1e3,
                                 dev_index=dev_index)
             bench_legs.run(B, out)
+        elif not args.full:
+            out["legs"] = "skipped (a plain run: --full runs them)"
         else:
             out["legs"] = "skipped (world > 1: `--legs all` runs them on rank 0 after the process group is gone)" if world > 1 \
                 else "skipped (--legs none)"

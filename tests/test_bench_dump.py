@@ -49,3 +49,11 @@ def test_steps_set_the_timed_steps():
     assert bench.parse_args(["--steps", "7", "--warmup", "0"]).steps == 7
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
+
+
+def test_full_is_off_by_default_and_the_legs_need_it():
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--legs", "none"]).legs == "none"
+    assert bench.parse_args(["--full", "--legs", "all"]).legs == "all"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--legs", "all"])

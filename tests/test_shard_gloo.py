@@ -60,6 +60,7 @@ import json
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,7 +69,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run_bench(nproc, extra_env=None, ensembles=4, frames=16, more=()):
     env = dict(os.environ)
     env.update(extra_env or {})
-    args = ["--ensembles", str(ensembles), "--frames", str(frames), "--steps", "2", "--warmup", "1", "--legs", "none"] + list(more)
+    args = ["--ensembles", str(ensembles), "--frames", str(frames), "--steps", "2", "--warmup", "1", "--full", "--legs", "none"] + list(more)
     if nproc == 1 and not (extra_env or {}).get("DABGPU_DIST_FORCE"):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args
     else:
@@ -86,7 +87,7 @@ def _plain_bench(gpus, env_extra, timeout=900):
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     env.update(env_extra)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--ensembles", "4", "--frames", "16", "--steps", "2",
-           "--warmup", "1"]            # (default --legs auto: none of the post-timing legs run when world > 1)
+           "--warmup", "1", "--full"]  # (default --legs auto: none of the post-timing legs run when world > 1)
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
 
 
@@ -200,7 +201,7 @@ def test_bench_line_keeps_the_contract():
     baseline of a bounded sample, both fine-frequency loops compared, nothing decoded wrongly."""
     env = dict(os.environ)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--ensembles", "4", "--frames", "16", "--steps", "3", "--warmup", "1",
-           "--cpu-seconds", "2", "--sustained-seconds", "0.2"]
+           "--full", "--cpu-seconds", "2", "--sustained-seconds", "0.2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -270,6 +271,38 @@ def test_bench_line_keeps_the_contract():
     assert cl["tracking"]["streams_tracking"] == 4 and cl["tracking"]["frames_desync_total"] == 0
 
 
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_timed_step_alone(tmp_path):
+    """Without --full a run sets up, warms up, times its steps and prints the line: the headline fields mean what they mean
+    in a full run, and nothing that takes a run or a check of its own is in it (the mover ceiling, the outputs against the
+    transmitted multiplexes, the fine loop's residual, the legs).  Its last step computes what the same arguments with
+    --full compute: the dumped outputs are identical."""
+    def run(*more):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--ensembles", "4", "--frames", "16", "--steps", "3", "--warmup", "1"]
+        r = subprocess.run(cmd + list(more), capture_output=True, text=True, timeout=900, env=dict(os.environ), cwd=ROOT)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    j = run("--dump-outputs", str(tmp_path / "plain"))
+    assert j["metric"].startswith("DAB Mode-I frames/sec") and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f32" and j["full"] is False and j["steps"] == 3 and j["warmup"] == 1 and j["n_gpus"] == 1
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 - 64) < 1e-6 * 64
+    ro = j["roofline"]
+    assert 0 < ro["frac"] < 1 and ro["frames_per_launch"] == 64 and ro["avg_launch_ms"] < j["ms_per_step"]
+    assert not [k for k in ro if "mover" in k] and not [k for k in j["per_rank"][0] if "mover" in k]
+    for k in ("fic_bit_exact", "msc_bit_exact", "fine_loop_residual_carriers", "with_decision_directed_loop", "sustained",
+              "roofline_fft_stage", "selective_soft_output", "single_ensemble", "host_fed", "host_mirror_end_to_end", "closed_loop"):
+        assert k not in j, k
+    assert j["cpu_baseline"] is None and j["value_own_estimator"] is None and j["legs"].startswith("skipped (a plain run")
+    full = run("--full", "--legs", "none", "--dump-outputs", str(tmp_path / "full"))
+    assert full["full"] is True and full["fic_bit_exact"] is True and full["msc_bit_exact"] is True
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "soft_bits.npy" in names
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)), n
+
+
 def test_self_launch_parent_never_loads_torch():
     """`python bench.py --gpus N` without a launcher: the parent starts the N ranks as a fresh `torch.distributed.run` child
     and relays its line.  It must reach that point -- and end -- without torch (let alone torch.cuda) in the process: a
@@ -315,7 +348,7 @@ def test_bench_line_carries_the_decoder_roofline():
     Run at a small shape with the lane kernels pinned (--decoder lane; the default shape takes them by itself) and every leg
     but the traffic measurement switched off."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--ensembles", "4", "--frames", "16", "--steps", "3", "--warmup", "1",
-           "--decoder", "lane", "--legs", "all", "--cpu-seconds", "0", "--sustained-seconds", "0", "--no-dd-leg", "--no-fft-stage",
+           "--decoder", "lane", "--full", "--legs", "all", "--cpu-seconds", "0", "--sustained-seconds", "0", "--no-dd-leg", "--no-fft-stage",
            "--no-selective", "--no-closed-loop", "--no-single-ensemble", "--no-host-fed", "--no-host-mirror"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ), cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -5,7 +5,7 @@ tag=${1:-r06}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 o=$root/gpurun_out/$tag; mkdir -p $o
 cd $root
-python3 bench.py > $o/bench.json 2> $o/bench.err                                  # the default line, every leg
+python3 bench.py --full > $o/bench.json 2> $o/bench.err                           # the full line, every leg
 tail -c 1500 $o/bench.json
 # per-kernel durations of the timed steps alone (no leg after the timed region launches the same kernels)
 tools/prof.sh $tag --legs none > $o/prof.log 2>&1
