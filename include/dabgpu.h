@@ -885,6 +885,107 @@ int dabgpu_tii_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_str
 int dabgpu_tii_decode(const dabgpu_tii_acc *acc, const dabgpu_tii_cfg *cfg, dabgpu_tii_entry *out, int max_out);
 
 /* ------------------------------------------------------------------------ */
+/* Channel impulse response (CIR, Mode I) from the phase reference symbol:    */
+/* where the paths of a single-frequency network arrive and how strongly.     */
+/*                                                                            */
+/* Per frame the 2048 samples [504, 2552) after the first sample of the PRS   */
+/* prefix (the front end's window) are corrected in frequency as the TII      */
+/* calls do (nco(n, round(f 2^32)), n from the window start) and transformed  */
+/* (X, unnormalised).  Over the 1536 carriers k = -768..768, k != 0, with the */
+/* Hann taper w(k) = 0.5 + 0.5 cos(pi k / 769), S = sum of w (= 768) and the   */
+/* PRS R (dabgpu_get_prs_reference):                                          */
+/*   h[n]       = sqrt(1536) / (2048 S) sum_k w(k) X[k] conj R[k]             */
+/*                exp(+2 pi i k n / 2048),  n = 0..2047                       */
+/*   tap[n]     = |h[n]|^2  (a path of gain g at integer delay d, unit mean    */
+/*                sample power: tap[d] = |g|^2)                               */
+/*   carrier[i] = (1536 / 2048^2) |X[k]|^2, untapered, i = 0..1535 for         */
+/*                k = -768..-1, 1..768 (1.0 on a flat unit-gain channel)       */
+/* Tap n is the delay from the window start; n >= 1024 reads as n - 2048      */
+/* (arrivals before the timing reference).  The taper keeps the sidelobes of   */
+/* a path off the sample grid from reading as echoes.                          */
+/* The calls ADD each stream's frames, in frame order, to d_acc[stream] (zero */
+/* it to start; no atomics: the sums repeat bit for bit, with or without       */
+/* d_frame).  d_frame, when not NULL, receives every frame's own record        */
+/* ([n_streams][frames_per_stream], frames = 1, or an all-zero record for a    */
+/* skipped slot); NULL needs no scratch from the caller.  d_iq is read in the  */
+/* context's sample format (dabgpu_set_iq_format); the records are the same    */
+/* for every format holding the same values.                                   */
+/*                                                                            */
+/* dabgpu_cir_frames_dev    frame (s, f) has its PRS prefix at d_iq +         */
+/*            (s*frames_per_stream + f)*frame_stride (even and >= 2552 when    */
+/*            there is more than one frame); the caller guarantees the 2552    */
+/*            samples from every prefix are readable.  d_freq_offset           */
+/*            [n_frames] cycles/sample, whole-carrier part included, as        */
+/*            dabgpu_ofdm_demod_frames_dev takes it, or NULL: each stream's     */
+/*            fine + coarse offset from the context's stream states            */
+/*            (DABGPU_ERR_ARG without stream states, DABGPU_ERR_CAPACITY for   */
+/*            more streams than there are states).                            */
+/* dabgpu_cir_acquired_dev  the slots dabgpu_acquire_dev / _tracked_dev wrote  */
+/*            ([n_streams][max_frames]) with their start and freq_offset; the  */
+/*            PRS prefix is at start + timing_margin (0..504).  Counted:       */
+/*            flags == 3 and start + timing_margin >= 0; other slots add       */
+/*            nothing.                                                        */
+/* dabgpu_cir_analyse       host only (no context, no device), on            */
+/*            p[n] = tap[n] / frames:                                         */
+/*            floor = median(p) / m(F), F = frames, m(F) = 1 - 1/(3F) +         */
+/*              8/(405 F^2) (the median of a mean of F unit exponentials; the  */
+/*              median is the mean of the 1024th and 1025th smallest p);       */
+/*            peak = max p.  Tap n (indices circular) is a path when           */
+/*              p[n] > p[n-1], p[n] >= p[n+1], p[n] >= floor 10^(min_snr_db/10) */
+/*              and p[n] >= peak 10^(-range_db/10).  Its delay is the signed   */
+/*              tap plus 0.5 (L- - L+) / (L- - 2 L0 + L+) on                  */
+/*              L = 10 log10(max(p, 1e-30)); level_db = 10 log10(p[n] / peak), */
+/*              snr_db = 10 log10(p[n] / floor); BEYOND_GUARD when             */
+/*              delay - first_delay > 504.  Paths by delay ascending.          */
+/*            report (may be NULL): rms_delay_spread weighted by the paths'    */
+/*              p (0 for one path); guard_ratio_db = 10 log10 of the power of  */
+/*              the paths within 504 samples of the first over the power of    */
+/*              those beyond (+inf when none is beyond); with no paths every   */
+/*              field after peak is 0.  Returns the number of paths (none for   */
+/*              frames == 0 or floor <= 0; nothing written beyond max_out),    */
+/*              DABGPU_ERR_ARG for a NULL acc, a NULL out with max_out > 0,    */
+/*              max_out < 0 or a cfg value that is not finite.  cfg NULL = the */
+/*              defaults.                                                     */
+/* Refusals (DABGPU_ERR_ARG / _CAPACITY) enqueue nothing and leave the outputs   */
+/* untouched.                                      */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_cir_acc {   /* DEVICE memory, 14 352 bytes: a stream's sums, or one frame's record */
+    float tap[2048];              /* sum over frames of |h[n]|^2                                         */
+    float carrier[1536];          /* sum over frames of the normalised |X_k|^2                           */
+    int32_t frames;               /* frames added                                                        */
+    int32_t reserved[3];          /* left as they are by the calls; 0 in per-frame records               */
+} dabgpu_cir_acc;
+
+typedef struct dabgpu_cir_cfg {
+    float min_snr_db;             /* a path stands this far above the noise floor (10.0)      */
+    float range_db;               /* and no further than this below the strongest tap (25.0)  */
+} dabgpu_cir_cfg;
+
+typedef struct dabgpu_cir_report {
+    int32_t frames, n_paths;
+    float floor, peak;            /* per-frame mean tap power: noise floor estimate, strongest tap      */
+    float first_delay, strongest_delay, rms_delay_spread;   /* samples                                   */
+    float guard_ratio_db;         /* power of paths within 504 samples of the first / power beyond      */
+} dabgpu_cir_report;
+
+#define DABGPU_CIR_BEYOND_GUARD 1 /* the path arrives more than 504 samples (the guard interval) after the first */
+typedef struct dabgpu_cir_path {
+    float delay;                  /* samples from the window start, signed, interpolated */
+    float level_db;               /* relative to the strongest tap                       */
+    float snr_db;                 /* relative to the noise floor                         */
+    int32_t flags;                /* DABGPU_CIR_*                                        */
+} dabgpu_cir_path;
+
+void dabgpu_cir_default_cfg(dabgpu_cir_cfg *cfg);
+int dabgpu_cir_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stride, int n_streams, int frames_per_stream,
+                          const float *d_freq_offset, dabgpu_cir_acc *d_frame, dabgpu_cir_acc *d_acc, void *stream);
+int dabgpu_cir_acquired_dev(dabgpu_ctx *ctx, const void *d_iq, size_t stream_stride, int n_streams, int max_frames,
+                            const dabgpu_acquired_frame *d_frames, int timing_margin, dabgpu_cir_acc *d_frame,
+                            dabgpu_cir_acc *d_acc, void *stream);
+int dabgpu_cir_analyse(const dabgpu_cir_acc *acc, const dabgpu_cir_cfg *cfg, dabgpu_cir_report *report,
+                       dabgpu_cir_path *out, int max_out);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

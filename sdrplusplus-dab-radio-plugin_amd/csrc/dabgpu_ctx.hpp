@@ -81,10 +81,10 @@ struct dabgpu_ctx {
     // per sub-channel (validation, grouping, code look-up), ~10 us of host time in front of and between its launches
     std::map<uint64_t, dabapi::DeviceCode *> code_by_descriptor;
     // slots 0..5: staging of the host-pointer entry points; slot 6: the stream / tracked / frame calls' own loop input
-    // (correlations or decision-directed sums); slot 7: the TII calls' per-frame records.  One caller stream at a time per
-    // context (dabgpu.h, conventions).
-    void *d_stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // (correlations or decision-directed sums); slot 7: the TII calls' per-frame records; slot 8: the CIR calls'.  One
+    // caller stream at a time per context (dabgpu.h, conventions).
+    void *d_stage[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t stage_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool timing = false;
     dabapi::Timer timers[4];
     int ofdm_parts_override = 0;

@@ -475,6 +475,30 @@ struct TiiArgs {
 };
 hipError_t launch_tii(const float2 *twiddle, const TiiArgs &a, hipStream_t s, int iq_format);
 
+// ---- channel impulse response from the phase reference symbol (cir_kernels.hip) --------
+// Window: the 2048 samples [504, 2552) after the first sample of the PRS prefix (the front end's).  Hann taper
+// w(k) = 0.5 + 0.5 cos(pi k / 769) over the 1536 carriers, whose sum is exactly 768.
+constexpr int CIR_WIN_BEGIN = 504, CIR_TAPS = 2048, CIR_CARRIERS = 1536;
+struct CirRecord {             // == dabgpu_cir_acc (14 352 bytes): per frame, or a stream's running sums
+    float tap[CIR_TAPS];       // |h[n]|^2
+    float carrier[CIR_CARRIERS];  // (1536 / 2048^2) |X_k|^2, k = -768..-1, 1..768
+    int32_t frames;
+    int32_t reserved[3];
+};
+struct CirArgs {
+    const float2 *iq;          // context's sample format
+    size_t stride;             // frame (frame calls) or stream (acquired calls) stride, complex samples
+    int n_streams, frames_per_stream;
+    const float *freq_offset;  // frame calls: [n_frames] cycles/sample, or nullptr: the stream states
+    const struct StreamState *state;
+    const AcquiredFrame *acq;  // acquired calls: [n_streams][frames_per_stream]
+    int timing_margin;         // acquired calls: PRS prefix = start + timing_margin
+    const int8_t *prs_qt;      // [2048] quarter turns of the PRS per bin, -1 = not a carrier
+    CirRecord *frame;          // [n_frames] per-frame records
+    CirRecord *acc;            // [n_streams] += the stream's frames, in frame order
+};
+hipError_t launch_cir(const float2 *twiddle, const CirArgs &a, hipStream_t s, int iq_format);
+
 // Let every kernel that takes dynamic LDS use the whole 160 KB of a CU: set once per context creation (on the
 // context's device) instead of per launch.
 hipError_t init_viterbi_kernel_attributes();

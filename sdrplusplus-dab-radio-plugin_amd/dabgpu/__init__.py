@@ -48,6 +48,7 @@ EXPORTS = [
     "dabgpu_mer_dev", "dabgpu_channel_ber_dev", "dabgpu_decode_stream_frames_quality",
     "dabgpu_set_iq_format", "dabgpu_get_iq_format",
     "dabgpu_tii_default_cfg", "dabgpu_tii_pattern", "dabgpu_tii_frames_dev", "dabgpu_tii_acquired_dev", "dabgpu_tii_decode",
+    "dabgpu_cir_default_cfg", "dabgpu_cir_frames_dev", "dabgpu_cir_acquired_dev", "dabgpu_cir_analyse",
 ]
 
 ABI_VERSION = 6
@@ -126,6 +127,21 @@ assert TII_ACC_DTYPE.itemsize == 784
 TII_ENTRY_DTYPE = np.dtype([("main_id", np.int32), ("sub_id", np.int32), ("level_db", np.float32), ("flags", np.int32)])
 assert TII_ENTRY_DTYPE.itemsize == 16
 TII_AMBIGUOUS = 1
+#: dabgpu_cir_acc: a stream's channel-impulse-response sums (device memory; zero it to start), or one frame's record
+CIR_ACC_DTYPE = np.dtype([("tap", np.float32, (2048,)), ("carrier", np.float32, (1536,)), ("frames", np.int32),
+                          ("reserved", np.int32, (3,))])
+assert CIR_ACC_DTYPE.itemsize == 14352
+#: dabgpu_cir_report: what cir_analyse found in one accumulator
+CIR_REPORT_DTYPE = np.dtype([("frames", np.int32), ("n_paths", np.int32), ("floor", np.float32), ("peak", np.float32),
+                             ("first_delay", np.float32), ("strongest_delay", np.float32), ("rms_delay_spread", np.float32),
+                             ("guard_ratio_db", np.float32)])
+assert CIR_REPORT_DTYPE.itemsize == 32
+#: dabgpu_cir_path: one path found by cir_analyse
+CIR_PATH_DTYPE = np.dtype([("delay", np.float32), ("level_db", np.float32), ("snr_db", np.float32), ("flags", np.int32)])
+assert CIR_PATH_DTYPE.itemsize == 16
+CIR_BEYOND_GUARD = 1
+#: Mode I sample rate, samples per microsecond
+SAMPLES_PER_US = 2.048
 
 
 def mer_db(rec):
@@ -203,6 +219,33 @@ def tii_decode(acc, min_level_db=3.0, max_out=24 * 70):
     if n < 0:
         raise DabGpuError(n, "dabgpu_tii_decode")
     return out[:min(n, max_out)].copy()
+
+
+class CirCfg(C.Structure):
+    _fields_ = [("min_snr_db", C.c_float), ("range_db", C.c_float)]
+
+
+def cir_analyse(acc, min_snr_db=10.0, range_db=25.0, max_out=64):
+    """Paths in one CIR_ACC_DTYPE accumulator (a host copy) -> (report CIR_REPORT_DTYPE, paths CIR_PATH_DTYPE array by
+    delay ascending) (dabgpu_cir_analyse: host only, no GPU)."""
+    acc = np.ascontiguousarray(np.asarray(acc, CIR_ACC_DTYPE).reshape(()))
+    cfg = CirCfg(min_snr_db, range_db)
+    report = np.zeros((), CIR_REPORT_DTYPE)
+    out = np.zeros(max(max_out, 1), CIR_PATH_DTYPE)
+    n = lib().dabgpu_cir_analyse(_p(acc), C.byref(cfg), _p(report), _p(out), max_out)
+    if n < 0:
+        raise DabGpuError(n, "dabgpu_cir_analyse")
+    return report[()], out[:min(n, max_out)].copy()
+
+
+def samples_to_us(samples):
+    """Delay in samples (2.048 MHz, Mode I) -> microseconds."""
+    return np.asarray(samples, np.float64) / SAMPLES_PER_US
+
+
+def samples_to_km(samples):
+    """Delay in samples -> the extra path length it stands for, km (light travels 0.299792458 km per microsecond)."""
+    return samples_to_us(samples) * 0.299792458
 
 
 def soft_selection(subchannels, with_fic=True):
@@ -333,6 +376,11 @@ def load_library(path):
     L.dabgpu_tii_frames_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp]
     L.dabgpu_tii_acquired_dev.argtypes = [vp, vp, sz, i, i, vp, i, vp, vp, vp]
     L.dabgpu_tii_decode.argtypes = [vp, C.POINTER(TiiCfg), vp, i]
+    L.dabgpu_cir_default_cfg.restype = None
+    L.dabgpu_cir_default_cfg.argtypes = [C.POINTER(CirCfg)]
+    L.dabgpu_cir_frames_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp]
+    L.dabgpu_cir_acquired_dev.argtypes = [vp, vp, sz, i, i, vp, i, vp, vp, vp]
+    L.dabgpu_cir_analyse.argtypes = [vp, C.POINTER(CirCfg), vp, vp, i]
     return L
 
 
@@ -807,6 +855,21 @@ class Context:
         (PRS prefix at start + timing_margin) whose null window lies inside the capture."""
         _check(self._lib.dabgpu_tii_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, timing_margin,
                                                  d_frame, d_acc, stream), "dabgpu_tii_acquired_dev")
+
+    def cir_frames_dev(self, d_iq, frame_stride, n_streams, frames_per_stream, d_acc, d_freq_offset=None, d_frame=None,
+                       stream=None):
+        """Channel impulse response of frames (s, f) whose PRS prefix is at d_iq + (s*frames_per_stream + f)*frame_stride
+        (the 2552 samples from it are read): d_acc [n_streams] (CIR_ACC_DTYPE) += the streams' frames; d_frame, if given,
+        every frame's record.  d_freq_offset None = the stream states' fine + coarse offsets."""
+        _check(self._lib.dabgpu_cir_frames_dev(self._h, d_iq, frame_stride, n_streams, frames_per_stream, d_freq_offset,
+                                               d_frame, d_acc, stream), "dabgpu_cir_frames_dev")
+
+    def cir_acquired_dev(self, d_iq, stream_stride, n_streams, max_frames, d_frames, d_acc, timing_margin=64, d_frame=None,
+                         stream=None):
+        """Channel impulse response of the locked, whole frames of acquire_dev / ofdm_demod_tracked_dev slots (PRS prefix
+        at start + timing_margin, inside the capture)."""
+        _check(self._lib.dabgpu_cir_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, timing_margin,
+                                                 d_frame, d_acc, stream), "dabgpu_cir_acquired_dev")
 
     def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
         """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).
