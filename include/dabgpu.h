@@ -476,6 +476,11 @@ int dabgpu_fft_symbols(dabgpu_ctx *ctx, const float *iq, size_t frame_stride, in
 /* out[f].peak_to_mean     impulse-response peak / mean power (threshold it    */
 /*               like impulse_peak_threshold_db)                               */
 /* out[f].coarse_peak_to_mean  same for the coarse correlation                 */
+/* A window whose correlation (or impulse response) is zero everywhere -- an   */
+/* all-zero window -- gives coarse_carriers 0 (time_offset 0) and ratio 0, so   */
+/* it fails every positive threshold and never carries a NaN into a stream's   */
+/* state.  The results are the same bit for bit for any 2^k scaling of the     */
+/* input: the correlations are normalised by a power of two before squaring.   */
 /* ------------------------------------------------------------------------ */
 typedef struct dabgpu_sync_result {
     int32_t coarse_carriers;

@@ -731,11 +731,18 @@ void oracle_sync_prs_ex(const float *sym, float freq_offset, int max_coarse, int
         const float re = R[2 * b], im = R[2 * b + 1];
         qt[b] = (re == 0.f && im == 0.f) ? -1 : (re > 0.5f ? 0 : (im > 0.5f ? 1 : (re < -0.5f ? 2 : 3)));
     }
+    /* a power-of-two scale brings the window's largest component to [0.5, 1): exact, so every result is the same for any
+       2^k scaling of the input, and |D_k|^2 (~ |x|^8) cannot overflow */
+    float amax = 0.0f;
+    for (int i = 2 * DAB_NB_CP; i < 2 * DAB_NB_SYM_PERIOD; i++) amax = fmaxf(amax, fabsf(sym[i]));
+    int e;
+    frexpf(amax, &e);
+    const float scale = ldexpf(1.0f, -(e < -126 ? -126 : (e > 126 ? 126 : e)));
     for (int n = 0; n < DAB_NB_FFT; n++) {
         const uint32_t ph = (uint32_t)n * (uint32_t)dphi;
         const double ang = 2.0 * M_PI * ((double)ph / 4294967296.0);
         const float wr = (float)cos(ang), wi = (float)sin(ang);
-        const float xr = sym[2 * (DAB_NB_CP + n)], xi = sym[2 * (DAB_NB_CP + n) + 1];
+        const float xr = sym[2 * (DAB_NB_CP + n)] * scale, xi = sym[2 * (DAB_NB_CP + n) + 1] * scale;
         y[2 * n] = xr * wr - xi * wi;
         y[2 * n + 1] = xr * wi + xi * wr;
     }
@@ -767,6 +774,7 @@ void oracle_sync_prs_ex(const float *sym, float freq_offset, int max_coarse, int
         sum += m;
         if (m > best) { best = m; best_k = k; }
     }
+    if (!(sum > 0.0f)) { best_k = 0; best = 0.0f; sum = 1.0f; }     /* all |D_k|^2 = 0 (a zero window): k = 0, ratio 0 */
     *k_out = best_k;
     *coarse_peak_to_mean = best / (sum / (float)(2 * max_coarse + 1));
     /* fine time: |IFFT(Z)| == |FFT(conj Z)| index for index */
@@ -800,7 +808,7 @@ void oracle_sync_prs_ex(const float *sym, float freq_offset, int max_coarse, int
         if (sc > pk) { pk = sc; pi = n; }
     }
     const float peak = M[pi], mean = tot / (float)DAB_NB_FFT;
-    if (first_path_rel > 0.0f) {
+    if (first_path_rel > 0.0f && tot > 0.0f) {                    /* (all taps 0, a zero window: tap 0, ratio 0) */
         const float a = first_path_rel * peak, b = 16.0f * mean;
         const float thr = a > b ? a : b;
         for (int d = DAB_NB_CP; d >= 1; d--)
@@ -808,6 +816,6 @@ void oracle_sync_prs_ex(const float *sym, float freq_offset, int max_coarse, int
     }
     free(M);
     *toff = (pi < DAB_NB_FFT / 2) ? pi : pi - DAB_NB_FFT;
-    *peak_to_mean = peak / mean;
+    *peak_to_mean = tot > 0.0f ? peak / mean : 0.0f;
     free(y); free(X); free(Q); free(Z); free(H);
 }

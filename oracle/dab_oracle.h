@@ -144,7 +144,9 @@ void oracle_sync_prs(const float *sym, float freq_offset, int max_coarse, int32_
  *   the peak is the first maximum of the score; *peak_to_mean = |h[peak]|^2 / mean (unweighted).
  *   first_path_rel > 0: the EARLIEST tap within 504 samples before the peak with |h|^2 >= max(first_path_rel *
  *   |h[peak]|^2, 16 * mean) replaces it (alignment to the first significant path; 0 = the scored peak itself).
- * max_coarse = 0: no whole-carrier search (k = 0). */
+ * max_coarse = 0: no whole-carrier search (k = 0).  All |D_k|^2 = 0 (an all-zero window): k = 0, ratio 0; all |h|^2 = 0:
+ * tap 0 (no first-path move), ratio 0.  The window is scaled by a power of two first (exact): the results do not depend
+ * on a 2^k scaling of the input, and |D_k|^2 cannot overflow. */
 void oracle_sync_prs_ex(const float *sym, float freq_offset, int max_coarse, int expected, float distance_prob,
                         float first_path_rel, int32_t *k, int32_t *toff, float *peak_to_mean,
                         float *coarse_peak_to_mean);

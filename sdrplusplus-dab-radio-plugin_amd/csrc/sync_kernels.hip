@@ -91,6 +91,26 @@ __device__ __forceinline__ void block_argmax_sum(Lds &sm, int tid, float m, int 
     __syncthreads();
 }
 
+// Power-of-two normalisation of a block-wide vector: every thread hands in the largest |component| of its values, the
+// wave's maximum goes to slot[wave] ahead of a barrier the caller already has; after it, block_scale() is 2^-e with the
+// block's maximum in [2^(e-1), 2^e).  Multiplying by it is exact, so what follows is the same bit for bit for any 2^k
+// scaling of the input, and the squares of the correlations cannot overflow (the unnormalised |N D_k|^2 grows as |x|^4
+// and overflowed float32 from |x| ~ 2^16 on).
+__device__ __forceinline__ void block_max_publish(float *slot, float amax, int tid) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    if ((tid & 63) == 0) slot[tid >> 6] = amax;
+}
+__device__ __forceinline__ float block_scale(const float *slot) {
+    float m = slot[0];
+#pragma unroll
+    for (int w = 1; w < WG / 64; w++) m = fmaxf(m, slot[w]);
+    int e;
+    frexpf(m, &e);                                             // (m = 0: e = 0, scale 1)
+    return ldexpf(1.0f, -min(max(e, -126), 126));
+}
+__device__ __forceinline__ float amax2(float2 v) { return fmaxf(fabsf(v.x), fabsf(v.y)); }
+
 // Fractional frequency error from the cyclic prefix of the PRS: products first .. first+375 of the candidate's prefix
 // against the samples 2048 later (inside the prefix for any candidate within +-64 samples of first - 64 early);
 // -angle / (2 pi 2048) cycles per sample.  Block-wide; ends with a barrier.
@@ -295,19 +315,27 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
     if constexpr (!LITE)
     if (do_coarse) {                                           // (uniform over the workgroup)
         // ---- Q[b] = X[b+1] conj X[b] -> t1 ----
+        float qmax = 0.0f;
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int b = tid + r * WG;
-            sm.t1[b] = cmulc(sm.x[(b + 1) & (NB_FFT - 1)], sm.x[b]);
+            const float2 q = cmulc(sm.x[(b + 1) & (NB_FFT - 1)], sm.x[b]);
+            sm.t1[b] = q;
+            qmax = fmaxf(qmax, amax2(q));
         }
+        block_max_publish(sm.red_m, qmax, tid);
         __syncthreads();
+        const float qscale = block_scale(sm.red_m);
         // ---- coarse frequency: D_k = sum_b Q[b+k] conj S[b] for ALL shifts at once as a circular correlation,
         //      D = IFFT(FFT(Q) conj FFT(S)); FFT(S) is a table, |IFFT(Z)| = |FFT(conj Z)| (the common 1/N does not
         //      change a peak-to-mean ratio).  Two more transforms instead of (2 max + 1) x 1535 complex adds. ----
         {
             float2 v[8];
 #pragma unroll
-            for (int r = 0; r < 8; r++) v[r] = sm.t1[tid + r * WG];
+            for (int r = 0; r < 8; r++) {
+                const float2 q = sm.t1[tid + r * WG];
+                v[r] = make_float2(q.x * qscale, q.y * qscale);
+            }
             __syncthreads();                                   // t1 is the transform's scratch from here on
             block_fft2048(v, sm.t1, sm.y, sm.tw, twc8, twc64, tid);
 #pragma unroll
@@ -329,13 +357,16 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
         }
         int best_idx;
         block_argmax_sum(sm, tid, my_m, my_k, my_s, best_m, best_idx, total);
-        khat = best_idx - max_coarse;
-        coarse_ptm = best_m / (total / float(2 * max_coarse + 1));
+        if (total > 0.0f) {                                    // (all |D_k|^2 = 0, a zero window: k = 0, ratio 0)
+            khat = best_idx - max_coarse;
+            coarse_ptm = best_m / (total / float(2 * max_coarse + 1));
+        }
     }
 
     // ---- fine time: |IFFT(Z)| = |FFT(conj Z)|, Z[b] = X[b+k^] conj R[b] on carriers ----
     {
         float2 v[8];
+        float zmax = 0.0f;
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int b = tid + r * WG;
@@ -346,8 +377,13 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
                 z.y = -z.y;
             }
             v[r] = z;
+            zmax = fmaxf(zmax, amax2(z));
         }
+        block_max_publish(sm.red_m, zmax, tid);
         __syncthreads();          // everyone has read x[] before the FFT overwrites it
+        const float zscale = block_scale(sm.red_m);
+#pragma unroll
+        for (int r = 0; r < 8; r++) v[r] = make_float2(v[r].x * zscale, v[r].y * zscale);
         block_fft2048(v, sm.t1, sm.x, tw, twc8, twc64, tid);
     }
     // power of every tap into pw[] (kept for the first-path scan), weighted score for the peak choice (PeakRule)
@@ -370,7 +406,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
     block_argmax_sum(sm, tid, my_m, my_n, my_s, best_m, best_n, total);   // (its barriers make y[] visible)
     const float peak = pw[best_n];
     const float mean = total / float(NB_FFT);
-    if (rule.first_path_rel > 0.0f) {
+    if (rule.first_path_rel > 0.0f && total > 0.0f) {          // (all taps 0, a zero window: tap 0, ratio 0)
         const float thr = fmaxf(__fmul_rn(rule.first_path_rel, peak), __fmul_rn(16.0f, mean));
         float my_d = 0.0f;
         for (int d = tid + 1; d <= NB_CP; d += WG)
@@ -382,7 +418,7 @@ __global__ __launch_bounds__(WG) void prs_sync_kernel(SyncTables tab, const floa
     }
     if (tid == 0) {
         const int toff = best_n < NB_FFT / 2 ? best_n : best_n - NB_FFT;
-        const float ptm = peak / mean;
+        const float ptm = total > 0.0f ? peak / mean : 0.0f;
         if constexpr (MODE == MODE_ACQ) {
             AcquiredFrame r;
             r.start = cand + toff - acq.margin;
