@@ -991,6 +991,148 @@ int dabgpu_cir_analyse(const dabgpu_cir_acc *acc, const dabgpu_cir_cfg *cfg, dab
                        dabgpu_cir_path *out, int max_out);
 
 /* ------------------------------------------------------------------------ */
+/* ETI(NI) output: what a decode call left on the  */
+/* device, written as one 6144-byte ETI(NI) frame per 24 ms CIF -- the FIC of   */
+/* that CIF, the sub-channel table and every listed sub-channel's bytes, the    */
+/* header and the data each under a CRC -- ready to be downloaded or written to */
+/* a file as it is.  All multi-bit fields big-endian, MSB first:               */
+/*   0   1  ERR    0xFF all three FIBs passed their CRC, 0xE1 otherwise,        */
+/*                 0x00 warm-up frame                                          */
+/*   1   3  FSYNC  07 3A B6 (FCT even) / F8 C5 49 (FCT odd)                    */
+/*   4   1  FCT    CIF count modulo 250                                        */
+/*   5   1  FICF (1 bit) = 1, NST (7) = number of streams                      */
+/*   6   2  FP (3) = CIF count modulo 8, MID (2) = 1, FL (11) = NST + 1 + 24 +  */
+/*                 2 * sum STL                                                 */
+/*   8   4 NST  STC per stream: SCID (6), SAD (10), TPL (6), STL (10) =         */
+/*                 bitrate_kbps * 3 / 8; streams by ascending SAD              */
+/*   ..  2  MNSC = FFFF;   2  CRC over bytes 4 .. end of MNSC                  */
+/*   ..  96 FIC: the CIF's three FIBs as the FIC decoder wrote them            */
+/*   ..  8 STL per stream: its bytes of this CIF as the MSC decoder wrote them */
+/*   ..  2  CRC over FIC + stream bytes;  2  RFU = FFFF;  4  TIST = FFFFFFFF    */
+/*   ..  0x55 up to 6144                                                       */
+/* TPL: UEP 0x10 | (level - 1); EEP 0x20 | (eep_type << 2) | (level - 1).  Both */
+/* CRCs are the FIB's (x^16 + x^12 + x^5 + 1, start FFFF, inverted).           */
+/*                                                                            */
+/* Alignment.  A frame carries the FIC and the sub-channel bytes of the SAME    */
+/* transmitted CIF.  Entry t of a sub-channel's decoder output is the logical   */
+/* frame transmitted at CIF t - 15 of the call, and the FIC is not interleaved: */
+/* output frame t = FIC of CIF t - 15 + every sub-channel's entry t.  The FIC   */
+/* of a call's last 15 CIFs waits in a per-stream history record               */
+/* (dabgpu_eti_history) for the next call, exactly as the de-interleaver state   */
+/* does: d_history_in / d_history_out [n_streams] records, 8-byte aligned, must */
+/* not alias; d_history_in may be NULL, and an all-zero record means the same   */
+/* (a stream that starts here).  Frames whose CIF lies before the start of the  */
+/* stream are WARM-UP frames: written, well-formed, both CRCs right, ERR = 0x00, */
+/* a zero FIC, DABGPU_ETI_WARMUP in their status.                               */
+/*                                                                            */
+/* CIF count.  Per stream and call the ANCHOR is the first CIF of the call whose */
+/* first FIB passed its CRC and begins with FIG 0/0 (05 00 EId EId, 5 bits of    */
+/* the upper count, 8 of the lower); CIF c of the call then counts              */
+/* count(anchor) + c - anchor modulo 5000 (upper modulo 20, lower modulo 250),   */
+/* the CIFs of the history included.  Without an anchor the call's first CIF    */
+/* continues the history's count, or is 0 without a history                     */
+/* (DABGPU_ETI_NO_ANCHOR on every frame of that stream and call).  A frame whose  */
+/* own first FIB is valid, begins with FIG 0/0 and says another count keeps the   */
+/* anchored one and gets DABGPU_ETI_COUNT_MISMATCH (a reconfigured or spliced     */
+/* stream).  d_cif_start, when not NULL, is [n_streams]: an entry >= 0 is the     */
+/* count of that stream's first CIF of this call and overrides anchor and history */
+/* (modulo 5000); a negative entry leaves the stream to the rule above.           */
+/*                                                                            */
+/* dabgpu_eti_layout   host only (no context, no device).  Validates n          */
+/*            sub-channels, orders them by start address and builds the part of   */
+/*            the header every frame of a call shares.  DABGPU_ERR_ARG for        */
+/*            n > 64, an id outside 0..63, a size outside the CIF, overlapping     */
+/*            sub-channels, a bit rate that is not a positive multiple of 8 (or    */
+/*            above 2728: STL has 10 bits), a level outside 1..4 (EEP) / 1..5      */
+/*            (UEP), an eep_type outside 0..1, or a frame longer than 6144 bytes.  */
+/*            The sub-channel's size and protection are NOT held to its bit rate   */
+/*            here (the decode call does that).  n = 0 is a frame with the FIC only. */
+/* dabgpu_eti_frames_dev   after a decode call on the same stream (d_fib          */
+/*            [n_streams*frames_per_stream][12][32], d_crc_ok [..][12], d_out[i]    */
+/*            [n_streams][frames_per_stream*4][bitrate_i*3] exactly as it wrote    */
+/*            them).  d_out is a HOST array of plan->nst DEVICE pointers (8-byte    */
+/*            aligned) in the order the sub-channels were given to                  */
+/*            dabgpu_eti_layout -- the decode call's order; plan->order maps the    */
+/*            frame's streams to it.  Writes d_eti [n_streams][frames_per_stream*4] */
+/*            [6144] (16-byte aligned) and d_status [n_streams][frames_per_stream*4] */
+/*            (8-byte aligned).  Two launches, no synchronisation.  A refused call   */
+/*            (DABGPU_ERR_ARG) enqueues nothing.                                     */
+/* dabgpu_eti_parse    host only.  Checks one 6144-byte frame -- FSYNC and its      */
+/*            parity, FICF, MID, FL against the STC, the length, both CRCs -- and    */
+/*            gives its parts.  Returns DABGPU_OK, DABGPU_ERR_ARG for a NULL         */
+/*            argument, or a positive DABGPU_ETI_BAD_* (info is filled as far as the  */
+/*            check that failed).  ERR, MNSC, RFU, TIST and the padding are not       */
+/*            judged.                                                                */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_ETI_FRAME_BYTES 6144
+#define DABGPU_ETI_MAX_STREAMS 64
+#define DABGPU_ETI_FIC_DELAY 15        /* CIFs a stream's FIC waits for its sub-channels */
+
+typedef struct dabgpu_eti_stream {
+    int32_t subchannel_id;             /* SCID, 0..63 (FIG 0/1) */
+    dabgpu_subchannel sc;
+} dabgpu_eti_stream;
+
+typedef struct dabgpu_eti_plan {
+    int32_t nst;                       /* streams per frame                                          */
+    int32_t fl;                        /* FL: 32-bit words of STC + MNSC/CRC + FIC + stream data     */
+    int32_t header_bytes;              /* 12 + 4 nst: bytes before the FIC                           */
+    int32_t data_bytes;                /* sum of the streams' bytes per CIF                          */
+    int32_t length;                    /* 4 fl + 16: bytes before the 0x55 padding                   */
+    int32_t reserved[3];               /* 0                                                          */
+    int32_t order[DABGPU_ETI_MAX_STREAMS];   /* order[k]: index, in the caller's list, of stream k    */
+    int32_t offset[DABGPU_ETI_MAX_STREAMS];  /* byte offset of stream k's data behind the FIC          */
+    int32_t bytes[DABGPU_ETI_MAX_STREAMS];   /* 8 STL of stream k = bitrate * 3                        */
+    uint8_t header[16 + 4 * DABGPU_ETI_MAX_STREAMS]; /* bytes 0 .. header_bytes - 1 with ERR, FSYNC,   */
+                                       /* FCT, FP and the CRC left 0                                 */
+} dabgpu_eti_plan;
+
+#define DABGPU_ETI_WARMUP         1    /* the CIF lies before the start of the stream: zero FIC, ERR = 0x00 */
+#define DABGPU_ETI_FIB_CRC        2    /* one of the three FIBs failed its CRC                              */
+#define DABGPU_ETI_NO_ANCHOR      4    /* no FIG 0/0 in this call: the count runs on from the history or 0   */
+#define DABGPU_ETI_COUNT_MISMATCH 8    /* the frame's own FIG 0/0 says another count                         */
+typedef struct dabgpu_eti_status {     /* per frame, 8 bytes */
+    uint16_t cif_count;                /* upper * 250 + lower, 0..4999                               */
+    uint8_t  flags;                    /* DABGPU_ETI_*                                               */
+    uint8_t  fib_ok;                   /* bit j = FIB j passed its CRC                               */
+    uint16_t length;                   /* bytes before the padding                                   */
+    uint16_t reserved;                 /* 0                                                          */
+} dabgpu_eti_status;
+
+typedef struct dabgpu_eti_history {    /* DEVICE memory, per stream, 1504 bytes */
+    uint8_t fib[DABGPU_ETI_FIC_DELAY][96];    /* the FIC groups of the call's last 15 CIFs, oldest first    */
+    uint8_t crc_ok[DABGPU_ETI_FIC_DELAY][3];  /* their CRC flags                                            */
+    uint8_t pad[3];
+    int32_t next_count;                /* CIF count of the first CIF of the next call                */
+    int32_t valid;                     /* how many of the 15 slots hold a CIF (the newest ones); 0:  */
+                                       /* nothing here, next_count included                          */
+    int32_t reserved[2];
+} dabgpu_eti_history;
+
+#define DABGPU_ETI_BAD_SYNC       1    /* FSYNC is neither pattern, or not the one FCT's parity asks for */
+#define DABGPU_ETI_BAD_HEADER     2    /* FICF, MID, NST or FL do not fit each other or the frame        */
+#define DABGPU_ETI_BAD_HEADER_CRC 3
+#define DABGPU_ETI_BAD_DATA_CRC   4
+typedef struct dabgpu_eti_info {
+    int32_t err, fct, fp, mid, nst, fl;
+    int32_t length;                    /* 4 fl + 16                                                  */
+    int32_t fic_offset;                /* where the 96 FIC bytes begin                               */
+    int32_t header_crc, data_crc;      /* as stored in the frame                                     */
+    int32_t reserved[2];
+    int32_t scid[DABGPU_ETI_MAX_STREAMS], sad[DABGPU_ETI_MAX_STREAMS], tpl[DABGPU_ETI_MAX_STREAMS],
+            stl[DABGPU_ETI_MAX_STREAMS];
+    int32_t offset[DABGPU_ETI_MAX_STREAMS];  /* where stream k's 8 stl bytes begin in the frame       */
+} dabgpu_eti_info;
+
+int dabgpu_eti_layout(const dabgpu_eti_stream *streams, int n, dabgpu_eti_plan *plan);
+size_t dabgpu_eti_history_bytes(void);     /* sizeof(dabgpu_eti_history) */
+int dabgpu_eti_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_streams, int frames_per_stream,
+                          const uint8_t *d_fib, const uint8_t *d_crc_ok, const uint8_t *const *d_out,
+                          const dabgpu_eti_history *d_history_in, dabgpu_eti_history *d_history_out,
+                          const int32_t *d_cif_start, uint8_t *d_eti, dabgpu_eti_status *d_status, void *stream);
+int dabgpu_eti_parse(const uint8_t *frame, dabgpu_eti_info *info);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */
@@ -1100,6 +1242,7 @@ int dabgpu_viterbi(dabgpu_ctx *ctx, const int8_t *punct, int n_codewords, const 
 /* the parts of 2 when it was the grouped codeword-per-lane launch (batches of  */
 /* >= 24 576 codewords): forward pass | traceback | de-interleaver history copy */
 /* (DABGPU_ERR_ARG when no timed call took that path).                          */
+/* 7 (both calls) = the ETI launches of dabgpu_eti_frames_dev.                  */
 /* ------------------------------------------------------------------------ */
 int dabgpu_set_timing(dabgpu_ctx *ctx, int enable);
 int dabgpu_last_kernel_ms(dabgpu_ctx *ctx, int which, float *ms);

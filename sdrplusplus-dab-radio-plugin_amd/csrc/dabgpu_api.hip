@@ -398,9 +398,9 @@ int dabgpu_set_timing(dabgpu_ctx *ctx, int enable) {
 }
 
 int dabgpu_last_kernel_ms(dabgpu_ctx *ctx, int which, float *ms) {
-    if (!ctx || !ms || which < 0 || which > 3) return DABGPU_ERR_ARG;
+    if (!ctx || !ms || which < 0 || (which > 3 && which != 7)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    Timer &t = ctx->timers[which];
+    Timer &t = ctx->timers[which == 7 ? 4 : which];
     if (t.recorded == 0) return DABGPU_ERR_ARG;
     const int i = int((t.recorded - 1) % TIMER_RING);
     HIP_TRY(hipEventSynchronize(t.stop[i]));
@@ -409,11 +409,12 @@ int dabgpu_last_kernel_ms(dabgpu_ctx *ctx, int which, float *ms) {
 }
 
 int dabgpu_mean_kernel_ms(dabgpu_ctx *ctx, int which, float *mean_ms, int *launches) {
-    if (!ctx || !mean_ms || which < 0 || which > 6) return DABGPU_ERR_ARG;
+    if (!ctx || !mean_ms || which < 0 || which > 7) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     // 4 / 5 / 6: the parts of slot 2's grouped lane decode (forward pass | traceback | history copy), where it recorded them
-    const int part = which >= 4 ? which - 4 : -1;
-    Timer &t = ctx->timers[part >= 0 ? 2 : which];
+    // 7: the ETI launches (slot 4)
+    const int part = which >= 4 && which <= 6 ? which - 4 : -1;
+    Timer &t = ctx->timers[part >= 0 ? 2 : which == 7 ? 4 : which];
     const int n = int(std::min<long>(t.recorded, TIMER_RING));
     double sum = 0.0;
     int used = 0;

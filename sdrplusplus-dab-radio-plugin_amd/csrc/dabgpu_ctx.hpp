@@ -81,12 +81,12 @@ struct dabgpu_ctx {
     // per sub-channel (validation, grouping, code look-up), ~10 us of host time in front of and between its launches
     std::map<uint64_t, dabapi::DeviceCode *> code_by_descriptor;
     // slots 0..5: staging of the host-pointer entry points; slot 6: the stream / tracked / frame calls' own loop input
-    // (correlations or decision-directed sums); slot 7: the TII calls' per-frame records; slot 8: the CIR calls'.  One
+    // (correlations or decision-directed sums); slot 7: the TII calls' per-frame records; slot 8: the CIR calls'; slot 9: the ETI call's per-stream CIF counts.  One
     // caller stream at a time per context (dabgpu.h, conventions).
-    void *d_stage[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void *d_stage[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t stage_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool timing = false;
-    dabapi::Timer timers[4];
+    dabapi::Timer timers[5];              // 0..3 as dabgpu_last_kernel_ms numbers them, 4 = the ETI launches (its index 7)
     int ofdm_parts_override = 0;
     const unsigned long long *d_keep = nullptr;          // current soft-bit selection table ([75][3] words) or nullptr
     std::vector<void *> keep_tables;                     // every table handed to a kernel so far (freed on destroy)

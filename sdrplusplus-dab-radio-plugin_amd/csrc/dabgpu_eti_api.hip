@@ -1,0 +1,233 @@
+// dabgpu_eti_api.hip -- the ETI(NI) entry points of the C ABI (include/dabgpu.h, "ETI(NI) output"): the host-side
+// layout and reader, and the device call that turns a decode call's buffers into frames (eti_kernels.hip).
+#include "dabgpu_ctx.hpp"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+
+using namespace dabapi;
+
+static_assert(sizeof(dabgpu_eti_history) == sizeof(dabk::EtiHistory) && sizeof(dabgpu_eti_status) == sizeof(dabk::EtiStatus),
+              "ABI structs mirror the kernels'");
+static_assert(offsetof(dabgpu_eti_history, crc_ok) == offsetof(dabk::EtiHistory, crc_ok) &&
+              offsetof(dabgpu_eti_history, next_count) == offsetof(dabk::EtiHistory, next_count) &&
+              offsetof(dabgpu_eti_history, valid) == offsetof(dabk::EtiHistory, valid), "ABI structs mirror the kernels'");
+static_assert(DABGPU_ETI_FRAME_BYTES == dabk::ETI_FRAME_BYTES && DABGPU_ETI_MAX_STREAMS == dabk::ETI_MAX_STREAMS &&
+              DABGPU_ETI_FIC_DELAY == dabk::ETI_FIC_DELAY, "ABI constants mirror the kernels'");
+
+namespace {
+
+constexpr int FIC_BYTES = dabk::ETI_FIC_BYTES;
+constexpr int TIMER_ETI = 4;                   // ctx->timers slot; dabgpu_last_kernel_ms / _mean_kernel_ms index 7
+
+// ---- CRC-16 (x^16 + x^12 + x^5 + 1) as polynomial arithmetic over GF(2)
+uint32_t gf_mul(uint32_t a, uint32_t b) {
+    uint32_t r = 0;
+    for (int i = 15; i >= 0; i--) {
+        r <<= 1;
+        if (r & 0x10000u) r ^= 0x11021u;
+        if ((b >> i) & 1u) r ^= a;
+    }
+    return r;
+}
+
+// x^n mod P
+uint32_t gf_xpow(unsigned long long n) {
+    uint32_t r = 1, sq = 2;
+    for (; n; n >>= 1) {
+        if (n & 1u) r = gf_mul(r, sq);
+        sq = gf_mul(sq, sq);
+    }
+    return r;
+}
+
+// start 0xFFFF, result inverted
+uint32_t crc16(const uint8_t *p, size_t n) {
+    uint32_t crc = 0xFFFFu;
+    for (size_t i = 0; i < n; i++) {
+        crc ^= uint32_t(p[i]) << 8;
+        for (int b = 0; b < 8; b++) crc = (crc & 0x8000u) ? ((crc << 1) ^ 0x1021u) & 0xFFFFu : (crc << 1) & 0xFFFFu;
+    }
+    return crc ^ 0xFFFFu;
+}
+
+// what dabgpu_eti_layout guarantees, checked again on a plan handed to the device call (it sizes every access of the kernels)
+bool plan_consistent(const dabgpu_eti_plan &p) {
+    if (p.nst < 0 || p.nst > DABGPU_ETI_MAX_STREAMS || p.header_bytes != 12 + 4 * p.nst) return false;
+    bool seen[DABGPU_ETI_MAX_STREAMS] = {};
+    int off = 0;
+    for (int k = 0; k < p.nst; k++) {
+        if (p.order[k] < 0 || p.order[k] >= p.nst || seen[p.order[k]]) return false;
+        seen[p.order[k]] = true;
+        if (p.bytes[k] <= 0 || p.bytes[k] % 24 || p.bytes[k] > 8 * 1023 || p.offset[k] != off) return false;
+        off += p.bytes[k];
+    }
+    return p.data_bytes == off && p.length == p.header_bytes + FIC_BYTES + off + 8 && p.length <= DABGPU_ETI_FRAME_BYTES &&
+           p.fl * 4 + 16 == p.length;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dabgpu_eti_history_bytes(void) { return sizeof(dabgpu_eti_history); }
+
+int dabgpu_eti_layout(const dabgpu_eti_stream *streams, int n, dabgpu_eti_plan *plan) {
+    if (!plan || n < 0 || n > DABGPU_ETI_MAX_STREAMS || (n > 0 && !streams)) return DABGPU_ERR_ARG;
+    char used[864] = {};
+    for (int i = 0; i < n; i++) {
+        const dabgpu_subchannel &sc = streams[i].sc;
+        if (streams[i].subchannel_id < 0 || streams[i].subchannel_id > 63) return DABGPU_ERR_ARG;
+        if (sc.start_address < 0 || sc.length <= 0 || sc.start_address > 863 || sc.length > 864 - sc.start_address) return DABGPU_ERR_ARG;
+        if (sc.bitrate_kbps <= 0 || sc.bitrate_kbps % 8 || sc.bitrate_kbps * 3 / 8 > 1023) return DABGPU_ERR_ARG;
+        if (sc.is_uep ? (sc.is_uep != 1 || sc.protection_level < 1 || sc.protection_level > 5)
+                      : (sc.protection_level < 1 || sc.protection_level > 4 || sc.eep_type < 0 || sc.eep_type > 1))
+            return DABGPU_ERR_ARG;
+        for (int cu = sc.start_address; cu < sc.start_address + sc.length; cu++) {
+            if (used[cu]) return DABGPU_ERR_ARG;
+            used[cu] = 1;
+        }
+    }
+    dabgpu_eti_plan p;
+    std::memset(&p, 0, sizeof p);
+    p.nst = n;
+    for (int k = 0; k < n; k++) p.order[k] = k;
+    std::sort(p.order, p.order + n, [&](int a, int b) { return streams[a].sc.start_address < streams[b].sc.start_address; });
+    int stl_sum = 0;
+    for (int k = 0; k < n; k++) {
+        const dabgpu_eti_stream &st = streams[p.order[k]];
+        const int stl = st.sc.bitrate_kbps * 3 / 8;
+        const int tpl = st.sc.is_uep ? 0x10 | (st.sc.protection_level - 1) : 0x20 | (st.sc.eep_type << 2) | (st.sc.protection_level - 1);
+        p.offset[k] = 8 * stl_sum;
+        p.bytes[k] = 8 * stl;
+        stl_sum += stl;
+        uint8_t *stc = p.header + 8 + 4 * k;
+        stc[0] = uint8_t((st.subchannel_id << 2) | (st.sc.start_address >> 8));
+        stc[1] = uint8_t(st.sc.start_address & 0xff);
+        stc[2] = uint8_t((tpl << 2) | (stl >> 8));
+        stc[3] = uint8_t(stl & 0xff);
+    }
+    p.fl = n + 1 + 24 + 2 * stl_sum;
+    p.header_bytes = 12 + 4 * n;
+    p.data_bytes = 8 * stl_sum;
+    p.length = 4 * p.fl + 16;
+    if (p.length > DABGPU_ETI_FRAME_BYTES) return DABGPU_ERR_ARG;
+    p.header[5] = uint8_t(0x80 | n);
+    p.header[6] = uint8_t((1 << 3) | (p.fl >> 8));             // FP = 0, MID = 1
+    p.header[7] = uint8_t(p.fl & 0xff);
+    p.header[8 + 4 * n] = 0xFF;                                // MNSC
+    p.header[9 + 4 * n] = 0xFF;
+    *plan = p;
+    return DABGPU_OK;
+}
+
+int dabgpu_eti_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_streams, int frames_per_stream,
+                          const uint8_t *d_fib, const uint8_t *d_crc_ok, const uint8_t *const *d_out,
+                          const dabgpu_eti_history *d_history_in, dabgpu_eti_history *d_history_out,
+                          const int32_t *d_cif_start, uint8_t *d_eti, dabgpu_eti_status *d_status, void *stream) {
+    if (!ctx || !plan || !d_fib || !d_crc_ok || !d_eti || !d_status || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;
+    if (!plan_consistent(*plan) || (plan->nst > 0 && !d_out)) return DABGPU_ERR_ARG;
+    const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((addr(d_fib) & 3u) || (addr(d_eti) & 15u) || (addr(d_status) & 7u) || (addr(d_history_in) & 7u) ||
+        (addr(d_history_out) & 7u) || (addr(d_cif_start) & 3u))
+        return DABGPU_ERR_ARG;
+    if (d_history_in && static_cast<const void *>(d_history_in) == static_cast<const void *>(d_history_out)) return DABGPU_ERR_ARG;
+    for (int i = 0; i < plan->nst; i++)
+        if (!d_out[i] || (addr(d_out[i]) & 7u)) return DABGPU_ERR_ARG;
+    if (size_t(n_streams) * size_t(frames_per_stream) * 4u > size_t(0x7fffffff) / 4u) return DABGPU_ERR_ARG;
+    if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;
+    DeviceGuard guard(ctx);
+
+    void *base = nullptr;
+    int rc = stage(ctx, 9, size_t(n_streams) * sizeof(int32_t), &base);
+    if (rc) return rc;
+
+    dabk::EtiArgs a{};
+    const int nst = plan->nst;
+    for (int k = 0; k < nst; k++) {
+        a.out[k] = d_out[plan->order[k]];
+        a.offset[k] = uint16_t(plan->offset[k]);
+        a.bytes[k] = uint16_t(plan->bytes[k]);
+    }
+    // the constant part of the header: the caller's plan is read for its numbers only, the bytes are laid out again
+    uint8_t hdr[16 + 4 * DABGPU_ETI_MAX_STREAMS] = {};
+    std::memcpy(hdr + 8, plan->header + 8, size_t(4 * nst));
+    hdr[5] = uint8_t(0x80 | nst);
+    hdr[6] = uint8_t((1 << 3) | (plan->fl >> 8));
+    hdr[7] = uint8_t(plan->fl & 0xff);
+    hdr[8 + 4 * nst] = 0xFF;
+    hdr[9 + 4 * nst] = 0xFF;
+    std::memcpy(a.header, hdr, size_t(8 + 4 * nst));
+    const int header_crc_bytes = 6 + 4 * nst;                  // FC, STC, MNSC
+    a.header_crc0 = uint16_t(crc16(hdr + 4, size_t(header_crc_bytes)));
+    a.fct_shift = uint16_t(gf_xpow(8ull * unsigned(header_crc_bytes - 1) + 16));
+    a.fp_shift = uint16_t(gf_xpow(8ull * unsigned(header_crc_bytes - 3) + 16));
+    const int data_len = FIC_BYTES + plan->data_bytes;         // a multiple of 8
+    a.chunk_words = (data_len / 4 + 63) / 64;
+    for (int lane = 0; lane < 64; lane++) a.lane_shift[lane] = uint16_t(gf_xpow(32ull * unsigned(a.chunk_words) * unsigned(63 - lane)));
+    a.data_init = uint16_t(gf_mul(0xFFFFu, gf_xpow(8ull * unsigned(data_len))));
+    a.fib = d_fib;
+    a.crc_ok = d_crc_ok;
+    a.history_in = reinterpret_cast<const dabk::EtiHistory *>(d_history_in);
+    a.base = static_cast<const int32_t *>(base);
+    a.eti = d_eti;
+    a.status = reinterpret_cast<dabk::EtiStatus *>(d_status);
+    a.n_streams = n_streams;
+    a.frames_per_stream = frames_per_stream;
+    a.nst = nst;
+    a.data_bytes = plan->data_bytes;
+
+    dabk::EtiAnchorArgs p{};
+    p.fib = d_fib;
+    p.crc_ok = d_crc_ok;
+    p.history_in = a.history_in;
+    p.history_out = reinterpret_cast<dabk::EtiHistory *>(d_history_out);
+    p.cif_start = d_cif_start;
+    p.base = static_cast<int32_t *>(base);
+    p.n_streams = n_streams;
+    p.frames_per_stream = frames_per_stream;
+
+    hipStream_t s = pick_stream(ctx, stream);
+    ScopedTimer timer(ctx, TIMER_ETI, s);
+    HIP_TRY(dabk::launch_eti(p, a, s));
+    return DABGPU_OK;
+}
+
+int dabgpu_eti_parse(const uint8_t *f, dabgpu_eti_info *info) {
+    if (!f || !info) return DABGPU_ERR_ARG;
+    dabgpu_eti_info r;
+    std::memset(&r, 0, sizeof r);
+    const auto done = [&](int code) { *info = r; return code; };
+    r.err = f[0];
+    r.fct = f[4];
+    r.nst = f[5] & 0x7f;
+    r.fp = f[6] >> 5;
+    r.mid = (f[6] >> 3) & 3;
+    r.fl = ((f[6] & 7) << 8) | f[7];
+    r.length = 4 * r.fl + 16;
+    const bool even = f[1] == 0x07 && f[2] == 0x3A && f[3] == 0xB6, odd = f[1] == 0xF8 && f[2] == 0xC5 && f[3] == 0x49;
+    if (!(even || odd) || odd != bool(r.fct & 1) || r.fct >= 250) return done(DABGPU_ETI_BAD_SYNC);
+    if (!(f[5] & 0x80) || r.mid != 1 || r.nst > DABGPU_ETI_MAX_STREAMS) return done(DABGPU_ETI_BAD_HEADER);
+    int stl_sum = 0;
+    for (int k = 0; k < r.nst; k++) {
+        const uint8_t *stc = f + 8 + 4 * k;
+        r.scid[k] = stc[0] >> 2;
+        r.sad[k] = ((stc[0] & 3) << 8) | stc[1];
+        r.tpl[k] = stc[2] >> 2;
+        r.stl[k] = ((stc[2] & 3) << 8) | stc[3];
+        r.offset[k] = 12 + 4 * r.nst + FIC_BYTES + 8 * stl_sum;
+        stl_sum += r.stl[k];
+    }
+    r.fic_offset = 12 + 4 * r.nst;
+    if (r.fl != r.nst + 1 + 24 + 2 * stl_sum || r.length > DABGPU_ETI_FRAME_BYTES) return done(DABGPU_ETI_BAD_HEADER);
+    const int crc_at = 10 + 4 * r.nst;
+    r.header_crc = (f[crc_at] << 8) | f[crc_at + 1];
+    const int eof_at = r.fic_offset + FIC_BYTES + 8 * stl_sum;
+    r.data_crc = (f[eof_at] << 8) | f[eof_at + 1];
+    if (uint32_t(r.header_crc) != crc16(f + 4, size_t(6 + 4 * r.nst))) return done(DABGPU_ETI_BAD_HEADER_CRC);
+    if (uint32_t(r.data_crc) != crc16(f + r.fic_offset, size_t(FIC_BYTES + 8 * stl_sum))) return done(DABGPU_ETI_BAD_DATA_CRC);
+    return done(DABGPU_OK);
+}
+
+}  // extern "C"

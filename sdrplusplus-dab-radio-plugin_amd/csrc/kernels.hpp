@@ -499,6 +499,52 @@ struct CirArgs {
 };
 hipError_t launch_cir(const float2 *twiddle, const CirArgs &a, hipStream_t s, int iq_format);
 
+// ---- ETI(NI) output (eti_kernels.hip) ---------------------------------------
+constexpr int ETI_FRAME_BYTES = 6144;
+constexpr int ETI_MAX_STREAMS = 64;
+constexpr int ETI_FIC_DELAY = 15;
+constexpr int ETI_FIC_BYTES = 96;
+constexpr int ETI_CIF_COUNTS = 5000;
+struct EtiHistory {            // == dabgpu_eti_history (1504 bytes)
+    uint8_t fib[ETI_FIC_DELAY][ETI_FIC_BYTES];
+    uint8_t crc_ok[ETI_FIC_DELAY][3];
+    uint8_t pad[3];
+    int32_t next_count, valid, reserved[2];
+};
+struct EtiStatus {             // == dabgpu_eti_status
+    uint16_t cif_count;
+    uint8_t flags, fib_ok;
+    uint16_t length, reserved;
+};
+// Everything a call's frames share, by value in the kernel arguments (~1.4 KB)
+struct EtiArgs {
+    const uint8_t *out[ETI_MAX_STREAMS];       // sub-channel k of the FRAME (plan order): [n_streams][n_cif][bytes[k]]
+    uint16_t offset[ETI_MAX_STREAMS];          // byte offset of its data behind the FIC
+    uint16_t bytes[ETI_MAX_STREAMS];
+    uint32_t header[2 + ETI_MAX_STREAMS];      // frame bytes 0 .. 8 + 4 nst as little-endian words (ERR, FSYNC, FCT, FP = 0)
+    uint16_t lane_shift[64];                   // x^(8 C (63 - lane)) mod P: moves a lane's chunk CRC to the end of the data
+    const uint8_t *fib, *crc_ok;
+    const EtiHistory *history_in;
+    const int32_t *base;                       // [n_streams] count of the call's first CIF | no-anchor << 16 (pre-pass)
+    uint8_t *eti;
+    EtiStatus *status;
+    int n_streams, frames_per_stream;
+    int nst, data_bytes;
+    int chunk_words;                           // C / 4: 32-bit words of FIC + data every lane folds
+    uint16_t header_crc0;                      // header CRC (finished) with FCT = FP = 0
+    uint16_t fct_shift, fp_shift;              // x^(8 (Lh - 1) + 16), x^(8 (Lh - 3) + 16) mod P: a byte's way to the header's end
+    uint16_t data_init;                        // 0xFFFF x^(8 L) mod P: the start value's way through FIC + data
+};
+struct EtiAnchorArgs {
+    const uint8_t *fib, *crc_ok;
+    const EtiHistory *history_in;
+    EtiHistory *history_out;
+    const int32_t *cif_start;
+    int32_t *base;
+    int n_streams, frames_per_stream;
+};
+hipError_t launch_eti(const EtiAnchorArgs &p, const EtiArgs &a, hipStream_t s);
+
 // Let every kernel that takes dynamic LDS use the whole 160 KB of a CU: set once per context creation (on the
 // context's device) instead of per launch.
 hipError_t init_viterbi_kernel_attributes();

@@ -49,6 +49,7 @@ EXPORTS = [
     "dabgpu_set_iq_format", "dabgpu_get_iq_format",
     "dabgpu_tii_default_cfg", "dabgpu_tii_pattern", "dabgpu_tii_frames_dev", "dabgpu_tii_acquired_dev", "dabgpu_tii_decode",
     "dabgpu_cir_default_cfg", "dabgpu_cir_frames_dev", "dabgpu_cir_acquired_dev", "dabgpu_cir_analyse",
+    "dabgpu_eti_layout", "dabgpu_eti_history_bytes", "dabgpu_eti_frames_dev", "dabgpu_eti_parse",
 ]
 
 ABI_VERSION = 6
@@ -140,6 +141,21 @@ assert CIR_REPORT_DTYPE.itemsize == 32
 CIR_PATH_DTYPE = np.dtype([("delay", np.float32), ("level_db", np.float32), ("snr_db", np.float32), ("flags", np.int32)])
 assert CIR_PATH_DTYPE.itemsize == 16
 CIR_BEYOND_GUARD = 1
+#: ETI(NI) output (include/dabgpu.h, "ETI(NI) output"): one 6144-byte frame per CIF
+ETI_FRAME_BYTES = 6144
+ETI_MAX_STREAMS = 64
+ETI_FIC_DELAY = 15
+ETI_WARMUP, ETI_FIB_CRC, ETI_NO_ANCHOR, ETI_COUNT_MISMATCH = 1, 2, 4, 8
+#: dabgpu_eti_status: one frame's record
+ETI_STATUS_DTYPE = np.dtype([("cif_count", np.uint16), ("flags", np.uint8), ("fib_ok", np.uint8), ("length", np.uint16),
+                             ("reserved", np.uint16)])
+assert ETI_STATUS_DTYPE.itemsize == 8
+#: dabgpu_eti_history: a stream's FIC delay line between two calls (device memory; all zero = a stream that starts)
+ETI_HISTORY_DTYPE = np.dtype([("fib", np.uint8, (15, 96)), ("crc_ok", np.uint8, (15, 3)), ("pad", np.uint8, (3,)),
+                              ("next_count", np.int32), ("valid", np.int32), ("reserved", np.int32, (2,))])
+assert ETI_HISTORY_DTYPE.itemsize == 1504
+ETI_PARSE_ERRORS = {1: "FSYNC wrong, or not the pattern FCT's parity asks for", 2: "FICF / MID / NST / FL inconsistent",
+                    3: "header CRC", 4: "data CRC"}
 #: Mode I sample rate, samples per microsecond
 SAMPLES_PER_US = 2.048
 
@@ -285,6 +301,60 @@ class Subchannel(C.Structure):
                 ("eep_type", C.c_int32), ("protection_level", C.c_int32), ("bitrate_kbps", C.c_int32)]
 
 
+class EtiStream(C.Structure):
+    """One stream of an ETI frame: the sub-channel's id (FIG 0/1) and its descriptor."""
+    _fields_ = [("subchannel_id", C.c_int32), ("sc", Subchannel)]
+
+
+class EtiPlan(C.Structure):
+    _fields_ = [("nst", C.c_int32), ("fl", C.c_int32), ("header_bytes", C.c_int32), ("data_bytes", C.c_int32),
+                ("length", C.c_int32), ("reserved", C.c_int32 * 3), ("order", C.c_int32 * 64), ("offset", C.c_int32 * 64),
+                ("bytes", C.c_int32 * 64), ("header", C.c_uint8 * 272)]
+
+
+class EtiInfo(C.Structure):
+    _fields_ = [("err", C.c_int32), ("fct", C.c_int32), ("fp", C.c_int32), ("mid", C.c_int32), ("nst", C.c_int32),
+                ("fl", C.c_int32), ("length", C.c_int32), ("fic_offset", C.c_int32), ("header_crc", C.c_int32),
+                ("data_crc", C.c_int32), ("reserved", C.c_int32 * 2), ("scid", C.c_int32 * 64), ("sad", C.c_int32 * 64),
+                ("tpl", C.c_int32 * 64), ("stl", C.c_int32 * 64), ("offset", C.c_int32 * 64)]
+
+
+def eti_layout(streams):
+    """Validate sub-channels [(subchannel_id, Subchannel) or EtiStream, ...] for an ETI frame and lay the frame out
+    (dabgpu_eti_layout: host only, no GPU) -> EtiPlan; plan.order[k] is the index in `streams` of the frame's k-th
+    stream (ascending start address).  DabGpuError (ERR_ARG) for a configuration an ETI frame cannot carry."""
+    items = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+    arr = (EtiStream * max(len(items), 1))(*items)
+    plan = EtiPlan()
+    _check(lib().dabgpu_eti_layout(arr, len(items), C.byref(plan)), "dabgpu_eti_layout")
+    return plan
+
+
+def eti_history_bytes():
+    return int(lib().dabgpu_eti_history_bytes())
+
+
+def eti_parse(frame):
+    """Check one 6144-byte ETI(NI) frame (sync, lengths, both CRCs; dabgpu_eti_parse: host only) and give its parts:
+    dict with err, fct, fp, nst, fl, length, streams [{scid, sad, tpl, stl, data}], fic (96 bytes).  ValueError for a
+    malformed frame."""
+    f = np.ascontiguousarray(np.frombuffer(bytes(frame), np.uint8) if isinstance(frame, (bytes, bytearray)) else frame, np.uint8)
+    if f.size != ETI_FRAME_BYTES:
+        raise ValueError("an ETI(NI) frame is %d bytes, got %d" % (ETI_FRAME_BYTES, f.size))
+    f = f.reshape(-1)
+    info = EtiInfo()
+    rc = lib().dabgpu_eti_parse(_p(f), C.byref(info))
+    if rc < 0:
+        raise DabGpuError(rc, "dabgpu_eti_parse")
+    if rc > 0:
+        raise ValueError("not a valid ETI(NI) frame: " + ETI_PARSE_ERRORS.get(rc, str(rc)))
+    streams = [{"scid": info.scid[k], "sad": info.sad[k], "tpl": info.tpl[k], "stl": info.stl[k],
+                "data": f[info.offset[k]:info.offset[k] + 8 * info.stl[k]].copy()} for k in range(info.nst)]
+    return {"err": info.err, "fct": info.fct, "fp": info.fp, "mid": info.mid, "nst": info.nst, "fl": info.fl,
+            "length": info.length, "header_crc": info.header_crc, "data_crc": info.data_crc,
+            "fic": f[info.fic_offset:info.fic_offset + 96].copy(), "streams": streams}
+
+
 _LIB = None
 
 
@@ -381,6 +451,11 @@ def load_library(path):
     L.dabgpu_cir_frames_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp]
     L.dabgpu_cir_acquired_dev.argtypes = [vp, vp, sz, i, i, vp, i, vp, vp, vp]
     L.dabgpu_cir_analyse.argtypes = [vp, C.POINTER(CirCfg), vp, vp, i]
+    L.dabgpu_eti_layout.argtypes = [vp, i, C.POINTER(EtiPlan)]
+    L.dabgpu_eti_history_bytes.restype = C.c_size_t
+    L.dabgpu_eti_history_bytes.argtypes = []
+    L.dabgpu_eti_frames_dev.argtypes = [vp, C.POINTER(EtiPlan), i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dabgpu_eti_parse.argtypes = [vp, C.POINTER(EtiInfo)]
     return L
 
 
@@ -870,6 +945,62 @@ class Context:
         at start + timing_margin, inside the capture)."""
         _check(self._lib.dabgpu_cir_acquired_dev(self._h, d_iq, stream_stride, n_streams, max_frames, d_frames, timing_margin,
                                                  d_frame, d_acc, stream), "dabgpu_cir_acquired_dev")
+
+    def eti_frames_dev(self, plan, n_streams, frames_per_stream, d_fib, d_crc_ok, d_out, d_eti, d_status, d_history_in=None,
+                       d_history_out=None, d_cif_start=None, stream=None):
+        """ETI(NI) frames from what a decode call left on the device (dabgpu_eti_frames_dev): d_fib, d_crc_ok and d_out
+        (list of device addresses in the order the plan's streams were given to eti_layout) -> d_eti [n_streams]
+        [frames_per_stream*4][6144], d_status (ETI_STATUS_DTYPE); frame t carries the FIC of CIF t - 15, which the
+        histories (ETI_HISTORY_DTYPE [n_streams]) carry from call to call.  Enqueues only."""
+        n = plan.nst
+        ptrs = (C.c_void_p * n)(*[C.c_void_p(x) for x in d_out]) if n else None
+        if n and len(d_out) != n:
+            raise ValueError("the plan has %d streams, d_out %d" % (n, len(d_out)))
+        _check(self._lib.dabgpu_eti_frames_dev(self._h, C.byref(plan), n_streams, frames_per_stream, d_fib, d_crc_ok, ptrs,
+                                               d_history_in, d_history_out, d_cif_start, d_eti, d_status, stream),
+               "dabgpu_eti_frames_dev")
+
+    def decode_frames_eti(self, soft, n_streams, streams, history=None):
+        """Soft bits (torch int8 tensor on this context's device, [n_streams*frames_per_stream][>= 230400]) -> ETI(NI):
+        decode_frames_dev + eti_frames_dev on device tensors.  streams: [(subchannel_id, Subchannel), ...].
+        history: what an earlier call on the same streams returned (None: the streams start here).
+        -> (eti uint8 [n_streams, n_cif, 6144], status uint8 [n_streams, n_cif, 8] (view as ETI_STATUS_DTYPE on the host),
+        history); all device tensors, the work is finished when the call returns."""
+        import torch
+        streams = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+        plan = eti_layout(streams)
+        scs = [s.sc for s in streams]
+        if soft.dtype != torch.int8 or soft.dim() != 2 or soft.stride(1) != 1 or soft.shape[0] % n_streams:
+            raise ValueError("soft must be an int8 tensor [n_streams*frames_per_stream][>= 230400]")
+        dev = soft.device
+        n_frames = soft.shape[0]
+        fps = n_frames // n_streams
+        n_cif = fps * 4
+        u8 = dict(dtype=torch.uint8, device=dev)
+        fib = torch.empty((n_frames, 12, 32), **u8)
+        ok = torch.empty((n_frames, 12), **u8)
+        nbytes = [self._lib.dabgpu_subchannel_bytes(C.byref(sc)) for sc in scs]
+        for nb in nbytes:
+            _check(min(nb, 0), "dabgpu_subchannel_bytes")
+        outs = [torch.empty((n_streams, n_cif, nb), **u8) for nb in nbytes]
+        if history is None:
+            msc_in, eti_in = None, None
+        else:
+            msc_in, eti_in = history
+        msc_out = [torch.empty((n_streams, 15, sc.length * 64), dtype=torch.int8, device=dev) for sc in scs]
+        eti_out = torch.empty((n_streams, eti_history_bytes()), **u8)
+        eti = torch.empty((n_streams, n_cif, ETI_FRAME_BYTES), **u8)
+        status = torch.empty((n_streams, n_cif, 8), **u8)
+        # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
+        torch.cuda.current_stream(dev).synchronize()
+        self.decode_frames_dev(soft.data_ptr(), soft.stride(0), n_streams, fps, fib.data_ptr(), ok.data_ptr(), scs,
+                               None if msc_in is None else [t.data_ptr() for t in msc_in], [t.data_ptr() for t in msc_out],
+                               [t.data_ptr() for t in outs])
+        self.eti_frames_dev(plan, n_streams, fps, fib.data_ptr(), ok.data_ptr(), [t.data_ptr() for t in outs], eti.data_ptr(),
+                            status.data_ptr(), d_history_in=None if eti_in is None else eti_in.data_ptr(),
+                            d_history_out=eti_out.data_ptr())
+        self.sync()
+        return eti, status, (msc_out, eti_out)
 
     def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
         """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).

@@ -779,9 +779,11 @@ class ServiceEnsemble:
     FIC made of FIG 0/0, 0/1, 0/2, 1/0, 1/1.  services = [(label, sid, subchannel_id, option, level, bitrate,
     start_cu), ...].  n_frames must be a multiple of 5 so that whole super-frames (5 logical frames) tile."""
 
-    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=()):
+    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True):
         """dab_services: DAB (MPEG layer II) services on UEP sub-channels, [(label, sid, subchannel_id, uep_index,
-        start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body)."""
+        start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body).
+        extras=False leaves the rotation to the labels alone (FIG 0/0, 0/1, 0/2, 0/10 and one label per CIF): what
+        four services leave room for in three FIBs."""
         assert n_frames % 5 == 0
         rng = np.random.default_rng(seed)
         self.n_frames, self.eid, self.label, self.services = n_frames, eid, label, services
@@ -825,14 +827,15 @@ class ServiceEnsemble:
         # alternative and that station's frequencies, the neighbouring ensemble carrying the first service
         all_sv = [(lab, sid, scid) for (lab, sid, scid, *_r) in services] + [(lab, sid, scid) for (lab, sid, scid, *_r) in self.dab_services]
         first_sid = all_sv[0][1]
-        labels += [fig0_9(0xE1, 2, 1),
-                   fig0_8([(sid, 0, scid) for (_l, sid, scid) in all_sv[:5]]),
-                   fig0_17([(sid, 1 + k % 30, 0x09 if k == 0 else None) for k, (_l, sid, _s) in enumerate(all_sv[:5])]),
-                   fig0_5([(scid, 0x09 + k) for k, (_l, _sid, scid) in enumerate(all_sv[:8])]),
-                   fig0_6(0x123, [first_sid], idlq=0), fig0_6(0x123, [0xC479], idlq=1),
-                   fig0_21([(0xC479, 8, 1, [98300000, 101100000]), (0xC182, 0, 0, [225648000])]),
-                   fig0_24([(first_sid, [0xC182])])]
-        labels += [fig1_4(sid, 0, (lab + " main")[:16]) for (lab, sid, _s) in all_sv[:3]]
+        if extras:
+            labels += [fig0_9(0xE1, 2, 1),
+                       fig0_8([(sid, 0, scid) for (_l, sid, scid) in all_sv[:5]]),
+                       fig0_17([(sid, 1 + k % 30, 0x09 if k == 0 else None) for k, (_l, sid, _s) in enumerate(all_sv[:5])]),
+                       fig0_5([(scid, 0x09 + k) for k, (_l, _sid, scid) in enumerate(all_sv[:8])]),
+                       fig0_6(0x123, [first_sid], idlq=0), fig0_6(0x123, [0xC479], idlq=1),
+                       fig0_21([(0xC479, 8, 1, [98300000, 101100000]), (0xC182, 0, 0, [225648000])]),
+                       fig0_24([(first_sid, [0xC182])])]
+            labels += [fig1_4(sid, 0, (lab + " main")[:16]) for (lab, sid, _s) in all_sv[:3]]
         self.fibs = np.zeros((n_frames, 12, 32), np.uint8)
         k = 0
         for f in range(n_frames):
