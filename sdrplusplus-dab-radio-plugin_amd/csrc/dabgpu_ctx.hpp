@@ -1,6 +1,7 @@
 // dabgpu_ctx.hpp -- the context behind the opaque dabgpu_ctx handle and the helpers the translation units of the C ABI
-// share (dabgpu_api.hip: context + front end, dabgpu_decode_api.hip: channel decoder, dabgpu_placement.hip: frame
-// buffers, dabgpu_pipeline.hip: the host-fed ring).  Internal to libdabgpu.
+// share (dabgpu_api.hip: context, tables, timing, stream state; dabgpu_ofdm_api.hip: front end, synchronisation,
+// acquisition, tracking; dabgpu_measure_api.hip: TII and CIR; dabgpu_decode_api.hip: channel decoder; dabgpu_eti_api.hip:
+// ETI(NI) output; dabgpu_placement.hip: frame buffers; dabgpu_pipeline.hip: the host-fed ring).  Internal to libdabgpu.
 #pragma once
 #include "../../include/dabgpu.h"
 
@@ -37,10 +38,32 @@ constexpr int TIMER_RING = 32;
 struct Timer {
     hipEvent_t start[TIMER_RING] = {}, stop[TIMER_RING] = {};
     // the grouped lane decode is two kernels (+ the history copy) inside one timed call: two more events split it into
-    // forward pass | traceback | history (dabgpu_mean_kernel_ms 4 / 5 / 6 read slot 2 through them)
+    // forward pass | traceback | history (dabgpu_mean_kernel_ms 4 / 5 / 6 read TIMER_MSC through them)
     hipEvent_t mid[TIMER_RING][2] = {};
     bool has_mid[TIMER_RING] = {};
     long recorded = 0;                   // launches timed since timing was switched on
+};
+
+// ctx->timers, and what dabgpu_last_kernel_ms / dabgpu_mean_kernel_ms call them (dabgpu.h): the first four by their own
+// numbers, the parts of TIMER_MSC's grouped lane decode as 4 / 5 / 6 (_mean_ only), the ETI launches as 7
+enum TimerSlot { TIMER_OFDM = 0, TIMER_FIC = 1, TIMER_MSC = 2, TIMER_FFT = 3, TIMER_ETI = 4, TIMER_SLOTS };
+enum { WHICH_MSC_FORWARD = 4, WHICH_MSC_TRACEBACK = 5, WHICH_MSC_HISTORY = 6, WHICH_ETI = 7 };
+
+// ctx->d_stage.  The first six are shared by role across the host-pointer entry points (two buffers of one call never
+// share one); the rest belong to one family of calls each.  One caller stream at a time per context (dabgpu.h, conventions).
+enum StageSlot {
+    STAGE_IQ = 0,           // samples going up
+    STAGE_SOFT = 1,         // soft bits: the front end's result, the decoder's input (DAB+ / plain Viterbi: their input bytes;
+                            // the one-frame call: its whole result block)
+    STAGE_AUX = 2,          // one small item per frame: frequency offsets going up; CRC flags, super-frame status coming down
+    STAGE_RESULT = 3,       // the call's result: correlations, sync results, FIBs, decoded bytes
+    STAGE_WIDE = 4,         // the large optional buffer: constellation, spectra; de-interleaver history going up
+    STAGE_HISTORY_OUT = 5,  // de-interleaver history coming down
+    STAGE_LOOP = 6,         // the stream / tracked / frame calls' own loop input (correlations or decision-directed sums)
+    STAGE_TII = 7,          // the TII calls' per-frame records
+    STAGE_CIR = 8,          // the CIR calls'
+    STAGE_ETI_COUNTS = 9,   // the ETI call's per-stream CIF counts
+    STAGE_SLOTS
 };
 
 struct Pipeline;                         // dabgpu_pipeline.hip
@@ -80,13 +103,10 @@ struct dabgpu_ctx {
     // 4 x (24 x bitrate + 6) flags of its puncture mask first: the plugin's per-frame decode call built it three times
     // per sub-channel (validation, grouping, code look-up), ~10 us of host time in front of and between its launches
     std::map<uint64_t, dabapi::DeviceCode *> code_by_descriptor;
-    // slots 0..5: staging of the host-pointer entry points; slot 6: the stream / tracked / frame calls' own loop input
-    // (correlations or decision-directed sums); slot 7: the TII calls' per-frame records; slot 8: the CIR calls'; slot 9: the ETI call's per-stream CIF counts.  One
-    // caller stream at a time per context (dabgpu.h, conventions).
-    void *d_stage[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void *d_stage[dabapi::STAGE_SLOTS] = {};             // grown on demand (dabapi::stage), freed by dabgpu_destroy
+    size_t stage_bytes[dabapi::STAGE_SLOTS] = {};
     bool timing = false;
-    dabapi::Timer timers[5];              // 0..3 as dabgpu_last_kernel_ms numbers them, 4 = the ETI launches (its index 7)
+    dabapi::Timer timers[dabapi::TIMER_SLOTS];
     int ofdm_parts_override = 0;
     const unsigned long long *d_keep = nullptr;          // current soft-bit selection table ([75][3] words) or nullptr
     std::vector<void *> keep_tables;                     // every table handed to a kernel so far (freed on destroy)
@@ -223,8 +243,16 @@ inline hipStream_t pick_stream(dabgpu_ctx *ctx, void *stream) {
     return stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
 }
 
+// the calls that read cf32 only (host-pointer calls, the FFT stage, the mover, a constellation output)
+inline bool cf32_only(const dabgpu_ctx *ctx) { return ctx->iq_format != dabk::IQ_CF32; }
+// a device IQ pointer must hold one complex sample of the context's format at its alignment
+inline bool iq_misaligned(const dabgpu_ctx *ctx, const void *d_iq) {
+    return (reinterpret_cast<uintptr_t>(d_iq) & (dabk::iq_sample_bytes(ctx->iq_format) - 1)) != 0;
+}
+
 // defined in dabgpu_api.hip
-int stage(dabgpu_ctx *ctx, int slot, size_t bytes, void **out);
+// the slot, grown to at least `bytes` (what it held is gone when it grows)
+int stage(dabgpu_ctx *ctx, StageSlot slot, size_t bytes, void **out);
 int get_code(dabgpu_ctx *ctx, dab::PunctureProfile &&prof, DeviceCode **out);
 void free_device_code(DeviceCode &dc);
 // the address the device reaches page-locked host memory under (hipHostMalloc / hipHostRegister: dabgpu_host_alloc), or
@@ -241,6 +269,34 @@ void stats_of(const dabk::StreamState &st, dabgpu_stats *out);
 // defined in dabgpu_placement.hip / dabgpu_pipeline.hip: what dabgpu_destroy calls
 void arena_destroy(dabgpu_ctx *ctx);
 void pipeline_destroy(dabgpu_ctx *ctx);
+
+// The transfers of a host-pointer entry point through the staging slots, on the context's stream: the call asks for
+// every slot it uses (room), fills the ones that carry input (up), runs its device-pointer twin on ctx->stream, copies
+// the results back (down) and waits (finish).  A slot's size is stated once, to room().  The first failure stays in `rc`
+// and turns every later step into a no-op, as the early return it stands for would.
+struct HostCall {
+    dabgpu_ctx *ctx;
+    int rc = DABGPU_OK;
+    size_t bytes[STAGE_LOOP] = {};                             // of the six shared slots, where this call asked for them
+    explicit HostCall(dabgpu_ctx *c) : ctx(c) {}
+    // (`wanted` = false: an optional buffer the caller did not pass takes no slot and stays nullptr)
+    void *room(StageSlot slot, size_t n, bool wanted = true) {
+        void *d = nullptr;
+        if (wanted && !rc && !(rc = stage(ctx, slot, n, &d))) bytes[slot] = n;
+        return d;
+    }
+    void up(StageSlot slot, const void *host) { copy(ctx->d_stage[slot], host, slot, hipMemcpyHostToDevice); }
+    void down(StageSlot slot, void *host) { copy(host, ctx->d_stage[slot], slot, hipMemcpyDeviceToHost); }
+    int finish() {
+        if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = DABGPU_ERR_HIP;
+        return rc;
+    }
+    // (a null host pointer or a slot this call did not ask for: nothing to copy)
+    void copy(void *dst, const void *src, StageSlot slot, hipMemcpyKind kind) {
+        if (rc || !dst || !src || !bytes[slot]) return;
+        if (hipMemcpyAsync(dst, src, bytes[slot], kind, ctx->stream) != hipSuccess) rc = DABGPU_ERR_HIP;
+    }
+};
 
 // No capacity unit of the CIF used twice (and none outside it): the state-keeping entry points (dabgpu_decode_stream_frames,
 // dabgpu_pipe_submit) key their de-interleaver rings by (start, size), so a sub-channel listed twice would share one ring --

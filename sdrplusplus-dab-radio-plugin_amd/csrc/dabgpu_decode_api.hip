@@ -48,7 +48,7 @@ int dabgpu_fic_decode_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_str
     if (n_frames > 1 && soft_stride < size_t(NB_FIC_BITS)) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
     hipStream_t s = pick_stream(ctx, stream);
-    ScopedTimer tm(ctx, 1, s);
+    ScopedTimer tm(ctx, TIMER_FIC, s);
     dabk::LaneScratch lsc{};
     int lrc;
     if (use_lane(ctx, ctx->fic.prof.nsteps, n_frames * NB_FIC_GROUPS, s, &lsc, &lrc)) {
@@ -66,21 +66,18 @@ int dabgpu_fic_decode(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, i
     if (!ctx || !soft || !fib || !crc_ok || n_frames < 0) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     if (n_frames == 0) return DABGPU_OK;
-    void *d_soft, *d_fib, *d_ok;
-    int rc;
-    const size_t nb_soft = size_t(n_frames - 1) * soft_stride + NB_FIC_BITS;
-    if ((rc = stage(ctx, 1, nb_soft, &d_soft))) return rc;
-    if ((rc = stage(ctx, 3, size_t(n_frames) * NB_FIBS * 32, &d_fib))) return rc;
-    if ((rc = stage(ctx, 2, size_t(n_frames) * NB_FIBS, &d_ok))) return rc;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d_soft, soft, nb_soft, hipMemcpyHostToDevice, s));
-    rc = dabgpu_fic_decode_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, n_frames,
-                               static_cast<uint8_t *>(d_fib), static_cast<uint8_t *>(d_ok), s);
+    HostCall h(ctx);
+    void *d_soft = h.room(STAGE_SOFT, size_t(n_frames - 1) * soft_stride + NB_FIC_BITS);
+    void *d_fib = h.room(STAGE_RESULT, size_t(n_frames) * NB_FIBS * 32);
+    void *d_ok = h.room(STAGE_AUX, size_t(n_frames) * NB_FIBS);
+    h.up(STAGE_SOFT, soft);
+    if (h.rc) return h.rc;
+    const int rc = dabgpu_fic_decode_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, n_frames,
+                                         static_cast<uint8_t *>(d_fib), static_cast<uint8_t *>(d_ok), ctx->stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(fib, d_fib, size_t(n_frames) * NB_FIBS * 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(crc_ok, d_ok, size_t(n_frames) * NB_FIBS, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    h.down(STAGE_RESULT, fib);
+    h.down(STAGE_AUX, crc_ok);
+    return h.finish();
 }
 
 // ---------------------------------------------------------------------------- MSC
@@ -190,7 +187,7 @@ int dabgpu_msc_decode_dev(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, const in
     a.hist_in = d_history_in;
     a.hist_out = d_history_out;
     a.out = d_out;
-    ScopedTimer tm(ctx, 2, s);
+    ScopedTimer tm(ctx, TIMER_MSC, s);
     dabk::LaneScratch lsc{};
     int lrc;
     if (use_lane(ctx, dc->prof.nsteps, n_streams * frames_per_stream * NB_CIFS, s, &lsc, &lrc, too_long)) {
@@ -213,26 +210,22 @@ int dabgpu_msc_decode(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, const int8_t
     if (nbytes < 0) return nbytes;
     const size_t nframes = size_t(n_streams) * frames_per_stream;
     if (nframes == 0) return DABGPU_OK;
-    const size_t nb_soft = (nframes - 1) * soft_stride + NB_FRAME_BITS;
     const size_t nb_hist = size_t(n_streams) * 15 * sc->length * CU_BITS;
-    const size_t nb_out = nframes * NB_CIFS * nbytes;
-    void *d_soft, *d_hi = nullptr, *d_ho = nullptr, *d_out;
-    int rc;
-    if ((rc = stage(ctx, 1, nb_soft, &d_soft))) return rc;
-    if ((rc = stage(ctx, 3, nb_out, &d_out))) return rc;
-    if (history_in && (rc = stage(ctx, 4, nb_hist, &d_hi))) return rc;
-    if (history_out && (rc = stage(ctx, 5, nb_hist, &d_ho))) return rc;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d_soft, soft, nb_soft, hipMemcpyHostToDevice, s));
-    if (history_in) HIP_TRY(hipMemcpyAsync(d_hi, history_in, nb_hist, hipMemcpyHostToDevice, s));
-    rc = dabgpu_msc_decode_dev(ctx, sc, static_cast<const int8_t *>(d_soft), soft_stride, n_streams,
-                               frames_per_stream, static_cast<const int8_t *>(d_hi), static_cast<int8_t *>(d_ho),
-                               static_cast<uint8_t *>(d_out), s);
+    HostCall h(ctx);
+    void *d_soft = h.room(STAGE_SOFT, (nframes - 1) * soft_stride + NB_FRAME_BITS);
+    void *d_out = h.room(STAGE_RESULT, nframes * NB_CIFS * nbytes);
+    void *d_hi = h.room(STAGE_WIDE, nb_hist, history_in != nullptr);
+    void *d_ho = h.room(STAGE_HISTORY_OUT, nb_hist, history_out != nullptr);
+    h.up(STAGE_SOFT, soft);
+    h.up(STAGE_WIDE, history_in);
+    if (h.rc) return h.rc;
+    const int rc = dabgpu_msc_decode_dev(ctx, sc, static_cast<const int8_t *>(d_soft), soft_stride, n_streams,
+                                         frames_per_stream, static_cast<const int8_t *>(d_hi), static_cast<int8_t *>(d_ho),
+                                         static_cast<uint8_t *>(d_out), ctx->stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, nb_out, hipMemcpyDeviceToHost, s));
-    if (history_out) HIP_TRY(hipMemcpyAsync(history_out, d_ho, nb_hist, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    h.down(STAGE_RESULT, out);
+    h.down(STAGE_HISTORY_OUT, history_out);
+    return h.finish();
 }
 
 // The FIC (d_fib != nullptr) and/or several sub-channels in one grouped lane launch.  Returns 0 when everything was
@@ -295,7 +288,7 @@ static int decode_grouped(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, co
         }
         ctx->lane_scratch_bytes = need;
     }
-    ScopedTimer tm(ctx, 2, s);
+    ScopedTimer tm(ctx, TIMER_MSC, s);
     dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes};
     HIP_TRY(dabk::launch_lane_group(items.data(), n_items, lsc, s, tm.mids()));
     for (const dabk::LaneGroupItem &it : items)
@@ -339,7 +332,7 @@ static int decode_subchannels(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, int 
         group = false;
     if (group) {
         hipStream_t s = pick_stream(ctx, stream);
-        ScopedTimer tm(ctx, 2, s);
+        ScopedTimer tm(ctx, TIMER_MSC, s);
         // a small batch's FIC rides along: its four codewords per frame are shorter than any sub-channel's, a launch
         // of their own would only queue up in front
         dabk::WaveFicItem fic{ctx->fic.tables(true), d_soft, soft_stride, n_streams * frames_per_stream, d_fib, d_crc_ok};
@@ -441,15 +434,14 @@ int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride
         hist_bytes[i] = size_t(n_streams) * 15 * sc[i].length * CU_BITS;
         hist_total += al(hist_bytes[i]);
     }
-    const size_t nb_soft = (nframes - 1) * soft_stride + NB_FRAME_BITS;
-    void *d_soft, *d_res, *d_hi = nullptr, *d_ho = nullptr;
-    int rc;
-    if ((rc = stage(ctx, 1, nb_soft, &d_soft))) return rc;
-    if ((rc = stage(ctx, 3, res_total, &d_res))) return rc;
-    if (hist_total && history_in && (rc = stage(ctx, 4, hist_total, &d_hi))) return rc;
-    if (hist_total && history_out && (rc = stage(ctx, 5, hist_total, &d_ho))) return rc;
+    HostCall h(ctx);
+    void *d_soft = h.room(STAGE_SOFT, (nframes - 1) * soft_stride + NB_FRAME_BITS);
+    void *d_res = h.room(STAGE_RESULT, res_total);
+    void *d_hi = h.room(STAGE_WIDE, hist_total, hist_total && history_in);
+    void *d_ho = h.room(STAGE_HISTORY_OUT, hist_total, hist_total && history_out);
+    h.up(STAGE_SOFT, soft);                                                            // the frames go up once
+    if (h.rc) return h.rc;
     hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d_soft, soft, nb_soft, hipMemcpyHostToDevice, s));            // the frames go up once
     std::vector<const int8_t *> p_hi(n_subchannels, nullptr);
     std::vector<int8_t *> p_ho(n_subchannels, nullptr);
     std::vector<uint8_t *> p_out(n_subchannels, nullptr);
@@ -463,9 +455,9 @@ int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride
         if (history_out && history_out[i]) p_ho[i] = reinterpret_cast<int8_t *>(static_cast<char *>(d_ho) + hist_off[i]);
     }
     uint8_t *d_fib = reinterpret_cast<uint8_t *>(res), *d_crc = reinterpret_cast<uint8_t *>(res + al(nb_fib));
-    rc = dabgpu_decode_frames_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, n_streams, frames_per_stream, d_fib,
-                                  d_crc, sc, n_subchannels, n_subchannels ? p_hi.data() : nullptr,
-                                  n_subchannels ? p_ho.data() : nullptr, n_subchannels ? p_out.data() : nullptr, s);
+    const int rc = dabgpu_decode_frames_dev(ctx, static_cast<const int8_t *>(d_soft), soft_stride, n_streams, frames_per_stream,
+                                            d_fib, d_crc, sc, n_subchannels, n_subchannels ? p_hi.data() : nullptr,
+                                            n_subchannels ? p_ho.data() : nullptr, n_subchannels ? p_out.data() : nullptr, s);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(fib, d_fib, nb_fib, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(crc_ok, d_crc, nb_crc, hipMemcpyDeviceToHost, s));
@@ -473,8 +465,7 @@ int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride
         HIP_TRY(hipMemcpyAsync(out[i], p_out[i], out_bytes[i], hipMemcpyDeviceToHost, s));
         if (p_ho[i]) HIP_TRY(hipMemcpyAsync(history_out[i], p_ho[i], hist_bytes[i], hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(hipStreamSynchronize(s));                                                  // one synchronisation
-    return DABGPU_OK;
+    return h.finish();                                                                 // one synchronisation
 }
 
 int dabgpu_decode_stream_reset(dabgpu_ctx *ctx) {
@@ -577,8 +568,8 @@ static int decode_stream_frames_body(dabgpu_ctx *ctx, const int8_t *soft, size_t
     const size_t nb_soft = size_t(n_frames - 1) * soft_stride + NB_FRAME_BITS;
     void *d_soft, *d_res;
     int rc;
-    if ((rc = stage(ctx, 1, nb_soft, &d_soft))) return rc;
-    if ((rc = stage(ctx, 3, res_total, &d_res))) return rc;
+    if ((rc = stage(ctx, STAGE_SOFT, nb_soft, &d_soft))) return rc;
+    if ((rc = stage(ctx, STAGE_RESULT, res_total, &d_res))) return rc;
     if ((rc = ensure_bounce(ctx, res_total))) return rc;
     if (injected_failure(ctx)) return DABGPU_ERR_HIP;            // (test hook: the caller's failure path drops every ring)
     // one upload (by a kernel when the soft bits lie in page-locked memory the device can address).  One frame with a
@@ -794,21 +785,19 @@ int dabgpu_dabplus_superframes(dabgpu_ctx *ctx, const uint8_t *in, size_t in_str
             return wait_for_signal(st, flag_host, flag_dev, seq, false, coherent);
         }
     }
-    void *d_in, *d_out, *d_st;
-    int rc;
-    if ((rc = stage(ctx, 1, nb_in, &d_in))) return rc;
-    if ((rc = stage(ctx, 3, nb_out, &d_out))) return rc;
-    if ((rc = stage(ctx, 2, sizeof(dabgpu_superframe_status) * n_superframes, &d_st))) return rc;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(d_in, in, nb_in, hipMemcpyHostToDevice, st));
-    rc = dabgpu_dabplus_superframes_dev(ctx, static_cast<const uint8_t *>(d_in), in_stride, n_superframes,
-                                        bitrate_kbps, static_cast<uint8_t *>(d_out),
-                                        static_cast<dabgpu_superframe_status *>(d_st), st);
+    HostCall h(ctx);
+    void *d_in = h.room(STAGE_SOFT, nb_in);
+    void *d_out = h.room(STAGE_RESULT, nb_out);
+    void *d_st = h.room(STAGE_AUX, sizeof(dabgpu_superframe_status) * n_superframes);
+    h.up(STAGE_SOFT, in);
+    if (h.rc) return h.rc;
+    const int rc = dabgpu_dabplus_superframes_dev(ctx, static_cast<const uint8_t *>(d_in), in_stride, n_superframes,
+                                                  bitrate_kbps, static_cast<uint8_t *>(d_out),
+                                                  static_cast<dabgpu_superframe_status *>(d_st), ctx->stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, nb_out, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(status, d_st, sizeof(dabgpu_superframe_status) * n_superframes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DABGPU_OK;
+    h.down(STAGE_RESULT, out);
+    h.down(STAGE_AUX, status);
+    return h.finish();
 }
 
 // ---------------------------------------------------------------------------- plain Viterbi
@@ -849,19 +838,17 @@ int dabgpu_viterbi(dabgpu_ctx *ctx, const int8_t *punct, int n_codewords, const 
     if (n_codewords == 0) return DABGPU_OK;
     size_t n_punct = 0;
     for (int i = 0; i < 4 * nsteps; i++) n_punct += mask[i] ? 1 : 0;
-    const size_t nb_in = size_t(n_codewords) * n_punct, nb_out = size_t(n_codewords) * ((nsteps - 6) / 8);
-    void *d_in, *d_out;
-    int rc;
-    if ((rc = stage(ctx, 1, nb_in ? nb_in : 1, &d_in))) return rc;
-    if ((rc = stage(ctx, 3, nb_out, &d_out))) return rc;
-    hipStream_t s = ctx->stream;
-    if (nb_in) HIP_TRY(hipMemcpyAsync(d_in, punct, nb_in, hipMemcpyHostToDevice, s));
-    rc = dabgpu_viterbi_dev(ctx, static_cast<const int8_t *>(d_in), n_codewords, mask, nsteps,
-                            static_cast<uint8_t *>(d_out), s);
+    const size_t nb_in = size_t(n_codewords) * n_punct;
+    HostCall h(ctx);
+    void *d_in = h.room(STAGE_SOFT, nb_in ? nb_in : 1);
+    void *d_out = h.room(STAGE_RESULT, size_t(n_codewords) * ((nsteps - 6) / 8));
+    if (nb_in) h.up(STAGE_SOFT, punct);                        // (a mask that keeps nothing: no byte of `punct` is read)
+    if (h.rc) return h.rc;
+    const int rc = dabgpu_viterbi_dev(ctx, static_cast<const int8_t *>(d_in), n_codewords, mask, nsteps,
+                                      static_cast<uint8_t *>(d_out), ctx->stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_bytes, d_out, nb_out, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    h.down(STAGE_RESULT, out_bytes);
+    return h.finish();
 }
 
 }  // extern "C"

@@ -19,7 +19,6 @@ static_assert(DABGPU_ETI_FRAME_BYTES == dabk::ETI_FRAME_BYTES && DABGPU_ETI_MAX_
 namespace {
 
 constexpr int FIC_BYTES = dabk::ETI_FIC_BYTES;
-constexpr int TIMER_ETI = 4;                   // ctx->timers slot; dabgpu_last_kernel_ms / _mean_kernel_ms index 7
 
 // ---- CRC-16 (x^16 + x^12 + x^5 + 1) as polynomial arithmetic over GF(2)
 uint32_t gf_mul(uint32_t a, uint32_t b) {
@@ -140,7 +139,7 @@ int dabgpu_eti_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_st
     DeviceGuard guard(ctx);
 
     void *base = nullptr;
-    int rc = stage(ctx, 9, size_t(n_streams) * sizeof(int32_t), &base);
+    int rc = stage(ctx, STAGE_ETI_COUNTS, size_t(n_streams) * sizeof(int32_t), &base);
     if (rc) return rc;
 
     dabk::EtiArgs a{};

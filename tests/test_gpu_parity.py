@@ -392,7 +392,7 @@ def test_full_size_front_end_launch_against_the_oracle(built):
         torch.cuda.synchronize()
         c.ofdm_demod_streams_dev(d_iq, L, E, F, 0.9, soft.data_ptr(), None, None)
         c.sync()
-        # the launch's plan: whole frames while they fill every wave slot of the chip, the rest cut (plan_runs, dabgpu_api.hip)
+        # the launch's plan: whole frames while they fill every wave slot of the chip, the rest cut (plan_runs, dabgpu_ofdm_api.hip)
         slots = 3072
         uncut = n // slots * slots
         assert uncut == 15360
