@@ -15,6 +15,12 @@
 // from all (a common offset never changes a decision); with start penalty 6144 (> 6*2*508, the largest lead a
 // wrong start state can gain before its path merges, so equivalent to the reference's "known start state") the
 // doubled values stay within +-24480 < 2^15.
+// What the tests reach of that (tests/test_decoder_reference.py, by an int64 reference): the largest distance of any
+// path metric from the slot-0 metric at the last multiple of 12 steps is 12*508 + 15*254 = 9906 single units = 19812
+// doubled, 81 % of the bound above.  That is also the largest any input within +-127 can reach (12 steps of growth
+// plus the largest lag of state 0 behind the best state, 15 differing code bits; max_excursion() there derives it),
+// and saturated clean codewords reach it: a change of the metric format or of the renormalisation period is tested
+// against exactly that.
 //
 // Layout.  Slot p (0..63) = register p/2, half p%2 holds state rotl6(p, t mod 6) at step t.  Going from t to t+1
 // only bit q = (5 - t) mod 6 of the slot index changes meaning (oldest bit out, newest bit in), so the two

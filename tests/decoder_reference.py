@@ -1,0 +1,353 @@
+"""An exact reference of the channel decoder, written from ETSI EN 300 401 (clauses 5.2.1, 11 and 12) in plain numpy
+with integer arithmetic only: convolutional encoder, puncturing, soft-decision Viterbi with int64 path metrics, energy
+dispersal, FIB CRC and the 16-CIF time de-interleaver, assembled into what dabgpu_viterbi*, dabgpu_fic_decode* and
+dabgpu_msc_decode* return.  Written without oracle/, dab_tables.hpp or the library, so that a misreading they share
+does not reach the judge; the one thing taken from the project is the 64-row UEP table of dabgpu/synth.py (pure
+Python), each row checked against the two identities of clause 11.3.1 before it is used.
+
+Conventions.  A soft bit is the received value of one coded bit, positive = 1, 0 = erased or punctured.  The metric
+of a codeword c (bits 0 / 1) against soft bits s is the correlation sum s_i (2 c_i - 1): with int64 sums it is exact,
+there is no rounding to budget for.  The shift register holds (a[i], a[i-1], .., a[i-6]) with a[i] in bit 6, which is
+how the standard's octal generators read; the state after step i is its upper six bits, so the two predecessors of
+state n are ((n << 1) | o) & 63 for o = a[i-6] = 0 / 1 ("the older bit").
+
+Nothing here knows about a start penalty, a renormalisation period or a tie rule of its own: the start state is KNOWN
+(states other than 0 do not exist at t = 0), the end state is 0 (six zero tail bits), and `best` -- the largest
+correlation any codeword reaches -- is the definition of maximum likelihood whatever a decoder does on ties."""
+import binascii
+
+import numpy as np
+
+GENERATORS = (0o133, 0o171, 0o145, 0o133)            # clause 11.1.1, MSB = the current bit
+
+# clause 11.1.2, table of puncturing vectors V_PI (PI = 1 .. 24), typed as the standard prints them
+_V_PI = """
+1100 1000 1000 1000 1000 1000 1000 1000
+1100 1000 1000 1000 1100 1000 1000 1000
+1100 1000 1100 1000 1100 1000 1000 1000
+1100 1000 1100 1000 1100 1000 1100 1000
+1100 1100 1100 1000 1100 1000 1100 1000
+1100 1100 1100 1000 1100 1100 1100 1000
+1100 1100 1100 1100 1100 1100 1100 1000
+1100 1100 1100 1100 1100 1100 1100 1100
+1110 1100 1100 1100 1100 1100 1100 1100
+1110 1100 1100 1100 1110 1100 1100 1100
+1110 1100 1110 1100 1110 1100 1100 1100
+1110 1100 1110 1100 1110 1100 1110 1100
+1110 1110 1110 1100 1110 1100 1110 1100
+1110 1110 1110 1100 1110 1110 1110 1100
+1110 1110 1110 1110 1110 1110 1110 1100
+1110 1110 1110 1110 1110 1110 1110 1110
+1111 1110 1110 1110 1110 1110 1110 1110
+1111 1110 1110 1110 1111 1110 1110 1110
+1111 1110 1111 1110 1111 1110 1110 1110
+1111 1110 1111 1110 1111 1110 1111 1110
+1111 1111 1111 1110 1111 1110 1111 1110
+1111 1111 1111 1110 1111 1111 1111 1110
+1111 1111 1111 1111 1111 1111 1111 1110
+1111 1111 1111 1111 1111 1111 1111 1111
+"""
+V_PI = np.array([[int(c) for c in line.replace(" ", "")] for line in _V_PI.strip().splitlines()], np.uint8)
+V_TAIL = np.array([int(c) for c in "110011001100110011001100"], np.uint8)      # the 24 tail bits: 12 are sent
+assert V_PI.shape == (24, 32) and all(int(V_PI[p - 1].sum()) == 8 + p for p in range(1, 25))
+
+NB_FIC_BITS, NB_CIF_BITS = 9216, 55296
+NEG_INF = -(1 << 50)                                   # "does not exist": no sum of 8-bit values comes near it
+
+
+# ------------------------------------------------------------------------------------------------ puncturing
+class Profile:
+    """A puncturing profile: mask [4 * nsteps] (1 = transmitted), nsteps trellis steps (information bits + 6),
+    kept transmitted bits, padding bits behind them (UEP), size in capacity units (0: not a sub-channel)."""
+
+    def __init__(self, blocks, padding=0, size_cu=0):
+        parts = [np.tile(V_PI[pi - 1], 4 * n) for n, pi in blocks if n > 0]        # a block is 128 mother bits
+        self.blocks = [(int(n), int(pi)) for n, pi in blocks]
+        self.mask = np.concatenate(parts + [V_TAIL])
+        self.nsteps = self.mask.size // 4
+        self.kept = int(self.mask.sum())
+        self.padding = int(padding)
+        self.size_cu = int(size_cu)
+        self.nbytes = (self.nsteps - 6) // 8
+
+
+def fic_profile():
+    """Clause 11.2.1, transmission mode I: 21 blocks PI 16, 3 blocks PI 15, the tail: 2304 of 3096 bits."""
+    p = Profile([(21, 16), (3, 15)])
+    assert p.nsteps == 774 and p.kept == 2304
+    return p
+
+
+def eep_profile(option, level, bitrate):
+    """Clause 11.3.2: option 0 = set A (bit rates 8 n), 1 = set B (32 n), protection levels 1 .. 4."""
+    if option == 0:
+        n, rem = divmod(bitrate, 8)
+        if level == 2 and n == 1:
+            blocks = [(5, 13), (1, 12)]
+        else:
+            blocks = {1: [(6 * n - 3, 24), (3, 23)], 2: [(2 * n - 3, 14), (4 * n + 3, 13)],
+                      3: [(6 * n - 3, 8), (3, 7)], 4: [(4 * n - 3, 3), (2 * n + 3, 2)]}[level]
+        cu = {1: 12, 2: 8, 3: 6, 4: 4}[level] * n
+    elif option == 1:
+        n, rem = divmod(bitrate, 32)
+        p1, p2 = {1: (10, 9), 2: (6, 5), 3: (4, 3), 4: (2, 1)}[level]
+        blocks = [(24 * n - 3, p1), (3, p2)]
+        cu = {1: 27, 2: 21, 3: 18, 4: 15}[level] * n
+    else:
+        raise ValueError("EEP option %r" % (option,))
+    if rem or n < 1:
+        raise ValueError("EEP bit rate %r" % (bitrate,))
+    p = Profile(blocks, 0, cu)
+    assert p.nsteps == bitrate * 24 + 6 and p.kept == cu * 64, (option, level, bitrate)
+    return p
+
+
+def uep_profile(index):
+    """Clause 11.3.1: row `index` of the table in dabgpu/synth.py (bit rate, level, size, L1..L4, PI1..PI4, padding),
+    used only after the row passes both identities: the blocks make bitrate * 24 / 32 blocks of 128 mother bits (so
+    nsteps == bitrate * 24 + 6), and the punctured length plus the padding fills size * 64 bits."""
+    from dabgpu.synth import _UEP_TABLE
+    br, _level, size, l1, l2, l3, l4, p1, p2, p3, p4, pad = _UEP_TABLE[index]
+    p = Profile([(l1, p1), (l2, p2), (l3, p3), (l4, p4)], pad, size)
+    if (l1 + l2 + l3 + l4) * 32 != br * 24 or p.nsteps != br * 24 + 6:
+        raise AssertionError("UEP row %d: %d blocks for %d kbit/s" % (index, l1 + l2 + l3 + l4, br))
+    if p.kept + pad != size * 64:
+        raise AssertionError("UEP row %d: %d bits + %d padding in %d CUs" % (index, p.kept, pad, size))
+    p.bitrate = br
+    return p
+
+
+def plain_mask(nsteps, pi):
+    """`nsteps - 6` information bits all punctured with V_PI, and the tail: the masks the plain Viterbi tests use."""
+    assert (nsteps - 6) % 8 == 0                        # a vector covers 32 mother bits = 8 steps
+    return np.concatenate([np.tile(V_PI[pi - 1], (nsteps - 6) // 8), V_TAIL])
+
+
+def depuncture(punct, mask):
+    """punct [B][kept] -> mother soft bits [B][mask.size] int64, 0 where nothing was sent."""
+    punct = np.atleast_2d(np.asarray(punct))
+    out = np.zeros((punct.shape[0], mask.size), np.int64)
+    out[:, np.flatnonzero(mask)] = punct[:, :int(mask.sum())]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ encoder
+def conv_encode(bits, start_state=0, tail=None):
+    """bits [B][n] -> mother codeword [B][4 (n + 6)]: the encoder of clause 11.1.1 followed by six tail bits (zeros as
+    the standard has them; `tail` = six other bits and `start_state` != 0 exist for the tests that tempt a decoder
+    with a transmitter that breaks the rule)."""
+    bits = np.atleast_2d(np.asarray(bits, np.uint8))
+    B, n = bits.shape
+    pre = np.array([(start_state >> k) & 1 for k in range(6)], np.uint8)          # a[-6] .. a[-1]; a[-1] = bit 5
+    t = np.zeros(6, np.uint8) if tail is None else np.asarray(tail, np.uint8)
+    a = np.concatenate([np.tile(pre, (B, 1)), bits, np.tile(t, (B, 1))], axis=1)  # a[:, 6 + i] = a_i
+    out = np.zeros((B, n + 6, 4), np.uint8)
+    for k, g in enumerate(GENERATORS):
+        for d in range(7):                                                          # delay d <-> bit 6 - d of g
+            if (g >> (6 - d)) & 1:
+                out[:, :, k] ^= a[:, 6 - d:6 - d + n + 6]
+    return out.reshape(B, -1)
+
+
+def prbs(n):
+    """Energy dispersal (clause 10): x^9 + x^5 + 1, the register all ones at the first bit."""
+    reg = 0x1FF
+    out = np.zeros(n, np.uint8)
+    for i in range(n):
+        b = ((reg >> 8) ^ (reg >> 4)) & 1
+        out[i] = b
+        reg = ((reg << 1) | b) & 0x1FF
+    return out
+
+
+def fib_crc_ok(fib):
+    """Clause 5.2.1: the CRC word of a 32-byte FIB is the complemented CCITT CRC (start value all ones) of bytes 0..29."""
+    f = bytes(bytearray(np.asarray(fib, np.uint8).tolist()))
+    return int((binascii.crc_hqx(f[:30], 0xFFFF) ^ 0xFFFF) == ((f[30] << 8) | f[31]))
+
+
+def fib_with_crc(data30):
+    d = bytes(bytearray(np.asarray(data30, np.uint8).tolist()))
+    c = binascii.crc_hqx(d, 0xFFFF) ^ 0xFFFF
+    return np.frombuffer(d + bytes([c >> 8, c & 0xFF]), np.uint8).copy()
+
+
+# ------------------------------------------------------------------------------------------------ Viterbi
+_N = np.arange(64)
+_PRED0 = (_N << 1) & 63                                 # older bit 0
+_PRED1 = _PRED0 | 1                                     # older bit 1
+
+
+def _branch_signs():
+    s = np.zeros((4, 128), np.int64)                    # column 2 n + o: the branch into state n from older bit o
+    for n in range(64):
+        for o in range(2):
+            reg = (n << 1) | o
+            for k, g in enumerate(GENERATORS):
+                s[k, 2 * n + o] = 2 * (bin(reg & g).count("1") & 1) - 1
+    return s
+
+
+_SIGNS = _branch_signs()
+_SHIFT = np.arange(64, dtype=np.uint64)
+
+DOCUMENTED = "older-bit-1 only when strictly larger"    # the rule the kernels and the oracle state
+OPPOSITE = "older-bit-1 also on a tie"
+
+
+class Decoded:
+    """What viterbi() found for a batch: best [B], the decisions of every node, and figures of the INPUT."""
+
+    def __init__(self, nsteps, best, dec, tie, excursion, spread, period):
+        self.nsteps, self.best, self._dec, self._tie = nsteps, best, dec, tie
+        self.excursion, self.spread, self.period = excursion, spread, period
+        self._cache = {}
+
+    def _trace(self, rule):
+        if rule not in self._cache:
+            assert rule in (DOCUMENTED, OPPOSITE)
+            B = self.best.size
+            s = np.zeros(B, np.uint64)
+            bits = np.zeros((B, self.nsteps), np.uint8)
+            tied = np.zeros(B, bool)
+            one = np.uint64(1)
+            for t in range(self.nsteps - 1, -1, -1):
+                bits[:, t] = (s >> np.uint64(5)).astype(np.uint8)                   # the bit that entered at step t
+                tie = (self._tie[t] >> s) & one
+                o = (self._dec[t] >> s) & one
+                if rule == OPPOSITE:
+                    o |= tie
+                tied |= tie.astype(bool)
+                s = ((s << one) | o) & np.uint64(63)
+            self._cache[rule] = (bits, tied, s)
+        return self._cache[rule]
+
+    def bits(self, rule=DOCUMENTED):
+        """One maximum-likelihood information sequence [B][nsteps - 6] under a stated tie rule."""
+        bits, _, start = self._trace(rule)
+        assert not start.any() and not bits[:, self.nsteps - 6:].any()              # from state 0, through a zero tail
+        return bits[:, :self.nsteps - 6]
+
+    def bytes(self, rule=DOCUMENTED):
+        return np.packbits(self.bits(rule), axis=1)
+
+    @property
+    def unique(self):
+        """True iff no node on the traced-back path had equal candidates: a second optimal path would have to merge
+        into the first at a node where both candidates are equal, so this is exactly "the optimum is unique"."""
+        return ~self._trace(DOCUMENTED)[1]
+
+
+def viterbi(mother, stats=True, period=12):
+    """mother [B][4 nsteps] integers -> Decoded.  Known start state, traceback from state 0, int64 correlation metric.
+    stats: also excursion [B] = max over t, s of |m_t(s) - m_{period floor(t / period)}(0)| (states that exist) and
+    spread [B] = max over t >= 6 of max_s m_t - min_s m_t, with m_t the metrics after t steps.  At t a multiple of
+    the period the excursion also counts the distance to the PREVIOUS reference m_{t - period}(0): that is what a
+    decoder which subtracts the state-0 metric every `period` steps holds just before it subtracts, and it is the
+    larger figure (a clean saturated codeword: 508 a step for 12 steps, not 11).  Both describe the input alone."""
+    mother = np.atleast_2d(np.asarray(mother)).astype(np.int64)
+    B = mother.shape[0]
+    nsteps = mother.shape[1] // 4
+    soft = mother.reshape(B, nsteps, 4)
+    m = np.full((B, 64), NEG_INF, np.int64)
+    m[:, 0] = 0
+    dec = np.zeros((nsteps, B), np.uint64)
+    tie = np.zeros((nsteps, B), np.uint64)
+    exc = np.zeros(B, np.int64)
+    spread = np.zeros(B, np.int64)
+    ref0 = np.zeros(B, np.int64)
+    for t in range(nsteps):
+        bm = soft[:, t, :] @ _SIGNS                                                 # [B][128]
+        c0 = m[:, _PRED0] + bm[:, 0::2]
+        c1 = m[:, _PRED1] + bm[:, 1::2]
+        d = c1 > c0
+        e = (c1 == c0) & (c0 > NEG_INF // 2)
+        m = np.where(d, c1, c0)
+        dec[t] = (d.astype(np.uint64) << _SHIFT).sum(axis=1, dtype=np.uint64)
+        tie[t] = (e.astype(np.uint64) << _SHIFT).sum(axis=1, dtype=np.uint64)
+        if stats:
+            u = t + 1                                                               # m is now m_u
+            hi = m.max(axis=1)
+            lo = np.where(m > NEG_INF // 2, m, hi[:, None]).min(axis=1)
+            if u >= 6:
+                spread = np.maximum(spread, hi - lo)
+            exc = np.maximum(exc, np.maximum(np.abs(hi - ref0), np.abs(lo - ref0)))
+            if u % period == 0:                                                     # (first against the old reference:
+                ref0 = m[:, 0].copy()                                               # `period` steps of growth, see above)
+                exc = np.maximum(exc, np.maximum(np.abs(hi - ref0), np.abs(lo - ref0)))
+    return Decoded(nsteps, m[:, 0].copy(), dec, tie, exc if stats else None, spread if stats else None, period)
+
+
+def metric_of(out_bytes, mother, dispersed=False):
+    """The correlation the codeword of `out_bytes` [B][nbytes] reaches against the mother soft bits [B][4 nsteps]
+    (punctured and erased positions 0, so they do not count).  dispersed: the bytes are a decoder's output after
+    energy dispersal was undone (FIC, MSC), so it is put back before encoding.  Judges any decoder's output without
+    comparing bits."""
+    bits = np.unpackbits(np.atleast_2d(np.asarray(out_bytes, np.uint8)), axis=1)
+    if dispersed:
+        bits = bits ^ prbs(bits.shape[1])[None, :]
+    code = conv_encode(bits).astype(np.int64) * 2 - 1
+    return (code * np.atleast_2d(np.asarray(mother)).astype(np.int64)).sum(axis=1)
+
+
+# ------------------------------------------------------------------------------------------------ FIC and MSC
+class Result:
+    pass
+
+
+def fic_reference(soft, rule=DOCUMENTED):
+    """soft [F][>= 9216] -> Result: fib [F][12][32], crc_ok [F][12], mother [4 F][3096], decoded (4 codewords a frame:
+    clause 11.2.1, three FIBs each)."""
+    soft = np.atleast_2d(np.asarray(soft))
+    F = soft.shape[0]
+    p = fic_profile()
+    r = Result()
+    r.mother = depuncture(soft[:, :NB_FIC_BITS].reshape(4 * F, 2304), p.mask)
+    r.decoded = viterbi(r.mother)
+    bits = r.decoded.bits(rule) ^ prbs(768)[None, :]
+    r.fib = np.packbits(bits, axis=1).reshape(F, 12, 32)
+    r.crc_ok = np.array([[fib_crc_ok(f) for f in fr] for fr in r.fib], np.uint8).reshape(F, 12)
+    return r
+
+
+def bitrev4(v):
+    return ((v & 1) << 3) | ((v & 2) << 1) | ((v & 4) >> 1) | ((v & 8) >> 3)
+
+
+TDI_DELAY = np.array([bitrev4(v) for v in range(16)])
+
+
+def time_interleave(frames):
+    """The transmitter (clause 12): bit i of logical frame r is sent bitrev4(i mod 16) CIFs late.  frames [R][nbits] ->
+    CIFs [R + 15][nbits], 0 where no logical frame of these reaches."""
+    R, nbits = frames.shape
+    out = np.zeros((R + 15, nbits), frames.dtype)
+    i = np.arange(nbits)
+    d = TDI_DELAY[i % 16]
+    for r in range(R):
+        out[r + d, i] = frames[r]
+    return out
+
+
+def time_deinterleave(cifs, history=None):
+    """cifs [T][nbits], history [15][nbits] = the 15 CIFs before them (None: zeros) -> logical frames [T][nbits]: row t
+    is the logical frame that is complete with CIF t, i.e. the one whose first bits went out with CIF t - 15."""
+    cifs = np.asarray(cifs)
+    T, nbits = cifs.shape
+    h = np.zeros((15, nbits), cifs.dtype) if history is None else np.asarray(history).reshape(15, nbits)
+    rows = np.concatenate([h, cifs])                    # row k = CIF k - 15
+    i = np.arange(nbits)
+    d = TDI_DELAY[i % 16]
+    return np.stack([rows[t + d, i] for t in range(T)]), rows[-15:].copy()
+
+
+def msc_reference(cifs, history, profile, rule=DOCUMENTED):
+    """cifs [T][size_cu * 64]: one sub-channel's bits of T consecutive CIFs of one stream; history as
+    time_deinterleave's -> Result: out [T][nbytes], history [15][nbits], mother, decoded."""
+    r = Result()
+    lf, r.history = time_deinterleave(cifs, history)
+    r.mother = depuncture(lf[:, :profile.kept], profile.mask)
+    r.decoded = viterbi(r.mother)
+    bits = r.decoded.bits(rule) ^ prbs(profile.nsteps - 6)[None, :]
+    r.out = np.packbits(bits, axis=1)
+    return r
