@@ -1133,6 +1133,81 @@ int dabgpu_eti_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_st
 int dabgpu_eti_parse(const uint8_t *frame, dabgpu_eti_info *info);
 
 /* ------------------------------------------------------------------------ */
+/* ETI(NI) to IQ: the way back.  n_streams         */
+/* ensembles of frames_per_stream transmission frames each; ensemble s gives    */
+/* 4 * frames_per_stream ETI frames d_eti[s][t][6144] laid out as above, and    */
+/* transmission frame f is made of ETI frames 4f .. 4f + 3:                      */
+/*   FIC   the 96 FIC bytes of ETI frame 4f + j are codeword j: energy          */
+/*         dispersal, the K = 7 rate-1/4 mother code with six tail bits, the     */
+/*         FIC puncturing (2304 bits); four codewords = the first 9216 bits.     */
+/*   MSC   a sub-channel's 8 STL bytes of ETI frame r: energy dispersal, the     */
+/*         mother code, its EEP-A / EEP-B / UEP puncturing, zero padding to       */
+/*         64 * size bits = coded[r].  Bit i of the sub-channel in the CIF of     */
+/*         ETI frame t is coded[t - D(i mod 16)][i], D = 0 8 4 12 2 10 6 14 1 9   */
+/*         5 13 3 11 7 15, t counted from the start of the stream ACROSS calls;   */
+/*         a frame before the start gives 0.  The sub-channel lies at CIF bits    */
+/*         64 SAD ..; every other CIF bit is 0.  CIF j follows the FIC at bit     */
+/*         9216 + 55296 j.                                                        */
+/*   OFDM  75 blocks of 3072 bits; block l - 1 gives q_n = ((1 - 2 p_n) +        */
+/*         j (1 - 2 p_(n+1536))) / sqrt 2 on carrier k_n of the frequency         */
+/*         interleaver, z_l = z_(l-1) q with z_0 the phase reference symbol;      */
+/*         every symbol is the inverse FFT at unit mean power behind its 504      */
+/*         prefix samples.  The frame: 2656 null samples, the PRS, 75 data        */
+/*         symbols = 196 608 cf32 samples, times cfg->gain.                        */
+/*   null  zeros, or with cfg->tii_main (0..69) and cfg->tii_sub (0..23) set the   */
+/*         TII symbol of that transmitter (its 32 carriers with the PRS's phase,   */
+/*         extended cyclically over the 2656 samples).                             */
+/* An ETI frame is TAKEN when its FSYNC is one of the two patterns and its         */
+/* FICF/NST, MID/FL and STC words are the plan's; any other frame is modulated     */
+/* as 96 zero FIC bytes and zero stream bytes and named in the status.  CRCs are   */
+/* not checked here (dabgpu_eti_parse does, on the host).  A transmission frame    */
+/* whose first ETI frame has FP mod 4 != 0 is flagged and modulated all the same.  */
+/*                                                                                */
+/* dabgpu_eti_streams_from_frame   host only.  The list dabgpu_eti_layout takes,    */
+/*            read back from one frame's STC (in the frame's order): SCID, start    */
+/*            address, bit rate from STL, protection from TPL, the size from the    */
+/*            EEP profile or the UEP table row.  streams holds 64 entries, *n       */
+/*            receives NST.  DABGPU_ERR_ARG for NST > 64 or a TPL/STL pair that      */
+/*            names no profile.                                                      */
+/* dabgpu_mod_default_cfg   gain 1, tii_main = tii_sub = -1 (a null symbol of zeros). */
+/* dabgpu_mod_state_bytes   size of the per-stream device record that carries the    */
+/*            time interleaver from call to call (what the next call needs of the    */
+/*            last 15 CIFs).  All zero = a stream that starts.                        */
+/* dabgpu_modulate_eti_dev   plan and streams: what dabgpu_eti_layout gave and took   */
+/*            (every sub-channel's size must be its profile's).  d_eti 16-byte        */
+/*            aligned.  d_state_in / d_state_out [n_streams] records, either may be    */
+/*            NULL (in: the streams start here), 16-byte aligned, not the same.        */
+/*            d_iq [n_streams*frames_per_stream] frames, frame_stride complex samples  */
+/*            apart (>= 196608, even), 16-byte aligned; samples between frames are not */
+/*            touched.  d_status [n_streams*frames_per_stream], 8-byte aligned.         */
+/*            Four launches (five when the TII table changes), no synchronisation;     */
+/*            a refused call (DABGPU_ERR_ARG / DABGPU_ERR_PROFILE) enqueues nothing.    */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_MOD_BAD_INPUT  1        /* at least one of the four ETI frames was not taken      */
+#define DABGPU_MOD_MISALIGNED 2        /* FP of the first ETI frame is not a multiple of 4       */
+typedef struct dabgpu_mod_status {     /* per transmission frame, 8 bytes */
+    uint32_t flags;                    /* DABGPU_MOD_*                                               */
+    uint8_t  refused;                  /* bit j = ETI frame 4f + j was not taken                     */
+    uint8_t  reserved[3];              /* 0                                                          */
+} dabgpu_mod_status;
+
+typedef struct dabgpu_mod_cfg {
+    float   gain;                      /* every sample is multiplied by it                           */
+    int32_t tii_main, tii_sub;         /* main 0..69 and sub 0..23 identifier, or both -1            */
+    int32_t reserved;                  /* 0                                                          */
+} dabgpu_mod_cfg;
+
+typedef struct dabgpu_mod_state dabgpu_mod_state;    /* DEVICE memory, opaque, dabgpu_mod_state_bytes() each */
+
+int dabgpu_eti_streams_from_frame(const uint8_t *frame, dabgpu_eti_stream *streams, int *n);
+void dabgpu_mod_default_cfg(dabgpu_mod_cfg *cfg);
+size_t dabgpu_mod_state_bytes(void);
+int dabgpu_modulate_eti_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, const dabgpu_eti_stream *streams,
+                            const dabgpu_mod_cfg *cfg, int n_streams, int frames_per_stream, const uint8_t *d_eti,
+                            const dabgpu_mod_state *d_state_in, dabgpu_mod_state *d_state_out, float *d_iq,
+                            size_t frame_stride, dabgpu_mod_status *d_status, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */
@@ -1243,6 +1318,8 @@ int dabgpu_viterbi(dabgpu_ctx *ctx, const int8_t *punct, int n_codewords, const 
 /* >= 24 576 codewords): forward pass | traceback | de-interleaver history copy */
 /* (DABGPU_ERR_ARG when no timed call took that path).                          */
 /* 7 (both calls) = the ETI launches of dabgpu_eti_frames_dev.                  */
+/* 8 / 9 (both calls) = dabgpu_modulate_eti_dev: the encoder with its pre-pass | */
+/* the symbol kernel.                                                           */
 /* ------------------------------------------------------------------------ */
 int dabgpu_set_timing(dabgpu_ctx *ctx, int enable);
 int dabgpu_last_kernel_ms(dabgpu_ctx *ctx, int which, float *ms);

@@ -128,9 +128,9 @@ inline PunctureProfile make_fic_profile() {
 }
 
 // clause 11.3.2 (EEP); returns false if the profile is invalid. size_cu receives the size.
-inline bool make_eep_profile(int type, int level, int bitrate, PunctureProfile &p, int &size_cu) {
+// the two runs of blocks (of 128 mother bits) of an EEP profile and their puncturing indices, before any mask is built
+inline bool eep_runs(int type, int level, int bitrate, int &L1, int &L2, int &P1, int &P2, int &size_cu) {
     if (level < 1 || level > 4 || bitrate <= 0) return false;
-    int L1, L2, P1, P2;
     if (type == 0) {
         if (bitrate % 8) return false;
         const int n = bitrate / 8;
@@ -151,6 +151,12 @@ inline bool make_eep_profile(int type, int level, int bitrate, PunctureProfile &
     } else {
         return false;
     }
+    return true;
+}
+
+inline bool make_eep_profile(int type, int level, int bitrate, PunctureProfile &p, int &size_cu) {
+    int L1, L2, P1, P2;
+    if (!eep_runs(type, level, bitrate, L1, L2, P1, P2, size_cu)) return false;
     p = PunctureProfile();
     append_blocks(p.mask, L1, P1);
     append_blocks(p.mask, L2, P2);

@@ -145,7 +145,8 @@ int build_fic_code(dabgpu_ctx *ctx) {
 // 0 / 1 / 2 the forward pass | traceback | history copy of TIMER_MSC's grouped lane decode.  nullptr: no such number.
 Timer *timer_of(dabgpu_ctx *ctx, int which, int *part) {
     *part = which >= WHICH_MSC_FORWARD && which <= WHICH_MSC_HISTORY ? which - WHICH_MSC_FORWARD : -1;
-    if (which < 0 || which > WHICH_ETI) return nullptr;
+    if (which < 0 || which > WHICH_MOD_SYMBOLS) return nullptr;
+    if (which == WHICH_MOD_ENCODE || which == WHICH_MOD_SYMBOLS) return &ctx->timers[which == WHICH_MOD_ENCODE ? TIMER_MOD_ENCODE : TIMER_MOD_SYMBOLS];
     return &ctx->timers[*part >= 0 ? TIMER_MSC : which == WHICH_ETI ? TIMER_ETI : which];
 }
 }  // namespace
@@ -385,6 +386,7 @@ void dabgpu_destroy(dabgpu_ctx *ctx) {
     for (void *p : ctx->d_stage) if (p) (void)hipFree(p);
     if (ctx->d_lane_scratch) (void)hipFree(ctx->d_lane_scratch);
     if (ctx->d_acq_scratch) (void)hipFree(ctx->d_acq_scratch);
+    if (ctx->d_mod_tables) (void)hipFree(ctx->d_mod_tables);
     for (void *p : ctx->keep_tables) (void)hipFree(p);
     for (Timer &t : ctx->timers)
         for (int i = 0; i < TIMER_RING; i++) {

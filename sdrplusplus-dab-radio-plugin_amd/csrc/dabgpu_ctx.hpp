@@ -1,7 +1,7 @@
 // dabgpu_ctx.hpp -- the context behind the opaque dabgpu_ctx handle and the helpers the translation units of the C ABI
 // share (dabgpu_api.hip: context, tables, timing, stream state; dabgpu_ofdm_api.hip: front end, synchronisation,
 // acquisition, tracking; dabgpu_measure_api.hip: TII and CIR; dabgpu_decode_api.hip: channel decoder; dabgpu_eti_api.hip:
-// ETI(NI) output; dabgpu_placement.hip: frame buffers; dabgpu_pipeline.hip: the host-fed ring).  Internal to libdabgpu.
+// ETI(NI) output; dabgpu_mod_api.hip: ETI(NI) to IQ; dabgpu_placement.hip: frame buffers; dabgpu_pipeline.hip: the host-fed ring).  Internal to libdabgpu.
 #pragma once
 #include "../../include/dabgpu.h"
 
@@ -45,9 +45,9 @@ struct Timer {
 };
 
 // ctx->timers, and what dabgpu_last_kernel_ms / dabgpu_mean_kernel_ms call them (dabgpu.h): the first four by their own
-// numbers, the parts of TIMER_MSC's grouped lane decode as 4 / 5 / 6 (_mean_ only), the ETI launches as 7
-enum TimerSlot { TIMER_OFDM = 0, TIMER_FIC = 1, TIMER_MSC = 2, TIMER_FFT = 3, TIMER_ETI = 4, TIMER_SLOTS };
-enum { WHICH_MSC_FORWARD = 4, WHICH_MSC_TRACEBACK = 5, WHICH_MSC_HISTORY = 6, WHICH_ETI = 7 };
+// numbers, the parts of TIMER_MSC's grouped lane decode as 4 / 5 / 6 (_mean_ only), the ETI launches as 7, the modulator's encoder (with its pre-pass) and symbol kernel as 8 / 9
+enum TimerSlot { TIMER_OFDM = 0, TIMER_FIC = 1, TIMER_MSC = 2, TIMER_FFT = 3, TIMER_ETI = 4, TIMER_MOD_ENCODE = 5, TIMER_MOD_SYMBOLS = 6, TIMER_SLOTS };
+enum { WHICH_MSC_FORWARD = 4, WHICH_MSC_TRACEBACK = 5, WHICH_MSC_HISTORY = 6, WHICH_ETI = 7, WHICH_MOD_ENCODE = 8, WHICH_MOD_SYMBOLS = 9 };
 
 // ctx->d_stage.  The first six are shared by role across the host-pointer entry points (two buffers of one call never
 // share one); the rest belong to one family of calls each.  One caller stream at a time per context (dabgpu.h, conventions).
@@ -63,6 +63,8 @@ enum StageSlot {
     STAGE_TII = 7,          // the TII calls' per-frame records
     STAGE_CIR = 8,          // the CIR calls'
     STAGE_ETI_COUNTS = 9,   // the ETI call's per-stream CIF counts
+    STAGE_MOD_CODED = 10,   // the modulator's coded records, one per ETI frame
+    STAGE_MOD_CUM = 11,     // ... and running quarter turns, one pair of bit planes per data symbol
     STAGE_SLOTS
 };
 
@@ -144,6 +146,8 @@ struct dabgpu_ctx {
     dabapi::Arena arena;                 // dabgpu_alloc_frame_buffers(DABGPU_PLACE_DOMAINS)
     dabapi::Pipeline *pipe = nullptr;    // dabgpu_pipe_open
     int iq_format = 0;                   // DABGPU_IQ_* of the samples the device-pointer calls read (dabgpu_set_iq_format)
+    void *d_mod_tables = nullptr;        // dabgpu_modulate_eti_dev: PRBS bytes, bin -> data index, the TII null symbol (made on first use)
+    int mod_tii_main = -2, mod_tii_sub = -2;             // the transmitter whose null symbol the table holds
 };
 
 namespace dabapi {

@@ -545,6 +545,57 @@ struct EtiAnchorArgs {
 };
 hipError_t launch_eti(const EtiAnchorArgs &p, const EtiArgs &a, hipStream_t s);
 
+// ---- modulator: ETI(NI) frames to Mode-I IQ (mod_kernels.hip) -----------------
+// One ETI frame's coded bits ("coded record"): the 2304 punctured FIC bits of its three FIBs, then the 55 296 bits of its
+// CIF BEFORE time interleaving (every sub-channel's punctured codeword at 64 SAD, zeros elsewhere), bit i in bit i % 32
+// of word i / 32.
+constexpr int MOD_FIC_WORDS = 72, MOD_CIF_WORDS = 1728, MOD_CODED_WORDS = MOD_FIC_WORDS + MOD_CIF_WORDS;
+constexpr int MOD_DEPTH = 15;                  // CIFs the time interleaver looks back
+constexpr int MOD_SYM_WORDS = 96;              // the 3072 bits of one data symbol
+constexpr int MOD_ITEMS = 77;                  // null symbol, PRS, 75 data symbols
+constexpr int MOD_PRBS_BYTES = 511;            // the energy-dispersal sequence repeats after 511 bits, so after 511 bytes too
+constexpr int MOD_BAD_INPUT = 1, MOD_MISALIGNED = 2;
+struct ModState {              // == dabgpu_mod_state (103 680 bytes): the CIF parts of the last 15 coded records, oldest first
+    uint32_t cif[MOD_DEPTH][MOD_CIF_WORDS];
+};
+struct ModStatus {             // == dabgpu_mod_status
+    uint32_t flags;
+    uint8_t refused, reserved[3];
+};
+struct ModCode {               // one codeword of an ETI frame: up to four runs of 128-bit blocks, then the tail
+    uint16_t in_offset, in_bytes;              // where its bytes are in the frame
+    uint16_t out_word;                         // first word of its punctured bits in the coded record
+    uint16_t blocks[4];
+    uint8_t pi[4];
+};
+struct ModTables {
+    const uint8_t *prbs;       // [511] energy-dispersal bytes
+    const int16_t *n_of_bin;   // [2048] data index n of FFT bin b, -1 = not a carrier
+    const int8_t *prs_qt;      // [2048] quarter turns of the PRS per bin
+    const float2 *twiddle;     // SyncTables::twiddle
+    const float2 *null_symbol; // [2656] the TII null symbol at gain 1, or nullptr = zeros
+};
+struct ModArgs {               // by value in the kernel arguments (~1.7 KB)
+    ModCode code[1 + ETI_MAX_STREAMS];         // [0] the FIC, then the plan's streams
+    uint32_t header[2 + ETI_MAX_STREAMS];      // the plan's frame bytes 0 .. 8 + 4 nst as little-endian words
+    int n_codes, nst;
+    const uint8_t *eti;        // [n_streams][n_cif][6144]
+    const ModState *state_in;
+    ModState *state_out;
+    uint32_t *coded;           // [n_streams][n_cif][MOD_CODED_WORDS]
+    uint32_t *cum;             // [n_frames][75][96]: per data symbol the running sum of the quarter turns, low bits | high bits
+    float2 *iq;
+    size_t frame_stride;
+    ModStatus *status;
+    float gain;
+    int n_streams, frames_per_stream;
+};
+// two launches each; `symbols` follows `encode` on the same stream
+hipError_t launch_mod_encode(const ModTables &t, const ModArgs &a, hipStream_t s);
+hipError_t launch_mod_symbols(const ModTables &t, const ModArgs &a, hipStream_t s);
+// the null symbol of transmitter (main p, sub c) at gain 1 into out[2656]
+hipError_t launch_mod_tii(const int8_t *prs_qt, int main_id, int sub_id, float2 *out, hipStream_t s);
+
 // Let every kernel that takes dynamic LDS use the whole 160 KB of a CU: set once per context creation (on the
 // context's device) instead of per launch.
 hipError_t init_viterbi_kernel_attributes();

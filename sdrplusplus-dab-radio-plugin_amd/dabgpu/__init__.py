@@ -50,6 +50,7 @@ EXPORTS = [
     "dabgpu_tii_default_cfg", "dabgpu_tii_pattern", "dabgpu_tii_frames_dev", "dabgpu_tii_acquired_dev", "dabgpu_tii_decode",
     "dabgpu_cir_default_cfg", "dabgpu_cir_frames_dev", "dabgpu_cir_acquired_dev", "dabgpu_cir_analyse",
     "dabgpu_eti_layout", "dabgpu_eti_history_bytes", "dabgpu_eti_frames_dev", "dabgpu_eti_parse",
+    "dabgpu_eti_streams_from_frame", "dabgpu_mod_default_cfg", "dabgpu_mod_state_bytes", "dabgpu_modulate_eti_dev",
 ]
 
 ABI_VERSION = 6
@@ -334,6 +335,46 @@ def eti_history_bytes():
     return int(lib().dabgpu_eti_history_bytes())
 
 
+#: ETI(NI) to IQ (include/dabgpu.h, "ETI(NI) to IQ"): dabgpu_mod_status, one transmission frame's record
+MOD_BAD_INPUT, MOD_MISALIGNED = 1, 2
+MOD_STATUS_DTYPE = np.dtype([("flags", np.uint32), ("refused", np.uint8), ("reserved", np.uint8, (3,))])
+assert MOD_STATUS_DTYPE.itemsize == 8
+#: mean_kernel_ms / last_kernel_ms selectors of the modulator: the encoder with its pre-pass, the symbol kernel
+WHICH_MOD_ENCODE, WHICH_MOD_SYMBOLS = 8, 9
+
+
+class ModCfg(C.Structure):
+    """dabgpu_mod_cfg: gain, and the transmitter whose identification the null symbol carries (-1, -1: zeros)."""
+    _fields_ = [("gain", C.c_float), ("tii_main", C.c_int32), ("tii_sub", C.c_int32), ("reserved", C.c_int32)]
+
+
+def mod_cfg(**kw):
+    c = ModCfg()
+    lib().dabgpu_mod_default_cfg(C.byref(c))
+    for k, v in kw.items():
+        if not hasattr(c, k):
+            raise TypeError("dabgpu_mod_cfg has no field " + k)
+        setattr(c, k, v)
+    return c
+
+
+def mod_state_bytes():
+    return int(lib().dabgpu_mod_state_bytes())
+
+
+def eti_streams(frame):
+    """The stream list of one 6144-byte ETI(NI) frame, read back from its STC (dabgpu_eti_streams_from_frame: host only):
+    [EtiStream, ...] in the frame's order, what eti_layout takes.  DabGpuError (ERR_ARG) for a TPL/STL pair that names
+    no protection profile."""
+    f = np.ascontiguousarray(np.frombuffer(bytes(frame), np.uint8) if isinstance(frame, (bytes, bytearray)) else frame, np.uint8)
+    if f.size != ETI_FRAME_BYTES:
+        raise ValueError("an ETI(NI) frame is %d bytes, got %d" % (ETI_FRAME_BYTES, f.size))
+    arr = (EtiStream * ETI_MAX_STREAMS)()
+    n = C.c_int(0)
+    _check(lib().dabgpu_eti_streams_from_frame(_p(f.reshape(-1)), arr, C.byref(n)), "dabgpu_eti_streams_from_frame")
+    return [EtiStream(arr[k].subchannel_id, arr[k].sc) for k in range(n.value)]
+
+
 def eti_parse(frame):
     """Check one 6144-byte ETI(NI) frame (sync, lengths, both CRCs; dabgpu_eti_parse: host only) and give its parts:
     dict with err, fct, fp, nst, fl, length, streams [{scid, sad, tpl, stl, data}], fic (96 bytes).  ValueError for a
@@ -456,6 +497,12 @@ def load_library(path):
     L.dabgpu_eti_history_bytes.argtypes = []
     L.dabgpu_eti_frames_dev.argtypes = [vp, C.POINTER(EtiPlan), i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dabgpu_eti_parse.argtypes = [vp, C.POINTER(EtiInfo)]
+    L.dabgpu_eti_streams_from_frame.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    L.dabgpu_mod_default_cfg.restype = None
+    L.dabgpu_mod_default_cfg.argtypes = [C.POINTER(ModCfg)]
+    L.dabgpu_mod_state_bytes.restype = C.c_size_t
+    L.dabgpu_mod_state_bytes.argtypes = []
+    L.dabgpu_modulate_eti_dev.argtypes = [vp, C.POINTER(EtiPlan), vp, C.POINTER(ModCfg), i, i, vp, vp, vp, vp, sz, vp, vp]
     return L
 
 
@@ -1001,6 +1048,49 @@ class Context:
                             d_history_out=eti_out.data_ptr())
         self.sync()
         return eti, status, (msc_out, eti_out)
+
+    def modulate_eti_dev(self, plan, streams, n_streams, frames_per_stream, d_eti, d_iq, d_status, cfg=None, d_state_in=None,
+                         d_state_out=None, frame_stride=NB_FRAME_SAMPLES, stream=None):
+        """ETI(NI) frames d_eti [n_streams][frames_per_stream*4][6144] -> Mode-I IQ d_iq [n_streams*frames_per_stream] frames of
+        complex64, frame_stride samples apart, and d_status (MOD_STATUS_DTYPE) per transmission frame
+        (dabgpu_modulate_eti_dev).  streams: the list eti_layout made `plan` from.  The states (mod_state_bytes() per stream)
+        carry the time interleaver from call to call.  Enqueues only."""
+        items = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+        arr = (EtiStream * max(len(items), 1))(*items)
+        if len(items) != plan.nst:
+            raise ValueError("the plan has %d streams, the list %d" % (plan.nst, len(items)))
+        _check(self._lib.dabgpu_modulate_eti_dev(self._h, C.byref(plan), arr, None if cfg is None else C.byref(cfg), n_streams,
+                                                 frames_per_stream, d_eti, d_state_in, d_state_out, d_iq, frame_stride, d_status,
+                                                 stream), "dabgpu_modulate_eti_dev")
+
+    def modulate_eti(self, eti, streams, cfg=None, state=None, frame_stride=NB_FRAME_SAMPLES, out=None):
+        """eti: torch uint8 tensor [n_streams][n_cif][6144] on this context's device (n_cif a multiple of 4); streams:
+        [(subchannel_id, Subchannel) or EtiStream, ...] (eti_streams(frame) reads them from a frame).  state: what an earlier
+        call on the same streams returned (None: the streams start here).  out: a complex64 tensor
+        [n_streams * n_cif / 4][frame_stride] to write into (only the 196 608 samples of every frame are touched).
+        -> (iq complex64 [n_frames][frame_stride], status uint8 [n_frames][8] (view as MOD_STATUS_DTYPE on the host), state);
+        device tensors, the work is finished when the call returns."""
+        import torch
+        if eti.dtype != torch.uint8 or eti.dim() != 3 or eti.shape[2] != ETI_FRAME_BYTES or eti.shape[1] % 4 or not eti.is_contiguous():
+            raise ValueError("eti must be a contiguous uint8 tensor [n_streams][4 * frames][6144]")
+        items = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+        plan = eti_layout(items)
+        dev = eti.device
+        n_streams, fps = eti.shape[0], eti.shape[1] // 4
+        n_frames = n_streams * fps
+        if out is None:
+            out = torch.empty((n_frames, frame_stride), dtype=torch.complex64, device=dev)
+        elif out.dtype != torch.complex64 or tuple(out.shape) != (n_frames, frame_stride) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous complex64 tensor [%d][%d]" % (n_frames, frame_stride))
+        status = torch.empty((n_frames, 8), dtype=torch.uint8, device=dev)
+        state_out = torch.empty((n_streams, mod_state_bytes()), dtype=torch.uint8, device=dev)
+        # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
+        torch.cuda.current_stream(dev).synchronize()
+        self.modulate_eti_dev(plan, items, n_streams, fps, eti.data_ptr(), out.data_ptr(), status.data_ptr(), cfg=cfg,
+                              d_state_in=None if state is None else state.data_ptr(), d_state_out=state_out.data_ptr(),
+                              frame_stride=frame_stride)
+        self.sync()
+        return out, status, state_out
 
     def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
         """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).
