@@ -373,7 +373,7 @@ void dabgpu_destroy(dabgpu_ctx *ctx) {
     DeviceGuard guard(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->d_states) (void)hipFree(ctx->d_states);
-    for (auto &h : ctx->sub_history) { (void)hipFree(h.ring[0]); (void)hipFree(h.ring[1]); }
+    ctx->sub_history.clear();
     if (ctx->h_bounce) (void)hipHostFree(ctx->h_bounce);
     if (ctx->d_twiddle) (void)hipFree(ctx->d_twiddle);
     if (ctx->d_bin_of_n) (void)hipFree(ctx->d_bin_of_n);

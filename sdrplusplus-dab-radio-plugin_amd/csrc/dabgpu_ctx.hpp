@@ -1,7 +1,8 @@
 // dabgpu_ctx.hpp -- the context behind the opaque dabgpu_ctx handle and the helpers the translation units of the C ABI
 // share (dabgpu_api.hip: context, tables, timing, stream state; dabgpu_ofdm_api.hip: front end, synchronisation,
-// acquisition, tracking; dabgpu_measure_api.hip: TII and CIR; dabgpu_decode_api.hip: channel decoder; dabgpu_eti_api.hip:
-// ETI(NI) output; dabgpu_mod_api.hip: ETI(NI) to IQ; dabgpu_placement.hip: frame buffers; dabgpu_pipeline.hip: the host-fed ring).  Internal to libdabgpu.
+// acquisition, tracking; dabgpu_measure_api.hip: TII, CIR, reception quality; dabgpu_decode_api.hip: channel decoder;
+// dabgpu_eti_api.hip: ETI(NI) output; dabgpu_mod_api.hip: ETI(NI) to IQ; dabgpu_placement.hip: frame buffers;
+// dabgpu_pipeline.hip: the host-fed ring; decode_plan.hpp: what the decoder's entry points share).  Internal to libdabgpu.
 #pragma once
 #include "../../include/dabgpu.h"
 
@@ -70,6 +71,63 @@ enum StageSlot {
 
 struct Pipeline;                         // dabgpu_pipeline.hip
 
+// The de-interleaver rings of the sub-channels a state-keeping call decodes (dabgpu_decode_stream_frames: one stream;
+// dabgpu_pipe_submit: n_streams of them), kept on the device between calls and double-buffered: [n_streams][15][bits] a
+// side.  A call acquires the ring of every sub-channel it lists, decodes from in() to out() and commits.  A ring that
+// misses a call no longer continues its streams: commit drops it, and a later call starts that sub-channel from erasures
+// (this also bounds the set over any number of reconfigurations).  A call that fails after its first acquire leaves
+// rings that have missed this frame: its caller clears the set.
+struct HistoryRings {
+    struct Ring {
+        int start_address, length, n_streams;
+        int8_t *buf[2];
+        int cur;
+        bool live;                       // acquired by the current call
+    };
+    std::vector<Ring> rings;
+    // the ring of (start, length, n_streams) from the call before, or a new one whose input side is erased on `s`: its
+    // index for in() / out(), or DABGPU_ERR_* (< 0)
+    int acquire(int start_address, int length, int n_streams, hipStream_t s) {
+        int k = -1;
+        for (size_t j = 0; j < rings.size(); j++)
+            if (rings[j].start_address == start_address && rings[j].length == length && rings[j].n_streams == n_streams) k = int(j);
+        if (k < 0) {
+            Ring r{};
+            r.start_address = start_address;
+            r.length = length;
+            r.n_streams = n_streams;
+            const size_t bytes = size_t(n_streams) * 15 * size_t(length) * dab::CU_BITS;
+            if (hipMalloc(reinterpret_cast<void **>(&r.buf[0]), bytes) != hipSuccess) return DABGPU_ERR_NOMEM;
+            if (hipMalloc(reinterpret_cast<void **>(&r.buf[1]), bytes) != hipSuccess) { (void)hipFree(r.buf[0]); return DABGPU_ERR_NOMEM; }
+            k = int(rings.size());
+            rings.push_back(r);
+            if (hipMemsetAsync(r.buf[0], 0, bytes, s) != hipSuccess) return DABGPU_ERR_HIP;
+        }
+        rings[size_t(k)].live = true;
+        return k;
+    }
+    const int8_t *in(int k) const { return rings[size_t(k)].buf[rings[size_t(k)].cur]; }
+    int8_t *out(int k) const { return rings[size_t(k)].buf[rings[size_t(k)].cur ^ 1]; }
+    // the call went through: what it wrote is the next call's input; the rings it left out go
+    // (`busy`: a stream whose work may still use them, waited for before the first one is freed)
+    void commit(hipStream_t busy = nullptr) {
+        size_t kept = 0;
+        bool dropped = false;
+        for (Ring &r : rings) {
+            if (r.live) { r.live = false; r.cur ^= 1; rings[kept++] = r; continue; }
+            if (busy && !dropped) (void)hipStreamSynchronize(busy);
+            dropped = true;
+            (void)hipFree(r.buf[0]);
+            (void)hipFree(r.buf[1]);
+        }
+        rings.resize(kept);
+    }
+    void clear() {
+        for (Ring &r : rings) { (void)hipFree(r.buf[0]); (void)hipFree(r.buf[1]); }
+        rings.clear();
+    }
+};
+
 // The domain-aware frame buffers of a context live inside TWO address ranges, both reserved by the first such allocation
 // and given back by dabgpu_destroy only (dabgpu_placement.hip): `probe` is where physical chunks are mapped while their
 // HBM domains are found, `pair` is where the pair handed to the caller is mapped.  (Two, not one: access rights are only
@@ -131,15 +189,7 @@ struct dabgpu_ctx {
     bool loop_dd = false;                // stream call without a correlation buffer: decision-directed fine loop
     float dd_gate = 2.5f;                // decision-directed loop: quality gate (dabgpu_set_loop_gate, dabk::dd_loop_error)
     int keep_symbols = 75;               // data symbols per frame the current selection demodulates (75: no selection)
-    // dabgpu_decode_stream_frames: de-interleaver rings of the stream's sub-channels, kept on the device between calls
-    struct SubHistory {
-        int start_address, length;
-        size_t bytes;
-        int8_t *ring[2];
-        int cur;
-        bool live;                       // decoded in the current call (a ring that misses a frame is stale: dropped)
-    };
-    std::vector<SubHistory> sub_history;
+    dabapi::HistoryRings sub_history;    // dabgpu_decode_stream_frames: the stream's sub-channels
     void *h_bounce = nullptr;            // page-locked landing area of that call's single download (+ 64 bytes: the
     size_t h_bounce_bytes = 0;           // word wait_for_signal watches sits behind the payload)
     unsigned long long signal_seq = 0;   // number of the last one-frame call that ended through wait_for_signal
@@ -210,7 +260,7 @@ struct ScopedTimer {
 // wake-up; instead a one-thread launch behind the call's last kernel stores the call's number into a word of the page-locked
 // landing area and the host watches that word -- for at most SIGNAL_SPIN_US (no frame call takes that long on an idle
 // device; a core is never held longer), then it sleeps on the stream after all.
-// `flag_host` / `flag_dev`: the two addresses of the word; `seq`: this call's number.
+// `w`: the two addresses of the word and this call's number.
 // (already_signalled: the last kernel of the call stores the word itself -- a single-workgroup launch can)
 // results_coherent: the kernels of these calls write their results straight into page-locked HOST memory, and
 // a watched word orders nothing for memory the device does not write coherently: HIP guarantees host visibility of kernel
@@ -218,14 +268,23 @@ struct ScopedTimer {
 // only when every such buffer is KNOWN to be coherent -- the context's own landing area and buffers from dabgpu_host_alloc
 // (known_coherent_host) -- and the call ends in hipStreamSynchronize otherwise.
 constexpr long SIGNAL_SPIN_US = 200;
-inline int wait_for_signal(hipStream_t s, volatile unsigned long long *flag_host, unsigned long long *flag_dev, unsigned long long seq,
-                           bool already_signalled = false, bool results_coherent = true) {
+// the watched word: the last 64 bytes of the landing area (ensure_bounce first), and the number of the call that takes it.
+// `h_dev`: the address the device reaches ctx->h_bounce under.
+struct SignalWord {
+    volatile unsigned long long *host;
+    unsigned long long *dev;
+    unsigned long long seq;
+    SignalWord(dabgpu_ctx *ctx, void *h_dev)
+        : host(reinterpret_cast<volatile unsigned long long *>(static_cast<char *>(ctx->h_bounce) + ctx->h_bounce_bytes - 64)),
+          dev(reinterpret_cast<unsigned long long *>(static_cast<char *>(h_dev) + ctx->h_bounce_bytes - 64)), seq(++ctx->signal_seq) {}
+};
+inline int wait_for_signal(hipStream_t s, const SignalWord &w, bool already_signalled = false, bool results_coherent = true) {
     if (!results_coherent) return hipStreamSynchronize(s) == hipSuccess ? DABGPU_OK : DABGPU_ERR_HIP;
-    if (!already_signalled && dabk::launch_signal(flag_dev, seq, s) != hipSuccess) return DABGPU_ERR_HIP;
+    if (!already_signalled && dabk::launch_signal(w.dev, w.seq, s) != hipSuccess) return DABGPU_ERR_HIP;
     const auto give_up = std::chrono::steady_clock::now() + std::chrono::microseconds(SIGNAL_SPIN_US);
     for (;;) {
         for (int i = 0; i < 64; i++) {
-            if (*flag_host == seq) {
+            if (*w.host == w.seq) {
                 __atomic_thread_fence(__ATOMIC_ACQUIRE);
                 return DABGPU_OK;
             }

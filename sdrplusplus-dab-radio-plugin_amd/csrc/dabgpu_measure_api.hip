@@ -1,6 +1,7 @@
 // dabgpu_measure_api.hip -- the measurement entry points of the C ABI (include/dabgpu.h): transmitter identification (TII)
-// from the null symbol, channel impulse response (CIR) from the phase reference symbol; their host-side decoders.
-#include "dabgpu_ctx.hpp"
+// from the null symbol, channel impulse response (CIR) from the phase reference symbol; their host-side decoders;
+// reception quality (MER, pre-Viterbi channel BER) from what the front end and the decoder left on the device.
+#include "decode_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -247,6 +248,69 @@ int dabgpu_cir_analyse(const dabgpu_cir_acc *acc, const dabgpu_cir_cfg *cfg, dab
     }
     if (report) *report = r;
     return n_paths;
+}
+
+// ---------------------------------------------------------------------------- reception quality
+static_assert(sizeof(dabgpu_mer) == sizeof(dabk::MerSums), "ABI struct mirrors the kernel's");
+static_assert(sizeof(dabgpu_ber_count) == 8, "{errors, bits}: one uint2 per codeword");
+
+int dabgpu_mer_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_frames, int first_symbol, int n_symbols,
+                   dabgpu_mer *d_out, void *stream) {
+    if (!ctx || !d_soft || !d_out || n_frames < 0) return DABGPU_ERR_ARG;
+    if (first_symbol < 0 || n_symbols < 1 || first_symbol + n_symbols > NB_DATA_SYMBOLS) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    const size_t stride = n_frames > 1 ? soft_stride : 0;     // (one frame: the stride is never used)
+    if (n_frames > 1 && stride < size_t(first_symbol + n_symbols) * NB_SYM_BITS) return DABGPU_ERR_ARG;
+    if (((reinterpret_cast<uintptr_t>(d_soft) | stride) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return DABGPU_ERR_ARG;
+    if (n_frames == 0) return DABGPU_OK;
+    HIP_TRY(dabk::launch_mer(d_soft, stride, n_frames, first_symbol, n_symbols, reinterpret_cast<dabk::MerSums *>(d_out),
+                             pick_stream(ctx, stream)));
+    return DABGPU_OK;
+}
+
+int dabgpu_channel_ber_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream,
+                           const uint8_t *d_fib, dabgpu_ber_count *d_fic, const dabgpu_subchannel *sc, int n_subchannels,
+                           const int8_t *const *d_history_in, const uint8_t *const *d_out, dabgpu_ber_count *const *d_msc,
+                           void *stream) {
+    if (!ctx || !d_soft || n_streams < 0 || frames_per_stream < 0 || n_subchannels < 0) return DABGPU_ERR_ARG;
+    if (d_fib && (!d_fic || (reinterpret_cast<uintptr_t>(d_fic) & 7))) return DABGPU_ERR_ARG;
+    if (n_subchannels > 0 && (!sc || !d_out || !d_msc)) return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    const size_t nframes = size_t(n_streams) * frames_per_stream;
+    if (nframes > 1 && soft_stride < size_t(n_subchannels > 0 ? NB_FRAME_BITS : NB_FIC_BITS)) return DABGPU_ERR_ARG;
+    // validate everything before enqueueing anything: profiles, bounds, no overlap inside the CIF (as the decode calls)
+    std::vector<dabk::BerItem> items;
+    if (d_fib) {
+        dabk::BerItem it{};
+        it.nsteps = ctx->fic.prof.nsteps;
+        it.prbs_bytes = ctx->fic.d_prbs;
+        it.punct_idx = ctx->fic.d_punct_idx;
+        it.args.soft = d_soft;
+        it.args.soft_stride = soft_stride;
+        it.args.n_streams = n_streams;
+        it.args.frames_per_stream = frames_per_stream;
+        it.args.out = const_cast<uint8_t *>(d_fib);       // (read only)
+        it.is_fic = true;
+        it.counts = reinterpret_cast<uint32_t *>(d_fic);
+        items.push_back(it);
+    }
+    const SubchannelPlan plan(ctx, sc, n_subchannels, d_out);
+    if (plan.rc) return plan.rc;
+    for (int i = 0; i < n_subchannels; i++) {
+        if (!d_msc[i] || (reinterpret_cast<uintptr_t>(d_msc[i]) & 7)) return DABGPU_ERR_ARG;
+        const DeviceCode *dc = plan.code[size_t(i)];
+        dabk::BerItem it{};
+        it.nsteps = dc->prof.nsteps;
+        it.prbs_bytes = dc->d_prbs;
+        it.punct_idx = dc->d_punct_idx;
+        it.args = msc_args(sc[i], d_soft, soft_stride, n_streams, frames_per_stream, d_history_in ? d_history_in[i] : nullptr, nullptr,
+                           const_cast<uint8_t *>(d_out[i]));    // (read only)
+        it.counts = reinterpret_cast<uint32_t *>(d_msc[i]);
+        items.push_back(it);
+    }
+    if (nframes == 0 || items.empty()) return DABGPU_OK;
+    HIP_TRY(dabk::launch_channel_ber(items.data(), int(items.size()), pick_stream(ctx, stream)));
+    return DABGPU_OK;
 }
 
 }  // extern "C"

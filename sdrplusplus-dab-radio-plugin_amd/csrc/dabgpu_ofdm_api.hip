@@ -772,12 +772,8 @@ int dabgpu_ofdm_demod_stream_frame(dabgpu_ctx *ctx, int stream_index, const floa
         HIP_TRY(hipStreamSynchronize(s));                                                // a copy-engine transfer ends the usual way)
     } else {
         // one synchronisation: the word behind the landing area's payload (the area is at least nb_res + 64 bytes)
-        const size_t off_flag = ctx->h_bounce_bytes - 64;
         // (the soft bits may have gone straight into the caller's buffer: the word is watched only when that buffer is coherent)
-        if ((rc = wait_for_signal(s, reinterpret_cast<volatile unsigned long long *>(static_cast<char *>(ctx->h_bounce) + off_flag),
-                                  reinterpret_cast<unsigned long long *>(hd + off_flag), ++ctx->signal_seq, false,
-                                  !soft_alias || known_coherent_host(soft, NB_FRAME_BITS))))
-            return rc;
+        if ((rc = wait_for_signal(s, SignalWord(ctx, hd), false, !soft_alias || known_coherent_host(soft, NB_FRAME_BITS)))) return rc;
     }
     ctx->ev_states_pending = false;
     const char *hb = static_cast<const char *>(ctx->h_bounce);

@@ -1,11 +1,11 @@
 // dabgpu_pipeline.hip -- the host-fed ring (dabgpu_pipe_*): dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a caller
 // whose samples start in host memory (files, a network), without the synchronous calls' serial upload -> kernels ->
 // download.  The reference runs the same two stages on two threads with a 2-frame ring between them
-// (/root/reference/src/radio_block.cpp:23-44); here the ring is `slots` device staging sets, and three engines work
+// (src/radio_block.cpp:23-44 there); here the ring is `slots` device staging sets, and three engines work
 // at once: the upload of batch k+1 (copy stream), the kernels of batch k (the context stream), the download of batch
 // k-1 (a second copy stream).  Ordering is by events; the host only ever blocks in dabgpu_pipe_wait (and in a submit
 // that finds every slot still busy).
-#include "dabgpu_ctx.hpp"
+#include "decode_plan.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -31,21 +31,8 @@ struct Pipeline {
     size_t frame_stride = 0;
     int iq_format = 0;                               // the context's sample format when the ring opened (DABGPU_IQ_*)
     int64_t next_ticket = 0;
-    // de-interleaver rings of the sub-channels the ring decodes, on the device, double-buffered: [n_streams][15][bits]
-    struct Ring {
-        int start_address, length, n_streams;
-        size_t bytes;
-        int8_t *buf[2];
-        int cur;
-        bool live;
-    };
-    std::vector<Ring> rings;
+    HistoryRings rings;                              // of the sub-channels the ring decodes
 };
-
-static void free_rings(Pipeline *p) {
-    for (auto &r : p->rings) { (void)hipFree(r.buf[0]); (void)hipFree(r.buf[1]); }
-    p->rings.clear();
-}
 
 void pipeline_destroy(dabgpu_ctx *ctx) {
     Pipeline *p = ctx->pipe;
@@ -60,7 +47,7 @@ void pipeline_destroy(dabgpu_ctx *ctx) {
         if (s.d_fo) (void)hipFree(s.d_fo);
         for (hipEvent_t e : {s.up, s.comp, s.done}) if (e) (void)hipEventDestroy(e);
     }
-    free_rings(p);
+    p->rings.clear();
     if (p->s_up) (void)hipStreamDestroy(p->s_up);
     if (p->s_down) (void)hipStreamDestroy(p->s_down);
     (void)hipGetLastError();
@@ -113,13 +100,13 @@ int dabgpu_pipe_reset(dabgpu_ctx *ctx) {
     if (!ctx || !ctx->pipe) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    free_rings(ctx->pipe);
+    ctx->pipe->rings.clear();
     return DABGPU_OK;
 }
 
-static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
-                       float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
-                       uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket);
+static int submit_body(dabgpu_ctx *ctx, const SubchannelPlan &plan, const void *iq, int n_streams, int frames_per_stream,
+                       const float *freq_offset, float fine_freq_update_beta, int8_t *soft, uint8_t *fib, uint8_t *crc_ok,
+                       uint8_t *const *out, int64_t *ticket);
 
 int dabgpu_pipe_submit(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
                        float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
@@ -133,16 +120,13 @@ int dabgpu_pipe_submit(dabgpu_ctx *ctx, const void *iq, int n_streams, int frame
         if (n_streams > ctx->n_states) return DABGPU_ERR_CAPACITY;              // closed loop: dabgpu_streams_reset first
         if (!(fine_freq_update_beta >= 0.f && fine_freq_update_beta <= 1.f)) return DABGPU_ERR_ARG;
     }
-    // argument errors are refused here, before a slot or a ring is touched: the ring's state survives them
-    for (int i = 0; i < n_subchannels; i++) {
-        const int nbytes = dabgpu_subchannel_bytes(&sc[i]);
-        if (nbytes < 0) return nbytes;
-        if (!out[i]) return DABGPU_ERR_ARG;
-    }
-    if (!subchannels_disjoint(sc, n_subchannels)) return DABGPU_ERR_ARG;
     DeviceGuard guard(ctx);
-    const int rc = submit_body(ctx, iq, n_streams, frames_per_stream, freq_offset, fine_freq_update_beta, sc, n_subchannels, soft, fib,
-                               crc_ok, out, ticket);
+    // argument errors (a length no decoder holds among them) are refused here, before a slot or a ring is touched: the
+    // ring's state survives them
+    const SubchannelPlan plan(ctx, sc, n_subchannels, out);
+    if (plan.rc) return plan.rc;
+    const int rc = submit_body(ctx, plan, iq, n_streams, frames_per_stream, freq_offset, fine_freq_update_beta, soft, fib, crc_ok, out,
+                               ticket);
     if (rc != DABGPU_OK) {
         // A runtime call failed part-way: a ring may exist that was never zeroed, copies into the caller's buffers may be
         // in flight behind a slot that is not marked busy, and every ring has missed this batch.  Everything enqueued so
@@ -152,39 +136,27 @@ int dabgpu_pipe_submit(dabgpu_ctx *ctx, const void *iq, int n_streams, int frame
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamSynchronize(p->s_down);
         (void)hipGetLastError();
-        free_rings(p);
+        p->rings.clear();
     }
     return rc;
 }
 
-static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frames_per_stream, const float *freq_offset,
-                       float fine_freq_update_beta, const dabgpu_subchannel *sc, int n_subchannels, int8_t *soft, uint8_t *fib,
-                       uint8_t *crc_ok, uint8_t *const *out, int64_t *ticket) {
+static int submit_body(dabgpu_ctx *ctx, const SubchannelPlan &plan, const void *iq, int n_streams, int frames_per_stream,
+                       const float *freq_offset, float fine_freq_update_beta, int8_t *soft, uint8_t *fib, uint8_t *crc_ok,
+                       uint8_t *const *out, int64_t *ticket) {
     Pipeline *p = ctx->pipe;
     const int n_frames = n_streams * frames_per_stream;
-    // layout of the slot's result block: [fib | crc | out_0 | out_1 ...]
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t nb_fib = size_t(n_frames) * NB_FIBS * 32, nb_crc = size_t(n_frames) * NB_FIBS;
-    const size_t nsc = size_t(n_subchannels);
-    std::vector<size_t> out_off(nsc), out_bytes(nsc);
-    size_t res_total = al(nb_fib) + al(nb_crc);
-    for (int i = 0; i < n_subchannels; i++) {
-        const int nbytes = dabgpu_subchannel_bytes(&sc[i]);
-        if (nbytes < 0) return nbytes;
-        if (!out[i]) return DABGPU_ERR_ARG;
-        out_off[size_t(i)] = res_total;
-        out_bytes[size_t(i)] = size_t(n_frames) * NB_CIFS * size_t(nbytes);
-        res_total += al(out_bytes[size_t(i)]);
-    }
+    const int n_subchannels = plan.n;
+    const ResultLayout lay(size_t(n_frames), plan);             // of the slot's result block
     Pipeline::Slot &s = p->slots[size_t(p->next_ticket % int64_t(p->slots.size()))];
     // the slot's previous batch must have left it (its caller may not have waited for it yet)
     if (s.busy) { HIP_TRY(hipEventSynchronize(s.done)); s.busy = false; }
-    if (s.res_bytes < res_total) {
+    if (s.res_bytes < lay.total) {
         if (s.d_res) (void)hipFree(s.d_res);
         s.d_res = nullptr;
         s.res_bytes = 0;
-        if (hipMalloc(&s.d_res, res_total) != hipSuccess) return DABGPU_ERR_NOMEM;
-        s.res_bytes = res_total;
+        if (hipMalloc(&s.d_res, lay.total) != hipSuccess) return DABGPU_ERR_NOMEM;
+        s.res_bytes = lay.total;
     }
     // the rings of this batch's sub-channels (a sub-channel seen for the first time, with another stream count, or left
     // out of the batch before starts from erasures: a ring that misses a batch no longer continues its streams)
@@ -192,28 +164,12 @@ static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frame
     std::vector<const int8_t *> p_hi(size_t(n_subchannels), nullptr);
     std::vector<int8_t *> p_ho(size_t(n_subchannels), nullptr);
     std::vector<uint8_t *> p_out(size_t(n_subchannels), nullptr);
-    std::vector<int> ring_of(size_t(n_subchannels), -1);
     for (int i = 0; i < n_subchannels; i++) {
-        for (size_t k = 0; k < p->rings.size(); k++)
-            if (p->rings[k].start_address == sc[i].start_address && p->rings[k].length == sc[i].length && p->rings[k].n_streams == n_streams)
-                ring_of[size_t(i)] = int(k);
-        if (ring_of[size_t(i)] < 0) {
-            Pipeline::Ring r{};
-            r.start_address = sc[i].start_address;
-            r.length = sc[i].length;
-            r.n_streams = n_streams;
-            r.bytes = size_t(n_streams) * 15 * size_t(sc[i].length) * CU_BITS;
-            if (hipMalloc(reinterpret_cast<void **>(&r.buf[0]), r.bytes) != hipSuccess) return DABGPU_ERR_NOMEM;
-            if (hipMalloc(reinterpret_cast<void **>(&r.buf[1]), r.bytes) != hipSuccess) { (void)hipFree(r.buf[0]); return DABGPU_ERR_NOMEM; }
-            ring_of[size_t(i)] = int(p->rings.size());
-            p->rings.push_back(r);
-            HIP_TRY(hipMemsetAsync(r.buf[0], 0, r.bytes, sc_stream));
-        }
-        Pipeline::Ring &r = p->rings[size_t(ring_of[size_t(i)])];
-        r.live = true;
-        p_hi[size_t(i)] = r.buf[r.cur];
-        p_ho[size_t(i)] = r.buf[r.cur ^ 1];
-        p_out[size_t(i)] = static_cast<uint8_t *>(s.d_res) + out_off[size_t(i)];
+        const int k = p->rings.acquire(plan.sc[i].start_address, plan.sc[i].length, n_streams, sc_stream);
+        if (k < 0) return k;
+        p_hi[size_t(i)] = p->rings.in(k);
+        p_ho[size_t(i)] = p->rings.out(k);
+        p_out[size_t(i)] = static_cast<uint8_t *>(s.d_res) + lay.off_out[size_t(i)];
     }
     // ---- upload (copy stream) ----
     const size_t nb_iq = (size_t(n_frames - 1) * p->frame_stride + size_t(NB_FRAME_SYMBOLS) * NB_SYM_PERIOD) * dabk::iq_sample_bytes(p->iq_format);
@@ -229,23 +185,13 @@ static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frame
     else
         rc = dabgpu_ofdm_demod_streams_dev(ctx, s.d_iq, p->frame_stride, n_streams, frames_per_stream, fine_freq_update_beta,
                                            static_cast<int8_t *>(s.d_soft), nullptr, nullptr, sc_stream);
-    uint8_t *d_fib = static_cast<uint8_t *>(s.d_res), *d_crc = d_fib + al(nb_fib);
+    uint8_t *d_fib = static_cast<uint8_t *>(s.d_res), *d_crc = d_fib + lay.off_crc;
     if (!rc)
-        rc = dabgpu_decode_frames_dev(ctx, static_cast<const int8_t *>(s.d_soft), NB_FRAME_BITS, n_streams, frames_per_stream, d_fib,
-                                      d_crc, sc, n_subchannels, n_subchannels ? p_hi.data() : nullptr,
-                                      n_subchannels ? p_ho.data() : nullptr, n_subchannels ? p_out.data() : nullptr, sc_stream);
+        rc = decode_frames_planned(ctx, plan, static_cast<const int8_t *>(s.d_soft), NB_FRAME_BITS, n_streams, frames_per_stream, d_fib,
+                                   d_crc, p_hi.data(), p_ho.data(), p_out.data(), sc_stream);
     if (rc) return rc;                                          // (the caller of this body drops the rings)
     HIP_TRY(hipEventRecord(s.comp, sc_stream));
-    for (int i = 0; i < n_subchannels; i++) p->rings[size_t(ring_of[size_t(i)])].cur ^= 1;
-    {
-        size_t kept = 0;
-        bool dropped = false;
-        for (auto &r : p->rings) {
-            if (r.live) { r.live = false; p->rings[kept++] = r; }
-            else { if (!dropped) { (void)hipStreamSynchronize(sc_stream); dropped = true; } (void)hipFree(r.buf[0]); (void)hipFree(r.buf[1]); }
-        }
-        p->rings.resize(kept);
-    }
+    p->rings.commit(sc_stream);
     // ---- download (second copy stream) ----
     HIP_TRY(hipStreamWaitEvent(p->s_down, s.comp, 0));
     if (soft) {
@@ -257,10 +203,10 @@ static int submit_body(dabgpu_ctx *ctx, const void *iq, int n_streams, int frame
             HIP_TRY(hipMemcpyAsync(soft, s.d_soft, size_t(n_frames) * NB_FRAME_BITS, hipMemcpyDeviceToHost, p->s_down));
         }
     }
-    HIP_TRY(hipMemcpyAsync(fib, d_fib, nb_fib, hipMemcpyDeviceToHost, p->s_down));
-    HIP_TRY(hipMemcpyAsync(crc_ok, d_crc, nb_crc, hipMemcpyDeviceToHost, p->s_down));
+    HIP_TRY(hipMemcpyAsync(fib, d_fib, lay.nb_fib, hipMemcpyDeviceToHost, p->s_down));
+    HIP_TRY(hipMemcpyAsync(crc_ok, d_crc, lay.nb_crc, hipMemcpyDeviceToHost, p->s_down));
     for (int i = 0; i < n_subchannels; i++)
-        HIP_TRY(hipMemcpyAsync(out[i], p_out[size_t(i)], out_bytes[size_t(i)], hipMemcpyDeviceToHost, p->s_down));
+        HIP_TRY(hipMemcpyAsync(out[i], p_out[size_t(i)], lay.out_bytes[size_t(i)], hipMemcpyDeviceToHost, p->s_down));
     HIP_TRY(hipEventRecord(s.done, p->s_down));
     s.ticket = p->next_ticket;
     s.busy = true;
