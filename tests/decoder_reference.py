@@ -113,7 +113,7 @@ def uep_profile(index):
         raise AssertionError("UEP row %d: %d blocks for %d kbit/s" % (index, l1 + l2 + l3 + l4, br))
     if p.kept + pad != size * 64:
         raise AssertionError("UEP row %d: %d bits + %d padding in %d CUs" % (index, p.kept, pad, size))
-    p.bitrate = br
+    p.bitrate, p.level = br, _level
     return p
 
 
