@@ -732,6 +732,49 @@ int dabgpu_decode_frames_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_
                              int n_subchannels, const int8_t *const *d_history_in, int8_t *const *d_history_out,
                              uint8_t *const *d_out, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* A batch of DIFFERENT ensembles (a monitoring receiver, a band scan): every  */
+/* stream has its own multiplex -- its own number of sub-channels, start       */
+/* addresses, sizes and protection profiles.                                    */
+/*                                                                            */
+/* dabgpu_decode_ensembles_dev  dabgpu_decode_frames_dev with one sub-channel   */
+/*            list PER STREAM.  Streams that are a multiple of 16 frames long,   */
+/*            with the alignment a grouped launch wants (soft bits, history in   */
+/*            on 16 bytes, outputs on 4), put the FIC of all frames and every     */
+/*            (stream, sub-channel) pair through ONE forward and ONE traceback     */
+/*            launch, whatever their number, and all history rings through a       */
+/*            third; any other shape is decoded part by part, stream by stream,     */
+/*            with the same results.  Checks and status codes per stream as         */
+/*            dabgpu_decode_frames_dev; everything is checked before anything is     */
+/*            enqueued, so a refused call leaves every output as it was.              */
+/* dabgpu_fig_subchannels  (host) the list to pass for one stream, read from the  */
+/*            FIBs an earlier call decoded: FIC pass with no entries, this        */
+/*            function per stream, then the call with the plans                    */
+/*            (INTEGRATION.md section 13).                                        */
+/* ------------------------------------------------------------------------ */
+/* n_streams ensembles, each with ITS OWN sub-channel list, in one call.
+ * sc        all lists one after the other (HOST); stream s owns entries sc_first[s] .. sc_first[s+1]-1
+ * sc_first  [n_streams + 1] (HOST), sc_first[0] = 0, non-decreasing; a stream may own no entry (FIC only);
+ *           at most 64 entries per stream
+ * per entry j of stream s (HOST arrays of DEVICE pointers, sc_first[n_streams] long):
+ *   d_history_in[j] / d_history_out[j]   [15][length_j*64] int8, as dabgpu_msc_decode_dev for ONE stream; the arrays or
+ *                                        single pointers may be NULL (in: erasures); in != out
+ *   d_out[j]                             [frames_per_stream*4][bitrate_j*3]
+ * d_fib / d_crc_ok as dabgpu_decode_frames_dev, or both NULL (sub-channels only).
+ * Entries of ONE stream must not overlap in the CIF; entries of different streams may use the same capacity units. */
+int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams,
+                                int frames_per_stream, uint8_t *d_fib, uint8_t *d_crc_ok,
+                                const dabgpu_subchannel *sc, const int32_t *sc_first,
+                                const int8_t *const *d_history_in, int8_t *const *d_history_out,
+                                uint8_t *const *d_out, void *stream);
+
+/* host only: the sub-channel organisation (FIG 0/1, current configuration, C/N = 0) found in CRC-clean FIBs of ONE
+ * ensemble, sorted by start address, each sub-channel once; short form through dabgpu_uep_subchannel, long form
+ * option 0 = EEP-A / 1 = EEP-B with the bit rate its size and level imply (a reserved option is passed over).
+ * fib [n_frames][12][32], crc_ok [n_frames][12].  *n receives the count;
+ * DABGPU_ERR_CAPACITY if max is too small, DABGPU_ERR_PROFILE if an announced pair names no profile. */
+int dabgpu_fig_subchannels(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_subchannel *out, int max, int *n);
+
 /* Host-pointer form for the plugin's one-frame-at-a-time use (BasicRadio::Process, src/radio_block.cpp:42): the
  * frames are uploaded ONCE, the FIC and every sub-channel are decoded from that copy, the results come back in one
  * batch of copies, one synchronisation.  history_in / history_out / out are HOST arrays of HOST pointers. */

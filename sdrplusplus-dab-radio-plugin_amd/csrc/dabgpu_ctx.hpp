@@ -66,6 +66,7 @@ enum StageSlot {
     STAGE_ETI_COUNTS = 9,   // the ETI call's per-stream CIF counts
     STAGE_MOD_CODED = 10,   // the modulator's coded records, one per ETI frame
     STAGE_MOD_CUM = 11,     // ... and running quarter turns, one pair of bit planes per data symbol
+    STAGE_ENSEMBLES = 12,   // dabgpu_decode_ensembles_dev: the entry table of the ragged grouped lane launch
     STAGE_SLOTS
 };
 

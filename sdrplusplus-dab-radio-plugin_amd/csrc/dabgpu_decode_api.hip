@@ -104,6 +104,60 @@ int decode_grouped(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, const Sub
     return 0;
 }
 
+// The FIC of every frame (d_fib != nullptr) and every (stream, sub-channel) entry of a batch of ensembles in one ragged
+// grouped lane launch.  Returns 0 when everything was enqueued, 1 when the launch does not apply (whole 64-codeword groups
+// inside one stream: frames_per_stream a multiple of 16; the alignment rules of lane_group_fusable for every entry; a
+// context that may use the fused lane kernels), < 0 on errors.  No batch-size threshold: the alternative is not the wave
+// kernels on the whole batch but one small call per stream.
+int decode_ensembles_grouped(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, const EnsemblePlan &plan, const int8_t *d_soft,
+                             size_t soft_stride, int frames_per_stream, const int8_t *const *d_history_in,
+                             int8_t *const *d_history_out, uint8_t *const *d_out, void *stream) {
+    if (frames_per_stream % 16 != 0 || ctx->lane_mode == 0 || ctx->lane_unfused || soft_stride < size_t(NB_FRAME_BITS)) return 1;
+    std::vector<dabk::LaneGroupItem> items;
+    items.reserve(size_t(plan.total) + 1);
+    if (d_fib) {
+        dabk::LaneGroupItem it{};
+        it.code = ctx->fic.tables(true);
+        it.tables = ctx->fic.lane_tables();
+        it.args.soft = d_soft;
+        it.args.soft_stride = soft_stride;
+        it.args.n_streams = plan.n_streams;
+        it.args.frames_per_stream = frames_per_stream;
+        it.args.out = d_fib;
+        it.is_fic = true;
+        it.crc_ok = d_crc_ok;
+        if (((reinterpret_cast<uintptr_t>(d_soft) | soft_stride) & 15) || (reinterpret_cast<uintptr_t>(d_fib) & 3)) return 1;
+        items.push_back(it);
+    }
+    for (int s = 0; s < plan.n_streams; s++)
+        for (int i = plan.first[s]; i < plan.first[s + 1]; i++) {
+            const DeviceCode *dc = plan.code[size_t(i)];
+            dabk::LaneGroupItem it{};
+            it.code = dc->tables(true);
+            it.tables = dc->lane_tables();
+            it.args = msc_args(plan.sc[i], d_soft + size_t(s) * frames_per_stream * soft_stride, soft_stride, 1, frames_per_stream,
+                               d_history_in ? d_history_in[i] : nullptr, d_history_out ? d_history_out[i] : nullptr, d_out[i]);
+            if (!dabk::lane_supported(dc->prof.nsteps) || !it.tables.fused_desc || !it.tables.fused_tiles ||
+                !dabk::lane_group_fusable(it.args))
+                return 1;
+            items.push_back(it);
+        }
+    const int n_items = int(items.size());
+    if (n_items == 0) return 0;
+    hipStream_t s = pick_stream(ctx, stream);
+    int rc;
+    if (!lane_scratch(ctx, dabk::lane_group_scratch_bytes(items.data(), n_items), s, &rc)) return rc ? rc : 1;
+    const size_t table_bytes = dabk::lane_ragged_table_bytes(items.data(), n_items);
+    // (growing the table must not race with a launch that still reads the old one)
+    if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
+    void *d_table = nullptr;
+    if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &d_table)) return 1;
+    ScopedTimer tm(ctx, TIMER_MSC, s);
+    dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes};
+    HIP_TRY(dabk::launch_lane_ragged(items.data(), n_items, lsc, d_table, ctx->stage_bytes[STAGE_ENSEMBLES], s, tm.mids()));
+    return 0;
+}
+
 // Sub-channels that do not go through the grouped lane launch.  Small batches (each sub-channel below the lane
 // kernels' threshold: the plugin's one frame at a time) go through ONE launch of the wave-per-codeword kernel and one
 // for the history rings; anything else is decoded sub-channel by sub-channel.
@@ -405,6 +459,100 @@ int dabgpu_decode_frames_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_
     if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;
     return decode_frames_planned(ctx, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok, d_history_in,
                                  d_history_out, d_out, stream);
+}
+
+int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream,
+                                uint8_t *d_fib, uint8_t *d_crc_ok, const dabgpu_subchannel *sc, const int32_t *sc_first,
+                                const int8_t *const *d_history_in, int8_t *const *d_history_out, uint8_t *const *d_out,
+                                void *stream) {
+    if (!ctx || !d_soft || !sc_first || n_streams < 0 || frames_per_stream < 0 || (d_fib == nullptr) != (d_crc_ok == nullptr))
+        return DABGPU_ERR_ARG;
+    DeviceGuard guard(ctx);
+    if (soft_stride < size_t(NB_FRAME_BITS) && size_t(n_streams) * frames_per_stream > 1) return DABGPU_ERR_ARG;
+    // everything is checked before anything is enqueued: a refused call leaves every output as it was
+    const EnsemblePlan plan(ctx, sc, sc_first, n_streams, d_out);
+    if (plan.rc) return plan.rc;
+    for (int i = 0; i < plan.total; i++)
+        if (d_history_in && d_history_out && d_history_in[i] && d_history_in[i] == d_history_out[i]) return DABGPU_ERR_ARG;
+    if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;
+    const int g = decode_ensembles_grouped(ctx, d_fib, d_crc_ok, plan, d_soft, soft_stride, frames_per_stream, d_history_in,
+                                           d_history_out, d_out, stream);
+    if (g <= 0) return g;
+    // any other shape: the same bytes part by part, stream by stream
+    for (int s = 0; s < n_streams; s++) {
+        const int i0 = sc_first[s], n = plan.count(s);
+        const int8_t *soft_s = d_soft + size_t(s) * frames_per_stream * soft_stride;
+        const SubchannelPlan sub(ctx, sc + i0, n, d_out + i0);
+        if (sub.rc) return sub.rc;
+        const int8_t *const *hi = d_history_in ? d_history_in + i0 : nullptr;
+        int8_t *const *ho = d_history_out ? d_history_out + i0 : nullptr;
+        int rc;
+        if (d_fib) {
+            rc = decode_frames_planned(ctx, sub, soft_s, soft_stride, 1, frames_per_stream,
+                                       d_fib + size_t(s) * frames_per_stream * NB_FIBS * 32,
+                                       d_crc_ok + size_t(s) * frames_per_stream * NB_FIBS, hi, ho, d_out + i0, stream);
+        } else {
+            rc = decode_grouped(ctx, nullptr, nullptr, sub, soft_s, soft_stride, 1, frames_per_stream, hi, ho, d_out + i0, stream);
+            if (rc > 0) rc = decode_subchannels(ctx, sub, soft_s, soft_stride, 1, frames_per_stream, hi, ho, d_out + i0, stream);
+        }
+        if (rc) return rc;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_fig_subchannels(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_subchannel *out, int max, int *n) {
+    if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
+    // FIG 0/1 (ETSI EN 300 401 clause 6.2.1): SubChId (6), start address (10), then the short form -- 0, table switch (1),
+    // table index (6) -- or the long form -- 1, option (3), protection level (2), size (10)
+    dabgpu_subchannel found[64];
+    bool seen[64] = {};
+    int count = 0;
+    for (int k = 0; k < n_frames * NB_FIBS; k++) {
+        if (!crc_ok[k]) continue;
+        const uint8_t *d = fib + size_t(k) * 32;
+        for (int i = 0; i < 30;) {
+            if (d[i] == 0xFF) break;
+            const int type = d[i] >> 5, len = d[i] & 0x1F;
+            if (len == 0 || i + 1 + len > 30) break;
+            const uint8_t *b = d + i + 1;
+            i += 1 + len;
+            // type 0, extension 1, current configuration (C/N = 0)
+            if (type != 0 || (b[0] & 0x1F) != 1 || (b[0] & 0x80)) continue;
+            for (int j = 1; j + 3 <= len;) {
+                const int id = b[j] >> 2, start = ((b[j] & 3) << 8) | b[j + 1];
+                dabgpu_subchannel sc{};
+                if (b[j + 2] & 0x80) {
+                    if (j + 4 > len) break;
+                    const int option = (b[j + 2] >> 4) & 7, level = ((b[j + 2] >> 2) & 3) + 1, size = ((b[j + 2] & 3) << 8) | b[j + 3];
+                    j += 4;
+                    if (option > 1) continue;                  // reserved option: not an entry a receiver can use
+                    if (seen[id]) continue;
+                    // the bit rate the size implies: n times the level's capacity units, 8 n (A) or 32 n (B) kbit/s
+                    static const int CU_A[4] = {12, 8, 6, 4}, CU_B[4] = {27, 21, 18, 15};
+                    const int unit = option ? CU_B[level - 1] : CU_A[level - 1];
+                    if (size == 0 || size % unit) return DABGPU_ERR_PROFILE;
+                    sc = dabgpu_subchannel{start, size, 0, option, level, (option ? 32 : 8) * (size / unit)};
+                    dab::PunctureProfile prof;
+                    const int rc = subchannel_profile(&sc, prof);
+                    if (rc) return rc;
+                } else {
+                    const int table_switch = (b[j + 2] >> 6) & 1, index = b[j + 2] & 0x3F;
+                    j += 3;
+                    if (seen[id]) continue;
+                    if (table_switch) return DABGPU_ERR_PROFILE;
+                    const int rc = dabgpu_uep_subchannel(index, start, &sc);
+                    if (rc) return rc;
+                }
+                seen[id] = true;
+                found[count++] = sc;
+            }
+        }
+    }
+    std::stable_sort(found, found + count, [](const dabgpu_subchannel &a, const dabgpu_subchannel &b) { return a.start_address < b.start_address; });
+    *n = count;
+    if (count > max) return DABGPU_ERR_CAPACITY;
+    for (int i = 0; i < count; i++) out[i] = found[i];
+    return DABGPU_OK;
 }
 
 int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_streams, int frames_per_stream,

@@ -69,6 +69,37 @@ struct SubchannelPlan {
     size_t out_bytes(int i, size_t n_frames) const { return n_frames * dab::NB_CIFS * cif_bytes(i); }
 };
 
+// The ragged counterpart: n_streams lists one after the other, stream s owning entries first[s] .. first[s + 1] - 1
+// (dabgpu_decode_ensembles_dev).  The same checks and status codes per stream, in stream order, before anything is
+// enqueued: the shape of `first` (starts at 0, never decreases, at most MAX_PER_STREAM entries a stream), then every entry's
+// descriptor and output pointer, then no capacity unit used twice INSIDE a stream -- different streams are different
+// ensembles and may use the same units.  Codes come through lookup_code, so the descriptor cache is shared.
+struct EnsemblePlan {
+    static constexpr int MAX_PER_STREAM = 64;     // what a multiplex can announce (FIG 0/1: 6-bit SubChId)
+    const dabgpu_subchannel *sc;
+    const int32_t *first;
+    int n_streams;
+    int total = 0;
+    std::vector<DeviceCode *> code;
+    int rc = DABGPU_OK;
+    template <class T>
+    EnsemblePlan(dabgpu_ctx *ctx, const dabgpu_subchannel *sc_, const int32_t *first_, int n_streams_, T *const *out)
+        : sc(sc_), first(first_), n_streams(n_streams_) {
+        if (!first || first[0] != 0) { rc = DABGPU_ERR_ARG; return; }
+        for (int s = 0; s < n_streams; s++)
+            if (first[s + 1] < first[s] || first[s + 1] - first[s] > MAX_PER_STREAM) { rc = DABGPU_ERR_ARG; return; }
+        total = first[n_streams];
+        if (total > 0 && (!sc || !out)) { rc = DABGPU_ERR_ARG; return; }
+        code.assign(size_t(total), nullptr);
+        for (int s = 0; !rc && s < n_streams; s++) {
+            for (int i = first[s]; !rc && i < first[s + 1]; i++)
+                if (!(rc = lookup_code(ctx, &sc[i], &code[size_t(i)])) && !out[i]) rc = DABGPU_ERR_ARG;
+            if (!rc && !subchannels_disjoint(sc + first[s], count(s))) rc = DABGPU_ERR_ARG;
+        }
+    }
+    int count(int s) const { return first[s + 1] - first[s]; }
+};
+
 // the decode / history / BER kernels' arguments for one sub-channel of a batch of frames
 inline dabk::MscArgs msc_args(const dabgpu_subchannel &sc, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream,
                               const int8_t *hist_in, int8_t *hist_out, uint8_t *out) {

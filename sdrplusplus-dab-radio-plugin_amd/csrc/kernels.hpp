@@ -407,6 +407,15 @@ bool lane_group_fusable(const MscArgs &a);
 size_t lane_group_scratch_bytes(const LaneGroupItem *items, int n);
 // mid (optional, timing only): two events, recorded behind the forward pass and behind the traceback of the last pack
 hipError_t launch_lane_group(const LaneGroupItem *items, int n, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid = nullptr);
+// Ragged grouped launch: the same items in any number -- the FIC of every frame and one item per (stream, sub-channel) of a
+// batch of ensembles that each have their own multiplex (args.n_streams = 1, args.soft = that stream's first frame) -- still
+// in ONE forward and ONE traceback launch.  The entry table goes through `d_table` (device memory, 16-byte aligned, at least
+// lane_ragged_table_bytes(); uploaded on `s`) instead of the kernel arguments; entries are dispatched longest codeword
+// first; scratch as lane_group_scratch_bytes().  The history rings (args.hist_out) are written by a third launch over the
+// same table.
+size_t lane_ragged_table_bytes(const LaneGroupItem *items, int n);
+hipError_t launch_lane_ragged(const LaneGroupItem *items, int n, const LaneScratch &sc, void *d_table, size_t table_bytes,
+                              hipStream_t s, hipEvent_t *mid = nullptr);
 // Dynamic-LDS request (>= lds) that makes every CU hold the same number of workgroups of a `grid`-workgroup
 // launch when at most `o_cap` fit per CU otherwise (the dispatcher fills CUs greedily).
 size_t balanced_lds_bytes(unsigned grid, size_t lds, unsigned o_cap);

@@ -692,6 +692,86 @@ __global__ __launch_bounds__(64) void lane_traceback_grouped_kernel(const LaneEn
                         lane_tile_fits(en.nsteps) ? tile : nullptr, threadIdx.x);
 }
 
+// Ragged grouped launch: the FIC and every (stream, sub-channel) pair of a batch of ensembles that each have their own
+// multiplex -- any number of entries, on the order of a thousand for 64 ensembles, where the by-value pack above holds 16.
+// The entry table lives in device memory ([n] RaggedEntry, then [total_groups] int32: the entry of every group, in dispatch
+// order) and a wave reads its entry through wave-uniform indices, so the lookup is scalar loads and every field stays in
+// SGPRs, as with the pack.  What the by-value pack was chosen to avoid -- pointers out of a device table are generic, their
+// accesses flat -- is avoided by what the table holds: addresses as 64-bit integers, which the kernels turn into
+// global-address-space pointers before anything is read or written through them.  The bodies are the grouped kernels'.
+struct RaggedEntry {            // 128 bytes
+    uint64_t soft, hist, desc, tiles, prbs, out, crc_ok, dec;     // device addresses (0 = none), see LaneEntry
+    uint64_t stride;
+    uint64_t hist_out;          // ring to write behind the decode (0: none; never the FIC entry)
+    int32_t cifs_per_stream, base_off, per_cif, nbits, d_force;   // LSrcMsc
+    int32_t nsteps, n_codewords, first_group;
+    int32_t hist_vec16;         // hist_out is 16-byte aligned: the ring is copied in 16-byte pieces
+    int32_t reserved[3];
+};
+static_assert(sizeof(RaggedEntry) == 128, "one entry is sixteen quad-words of scalar loads");
+
+template <class T>
+__device__ __forceinline__ T *global_ptr(uint64_t address) {
+    typedef T __attribute__((address_space(1))) * G;
+    return (T *)reinterpret_cast<G>(address);                     // (global -> generic: the compiler keeps track of the origin)
+}
+__device__ __forceinline__ LSrcMsc ragged_src(const RaggedEntry &en) {
+    return LSrcMsc{global_ptr<const int8_t>(en.soft), size_t(en.stride), global_ptr<const int8_t>(en.hist), en.cifs_per_stream,
+                   en.base_off, en.per_cif, en.nbits, en.d_force};
+}
+
+__global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_ragged_kernel(const RaggedEntry *__restrict__ table,
+                                                                               const int32_t *__restrict__ entry_of_group,
+                                                                               int total_groups, int prio_nsteps) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int group = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);
+    if (group >= total_groups) return;
+    const RaggedEntry en = table[__builtin_amdgcn_readfirstlane(entry_of_group[group])];
+    const LSrcMsc src = ragged_src(en);
+    // (the priority rule of lane_forward_grouped_kernel; the launcher sets prio_nsteps only where the whole launch is resident)
+    if (prio_nsteps > 0 && en.nsteps >= prio_nsteps) __builtin_amdgcn_s_setprio(1);
+    lane_forward_fused_body(src, global_ptr<const int32_t>(en.desc), global_ptr<const int32_t>(en.tiles), en.nsteps,
+                            group - en.first_group, en.n_codewords, global_ptr<uint2>(en.dec),
+                            fused_lds + wv * ((64 + LSrcMsc::PRE) * FPITCH), lane);
+}
+
+__global__ __launch_bounds__(64) void lane_traceback_ragged_kernel(const RaggedEntry *__restrict__ table,
+                                                                   const int32_t *__restrict__ entry_of_group) {
+    extern __shared__ uint32_t tile[];                        // sized for the longest entry whose tile fits
+    const int group = blockIdx.x;
+    const RaggedEntry en = table[entry_of_group[group]];
+    lane_traceback_body(global_ptr<const uint2>(en.dec), en.nsteps, en.n_codewords, group - en.first_group,
+                        global_ptr<const uint8_t>(en.prbs), global_ptr<uint8_t>(en.out), global_ptr<uint8_t>(en.crc_ok),
+                        lane_tile_fits(en.nsteps) ? tile : nullptr, threadIdx.x);
+}
+
+// The history rings of the same entries in one launch (blockIdx.y = entry): row h of a ring is CIF cifs - 15 + h of the
+// entry's stream.  Entries of this launch are at least 64 CIFs long, so every row comes from the call's own frames.
+constexpr int RAGGED_HIST_BLOCKS = 8;
+__global__ __launch_bounds__(256) void lane_history_ragged_kernel(const RaggedEntry *__restrict__ table) {
+    const RaggedEntry en = table[blockIdx.y];
+    if (!en.hist_out) return;
+    const LSrcMsc src = ragged_src(en);
+    int8_t *out = global_ptr<int8_t>(en.hist_out);
+    const int first = src.cifs_per_stream - 15;
+    const int tid = blockIdx.x * 256 + threadIdx.x;
+    if (en.hist_vec16) {
+        const int per_row = en.nbits >> 4;
+        for (int c = tid; c < 15 * per_row; c += RAGGED_HIST_BLOCKS * 256) {
+            const int h = c / per_row, k = c - h * per_row;
+            *reinterpret_cast<uint4 *>(out + size_t(h) * en.nbits + 16 * k) =
+                *reinterpret_cast<const uint4 *>(src.row(first + h) + 16 * k);
+        }
+    } else {
+        for (int c = tid; c < 15 * en.nbits; c += RAGGED_HIST_BLOCKS * 256) {
+            const int h = c / en.nbits, i = c - h * en.nbits;
+            out[c] = src.row(first + h)[i];
+        }
+    }
+}
+
 template <class Src>
 hipError_t run_lane(Src f, bool vec16, bool fusable, const CodeTables &c, const LaneTables &lt, int n_codewords,
                     const LaneScratch &sc, uint8_t *out, uint8_t *crc_ok, hipStream_t s) {
@@ -729,7 +809,9 @@ hipError_t init_lane_kernel_attributes() {
                           reinterpret_cast<const void *>(lane_forward_fused_kernel<LSrcMsc>),
                           reinterpret_cast<const void *>(lane_forward_grouped_kernel),
                           reinterpret_cast<const void *>(lane_traceback_kernel),
-                          reinterpret_cast<const void *>(lane_traceback_grouped_kernel)}) {
+                          reinterpret_cast<const void *>(lane_traceback_grouped_kernel),
+                          reinterpret_cast<const void *>(lane_forward_ragged_kernel),
+                          reinterpret_cast<const void *>(lane_traceback_ragged_kernel)}) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
     }
@@ -846,6 +928,96 @@ hipError_t launch_lane_group(const LaneGroupItem *items, int n, const LaneScratc
         hipLaunchKernelGGL(lane_traceback_grouped_kernel, dim3(unsigned(pack.total_groups)), dim3(64), tb_lds, s, pack);
         if (timed) (void)hipEventRecord(mid[1], s);
     }
+    return hipGetLastError();
+}
+
+static size_t item_groups(const LaneGroupItem &it) { return (item_codewords(it) + 63) / 64; }
+
+// the table as it is uploaded: [n] entries, then the groups' entry numbers, rounded up to whole entries
+static size_t ragged_table_slots(const LaneGroupItem *items, int n) {
+    size_t groups = 0;
+    for (int i = 0; i < n; i++) groups += item_groups(items[i]);
+    return size_t(n) + (groups * sizeof(int32_t) + sizeof(RaggedEntry) - 1) / sizeof(RaggedEntry);
+}
+size_t lane_ragged_table_bytes(const LaneGroupItem *items, int n) { return ragged_table_slots(items, n) * sizeof(RaggedEntry); }
+
+hipError_t launch_lane_ragged(const LaneGroupItem *items, int n, const LaneScratch &sc, void *d_table, size_t table_bytes,
+                              hipStream_t s, hipEvent_t *mid) {
+    if (n <= 0) return hipSuccess;
+    const size_t slots = ragged_table_slots(items, n);
+    if (n > 65535 || !sc.base || sc.bytes < lane_group_scratch_bytes(items, n) || !d_table || table_bytes < slots * sizeof(RaggedEntry) ||
+        (reinterpret_cast<uintptr_t>(d_table) & 15))
+        return hipErrorInvalidValue;
+    // Dispatch order: workgroups start in grid order, so the longest codewords go first and the short ones fill the end of the
+    // launch (a long wave started last would run on alone).  Every entry works on buffers of its own: the order changes no result.
+    std::vector<int> order(size_t(n), 0);
+    for (int i = 0; i < n; i++) order[size_t(i)] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].code.nsteps > items[b].code.nsteps; });
+    std::vector<RaggedEntry> host(slots);
+    int32_t *entry_of_group = reinterpret_cast<int32_t *>(host.data() + n);
+    auto address = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
+    char *p = static_cast<char *>(sc.base);
+    int total_groups = 0, max_nwords = 0, longest = 0, shortest = 0x7fffffff;
+    bool any_history = false;
+    for (int k = 0; k < n; k++) {
+        const LaneGroupItem &it = items[order[size_t(k)]];
+        const MscArgs &a = it.args;
+        if (!it.tables.fused_desc || !it.tables.fused_tiles || !lane_supported(it.code.nsteps)) return hipErrorInvalidValue;
+        const int n_codewords = int(item_codewords(it));
+        LSrcMsc src;
+        if (it.is_fic) {
+            if (!aligned16(a.soft, a.soft_stride) || (reinterpret_cast<uintptr_t>(a.out) & 3)) return hipErrorInvalidValue;
+            src = make_fic_src(a.soft, a.soft_stride, n_codewords);
+        } else {
+            if (!lane_group_fusable(a)) return hipErrorInvalidValue;
+            src = make_msc_src(a);
+        }
+        RaggedEntry e{};
+        e.soft = address(src.soft);
+        e.hist = address(src.hist);
+        e.desc = address(it.tables.fused_desc);
+        e.tiles = address(it.tables.fused_tiles);
+        e.prbs = address(it.code.prbs_bytes);
+        e.out = address(a.out);
+        e.crc_ok = it.is_fic ? address(it.crc_ok) : 0;
+        e.dec = address(p);
+        e.stride = src.stride;
+        e.hist_out = it.is_fic ? 0 : address(a.hist_out);
+        e.cifs_per_stream = src.cifs_per_stream;
+        e.base_off = src.base_off;
+        e.per_cif = src.per_cif;
+        e.nbits = src.nbits;
+        e.d_force = src.d_force;
+        e.nsteps = it.code.nsteps;
+        e.n_codewords = n_codewords;
+        e.first_group = total_groups;
+        e.hist_vec16 = (e.hist_out & 15) == 0;
+        any_history = any_history || e.hist_out != 0;
+        const int groups = int(item_groups(it));
+        for (int g = 0; g < groups; g++) entry_of_group[total_groups + g] = k;
+        total_groups += groups;
+        p += size_t(groups) * 64 * size_t(e.nsteps) * sizeof(uint2);
+        if (lane_tile_fits(e.nsteps)) max_nwords = std::max(max_nwords, (e.nsteps - 6) >> 5);
+        longest = std::max(longest, e.nsteps);
+        shortest = std::min(shortest, e.nsteps);
+        host[size_t(k)] = e;
+    }
+    if (total_groups == 0) return hipSuccess;
+    // (pageable memory: the copy has left `host` when the call returns)
+    hipError_t err = hipMemcpyAsync(d_table, host.data(), slots * sizeof(RaggedEntry), hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) return err;
+    const RaggedEntry *table = static_cast<const RaggedEntry *>(d_table);
+    const int32_t *d_entry_of_group = reinterpret_cast<const int32_t *>(table + n);
+    const unsigned fgrid = unsigned((total_groups + 3) / 4);
+    const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + LSrcMsc::PRE) * FPITCH, 3);
+    // the priority rule of launch_lane_group: only where every wave is resident at once
+    const int prio_nsteps = (total_groups <= 2 * 4 * resident_cus() && longest > shortest) ? longest : 0;
+    hipLaunchKernelGGL(lane_forward_ragged_kernel, dim3(fgrid), dim3(256), lds, s, table, d_entry_of_group, total_groups, prio_nsteps);
+    if (mid) (void)hipEventRecord(mid[0], s);
+    const size_t tb_lds = size_t(64) * (max_nwords | 1) * 4;
+    hipLaunchKernelGGL(lane_traceback_ragged_kernel, dim3(unsigned(total_groups)), dim3(64), tb_lds, s, table, d_entry_of_group);
+    if (mid) (void)hipEventRecord(mid[1], s);
+    if (any_history) hipLaunchKernelGGL(lane_history_ragged_kernel, dim3(RAGGED_HIST_BLOCKS, unsigned(n)), dim3(256), 0, s, table);
     return hipGetLastError();
 }
 

@@ -51,6 +51,7 @@ EXPORTS = [
     "dabgpu_cir_default_cfg", "dabgpu_cir_frames_dev", "dabgpu_cir_acquired_dev", "dabgpu_cir_analyse",
     "dabgpu_eti_layout", "dabgpu_eti_history_bytes", "dabgpu_eti_frames_dev", "dabgpu_eti_parse",
     "dabgpu_eti_streams_from_frame", "dabgpu_mod_default_cfg", "dabgpu_mod_state_bytes", "dabgpu_modulate_eti_dev",
+    "dabgpu_decode_ensembles_dev", "dabgpu_fig_subchannels",
 ]
 
 ABI_VERSION = 6
@@ -434,6 +435,8 @@ def load_library(path):
     L.dabgpu_msc_decode_multi_dev.argtypes = [vp, vp, i, vp, sz, i, i, vp, vp, vp, vp]
     L.dabgpu_decode_frames_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, i, vp, vp, vp, vp]
     L.dabgpu_decode_frames.argtypes = [vp, vp, sz, i, i, vp, vp, vp, i, vp, vp, vp]
+    L.dabgpu_decode_ensembles_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dabgpu_fig_subchannels.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -614,6 +617,20 @@ def uep_subchannel(table_index, start_address):
     sc = Subchannel()
     _check(lib().dabgpu_uep_subchannel(table_index, start_address, C.byref(sc)), "dabgpu_uep_subchannel")
     return sc
+
+
+def fig_subchannels(fib, crc_ok, max_out=64):
+    """The sub-channel list one ensemble announces (FIG 0/1) in its CRC-clean FIBs, sorted by start address: fib
+    [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of Subchannel (no GPU needed)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    arr = (Subchannel * max(max_out, 1))()
+    n = C.c_int(0)
+    _check(lib().dabgpu_fig_subchannels(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_subchannels")
+    return [Subchannel(a.start_address, a.length, a.is_uep, a.eep_type, a.protection_level, a.bitrate_kbps) for a in arr[:n.value]]
 
 
 # ------------------------------------------------------------------ context
@@ -1197,6 +1214,33 @@ class Context:
         _check(self._lib.dabgpu_decode_frames_dev(self._h, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok,
                                               arr, n, ptrs(d_hist_in), ptrs(d_hist_out), ptrs(d_out), stream),
                "dabgpu_decode_frames_dev")
+
+    def decode_ensembles_dev(self, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok, scs, d_hist_in, d_hist_out,
+                             d_out, stream=None, sc_first=None):
+        """decode_frames_dev for ensembles that each have their own multiplex: scs, d_hist_in, d_hist_out, d_out are lists
+        (one per stream) of lists (one per sub-channel of that stream) of Subchannel / device addresses; d_hist_in and
+        d_hist_out may be None, d_fib and d_crc_ok both None (sub-channels only).  sc_first: the [n_streams + 1] offsets to
+        pass instead of the ones the lists imply (the library checks them)."""
+        if len(scs) != n_streams:
+            raise ValueError("one sub-channel list per stream")
+        flat = [sc for lst in scs for sc in lst]
+        n = len(flat)
+        if sc_first is None:
+            sc_first = np.cumsum([0] + [len(lst) for lst in scs]).tolist()
+        if len(sc_first) != n_streams + 1:
+            raise ValueError("sc_first has n_streams + 1 entries")
+        first = (C.c_int32 * (n_streams + 1))(*[int(x) for x in sc_first])
+        arr = (Subchannel * max(n, 1))(*flat)
+        def ptrs(lsts):
+            if lsts is None or n == 0:
+                return None
+            vals = [x for lst in lsts for x in lst]
+            if len(vals) != n:
+                raise ValueError("one address per sub-channel of every stream")
+            return (C.c_void_p * n)(*[C.c_void_p(x) if x else None for x in vals])
+        _check(self._lib.dabgpu_decode_ensembles_dev(self._h, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok,
+                                                     arr, first, ptrs(d_hist_in), ptrs(d_hist_out), ptrs(d_out), stream),
+               "dabgpu_decode_ensembles_dev")
 
     def mer_dev(self, d_soft, soft_stride, n_frames, d_out, first_symbol=0, n_symbols=75, stream=None):
         """MER sums of data symbols [first_symbol, first_symbol + n_symbols) per frame -> d_out [n_frames] (MER_DTYPE)."""
