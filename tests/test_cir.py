@@ -288,10 +288,14 @@ def host(t):
     return t.cpu().numpy().view(dabgpu.CIR_ACC_DTYPE).reshape(-1)
 
 
-def close(rec, taps, cars):
-    for r, t, c in zip(np.atleast_1d(rec), np.atleast_2d(taps), np.atleast_2d(cars)):
-        assert np.abs(r["tap"] - t).max() <= 1e-4 * t.max()
-        assert np.abs(r["carrier"] - c).max() <= 1e-4 * c.max()
+def close(rec, taps, cars, tap_budgets, car_budgets):
+    """every tap and every carrier within the budget cir_reference.py derives for it (each at most 1e-4 of the record's
+    largest tap, carrier)"""
+    for r, t, c, tb, cb in zip(np.atleast_1d(rec), np.atleast_2d(taps), np.atleast_2d(cars), np.atleast_2d(tap_budgets),
+                               np.atleast_2d(car_budgets)):
+        assert np.all(tb <= 1e-4 * t.max()) and np.all(cb <= 1e-4 * c.max())
+        assert np.all(np.abs(r["tap"] - t) <= tb)
+        assert np.all(np.abs(r["carrier"] - c) <= cb)
 
 
 def frame_order_sum(records, S, F, calls=1):
@@ -326,7 +330,7 @@ def test_gpu_records_match_reference_and_sums_repeat(cctx):
         y = np.concatenate([y, np.zeros(SYM, np.complex64)])
         fo = np.repeat(-cfo, F) + rng.uniform(-0.01, 0.01, S * F) / 2048
         starts = [i * stride for i in range(S * F)]
-        taps, cars = R.records(y.astype(np.complex128), starts, fo)
+        ref = R.records(y.astype(np.complex128), starts, fo, budgets=True)
         d = dev(torch, y)
         d_fo = dev(torch, fo.astype(np.float32))
         runs = []
@@ -339,7 +343,7 @@ def test_gpu_records_match_reference_and_sums_repeat(cctx):
             cctx.sync()
             runs.append((acc.cpu().numpy().copy(), host(frame).copy()))
         fr = runs[0][1]
-        close(fr, taps, cars)
+        close(fr, *ref)
         assert (fr["frames"] == 1).all() and (fr["reserved"] == 0).all()
         assert (runs[0][1].view(np.uint8) == runs[1][1].view(np.uint8)).all()
         assert (runs[0][0] == runs[1][0]).all() and (runs[0][0] == runs[2][0]).all()
@@ -455,8 +459,8 @@ def test_gpu_integer_formats_bit_exact(built):
                 out[name] = (acc.cpu().numpy(), frame.cpu().numpy())
             assert (out["cf32"][0] == out[fmt][0]).all() and (out["cf32"][1] == out[fmt][1]).all(), fmt
             fr = out[fmt][1].view(dabgpu.CIR_ACC_DTYPE).reshape(-1)
-            taps, cars = R.records(f.view(np.complex64).ravel().astype(np.complex128), [i * st for i in range(F)], fo)
-            close(fr, taps, cars)
+            ref = R.records(f.view(np.complex64).ravel().astype(np.complex128), [i * st for i in range(F)], fo, budgets=True)
+            close(fr, *ref)
     finally:
         c.set_iq_format(dabgpu.IQ_CF32)
         c.close()
@@ -499,8 +503,8 @@ def test_gpu_acquired_and_tracked_capture(cctx):
         assert a["frames"] == inside.sum() and (rec["frames"] == inside).all()
         assert (rec[~inside].view(np.uint8) == 0).all()
         sel = np.flatnonzero(inside)
-        taps, cars = R.records(x[base:].astype(np.complex128), fr["start"][sel] + 64, fr["freq_offset"][sel].astype(np.float64))
-        close(rec[sel], taps, cars)
+        ref = R.records(x[base:].astype(np.complex128), fr["start"][sel] + 64, fr["freq_offset"][sel].astype(np.float64), budgets=True)
+        close(rec[sel], *ref)
         _, got = dabgpu.cir_analyse(a)
         assert len(got) == 2, (what, paths_of(got))
         assert abs(float(got[1]["delay"] - got[0]["delay"]) - 29.0) <= 0.1, (what, paths_of(got))
@@ -572,8 +576,7 @@ def test_gpu_full_size_launch(built):
         rec = frame[torch.from_numpy(pick).to("cuda:0")].cpu().numpy().view(dabgpu.CIR_ACC_DTYPE).reshape(-1)
         for i, r in zip(pick, rec):
             w = d[i * SYM + 504:i * SYM + 2552].cpu().numpy().astype(np.complex128)
-            taps, cars = R.record(w)
-            close(r, taps, cars)
+            close(r, *R.record(w, budgets=True))
         for s in range(S):
             _, got = dabgpu.cir_analyse(a[s])
             got = paths_of(got)

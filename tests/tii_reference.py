@@ -4,10 +4,40 @@ dabgpu_tii_*: the carrier sets, the pattern table (generated here, not copied fr
 
 The two conventions restated from memory -- which bit of a pattern is position b = 0, and the four carrier bases -- are
 kept here once, as they are kept once in the library (csrc/kernels.hpp).  What the tests pin is that the two agree and that
-the bases partition the 1536 carriers, not the standard's numbering."""
+the bases partition the 1536 carriers, not the standard's numbering.
+
+The frequency correction is the one the kernels apply: the correction f is taken as the float32 the device holds and
+quantised to the 32-bit phase step dphi = llrint(f 2^32) mod 2^32 (ties to even); sample n of the WINDOW (n = 0 at its
+first sample) is multiplied by exp(2 pi i frac(n dphi / 2^32)), the phase formed in exact integer arithmetic
+(ofdm_reference.dphi_of / nco).  dphi = 0 leaves the samples as they are.
+
+Error budgets.  U = 2^-24; every budget is a forward-error bound of a correct float32 implementation of the same
+operation, built as ofdm_reference.py builds its own (Higham: sums section 3.1, FFT theorem 24.2; C_FFT = 7 per radix-2
+stage).
+- C_NCO_DIRECT = 8 is the constant of the direct nco(n, dphi) these kernels call, with no running rotation: per sample
+  the phase float(int32 n dphi) carries half an ulp of a 24-bit mantissa (2^-26 of a turn: 2 pi 2^-26 = 1.6 U in the
+  phasor), sincospif 2 ulp per component (2 sqrt 2 U = 2.9 U), and the complex product two roundings per component
+  (3 U): 7.5 U, rounded up.  It is a sixteenth of ofdm_reference.C_NCO (128), which pays for 15 rotations of a running
+  phasor, and it is 0 where dphi == 0 (the kernels skip the product).
+- Spectrum: E_X = (C_FFT 11 + C_nco) U ||y||_2 per bin, y the 2048 corrected samples: the 2-norm bound of the whole
+  transform spread over its bins (Parseval), as ofdm_reference's E_l.
+- A power |X_k|^2 moves by at most 2 |X_k| E_X + E_X^2, and its own arithmetic (two products, one sum) by
+  gamma_2 (|X_k| + E_X)^2.
+- Cell: 8 powers summed in order: sum (2 |X_k| E_X + E_X^2) + C_CELL U sum (|X_k| + E_X)^2, C_CELL = 2 + 8 (gamma_2
+  of a power, gamma_7 of the sum, rounded up).
+- Floor: the mean of 304 powers through a fixed tree: two powers added per lane (1), six levels inside a wave (6),
+  the four waves in order (3), the division by 304 (1), on top of a power's gamma_2: C_FLOOR = 13, so
+  (sum (2 |X_k| E_X + E_X^2) + C_FLOOR U sum (|X_k| + E_X)^2) / 304.
+The accumulators carry no budget: a call's sum is bit for bit the sequential float32 frame-order sum of its records
+added to what the accumulator held, the frame count added as an integer."""
 import math
 
 import numpy as np
+
+from ofdm_reference import C_FFT, C_NCO, LOG2N, U, dphi_of, nco
+
+C_NCO_DIRECT, C_CELL, C_FLOOR = 8.0, 10.0, 13.0
+assert C_NCO_DIRECT <= C_NCO
 
 NB_FFT = 2048
 COMBS, POSITIONS, PATTERNS = 24, 8, 70
@@ -42,29 +72,47 @@ def noise_bins():
     return np.concatenate([k, NB_FFT - k])
 
 
-def record(window, freq_offset=0.0):
-    """One frame: window = the 2048 samples [-2352, -304) before its PRS prefix -> (cells [24][8], floor), float64.  The
-    correction exp(2 pi i f n) starts at the window's first sample (the phase does not reach a power)."""
-    x = np.asarray(window, np.complex128)
-    if freq_offset:
-        x = x * np.exp(2j * np.pi * float(freq_offset) * np.arange(NB_FFT))
-    P = np.abs(np.fft.fft(x)) ** 2
-    cells = np.zeros((COMBS, POSITIONS))
-    for c in range(COMBS):
-        for b in range(POSITIONS):
-            cells[c, b] = sum(P[k % NB_FFT] for k in cell_carriers(c, b))
-    return cells, P[noise_bins()].mean()
+CELL_BINS = np.array([[[k % NB_FFT for k in cell_carriers(c, b)] for b in range(POSITIONS)] for c in range(COMBS)])
 
 
-def records(iq, prs_starts, freq_offsets=None):
-    """Records of the frames whose PRS prefixes start at prs_starts in the 1-D array iq -> (cells [n][24][8], floor [n])."""
-    out_c, out_f = [], []
+def spectrum(window, freq_offset=0.0):
+    """(X [2048] complex128, E_X): the corrected window's transform and its per-bin budget."""
+    x = np.asarray(window, np.complex128).reshape(NB_FFT)
+    dphi = dphi_of(freq_offset)
+    y = x * nco(NB_FFT, dphi) if dphi else x
+    e = (C_FFT * LOG2N + (C_NCO_DIRECT if dphi else 0.0)) * U * math.sqrt(float((np.abs(y) ** 2).sum()))
+    return np.fft.fft(y), e
+
+
+def power_terms(X, e):
+    """Per bin: (|X|^2, what the spectral budget moves it by, the bound its own rounding scales with)."""
+    m = np.abs(X)
+    return m ** 2, 2.0 * m * e + e * e, (m + e) ** 2
+
+
+def record(window, freq_offset=0.0, budgets=False):
+    """One frame: window = the 2048 samples [-2352, -304) before its PRS prefix -> (cells [24][8], floor), float64, and
+    with budgets=True also (cell budget [24][8], floor budget).  The correction starts at the window's first sample."""
+    X, e = spectrum(window, freq_offset)
+    P, dP, R = power_terms(X, e)
+    cells = P[CELL_BINS].sum(axis=2)
+    nb = noise_bins()
+    floor = P[nb].mean()
+    if not budgets:
+        return cells, floor
+    cell_b = dP[CELL_BINS].sum(axis=2) + C_CELL * U * R[CELL_BINS].sum(axis=2)
+    floor_b = (dP[nb].sum() + C_FLOOR * U * R[nb].sum()) / nb.size
+    return cells, floor, cell_b, floor_b
+
+
+def records(iq, prs_starts, freq_offsets=None, budgets=False):
+    """Records of the frames whose PRS prefixes start at prs_starts in the 1-D array iq -> (cells [n][24][8], floor [n]),
+    with budgets=True also (cell budgets [n][24][8], floor budgets [n])."""
+    out = []
     for i, s in enumerate(prs_starts):
         s = int(s)
-        c, f = record(iq[s - WIN_BEGIN:s - WIN_END], 0.0 if freq_offsets is None else freq_offsets[i])
-        out_c.append(c)
-        out_f.append(f)
-    return np.array(out_c), np.array(out_f)
+        out.append(record(iq[s - WIN_BEGIN:s - WIN_END], 0.0 if freq_offsets is None else freq_offsets[i], budgets))
+    return tuple(np.array(a) for a in zip(*out))
 
 
 def decode(cells, floor, frames=1, min_level_db=3.0):
