@@ -775,6 +775,24 @@ int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t so
  * DABGPU_ERR_CAPACITY if max is too small, DABGPU_ERR_PROFILE if an announced pair names no profile. */
 int dabgpu_fig_subchannels(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_subchannel *out, int max, int *n);
 
+/* host only: which of those sub-channels carry audio, and which kind -- what the reference lists per service before it
+ * shows a DAB+ channel's flags (/root/reference/src/render_radio_block.cpp:414-437 are drawn for the sub-channels whose
+ * component says ASCTy 63).  FIG 0/2 (clause 6.3.1), both P/D forms, current configuration of this ensemble (C/N = 0,
+ * OE = 0): the MSC stream audio components (TMId = 0), joined through FIG 0/1 to the start address the entries of
+ * dabgpu_fig_subchannels carry.  Each SubChId once (its first component), sorted by start address; a component whose
+ * sub-channel the same FIBs have not announced (or announce with a reserved long-form option) is left out.
+ * *n receives the count; DABGPU_ERR_CAPACITY if max is too small (nothing written). */
+typedef struct dabgpu_audio_component {
+    uint32_t sid;               /* 16-bit (P/D = 0) or 32-bit (P/D = 1) service identifier */
+    int32_t subchid;
+    int32_t start_address;      /* CU, as dabgpu_subchannel.start_address                 */
+    int32_t ascty;              /* 0 = DAB (MPEG layer II), 63 = DAB+ (HE-AAC super-frames) */
+    int32_t primary;            /* P/S flag                                                */
+    int32_t reserved[3];
+} dabgpu_audio_component;
+int dabgpu_fig_audio_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_audio_component *out, int max,
+                                int *n);
+
 /* Host-pointer form for the plugin's one-frame-at-a-time use (BasicRadio::Process, src/radio_block.cpp:42): the
  * frames are uploaded ONCE, the FIC and every sub-channel are decoded from that copy, the results come back in one
  * batch of copies, one synchronisation.  history_in / history_out / out are HOST arrays of HOST pointers. */
@@ -1303,7 +1321,8 @@ int dabgpu_pipe_close(dabgpu_ctx *ctx);
 /* in        super-frame f = 5 consecutive logical frames of a DAB+ subchannel */
 /*           (the bytes dabgpu_msc_decode produces) = 15*bitrate bytes,        */
 /*           starting at in + f*in_stride.  The caller finds the alignment by   */
-/*           trying the 5 possible logical-frame offsets until firecode_ok.     */
+/*           trying the 5 possible logical-frame offsets until firecode_ok      */
+/*           (a batch: dabgpu_dabplus_follow_dev below finds and keeps it).     */
 /* out       [n][110*s] corrected data part (s = bitrate/8)                    */
 /* status[f] firecode_ok (after RS), rs_corrected bytes, rs_uncorrectable       */
 /*           codewords (of s), num_aus (0 when the Fire code fails),            */
@@ -1325,6 +1344,79 @@ int dabgpu_dabplus_superframes_dev(dabgpu_ctx *ctx, const uint8_t *d_in, size_t 
                                    void *stream);
 int dabgpu_dabplus_superframes(dabgpu_ctx *ctx, const uint8_t *in, size_t in_stride, int n_superframes,
                                int bitrate_kbps, uint8_t *out, dabgpu_superframe_status *status);
+
+/* ------------------------------------------------------------------------ */
+/* Following every DAB+ sub-channel of a batch to super-frames on the device:  */
+/* alignment, carry between calls, then the checks above -- what stands        */
+/* behind the "Firecode / RS / AU" flags and the super-frame header of every    */
+/* DAB+ service the reference shows                                            */
+/*   (/root/reference/src/render_radio_block.cpp:414-437)                       */
+/* for a monitoring receiver that decodes many ensembles per call              */
+/* (dabgpu_decode_ensembles_dev).                    */
+/*                                                                            */
+/* One entry per followed sub-channel; one call takes the n_cifs logical        */
+/* frames every entry's decode call produced (its d_out[j]) and two launches:   */
+/* one wave per entry finds the phase, one workgroup per super-frame decodes.   */
+/*                                                                            */
+/* The contract of one entry in one call.  F = the `held` frames of carry_in    */
+/* followed by the n_cifs new ones, T = held + n_cifs.  Frame i is a RAW HIT    */
+/* when its first 11 bytes, uncorrected, are not all zero and the Fire code     */
+/* over bytes 2..10 equals bytes 0..1.  votes[r] = hits at i = r (mod 5),       */
+/* raw_hits = their sum.  The phase p: with a synced carry 0, unless a residue   */
+/* has strictly more votes than residue 0 -- then, and with a carry that is      */
+/* not synced, the smallest residue with the maximum, if that is > 0; else no    */
+/* phase.  No phase: n_superframes = 0, phase = -1, carry_out holds the last     */
+/* min(4, T) frames with synced = 0, dropped = the rest.  With a phase:          */
+/* n_superframes = (T - p) / 5, super-frame k = frames p + 5k .. p + 5k + 4,      */
+/* dropped = p, carry_out holds the 0..4 frames from p + 5 n_superframes on,      */
+/* synced = 1 iff votes[p] > 0 or n_superframes = 0.  Every emitted super-frame   */
+/* gets exactly what dabgpu_dabplus_superframes_dev gives for the same 120 s      */
+/* bytes (RS, then the Fire code, then the AU table and CRCs): d_data[k] and      */
+/* d_status[k], k < n_superframes; rows beyond are not written.  A super-frame    */
+/* whose header has byte errors is decoded where the votes of the others put      */
+/* it, and comes out firecode_ok after RS.                                        */
+/*                                                                            */
+/* The search reads the raw header because an RS pass at all five phases costs   */
+/* five times the kernel; one phase per entry per call is enough because the     */
+/* CIFs of a call are contiguous by construction.  The limit: a call none of     */
+/* whose start frames has a clean raw header finds no phase (or keeps the one    */
+/* it was on), however well RS would have repaired them.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_dabplus_follow_result {
+    int32_t n_superframes;      /* emitted by this call                                             */
+    int32_t phase;              /* p, or -1 = none                                                   */
+    int32_t synced;             /* what carry_out says                                               */
+    int32_t dropped;            /* frames of F that belong to no super-frame and are not carried      */
+    int32_t raw_hits;
+    int32_t held;               /* frames in carry_out, 0..4                                          */
+    int32_t reserved[2];
+} dabgpu_dabplus_follow_result;
+
+typedef struct dabgpu_dabplus_entry {       /* HOST array, one per followed sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_in;        /* [n_cifs][in_stride] logical frames: the d_out[j] of the decode calls            */
+    size_t in_stride;           /* >= bitrate*3                                                                    */
+    int32_t bitrate_kbps;       /* multiple of 8, 8 .. 512 (the range of dabgpu_dabplus_superframes_dev)           */
+    const void *d_carry_in;     /* dabgpu_dabplus_carry_bytes(bitrate) bytes on a 16-byte boundary, or NULL = fresh */
+                                /* start; an all-zero record is a fresh start too (as is one whose held is not 0..4) */
+    void *d_carry_out;          /* same size and alignment; != d_carry_in; overlaps nothing else of the call        */
+                                /* (written whole: header, held frames, zeros behind them)                         */
+    uint8_t *d_data;            /* [(n_cifs+4)/5][110*s]                                                           */
+    dabgpu_superframe_status *d_status;      /* [(n_cifs+4)/5]                                                     */
+    dabgpu_dabplus_follow_result *d_result;  /* one record                                                         */
+} dabgpu_dabplus_entry;
+
+/* bytes of one carry record: a 16-byte header {int32 synced, held, 0, 0} and 4 logical frames of bitrate*3 bytes, rounded
+ * up to 16; 0 for a bit rate the follow call refuses */
+size_t dabgpu_dabplus_carry_bytes(int bitrate_kbps);
+
+/* entries [n_entries] (HOST), any mix of bit rates; n_cifs logical frames per entry (frames_per_stream * 4 of the decode
+ * call).  Everything is checked before anything is enqueued, so a refused call leaves every output as it was:
+ * DABGPU_ERR_ARG for a NULL context or table, negative counts, a bit rate outside 8 .. 512 or no multiple of 8,
+ * in_stride < bitrate*3 (with more than one frame), a NULL pointer other than d_carry_in (d_in may be NULL with
+ * n_cifs = 0, d_data / d_status with n_cifs = 0), a carry record off its 16-byte boundary, d_carry_in and d_carry_out that
+ * are equal or overlap, d_status or d_result off a 4-byte boundary.  No host synchronisation, no host-pointer twin: the
+ * one-frame path of the plugin stays on dabgpu_dabplus_superframes. */
+int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entries, int n_entries, int n_cifs, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

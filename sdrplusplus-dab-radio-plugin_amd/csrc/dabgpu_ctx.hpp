@@ -67,6 +67,7 @@ enum StageSlot {
     STAGE_MOD_CODED = 10,   // the modulator's coded records, one per ETI frame
     STAGE_MOD_CUM = 11,     // ... and running quarter turns, one pair of bit planes per data symbol
     STAGE_ENSEMBLES = 12,   // dabgpu_decode_ensembles_dev: the entry table of the ragged grouped lane launch
+    STAGE_DABPLUS = 13,     // dabgpu_dabplus_follow_dev: the entry table and the plans of the align / follow launches
     STAGE_SLOTS
 };
 

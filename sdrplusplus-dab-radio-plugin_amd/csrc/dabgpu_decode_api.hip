@@ -1,5 +1,5 @@
 // dabgpu_decode_api.hip -- the channel-decoder entry points of the C ABI (include/dabgpu.h): FIC, MSC sub-channels,
-// whole frames, the one-stream host call, DAB+ super-frames, plain Viterbi.
+// whole frames, the one-stream host call, DAB+ super-frames and following DAB+ sub-channels to them, plain Viterbi.
 #include "decode_plan.hpp"
 
 #include <algorithm>
@@ -555,6 +555,76 @@ int dabgpu_fig_subchannels(const uint8_t *fib, const uint8_t *crc_ok, int n_fram
     return DABGPU_OK;
 }
 
+int dabgpu_fig_audio_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_audio_component *out, int max,
+                                int *n) {
+    if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
+    // FIG 0/1 gives SubChId -> start address (the entries dabgpu_fig_subchannels lists); FIG 0/2 (EN 300 401 clause 6.3.1)
+    // gives per service: SId (16 bits, or 32 with P/D = 1), Rfa (1) CAId (3) NumComponents (4), then two bytes per component --
+    // TMId (2), and for TMId = 0: ASCTy (6), SubChId (6), P/S (1), CA flag (1)
+    int start_of[64];
+    for (int i = 0; i < 64; i++) start_of[i] = -1;
+    dabgpu_audio_component found[64];
+    bool seen[64] = {};
+    int count = 0;
+    for (int pass = 0; pass < 2; pass++) {                      // 0: the sub-channel organisation; 1: the services
+        for (int k = 0; k < n_frames * NB_FIBS; k++) {
+            if (!crc_ok[k]) continue;
+            const uint8_t *d = fib + size_t(k) * 32;
+            for (int i = 0; i < 30;) {
+                if (d[i] == 0xFF) break;
+                const int type = d[i] >> 5, len = d[i] & 0x1F;
+                if (len == 0 || i + 1 + len > 30) break;
+                const uint8_t *b = d + i + 1;
+                i += 1 + len;
+                // type 0, current configuration (C/N = 0), this ensemble (OE = 0)
+                if (type != 0 || (b[0] & 0xC0)) continue;
+                const int ext = b[0] & 0x1F, pd = (b[0] >> 5) & 1;
+                if (pass == 0 && ext == 1) {
+                    for (int j = 1; j + 3 <= len;) {
+                        const int id = b[j] >> 2, start = ((b[j] & 3) << 8) | b[j + 1];
+                        if (b[j + 2] & 0x80) {
+                            if (j + 4 > len) break;
+                            const int option = (b[j + 2] >> 4) & 7;
+                            j += 4;
+                            if (option > 1) continue;          // (passed over by dabgpu_fig_subchannels as well)
+                        } else {
+                            j += 3;
+                        }
+                        if (start_of[id] < 0) start_of[id] = start;
+                    }
+                } else if (pass == 1 && ext == 2) {
+                    const int sid_bytes = pd ? 4 : 2;
+                    for (int j = 1; j + sid_bytes + 1 <= len;) {
+                        uint32_t sid = 0;
+                        for (int q = 0; q < sid_bytes; q++) sid = (sid << 8) | b[j + q];
+                        const int ncomp = b[j + sid_bytes] & 0x0F;
+                        j += sid_bytes + 1;
+                        if (j + 2 * ncomp > len) break;
+                        for (int c = 0; c < ncomp; c++, j += 2) {
+                            if (b[j] >> 6) continue;           // TMId != 0: data, FIDC or packet mode
+                            const int id = b[j + 1] >> 2;
+                            if (seen[id] || start_of[id] < 0) continue;
+                            seen[id] = true;
+                            dabgpu_audio_component a{};
+                            a.sid = sid;
+                            a.subchid = id;
+                            a.start_address = start_of[id];
+                            a.ascty = b[j] & 0x3F;
+                            a.primary = (b[j + 1] >> 1) & 1;
+                            found[count++] = a;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    std::stable_sort(found, found + count, [](const dabgpu_audio_component &a, const dabgpu_audio_component &b) { return a.start_address < b.start_address; });
+    *n = count;
+    if (count > max) return DABGPU_ERR_CAPACITY;
+    for (int i = 0; i < count; i++) out[i] = found[i];
+    return DABGPU_OK;
+}
+
 int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_streams, int frames_per_stream,
                          uint8_t *fib, uint8_t *crc_ok, const dabgpu_subchannel *sc, int n_subchannels,
                          const int8_t *const *history_in, int8_t *const *history_out, uint8_t *const *out) {
@@ -711,6 +781,57 @@ int dabgpu_dabplus_superframes(dabgpu_ctx *ctx, const uint8_t *in, size_t in_str
     h.down(STAGE_RESULT, out);
     h.down(STAGE_AUX, status);
     return h.finish();
+}
+
+// ---------------------------------------------------------------------------- DAB+: following sub-channels
+static_assert(sizeof(dabgpu_dabplus_follow_result) == sizeof(dabk::FollowResult), "ABI struct mirrors the kernel's");
+
+static bool follow_bitrate_ok(int bitrate_kbps) { return bitrate_kbps >= 8 && bitrate_kbps <= 512 && bitrate_kbps % 8 == 0; }
+
+size_t dabgpu_dabplus_carry_bytes(int bitrate_kbps) {
+    return follow_bitrate_ok(bitrate_kbps) ? dabk::follow_carry_bytes(bitrate_kbps / 8) : 0;
+}
+
+int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entries, int n_entries, int n_cifs, void *stream) {
+    if (!ctx || n_entries < 0 || n_cifs < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
+    // everything is checked before anything is enqueued: a refused call leaves every output as it was
+    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
+    const int max_sf = (n_cifs + 4) / 5;
+    std::vector<dabk::FollowEntry> table(size_t(n_entries), dabk::FollowEntry{});
+    for (int i = 0; i < n_entries; i++) {
+        const dabgpu_dabplus_entry &e = entries[i];
+        if (!follow_bitrate_ok(e.bitrate_kbps)) return DABGPU_ERR_ARG;
+        const int s = e.bitrate_kbps / 8;
+        if (n_cifs > 0 && !e.d_in) return DABGPU_ERR_ARG;
+        if (n_cifs > 1 && e.in_stride < size_t(24) * s) return DABGPU_ERR_ARG;
+        if (max_sf > 0 && (!e.d_data || !e.d_status)) return DABGPU_ERR_ARG;
+        if (!e.d_carry_out || !e.d_result) return DABGPU_ERR_ARG;
+        if ((addr(e.d_carry_in) | addr(e.d_carry_out)) & 15) return DABGPU_ERR_ARG;
+        if ((addr(e.d_status) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
+        const uint64_t cb = dabk::follow_carry_bytes(s);
+        if (e.d_carry_in && addr(e.d_carry_in) < addr(e.d_carry_out) + cb && addr(e.d_carry_out) < addr(e.d_carry_in) + cb)
+            return DABGPU_ERR_ARG;
+        dabk::FollowEntry &t = table[size_t(i)];
+        t.in = addr(e.d_in);
+        t.carry_in = addr(e.d_carry_in);
+        t.carry_out = addr(e.d_carry_out);
+        t.data = addr(e.d_data);
+        t.status = addr(e.d_status);
+        t.result = addr(e.d_result);
+        t.in_stride = e.in_stride;
+        t.s = s;
+    }
+    if (n_entries == 0) return DABGPU_OK;
+    DeviceGuard guard(ctx);
+    hipStream_t s = pick_stream(ctx, stream);
+    const size_t table_bytes = dabk::follow_table_bytes(n_entries);
+    // (growing the table must not race with a launch that still reads the old one)
+    if (ctx->stage_bytes[STAGE_DABPLUS] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
+    void *d_table = nullptr;
+    const int rc = stage(ctx, STAGE_DABPLUS, table_bytes, &d_table);
+    if (rc) return rc;
+    HIP_TRY(dabk::launch_dabplus_follow(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_DABPLUS], s));
+    return DABGPU_OK;
 }
 
 // ---------------------------------------------------------------------------- plain Viterbi

@@ -316,6 +316,35 @@ hipError_t launch_dabplus_superframes(const uint8_t *in, size_t in_stride, int n
                                       SuperframeStatus *status, hipStream_t stream, unsigned long long *done_flag = nullptr,
                                       unsigned long long done_seq = 0);
 
+// Following DAB+ sub-channels to super-frames (dabgpu_dabplus_follow_dev): one entry per followed sub-channel, uploaded
+// as a table; the align kernel (one wave per entry) finds each entry's phase from the raw Fire check of every logical
+// frame, writes its plan behind the table, the result record and the carry record; the follow kernel (one workgroup per
+// possible super-frame) decodes the super-frames the plans name.  No host synchronisation in between.
+struct alignas(16) FollowEntry {
+    uint64_t in;               // [n_cifs][in_stride] logical frames of 24 s bytes
+    uint64_t carry_in;         // carry record or 0: 16-byte header {synced, held, 0, 0}, then 4 frames of 24 s bytes
+    uint64_t carry_out;
+    uint64_t data;             // [(n_cifs + 4) / 5][110 s]
+    uint64_t status;           // [(n_cifs + 4) / 5] SuperframeStatus
+    uint64_t result;           // one FollowResult
+    uint64_t in_stride;
+    int32_t s;                 // bitrate / 8
+    int32_t reserved;
+};
+struct alignas(16) FollowPlan {
+    int32_t phase, n_superframes, held, reserved;
+};
+struct FollowResult {          // == dabgpu_dabplus_follow_result
+    int32_t n_superframes, phase, synced, dropped, raw_hits, held, reserved[2];
+};
+constexpr size_t FOLLOW_CARRY_HEADER = 16;
+inline size_t follow_carry_bytes(int s) { return (FOLLOW_CARRY_HEADER + size_t(4) * 24 * size_t(s) + 15) & ~size_t(15); }
+// bytes of device memory the table and the plans take (16-byte aligned)
+size_t follow_table_bytes(int n_entries);
+// `entries`: HOST array (copied to d_table on `stream` before the kernels); every pointer checked by the caller
+hipError_t launch_dabplus_follow(const FollowEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes,
+                                 hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

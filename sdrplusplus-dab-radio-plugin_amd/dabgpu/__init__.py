@@ -52,6 +52,7 @@ EXPORTS = [
     "dabgpu_eti_layout", "dabgpu_eti_history_bytes", "dabgpu_eti_frames_dev", "dabgpu_eti_parse",
     "dabgpu_eti_streams_from_frame", "dabgpu_mod_default_cfg", "dabgpu_mod_state_bytes", "dabgpu_modulate_eti_dev",
     "dabgpu_decode_ensembles_dev", "dabgpu_fig_subchannels",
+    "dabgpu_dabplus_follow_dev", "dabgpu_dabplus_carry_bytes", "dabgpu_fig_audio_components",
 ]
 
 ABI_VERSION = 6
@@ -123,6 +124,16 @@ SUPERFRAME_STATUS_DTYPE = np.dtype([("firecode_ok", np.int32), ("rs_corrected", 
                                     ("num_aus", np.int32), ("au_crc_mask", np.int32), ("au_start", np.int32, (8,)),
                                     ("reserved", np.int32, (3,))])
 assert SUPERFRAME_STATUS_DTYPE.itemsize == 64
+#: dabgpu_dabplus_follow_result: what one entry of Context.dabplus_follow_dev did in one call (device memory)
+DABPLUS_FOLLOW_RESULT_DTYPE = np.dtype([("n_superframes", np.int32), ("phase", np.int32), ("synced", np.int32),
+                                        ("dropped", np.int32), ("raw_hits", np.int32), ("held", np.int32),
+                                        ("reserved", np.int32, (2,))])
+assert DABPLUS_FOLLOW_RESULT_DTYPE.itemsize == 32
+#: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
+AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
+                                  ("primary", np.int32), ("reserved", np.int32, (3,))])
+assert AUDIO_COMPONENT_DTYPE.itemsize == 32
+ASCTY_DAB, ASCTY_DABPLUS = 0, 63
 #: dabgpu_tii_acc: a stream's transmitter-identification sums (device memory; zero it to start), or one frame's record
 TII_ACC_DTYPE = np.dtype([("cell", np.float32, (24, 8)), ("floor", np.float32), ("frames", np.int32), ("reserved", np.int32, (2,))])
 assert TII_ACC_DTYPE.itemsize == 784
@@ -177,6 +188,20 @@ def ber(counts):
     counts = np.asarray(counts)
     bits = int(counts["bits"].sum(dtype=np.uint64))
     return float(counts["errors"].sum(dtype=np.uint64)) / bits if bits else float("nan")
+
+
+class DabplusEntry(C.Structure):
+    """dabgpu_dabplus_entry: one followed DAB+ sub-channel of Context.dabplus_follow_dev (device addresses)."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
+                ("d_carry_out", C.c_void_p), ("d_data", C.c_void_p), ("d_status", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+class AudioComponent(C.Structure):
+    _fields_ = [("sid", C.c_uint32), ("subchid", C.c_int32), ("start_address", C.c_int32), ("ascty", C.c_int32),
+                ("primary", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+assert C.sizeof(AudioComponent) == AUDIO_COMPONENT_DTYPE.itemsize
 
 
 class SyncResult(C.Structure):
@@ -437,6 +462,10 @@ def load_library(path):
     L.dabgpu_decode_frames.argtypes = [vp, vp, sz, i, i, vp, vp, vp, i, vp, vp, vp]
     L.dabgpu_decode_ensembles_dev.argtypes = [vp, vp, sz, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dabgpu_fig_subchannels.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
+    L.dabgpu_fig_audio_components.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
+    L.dabgpu_dabplus_follow_dev.argtypes = [vp, C.POINTER(DabplusEntry), i, i, vp]
+    L.dabgpu_dabplus_carry_bytes.restype = C.c_size_t
+    L.dabgpu_dabplus_carry_bytes.argtypes = [i]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -631,6 +660,26 @@ def fig_subchannels(fib, crc_ok, max_out=64):
     n = C.c_int(0)
     _check(lib().dabgpu_fig_subchannels(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_subchannels")
     return [Subchannel(a.start_address, a.length, a.is_uep, a.eep_type, a.protection_level, a.bitrate_kbps) for a in arr[:n.value]]
+
+
+def fig_audio_components(fib, crc_ok, max_out=64):
+    """The MSC stream audio components one ensemble announces (FIG 0/2 joined to FIG 0/1) in its CRC-clean FIBs, each
+    sub-channel once, sorted by start address: fib [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of
+    AudioComponent (ascty 0 = DAB, 63 = DAB+; no GPU needed)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    arr = (AudioComponent * max(max_out, 1))()
+    n = C.c_int(0)
+    _check(lib().dabgpu_fig_audio_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_audio_components")
+    return [AudioComponent(a.sid, a.subchid, a.start_address, a.ascty, a.primary) for a in arr[:n.value]]
+
+
+def dabplus_carry_bytes(bitrate_kbps):
+    """Bytes of one carry record of Context.dabplus_follow_dev (0 for a bit rate it refuses)."""
+    return int(lib().dabgpu_dabplus_carry_bytes(bitrate_kbps))
 
 
 # ------------------------------------------------------------------ context
@@ -1132,6 +1181,14 @@ class Context:
         (SUPERFRAME_STATUS_DTYPE)."""
         _check(self._lib.dabgpu_dabplus_superframes_dev(self._h, d_in, in_stride, n, bitrate_kbps, d_out, d_status, stream),
                "dabgpu_dabplus_superframes_dev")
+
+    def dabplus_follow_dev(self, entries, n_cifs, stream=None):
+        """Follow DAB+ sub-channels to super-frames on the device: entries is a list of DabplusEntry (device addresses; any
+        mix of bit rates), each with n_cifs new logical frames.  Per entry: d_data / d_status rows [0, n_superframes),
+        d_result (DABPLUS_FOLLOW_RESULT_DTYPE) and d_carry_out, to be passed as d_carry_in of the next call."""
+        n = len(entries)
+        arr = (DabplusEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_dabplus_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dabplus_follow_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""
