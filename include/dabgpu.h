@@ -1451,7 +1451,11 @@ int dabgpu_viterbi(dabgpu_ctx *ctx, const int8_t *punct, int n_codewords, const 
 /* that were.  Both wait for the launches they read.  _mean_ only: 4 / 5 / 6 =  */
 /* the parts of 2 when it was the grouped codeword-per-lane launch (batches of  */
 /* >= 24 576 codewords): forward pass | traceback | de-interleaver history copy */
-/* (DABGPU_ERR_ARG when no timed call took that path).                          */
+/* (DABGPU_ERR_ARG when no timed call took that path).  A call has these parts  */
+/* only when its whole list went out as ONE forward and ONE traceback launch:   */
+/* dabgpu_decode_frames* / dabgpu_msc_decode_multi_dev with at most 16 entries  */
+/* (the FIC is one), or dabgpu_decode_ensembles_dev through its table.  A longer */
+/* list is several launch pairs: it counts for 2 and is passed over by 4 / 5 / 6. */
 /* 7 (both calls) = the ETI launches of dabgpu_eti_frames_dev.                  */
 /* 8 / 9 (both calls) = dabgpu_modulate_eti_dev: the encoder with its pre-pass | */
 /* the symbol kernel.                                                           */

@@ -238,16 +238,16 @@ struct ScopedTimer {
             (void)hipEventRecord(t.start[i], s);
         }
     }
-    // the two events a launch sequence records between its kernels (nullptr while timing is off)
+    // the two events a launch sequence may record between its kernels (nullptr while timing is off); when it has recorded
+    // both it says so with mids_recorded(): only then does this call count for the timer's parts
     hipEvent_t *mids() {
         if (!ctx->timing) return nullptr;
         Timer &t = ctx->timers[which];
-        const int i = int(t.recorded % TIMER_RING);
-        for (hipEvent_t &e : t.mid[i])
+        for (hipEvent_t &e : t.mid[int(t.recorded % TIMER_RING)])
             if (!e && hipEventCreate(&e) != hipSuccess) return nullptr;
-        t.has_mid[i] = true;
-        return t.mid[i];
+        return t.mid[int(t.recorded % TIMER_RING)];
     }
+    void mids_recorded() { ctx->timers[which].has_mid[int(ctx->timers[which].recorded % TIMER_RING)] = true; }
     ~ScopedTimer() {
         if (ctx->timing) {
             Timer &t = ctx->timers[which];

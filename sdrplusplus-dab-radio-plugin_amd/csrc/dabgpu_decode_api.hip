@@ -4,27 +4,90 @@
 
 #include <algorithm>
 #include <cstring>
+#include <optional>
+
+#include "lane_plan.hpp"
 
 using namespace dab;
 using namespace dabapi;
 
 namespace {
 
-// returns true and a scratch descriptor when the lane kernels should take this launch
-// (`force`: the codeword is too long for the wave-per-codeword kernels' LDS slab -- the lane kernels keep their
-// survivors in HBM and take any length)
-bool use_lane(dabgpu_ctx *ctx, int nsteps, int n_codewords, hipStream_t s, dabk::LaneScratch *sc, int *rc, bool force = false) {
-    *rc = DABGPU_OK;
-    if (!dabk::lane_supported(nsteps)) return false;
-    if (!force && (ctx->lane_mode == 0 || (ctx->lane_mode < 0 && n_codewords < LANE_MIN_CODEWORDS))) return false;
-    if (!lane_scratch(ctx, dabk::lane_scratch_bytes(nsteps, n_codewords), s, rc)) {
-        if (!*rc && (ctx->lane_mode > 0 || force)) *rc = DABGPU_ERR_NOMEM;
-        return false;                                         // (no room, not forced: fall back to the wave kernels)
+// THE lane/wave decision.  0: the wave kernels.  1: the lane kernels, if their scratch can be had -- a failed allocation
+// falls back to the wave kernels silently.  2: the lane kernels or DABGPU_ERR_NOMEM -- the context forces them
+// (DABGPU_FLAG_VITERBI_LANE), or a codeword is too long for the wave kernels' LDS slab (the lane kernels keep their
+// survivors in HBM and take any length).  `n_codewords`: a single item's own count; the grouped call's sum.
+int lane_policy(const dabgpu_ctx *ctx, long n_codewords, bool too_long) {
+    if (too_long || ctx->lane_mode > 0) return 2;
+    return (ctx->lane_mode < 0 && n_codewords >= LANE_MIN_CODEWORDS) ? 1 : 0;
+}
+
+dabk::LaneItem fic_item(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_stride, int n_streams, int frames_per_stream, uint8_t *d_fib,
+                        uint8_t *d_crc_ok) {
+    dabk::LaneItem it{};
+    it.code = ctx->fic.tables(true);
+    it.tables = ctx->fic.lane_tables();
+    it.args.soft = d_soft;
+    it.args.soft_stride = soft_stride;
+    it.args.n_streams = n_streams;
+    it.args.frames_per_stream = frames_per_stream;
+    it.args.out = d_fib;
+    it.kind = dabk::LaneItem::FIC;
+    it.crc_ok = d_crc_ok;
+    return it;
+}
+dabk::LaneItem msc_item(const DeviceCode *dc, const dabk::MscArgs &a) {
+    dabk::LaneItem it{};
+    it.code = dc->tables(true);
+    it.tables = dc->lane_tables();
+    it.args = a;
+    it.kind = dabk::LaneItem::SUBCHANNEL;
+    return it;
+}
+
+// A list of items through the lane kernels (`timer`: TIMER_FIC / TIMER_MSC, or < 0 for none).  Returns 0 when everything
+// was enqueued, 1 when the lane kernels do not apply (the caller falls back), < 0 on errors.
+//   one item (!by_table)  goes whatever its shape: fused where lane_item_fusable says so, through the prep kernel otherwise
+//                         (and always with DABGPU_FLAG_LANE_UNFUSED); `too_long` is its own length
+//   several items         all or nothing: every item fusable and the context not unfused, else the caller sends them one
+//                         by one; a failed allocation falls back too, so that each item applies the policy to itself; a
+//                         too-long codeword among them forces nothing (too_long = false)
+//   by_table              (dabgpu_decode_ensembles_dev) as several items, through the device table; no batch-size threshold:
+//                         the alternative is not the wave kernels on the whole batch but one small call per stream
+// The multi-item forms ask for the timer's parts (forward | traceback | history).
+int decode_lane(dabgpu_ctx *ctx, const std::vector<dabk::LaneItem> &items, bool too_long, int timer, bool by_table, void *stream) {
+    const int n = int(items.size());
+    const bool single = n == 1 && !by_table;
+    long total_cw = 0;
+    for (const dabk::LaneItem &it : items) {
+        if (!dabk::lane_supported(it.code.nsteps)) return 1;
+        total_cw += long(it.codewords());
     }
-    sc->base = ctx->d_lane_scratch;
-    sc->bytes = ctx->lane_scratch_bytes;
-    sc->unfused = ctx->lane_unfused;
-    return true;
+    const int policy = lane_policy(ctx, by_table ? long(LANE_MIN_CODEWORDS) : total_cw, too_long);
+    if (policy == 0) return 1;
+    if (!single) {
+        if (ctx->lane_unfused) return 1;
+        for (const dabk::LaneItem &it : items)
+            if (!dabk::lane_item_fusable(it)) return 1;
+    }
+    hipStream_t s = pick_stream(ctx, stream);
+    int rc;
+    if (!lane_scratch(ctx, dabk::lane_scratch_bytes(items.data(), n, ctx->lane_unfused), s, &rc))
+        return rc ? rc : (single && policy == 2) ? DABGPU_ERR_NOMEM : 1;
+    dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes, ctx->lane_unfused};
+    if (by_table) {
+        const size_t table_bytes = dabk::lane_table_bytes(items.data(), n);
+        // (growing the table must not race with a launch that still reads the old one)
+        if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
+        if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &lsc.table)) return 1;
+        lsc.table_bytes = ctx->stage_bytes[STAGE_ENSEMBLES];
+    }
+    std::optional<ScopedTimer> tm;
+    if (timer >= 0) tm.emplace(ctx, timer, s);
+    bool parts = false;
+    const hipError_t e = dabk::launch_lane(items.data(), n, lsc, s, (tm && !single) ? tm->mids() : nullptr, &parts);
+    if (tm && parts) tm->mids_recorded();
+    return e == hipSuccess ? 0 : DABGPU_ERR_HIP;
 }
 
 // one sub-channel in launches of its own (`dc`: its code tables where the caller's plan holds them, else looked up here)
@@ -40,122 +103,30 @@ int msc_decode_one(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, DeviceCode *dc,
     if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;
     const bool too_long = !dabk::viterbi_fits(dc->prof.nsteps);   // above ~800 kbit/s: only the lane kernels hold it
     if (too_long && !dabk::lane_supported(dc->prof.nsteps)) return DABGPU_ERR_CAPACITY;
-    hipStream_t s = pick_stream(ctx, stream);
     const dabk::MscArgs a = msc_args(*sc, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in, d_history_out, d_out);
-    ScopedTimer tm(ctx, TIMER_MSC, s);
-    dabk::LaneScratch lsc{};
-    int lrc;
-    if (use_lane(ctx, dc->prof.nsteps, n_streams * frames_per_stream * NB_CIFS, s, &lsc, &lrc, too_long)) {
-        HIP_TRY(dabk::launch_msc_decode_lane(dc->tables(true), dc->lane_tables(), a, lsc, s));
-        HIP_TRY(dabk::launch_msc_history(a, s));
-        return DABGPU_OK;
-    }
-    if (lrc) return lrc;
+    if ((rc = decode_lane(ctx, {msc_item(dc, a)}, too_long, TIMER_MSC, false, stream)) <= 0) return rc;
     if (too_long) return DABGPU_ERR_CAPACITY;
+    hipStream_t s = pick_stream(ctx, stream);
+    ScopedTimer tm(ctx, TIMER_MSC, s);
     HIP_TRY(dabk::launch_msc_decode(dc->tables(true), a, s));
     return DABGPU_OK;
 }
 
-// The FIC (d_fib != nullptr) and/or several sub-channels in one grouped lane launch.  Returns 0 when everything was
-// enqueued, 1 when the grouped path does not apply (caller falls back to one call per part), < 0 on errors.
-int decode_grouped(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, const SubchannelPlan &plan, const int8_t *d_soft,
+// The FIC (d_fib != nullptr) and/or several sub-channels in one grouped lane launch: decode_lane's answer.
+int decode_parts_lane(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, const SubchannelPlan &plan, const int8_t *d_soft,
                    size_t soft_stride, int n_streams, int frames_per_stream, const int8_t *const *d_history_in,
                    int8_t *const *d_history_out, uint8_t *const *d_out, void *stream) {
-    const int n_items = plan.n + (d_fib ? 1 : 0);
-    if (n_items < 2 || ctx->lane_mode == 0 || ctx->lane_unfused || !d_soft || n_streams <= 0 || frames_per_stream <= 0 ||
-        soft_stride < size_t(NB_FRAME_BITS))
+    if (plan.n + (d_fib ? 1 : 0) < 2 || !d_soft || n_streams <= 0 || frames_per_stream <= 0 || soft_stride < size_t(NB_FRAME_BITS))
         return 1;
-    const long total_cw = long(n_items) * n_streams * frames_per_stream * NB_CIFS;
-    if (ctx->lane_mode < 0 && total_cw < LANE_MIN_CODEWORDS) return 1;
-    std::vector<dabk::LaneGroupItem> items;
-    if (d_fib) {
-        dabk::LaneGroupItem it{};
-        it.code = ctx->fic.tables(true);
-        it.tables = ctx->fic.lane_tables();
-        it.args.soft = d_soft;
-        it.args.soft_stride = soft_stride;
-        it.args.n_streams = n_streams;
-        it.args.frames_per_stream = frames_per_stream;
-        it.args.out = d_fib;
-        it.is_fic = true;
-        it.crc_ok = d_crc_ok;
-        if (((reinterpret_cast<uintptr_t>(d_soft) | soft_stride) & 15) || (reinterpret_cast<uintptr_t>(d_fib) & 3)) return 1;
-        items.push_back(it);
-    }
+    std::vector<dabk::LaneItem> items;
+    if (d_fib) items.push_back(fic_item(ctx, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok));
     for (int i = 0; i < plan.n; i++) {
-        const DeviceCode *dc = plan.code[size_t(i)];
-        dabk::LaneGroupItem it{};
-        it.code = dc->tables(true);
-        it.tables = dc->lane_tables();
-        it.args = msc_args(plan.sc[i], d_soft, soft_stride, n_streams, frames_per_stream, d_history_in ? d_history_in[i] : nullptr,
-                           d_history_out ? d_history_out[i] : nullptr, d_out[i]);
-        if (it.args.hist_in && it.args.hist_in == it.args.hist_out) return DABGPU_ERR_ARG;
-        if (!dabk::lane_supported(dc->prof.nsteps) || !dabk::lane_group_fusable(it.args)) return 1;
-        items.push_back(it);
+        items.push_back(msc_item(plan.code[size_t(i)], msc_args(plan.sc[i], d_soft, soft_stride, n_streams, frames_per_stream,
+                                                                d_history_in ? d_history_in[i] : nullptr,
+                                                                d_history_out ? d_history_out[i] : nullptr, d_out[i])));
+        if (items.back().args.hist_in && items.back().args.hist_in == items.back().args.hist_out) return DABGPU_ERR_ARG;
     }
-    hipStream_t s = pick_stream(ctx, stream);
-    int rc;
-    if (!lane_scratch(ctx, dabk::lane_group_scratch_bytes(items.data(), n_items), s, &rc)) return rc ? rc : 1;
-    ScopedTimer tm(ctx, TIMER_MSC, s);
-    dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes};
-    HIP_TRY(dabk::launch_lane_group(items.data(), n_items, lsc, s, tm.mids()));
-    for (const dabk::LaneGroupItem &it : items)
-        if (!it.is_fic) HIP_TRY(dabk::launch_msc_history(it.args, s));
-    return 0;
-}
-
-// The FIC of every frame (d_fib != nullptr) and every (stream, sub-channel) entry of a batch of ensembles in one ragged
-// grouped lane launch.  Returns 0 when everything was enqueued, 1 when the launch does not apply (whole 64-codeword groups
-// inside one stream: frames_per_stream a multiple of 16; the alignment rules of lane_group_fusable for every entry; a
-// context that may use the fused lane kernels), < 0 on errors.  No batch-size threshold: the alternative is not the wave
-// kernels on the whole batch but one small call per stream.
-int decode_ensembles_grouped(dabgpu_ctx *ctx, uint8_t *d_fib, uint8_t *d_crc_ok, const EnsemblePlan &plan, const int8_t *d_soft,
-                             size_t soft_stride, int frames_per_stream, const int8_t *const *d_history_in,
-                             int8_t *const *d_history_out, uint8_t *const *d_out, void *stream) {
-    if (frames_per_stream % 16 != 0 || ctx->lane_mode == 0 || ctx->lane_unfused || soft_stride < size_t(NB_FRAME_BITS)) return 1;
-    std::vector<dabk::LaneGroupItem> items;
-    items.reserve(size_t(plan.total) + 1);
-    if (d_fib) {
-        dabk::LaneGroupItem it{};
-        it.code = ctx->fic.tables(true);
-        it.tables = ctx->fic.lane_tables();
-        it.args.soft = d_soft;
-        it.args.soft_stride = soft_stride;
-        it.args.n_streams = plan.n_streams;
-        it.args.frames_per_stream = frames_per_stream;
-        it.args.out = d_fib;
-        it.is_fic = true;
-        it.crc_ok = d_crc_ok;
-        if (((reinterpret_cast<uintptr_t>(d_soft) | soft_stride) & 15) || (reinterpret_cast<uintptr_t>(d_fib) & 3)) return 1;
-        items.push_back(it);
-    }
-    for (int s = 0; s < plan.n_streams; s++)
-        for (int i = plan.first[s]; i < plan.first[s + 1]; i++) {
-            const DeviceCode *dc = plan.code[size_t(i)];
-            dabk::LaneGroupItem it{};
-            it.code = dc->tables(true);
-            it.tables = dc->lane_tables();
-            it.args = msc_args(plan.sc[i], d_soft + size_t(s) * frames_per_stream * soft_stride, soft_stride, 1, frames_per_stream,
-                               d_history_in ? d_history_in[i] : nullptr, d_history_out ? d_history_out[i] : nullptr, d_out[i]);
-            if (!dabk::lane_supported(dc->prof.nsteps) || !it.tables.fused_desc || !it.tables.fused_tiles ||
-                !dabk::lane_group_fusable(it.args))
-                return 1;
-            items.push_back(it);
-        }
-    const int n_items = int(items.size());
-    if (n_items == 0) return 0;
-    hipStream_t s = pick_stream(ctx, stream);
-    int rc;
-    if (!lane_scratch(ctx, dabk::lane_group_scratch_bytes(items.data(), n_items), s, &rc)) return rc ? rc : 1;
-    const size_t table_bytes = dabk::lane_ragged_table_bytes(items.data(), n_items);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &d_table)) return 1;
-    ScopedTimer tm(ctx, TIMER_MSC, s);
-    dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes};
-    HIP_TRY(dabk::launch_lane_ragged(items.data(), n_items, lsc, d_table, ctx->stage_bytes[STAGE_ENSEMBLES], s, tm.mids()));
-    return 0;
+    return decode_lane(ctx, items, false, TIMER_MSC, false, stream);
 }
 
 // Sub-channels that do not go through the grouped lane launch.  Small batches (each sub-channel below the lane
@@ -165,8 +136,8 @@ int decode_subchannels(dabgpu_ctx *ctx, const SubchannelPlan &plan, const int8_t
                        int frames_per_stream, const int8_t *const *d_history_in, int8_t *const *d_history_out,
                        uint8_t *const *d_out, void *stream, uint8_t *d_fib = nullptr, uint8_t *d_crc_ok = nullptr) {
     const long cw_each = long(n_streams) * frames_per_stream * NB_CIFS;
-    bool group = plan.n >= 1 && plan.n + (d_fib ? 1 : 0) >= 2 && ctx->lane_mode <= 0 &&
-                 (ctx->lane_mode == 0 || cw_each < LANE_MIN_CODEWORDS) && d_soft && n_streams > 0 && frames_per_stream > 0;
+    bool group = plan.n >= 1 && plan.n + (d_fib ? 1 : 0) >= 2 && lane_policy(ctx, cw_each, false) == 0 && d_soft && n_streams > 0 &&
+                 frames_per_stream > 0;
     std::vector<dabk::WaveGroupItem> items;
     for (int i = 0; group && i < plan.n; i++) {
         const DeviceCode *dc = plan.code[size_t(i)];
@@ -306,7 +277,7 @@ int decode_stream_frames_body(dabgpu_ctx *ctx, const SubchannelPlan &plan, const
 int dabapi::decode_frames_planned(dabgpu_ctx *ctx, const SubchannelPlan &plan, const int8_t *d_soft, size_t soft_stride, int n_streams,
                                   int frames_per_stream, uint8_t *d_fib, uint8_t *d_crc_ok, const int8_t *const *d_history_in,
                                   int8_t *const *d_history_out, uint8_t *const *d_out, void *stream) {
-    const int g = decode_grouped(ctx, d_fib, d_crc_ok, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in,
+    const int g = decode_parts_lane(ctx, d_fib, d_crc_ok, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in,
                                  d_history_out, d_out, stream);
     if (g <= 0) return g;
     // (the FIC goes into the sub-channels' grouped wave launch when there is one, else it gets its own)
@@ -323,16 +294,10 @@ int dabgpu_fic_decode_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t soft_str
     DeviceGuard guard(ctx);
     if (n_frames > 1 && soft_stride < size_t(NB_FIC_BITS)) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
+    const int rc = decode_lane(ctx, {fic_item(ctx, d_soft, soft_stride, 1, n_frames, d_fib, d_crc_ok)}, false, TIMER_FIC, false, stream);
+    if (rc <= 0) return rc;
     hipStream_t s = pick_stream(ctx, stream);
     ScopedTimer tm(ctx, TIMER_FIC, s);
-    dabk::LaneScratch lsc{};
-    int lrc;
-    if (use_lane(ctx, ctx->fic.prof.nsteps, n_frames * NB_FIC_GROUPS, s, &lsc, &lrc)) {
-        HIP_TRY(dabk::launch_fic_decode_lane(ctx->fic.tables(true), ctx->fic.lane_tables(), d_soft, soft_stride, n_frames,
-                                             lsc, d_fib, d_crc_ok, s));
-        return DABGPU_OK;
-    }
-    if (lrc) return lrc;
     HIP_TRY(dabk::launch_fic_decode(ctx->fic.tables(true), d_soft, soft_stride, n_frames, d_fib, d_crc_ok, s));
     return DABGPU_OK;
 }
@@ -439,7 +404,7 @@ int dabgpu_msc_decode_multi_dev(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, in
     // validate everything before enqueueing anything: profiles, bounds, no overlap inside the CIF
     const SubchannelPlan plan(ctx, sc, n_subchannels, d_out);
     if (plan.rc) return plan.rc;
-    const int g = decode_grouped(ctx, nullptr, nullptr, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in,
+    const int g = decode_parts_lane(ctx, nullptr, nullptr, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in,
                                  d_history_out, d_out, stream);
     if (g <= 0) return g;                                      // done (0) or a real error (< 0); 1 = not applicable
     return decode_subchannels(ctx, plan, d_soft, soft_stride, n_streams, frames_per_stream, d_history_in, d_history_out, d_out,
@@ -475,9 +440,21 @@ int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t so
     for (int i = 0; i < plan.total; i++)
         if (d_history_in && d_history_out && d_history_in[i] && d_history_in[i] == d_history_out[i]) return DABGPU_ERR_ARG;
     if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;
-    const int g = decode_ensembles_grouped(ctx, d_fib, d_crc_ok, plan, d_soft, soft_stride, frames_per_stream, d_history_in,
-                                           d_history_out, d_out, stream);
-    if (g <= 0) return g;
+    // Everything in one launch through the device table when every stream is whole 64-codeword groups (the other conditions:
+    // decode_lane)
+    if (frames_per_stream % 16 == 0 && soft_stride >= size_t(NB_FRAME_BITS)) {
+        std::vector<dabk::LaneItem> items;
+        items.reserve(size_t(plan.total) + 1);
+        if (d_fib) items.push_back(fic_item(ctx, d_soft, soft_stride, n_streams, frames_per_stream, d_fib, d_crc_ok));
+        for (int s = 0; s < n_streams; s++)
+            for (int i = sc_first[s]; i < sc_first[s + 1]; i++)
+                items.push_back(msc_item(plan.code[size_t(i)],
+                                         msc_args(sc[i], d_soft + size_t(s) * frames_per_stream * soft_stride, soft_stride, 1, frames_per_stream,
+                                                  d_history_in ? d_history_in[i] : nullptr, d_history_out ? d_history_out[i] : nullptr, d_out[i])));
+        if (items.empty()) return DABGPU_OK;
+        const int g = decode_lane(ctx, items, false, TIMER_MSC, true, stream);
+        if (g <= 0) return g;
+    }
     // any other shape: the same bytes part by part, stream by stream
     for (int s = 0; s < n_streams; s++) {
         const int i0 = sc_first[s], n = plan.count(s);
@@ -492,7 +469,7 @@ int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t so
                                        d_fib + size_t(s) * frames_per_stream * NB_FIBS * 32,
                                        d_crc_ok + size_t(s) * frames_per_stream * NB_FIBS, hi, ho, d_out + i0, stream);
         } else {
-            rc = decode_grouped(ctx, nullptr, nullptr, sub, soft_s, soft_stride, 1, frames_per_stream, hi, ho, d_out + i0, stream);
+            rc = decode_parts_lane(ctx, nullptr, nullptr, sub, soft_s, soft_stride, 1, frames_per_stream, hi, ho, d_out + i0, stream);
             if (rc > 0) rc = decode_subchannels(ctx, sub, soft_s, soft_stride, 1, frames_per_stream, hi, ho, d_out + i0, stream);
         }
         if (rc) return rc;
@@ -850,17 +827,16 @@ int dabgpu_viterbi_dev(dabgpu_ctx *ctx, const int8_t *d_punct, int n_codewords, 
     DeviceCode *dc = nullptr;
     int rc = get_code(ctx, std::move(prof), &dc);
     if (rc) return rc;
-    hipStream_t s = pick_stream(ctx, stream);
-    dabk::LaneScratch lsc{};
-    int lrc;
-    if (use_lane(ctx, dc->prof.nsteps, n_codewords, s, &lsc, &lrc, too_long)) {
-        HIP_TRY(dabk::launch_viterbi_plain_lane(dc->tables(false), dc->lane_tables(), d_punct, n_codewords, lsc,
-                                                d_out_bytes, s));
-        return DABGPU_OK;
-    }
-    if (lrc) return lrc;
+    dabk::LaneItem it{};
+    it.code = dc->tables(false);
+    it.tables = dc->lane_tables();
+    it.args.soft = d_punct;
+    it.args.out = d_out_bytes;
+    it.kind = dabk::LaneItem::PLAIN;
+    it.n_plain = n_codewords;
+    if ((rc = decode_lane(ctx, {it}, too_long, -1, false, stream)) <= 0) return rc;
     if (too_long) return DABGPU_ERR_CAPACITY;
-    HIP_TRY(dabk::launch_viterbi_plain(dc->tables(false), d_punct, n_codewords, d_out_bytes, s));
+    HIP_TRY(dabk::launch_viterbi_plain(dc->tables(false), d_punct, n_codewords, d_out_bytes, pick_stream(ctx, stream)));
     return DABGPU_OK;
 }
 

@@ -399,14 +399,10 @@ bool wave_group_supported(int nsteps);
 bool wave_group_one_round(int max_nsteps, long n_waves);
 hipError_t launch_msc_decode_group(const WaveGroupItem *items, int n, hipStream_t s, const WaveFicItem *fic = nullptr);
 
-// ---- large-batch variant: one codeword per lane (viterbi_lane_kernels.hip) ----
-struct LaneScratch {
-    void *base;
-    size_t bytes;
-    bool unfused = false;      // DABGPU_FLAG_LANE_UNFUSED: depuncture in a pass of its own (lane_prep_kernel)
-};
-size_t lane_scratch_bytes(int nsteps, int n_codewords);
-bool lane_supported(int nsteps);
+// ---- large-batch variant: one codeword per lane (viterbi_lane_kernels.hip, lane_plan.hpp) ----
+// Whole phase cycles and whole 32-bit output words; any length (a codeword whose output tile does not fit into LDS
+// writes its words directly, lane_traceback_body).
+inline bool lane_supported(int nsteps) { return nsteps >= 38 && nsteps % 6 == 0 && ((nsteps - 6) & 31) == 0; }
 // per-profile tables of the lane kernels: punct_idx [4*nsteps] (punctured index of each mother bit, -1 = erased);
 // fused_desc [4*nsteps] and fused_tiles [2*ceil(nsteps/24)] from build_lane_fused_tables (may be null: prep path)
 struct LaneTables {
@@ -415,36 +411,43 @@ struct LaneTables {
     const int32_t *fused_tiles;
 };
 void build_lane_fused_tables(const uint8_t *mask, int nsteps, std::vector<int32_t> &desc, std::vector<int32_t> &tiles);
-hipError_t launch_fic_decode_lane(const CodeTables &c, const LaneTables &lt, const int8_t *soft, size_t soft_stride,
-                                  int n_frames, const LaneScratch &sc, uint8_t *fib, uint8_t *crc_ok, hipStream_t s);
-hipError_t launch_viterbi_plain_lane(const CodeTables &c, const LaneTables &lt, const int8_t *punct,
-                                     int n_codewords, const LaneScratch &sc, uint8_t *out, hipStream_t s);
-hipError_t launch_msc_decode_lane(const CodeTables &c, const LaneTables &lt, const MscArgs &a, const LaneScratch &sc,
-                                  hipStream_t s);
-// Grouped launch: the FIC and/or several sub-channels of the same frames, each with its own profile, in ONE forward
-// and ONE traceback launch.  Sub-channel items must pass lane_group_fusable(); all items lane_supported(nsteps).
-// For the FIC item only args.soft / soft_stride / n_streams / frames_per_stream / out (= FIBs) and crc_ok are used.
-// The history rings are updated by the caller (launch_msc_history per sub-channel).
-struct LaneGroupItem {
+// What one launch decodes: a sub-channel (every field of args), the FIC of the same frames (args.soft / soft_stride /
+// n_streams / frames_per_stream, args.out = the FIBs, crc_ok) or plain codewords (args.soft = the first one, code.n_punct
+// bytes each; args.out; n_plain of them).
+struct LaneItem {
+    enum Kind { SUBCHANNEL, FIC, PLAIN };
     CodeTables code;
     LaneTables tables;
     MscArgs args;
-    bool is_fic;
-    uint8_t *crc_ok;
+    Kind kind;
+    uint8_t *crc_ok;           // FIC: CRC flag per FIB
+    int n_plain;               // PLAIN: codewords
+    size_t codewords() const { return kind == PLAIN ? size_t(n_plain) : size_t(args.n_streams) * args.frames_per_stream * 4; }
 };
-bool lane_group_fusable(const MscArgs &a);
-size_t lane_group_scratch_bytes(const LaneGroupItem *items, int n);
-// mid (optional, timing only): two events, recorded behind the forward pass and behind the traceback of the last pack
-hipError_t launch_lane_group(const LaneGroupItem *items, int n, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid = nullptr);
-// Ragged grouped launch: the same items in any number -- the FIC of every frame and one item per (stream, sub-channel) of a
-// batch of ensembles that each have their own multiplex (args.n_streams = 1, args.soft = that stream's first frame) -- still
-// in ONE forward and ONE traceback launch.  The entry table goes through `d_table` (device memory, 16-byte aligned, at least
-// lane_ragged_table_bytes(); uploaded on `s`) instead of the kernel arguments; entries are dispatched longest codeword
-// first; scratch as lane_group_scratch_bytes().  The history rings (args.hist_out) are written by a third launch over the
-// same table.
-size_t lane_ragged_table_bytes(const LaneGroupItem *items, int n);
-hipError_t launch_lane_ragged(const LaneGroupItem *items, int n, const LaneScratch &sc, void *d_table, size_t table_bytes,
-                              hipStream_t s, hipEvent_t *mid = nullptr);
+// The work buffer of a launch and, for the device-table transport, where the entry table goes (device memory, 16-byte
+// aligned, at least lane_table_bytes(); uploaded on the launch's stream).
+struct LaneScratch {
+    void *base;
+    size_t bytes;
+    bool unfused = false;      // DABGPU_FLAG_LANE_UNFUSED: depuncture in a pass of its own (lane_prep_kernel)
+    void *table = nullptr;
+    size_t table_bytes = 0;
+};
+// lane_plan.hpp states which items take the fused forward pass (lane_item_fusable) and how many bytes of LaneScratch a
+// list needs (lane_scratch_bytes).
+size_t lane_table_bytes(const LaneItem *items, int n);
+// THE launch of the lane kernels.  Every item must pass lane_supported(nsteps) and have a 4-byte aligned output.
+//   A list whose items all pass lane_item_fusable (and !sc.unfused): ONE forward and ONE traceback launch per transport
+//   unit -- by value in the kernel arguments (at most 16 entries per launch, longer lists in several), or, with sc.table,
+//   any number of entries through a table in device memory, dispatched longest codeword first.  (ONE such item that is the
+//   FIC or plain codewords: its forward pass is the same body on a 64-row window, lane_forward_fused_kernel.)
+//   ONE item that does not (or sc.unfused): lane_prep_kernel, lane_forward_kernel, the traceback on a pack of one.
+//   Anything else is hipErrorInvalidValue.
+// The history rings (args.hist_out of the sub-channel items) are written behind the last traceback.
+// mid (optional, timing only): two events, recorded behind the forward pass and behind the traceback -- only when the whole
+// list went out as one forward and one traceback launch; *mid_recorded says whether they were.
+hipError_t launch_lane(const LaneItem *items, int n, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid = nullptr,
+                       bool *mid_recorded = nullptr);
 // Dynamic-LDS request (>= lds) that makes every CU hold the same number of workgroups of a `grid`-workgroup
 // launch when at most `o_cap` fit per CU otherwise (the dispatcher fills CUs greedily).
 size_t balanced_lds_bytes(unsigned grid, size_t lds, unsigned o_cap);

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void mer_kernel(const int8_t *soft, size_t str
 // ---------------------------------------------------------------------------------------------------------
 constexpr int BER_GROUP_MAX = 16;
 struct BerEntry {
-    LSrcMsc src;
+    SoftSrc src;
     const int32_t *punct_idx;
     const uint8_t *prbs;
     const uint8_t *dec;        // decoded bytes, codeword g at dec + g*nbytes
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void channel_ber_kernel(const BerPack pack) {
     int ei = 0;
     while (ei + 1 < pack.n && wave >= pack.e[ei + 1].first_wave) ei++;
     const BerEntry &en = pack.e[ei];
-    const LSrcMsc src = en.src;
+    const SoftSrc src = en.src;
     const int g = wave - en.first_wave;
     const int nbytes = en.nbytes;
     const uint8_t *dec = en.dec + size_t(g) * nbytes;

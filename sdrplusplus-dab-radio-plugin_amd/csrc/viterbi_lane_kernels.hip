@@ -34,7 +34,7 @@
 #include "mem_stream.hpp"
 #include "kernels.hpp"
 #include "dab_tables.hpp"
-#include "soft_source.hpp"
+#include "lane_plan.hpp"
 
 namespace dabk {
 
@@ -88,17 +88,11 @@ __host__ __device__ constexpr int rotl6c(int v, int r) { return r == 0 ? v : (((
 // sign pattern of the branch (state n reached from its older-bit-0 predecessor): bit0 <-> (s0+s3), bit1 <-> s1, bit2 <-> s2
 __host__ __device__ constexpr int sig_of(int n) { return par7(n & 109) | (par7(n & 79) << 1) | (par7(n & 83) << 2); }
 
-// ---- where a codeword's punctured soft bits come from: LSrcFic / LSrcPlain / LSrcMsc (soft_source.hpp) ----
+// ---- where a codeword's punctured soft bits come from: SoftSrc (soft_source.hpp) ----
 // A descriptor is (delay * FPITCH + column) | column << 16: the low half is the window offset of a time-interleaved
-// bit, the high half the column alone for sources without interleaving (delay 0: FIC / plain codewords) or with a
-// forced delay (the FIC riding in a grouped launch: d_force = 15, its own row).  desc_shift / desc_extra pick the
-// half and the constant to add -- wave-uniform, so the per-byte work is one bit-field extract and one add.
-template <class Src>
-__device__ __forceinline__ int desc_shift(const Src &) { return 16; }
-template <class Src>
-__device__ __forceinline__ int desc_extra(const Src &) { return 0; }
-__device__ __forceinline__ int desc_shift(const LSrcMsc &s) { return s.d_force >= 0 ? 16 : 0; }
-__device__ __forceinline__ int desc_extra(const LSrcMsc &s) { return s.d_force >= 0 ? s.d_force * FPITCH : 0; }
+// bit, the high half the column alone for sources with a forced delay (the FIC, plain codewords: d_force = 15, the
+// codeword's own row).  Which half and which constant to add is wave-uniform, so the per-byte work is one bit-field
+// extract and one add.
 
 // ---------------------------------------------------------------------------------------------------------
 // K1: depuncture (+ time de-interleave) + transpose.  Block = (group of 64 codewords, tile of 64 steps).
@@ -111,10 +105,9 @@ constexpr int PREP_STEPS = 64;
 // padded to an odd number of dwords (64 steps: 17 chunks + 4 = 276 B = 69 dwords)
 constexpr int PREP_PITCH = ((4 * PREP_STEPS + 15) / 16 + 1) * 16 + 4;
 
-template <class Src>
-__global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *punct_idx, int nsteps, int n_codewords,
+__global__ __launch_bounds__(256) void lane_prep_kernel(SoftSrc src, const int32_t *punct_idx, int nsteps, int n_codewords,
                                                         int vec16, uint32_t *M) {
-    constexpr int ROWS = 64 + Src::PRE;
+    constexpr int ROWS = 64 + SoftSrc::PRE;
     __shared__ __attribute__((aligned(16))) uint8_t win[ROWS * PREP_PITCH];
     __shared__ int s_idx[4 * PREP_STEPS];
     __shared__ int s_lo, s_hi;
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *
             const int nchunks = (hi - lo_al + 15) >> 4;       // <= 17
             for (int i = tid; i < ROWS * nchunks; i += 256) {
                 const int row = i / nchunks, c = i - row * nchunks;
-                const int g = cw0 - Src::PRE + row;
+                const int g = cw0 - SoftSrc::PRE + row;
                 if (g < 0 || g >= n_codewords) continue;
                 const uint4 v = *reinterpret_cast<const uint4 *>(src.row(g) + lo_al + 16 * c);
                 uint32_t *d = reinterpret_cast<uint32_t *>(win + row * PREP_PITCH + 16 * c);
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *
             const int span = hi - lo_al;
             for (int i = tid; i < ROWS * span; i += 256) {
                 const int row = i / span, c = i - row * span;
-                const int g = cw0 - Src::PRE + row;
+                const int g = cw0 - SoftSrc::PRE + row;
                 if (g < 0 || g >= n_codewords) continue;
                 win[row * PREP_PITCH + c] = uint8_t(src.row(g)[lo_al + c]);
             }
@@ -158,12 +151,9 @@ __global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *
     __syncthreads();
     const int lane = tid & 63;
     const int r_eff = min(lane, n_codewords - 1 - cw0);       // lanes past the end repeat the last codeword
-    int t_in_stream = 0, stream = 0;
-    if constexpr (Src::PRE > 0) {
-        const int cw = cw0 + r_eff;
-        stream = cw / src.cifs_per_stream;
-        t_in_stream = cw - stream * src.cifs_per_stream;
-    }
+    const int cw = cw0 + r_eff;
+    const int stream = cw / src.cifs_per_stream;
+    const int t_in_stream = cw - stream * src.cifs_per_stream;
     for (int sstep = tid >> 6; sstep < PREP_STEPS; sstep += 4) {
         const int t = t0 + sstep;
         if (t >= nsteps) break;
@@ -173,15 +163,11 @@ __global__ __launch_bounds__(256) void lane_prep_kernel(Src src, const int32_t *
             const int idx = s_idx[4 * sstep + m];
             if (idx < 0) continue;
             unsigned v;
-            if constexpr (Src::PRE > 0) {
-                const int d = tdi_delay(idx);
-                if (t_in_stream + d >= 15) {
-                    v = win[(r_eff + d) * PREP_PITCH + (idx - lo_al)];
-                } else {                                      // before the stream's first CIF: carried history
-                    v = src.hist ? uint8_t(src.hist[(size_t(stream) * 15 + t_in_stream + d) * src.nbits + idx]) : 0u;
-                }
-            } else {
-                v = win[r_eff * PREP_PITCH + (idx - lo_al)];
+            const int d = src.d_force >= 0 ? src.d_force : tdi_delay(idx);
+            if (t_in_stream + d >= 15) {
+                v = win[(r_eff + d) * PREP_PITCH + (idx - lo_al)];
+            } else {                                          // before the stream's first CIF: carried history
+                v = src.hist ? uint8_t(src.hist[(size_t(stream) * 15 + t_in_stream + d) * src.nbits + idx]) : 0u;
             }
             w |= v << (8 * m);
         }
@@ -351,15 +337,12 @@ __global__ __launch_bounds__(256) void lane_forward_kernel(const uint32_t *Msoft
 
 // row r (0 .. 63+PRE) of the window of the group whose first codeword is cw0 -> first punctured byte, or nullptr
 // for a row that does not exist (reads as erasures)
-__device__ __forceinline__ const int8_t *fused_row(const LSrcFic &s, int cw0, int r, int n_codewords) {
+template <class Src>                                          // (PRE = 0: the codewords themselves)
+__device__ __forceinline__ const int8_t *fused_row(const Src &s, int cw0, int r, int n_codewords) {
     const int g = cw0 + r;
     return g < n_codewords ? s.row(g) : nullptr;
 }
-__device__ __forceinline__ const int8_t *fused_row(const LSrcPlain &s, int cw0, int r, int n_codewords) {
-    const int g = cw0 + r;
-    return g < n_codewords ? s.row(g) : nullptr;
-}
-__device__ __forceinline__ const int8_t *fused_row(const LSrcMsc &s, int cw0, int r, int n_codewords) {
+__device__ __forceinline__ const int8_t *fused_row(const SoftSrc &s, int cw0, int r, int n_codewords) {
     const int stream = cw0 / s.cifs_per_stream;
     const int v = cw0 - stream * s.cifs_per_stream - 15 + r;          // CIF of this stream, < 0 = carried history
     if (v < 0) return s.hist ? s.hist + (size_t(stream) * 15 + (15 + v)) * s.nbits : nullptr;
@@ -423,7 +406,7 @@ __device__ __forceinline__ void lane_forward_fused_body(const Src &src, const in
     // Descriptors of the next six steps are fetched while the current six are worked on: with one wave per SIMD
     // nothing else would hide their latency.  They are deliberately NOT restrict-qualified: as scalar loads they
     // share the LDS counter (lgkmcnt) and every wait for them also drains the window reads (measured slower).
-    const int dsh = desc_shift(src), dex = desc_extra(src);
+    const int dsh = src.d_force >= 0 ? 16 : 0, dex = src.d_force >= 0 ? src.d_force * FPITCH : 0;
     // where this lane's 24 soft bytes of the coming six steps sit in the window: descriptor -> offset -> address once, in
     // vector registers (two VALU per byte; as scalars they cost a v_readfirstlane, two SALU and a v_add per byte, and a
     // lone wave pays an issue turn for every one of them)
@@ -477,6 +460,7 @@ __device__ __forceinline__ void lane_forward_fused_body(const Src &src, const in
     }
 }
 
+// A single item without interleaving (LSrcFic, LSrcPlain): the body on a 64-row window.
 template <class Src>
 __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_fused_kernel(Src src, const int32_t *desc, const int32_t *tiles,
                                                                  int nsteps, int groups, int n_codewords, uint2 *dec) {
@@ -485,8 +469,7 @@ __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_fused_kernel(S
     const int wv = threadIdx.x >> 6;
     const int group = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);     // wave-uniform: pointers stay in SGPRs
     if (group >= groups) return;
-    lane_forward_fused_body(src, desc, tiles, nsteps, group, n_codewords, dec, fused_lds + wv * ((64 + Src::PRE) * FPITCH),
-                            lane);
+    lane_forward_fused_body(src, desc, tiles, nsteps, group, n_codewords, dec, fused_lds + wv * ((64 + Src::PRE) * FPITCH), lane);
 }
 
 // Grouped launch (every sub-channel of a multiplex in one launch): a wave looks up which
@@ -496,15 +479,6 @@ __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_fused_kernel(S
 // in device memory they were generic pointers in VGPRs: flat loads/stores that also tick the LDS counter, and a
 // quarter-rate v_mul_lo_u32 per soft byte for the window address).
 constexpr int LANE_GROUP_MAX = 16;        // entries per launch (16 x 112 B of kernel arguments); longer lists are chunked
-struct LaneEntry {
-    LSrcMsc src;
-    const int32_t *desc, *tiles;
-    const uint8_t *prbs;
-    uint8_t *out;
-    uint8_t *crc_ok;          // FIC entry: CRC flag per FIB; nullptr for sub-channels
-    uint2 *dec;
-    int nsteps, n_codewords, first_group, groups;
-};
 struct LaneEntryPack {
     int n;
     int total_groups;
@@ -525,7 +499,7 @@ __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_grouped_kernel
     const int group = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);
     if (group >= pack.total_groups) return;
     const LaneEntry &en = pack.e[find_entry(pack, group)];
-    const LSrcMsc src = en.src;
+    const SoftSrc src = en.src;
     // Codeword lengths differ between entries (FIC 774 steps, a 64 kbit/s sub-channel 1542).  When the whole launch is
     // resident at once -- two waves per SIMD, one of each -- the longer wave would run alone, at a single wave's issue rate,
     // for the last third of the launch.  The longest entry's waves therefore get the issue slots first; the shorter ones
@@ -534,7 +508,7 @@ __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_grouped_kernel
     // there a priority only hurt (whole multiplex +2.7 %): the launcher sets prio_nsteps to 0 for them.
     if (pack.prio_nsteps > 0 && en.nsteps >= pack.prio_nsteps) __builtin_amdgcn_s_setprio(1);
     lane_forward_fused_body(src, en.desc, en.tiles, en.nsteps, group - en.first_group, en.n_codewords, en.dec,
-                            fused_lds + wv * ((64 + LSrcMsc::PRE) * FPITCH), lane);
+                            fused_lds + wv * ((64 + SoftSrc::PRE) * FPITCH), lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -586,11 +560,6 @@ __device__ __forceinline__ void lane_tb_block_steps(const uint2 (&d)[32], unsign
         lane_tb_step_static<(Q0 + I) % 6, I>(d[I], p, word);
         lane_tb_block_steps<Q0, I + 1>(d, p, word);
     }
-}
-
-// does the traceback's output tile ([64][words | 1] dwords) fit into LDS?
-__host__ __device__ __forceinline__ bool lane_tile_fits(int nsteps) {
-    return size_t(64) * size_t(((nsteps - 6) >> 5) | 1) * 4 <= size_t(150) * 1024;
 }
 
 __device__ __forceinline__ unsigned crc16_byte_l(unsigned crc, unsigned byte) {
@@ -677,13 +646,6 @@ __device__ __forceinline__ void lane_traceback_body(const uint2 *dec, int nsteps
     }
 }
 
-__global__ __launch_bounds__(64) void lane_traceback_kernel(const uint2 *dec, int nsteps, int n_codewords,
-                                                            const uint8_t *prbs_bytes, uint8_t *out, uint8_t *crc_ok) {
-    extern __shared__ uint32_t tile[];                        // [64][nwords + 1], or nothing for over-long codewords
-    lane_traceback_body(dec, nsteps, n_codewords, blockIdx.x, prbs_bytes, out, crc_ok, lane_tile_fits(nsteps) ? tile : nullptr,
-                        threadIdx.x);
-}
-
 __global__ __launch_bounds__(64) void lane_traceback_grouped_kernel(const LaneEntryPack pack) {
     extern __shared__ uint32_t tile[];                        // sized for the longest entry
     const int group = blockIdx.x;
@@ -703,7 +665,7 @@ struct RaggedEntry {            // 128 bytes
     uint64_t soft, hist, desc, tiles, prbs, out, crc_ok, dec;     // device addresses (0 = none), see LaneEntry
     uint64_t stride;
     uint64_t hist_out;          // ring to write behind the decode (0: none; never the FIC entry)
-    int32_t cifs_per_stream, base_off, per_cif, nbits, d_force;   // LSrcMsc
+    int32_t cifs_per_stream, base_off, per_cif, nbits, d_force;   // SoftSrc
     int32_t nsteps, n_codewords, first_group;
     int32_t hist_vec16;         // hist_out is 16-byte aligned: the ring is copied in 16-byte pieces
     int32_t reserved[3];
@@ -715,8 +677,8 @@ __device__ __forceinline__ T *global_ptr(uint64_t address) {
     typedef T __attribute__((address_space(1))) * G;
     return (T *)reinterpret_cast<G>(address);                     // (global -> generic: the compiler keeps track of the origin)
 }
-__device__ __forceinline__ LSrcMsc ragged_src(const RaggedEntry &en) {
-    return LSrcMsc{global_ptr<const int8_t>(en.soft), size_t(en.stride), global_ptr<const int8_t>(en.hist), en.cifs_per_stream,
+__device__ __forceinline__ SoftSrc ragged_src(const RaggedEntry &en) {
+    return SoftSrc{global_ptr<const int8_t>(en.soft), size_t(en.stride), global_ptr<const int8_t>(en.hist), en.cifs_per_stream,
                    en.base_off, en.per_cif, en.nbits, en.d_force};
 }
 
@@ -729,12 +691,12 @@ __global__ LANE_FWD_ATTR __launch_bounds__(256) void lane_forward_ragged_kernel(
     const int group = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);
     if (group >= total_groups) return;
     const RaggedEntry en = table[__builtin_amdgcn_readfirstlane(entry_of_group[group])];
-    const LSrcMsc src = ragged_src(en);
+    const SoftSrc src = ragged_src(en);
     // (the priority rule of lane_forward_grouped_kernel; the launcher sets prio_nsteps only where the whole launch is resident)
     if (prio_nsteps > 0 && en.nsteps >= prio_nsteps) __builtin_amdgcn_s_setprio(1);
     lane_forward_fused_body(src, global_ptr<const int32_t>(en.desc), global_ptr<const int32_t>(en.tiles), en.nsteps,
                             group - en.first_group, en.n_codewords, global_ptr<uint2>(en.dec),
-                            fused_lds + wv * ((64 + LSrcMsc::PRE) * FPITCH), lane);
+                            fused_lds + wv * ((64 + SoftSrc::PRE) * FPITCH), lane);
 }
 
 __global__ __launch_bounds__(64) void lane_traceback_ragged_kernel(const RaggedEntry *__restrict__ table,
@@ -753,7 +715,7 @@ constexpr int RAGGED_HIST_BLOCKS = 8;
 __global__ __launch_bounds__(256) void lane_history_ragged_kernel(const RaggedEntry *__restrict__ table) {
     const RaggedEntry en = table[blockIdx.y];
     if (!en.hist_out) return;
-    const LSrcMsc src = ragged_src(en);
+    const SoftSrc src = ragged_src(en);
     int8_t *out = global_ptr<int8_t>(en.hist_out);
     const int first = src.cifs_per_stream - 15;
     const int tid = blockIdx.x * 256 + threadIdx.x;
@@ -772,43 +734,13 @@ __global__ __launch_bounds__(256) void lane_history_ragged_kernel(const RaggedEn
     }
 }
 
-template <class Src>
-hipError_t run_lane(Src f, bool vec16, bool fusable, const CodeTables &c, const LaneTables &lt, int n_codewords,
-                    const LaneScratch &sc, uint8_t *out, uint8_t *crc_ok, hipStream_t s) {
-    const int groups = (n_codewords + 63) / 64;
-    const int nwords = (c.nsteps - 6) >> 5;
-    const size_t need = lane_scratch_bytes(c.nsteps, n_codewords);
-    if (!sc.base || sc.bytes < need || (reinterpret_cast<uintptr_t>(out) & 3)) return hipErrorInvalidValue;
-    uint32_t *M = reinterpret_cast<uint32_t *>(sc.base);
-    uint2 *dec = reinterpret_cast<uint2 *>(M + size_t(groups) * c.nsteps * 64);
-    const unsigned fgrid = unsigned((groups + 3) / 4);
-    if (fusable && vec16 && lt.fused_desc && lt.fused_tiles && !sc.unfused) {
-        const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + Src::PRE) * FPITCH, 3);
-        hipLaunchKernelGGL((lane_forward_fused_kernel<Src>), dim3(fgrid), dim3(256), lds, s, f, lt.fused_desc, lt.fused_tiles,
-                           c.nsteps, groups, n_codewords, dec);
-    } else {
-        hipLaunchKernelGGL((lane_prep_kernel<Src>), dim3(unsigned((c.nsteps + PREP_STEPS - 1) / PREP_STEPS), unsigned(groups)),
-                           dim3(256), 0, s, f, lt.punct_idx, c.nsteps, n_codewords, int(vec16), M);
-        const size_t fwd_lds = balanced_lds_bytes(fgrid, 0, 8);
-        hipLaunchKernelGGL(lane_forward_kernel, dim3(fgrid), dim3(256), fwd_lds, s, M, c.nsteps, groups, dec);
-    }
-    const size_t tb_lds = lane_tile_fits(c.nsteps) ? size_t(64) * (nwords | 1) * 4 : 0;
-    hipLaunchKernelGGL(lane_traceback_kernel, dim3(unsigned(groups)), dim3(64), tb_lds, s, dec, c.nsteps, n_codewords,
-                       c.prbs_bytes, out, crc_ok);
-    return hipGetLastError();
-}
-
-inline bool aligned16(const void *p, size_t stride) { return ((reinterpret_cast<uintptr_t>(p) | stride) & 15) == 0; }
-
 }  // namespace
 
 hipError_t init_lane_kernel_attributes() {
     for (const void *k : {reinterpret_cast<const void *>(lane_forward_kernel),
                           reinterpret_cast<const void *>(lane_forward_fused_kernel<LSrcFic>),
                           reinterpret_cast<const void *>(lane_forward_fused_kernel<LSrcPlain>),
-                          reinterpret_cast<const void *>(lane_forward_fused_kernel<LSrcMsc>),
                           reinterpret_cast<const void *>(lane_forward_grouped_kernel),
-                          reinterpret_cast<const void *>(lane_traceback_kernel),
                           reinterpret_cast<const void *>(lane_traceback_grouped_kernel),
                           reinterpret_cast<const void *>(lane_forward_ragged_kernel),
                           reinterpret_cast<const void *>(lane_traceback_ragged_kernel)}) {
@@ -816,57 +748,6 @@ hipError_t init_lane_kernel_attributes() {
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-size_t lane_scratch_bytes(int nsteps, int n_codewords) {
-    const size_t groups = size_t((n_codewords + 63) / 64);
-    const size_t nwords = size_t((nsteps - 6) >> 5);
-    (void)nwords;
-    return groups * 64 * size_t(nsteps) * 12 + 256;           // soft dwords + survivor words
-}
-
-bool lane_supported(int nsteps) {
-    // whole phase cycles and whole 32-bit output words (any length: a codeword whose output tile does not fit into LDS
-    // writes its words directly, lane_traceback_body)
-    return nsteps >= 38 && nsteps % 6 == 0 && ((nsteps - 6) & 31) == 0;
-}
-
-hipError_t launch_fic_decode_lane(const CodeTables &c, const LaneTables &lt, const int8_t *soft, size_t soft_stride,
-                                  int n_frames, const LaneScratch &sc, uint8_t *fib, uint8_t *crc_ok, hipStream_t s) {
-    return run_lane(LSrcFic{soft, soft_stride}, aligned16(soft, soft_stride), true, c, lt, n_frames * NB_FIC_GROUPS, sc,
-                    fib, crc_ok, s);
-}
-
-hipError_t launch_viterbi_plain_lane(const CodeTables &c, const LaneTables &lt, const int8_t *punct,
-                                     int n_codewords, const LaneScratch &sc, uint8_t *out, hipStream_t s) {
-    return run_lane(LSrcPlain{punct, c.n_punct}, aligned16(punct, size_t(c.n_punct)), true, c, lt, n_codewords, sc, out,
-                    nullptr, s);
-}
-
-hipError_t launch_msc_decode_lane(const CodeTables &c, const LaneTables &lt, const MscArgs &a, const LaneScratch &sc,
-                                  hipStream_t s) {
-    const LSrcMsc f = make_msc_src(a);
-    // the fused forward pass wants whole groups inside one stream and 16-byte aligned history rows
-    const bool fusable = (a.frames_per_stream * NB_CIFS) % 64 == 0 &&
-                         (!a.hist_in || ((reinterpret_cast<uintptr_t>(a.hist_in) | size_t(a.nbits)) & 15) == 0);
-    return run_lane(f, aligned16(a.soft, a.soft_stride) && (a.start_bit & 15) == 0, fusable, c, lt,
-                    a.n_streams * a.frames_per_stream * NB_CIFS, sc, a.out, nullptr, s);
-}
-
-bool lane_group_fusable(const MscArgs &a) {
-    return (a.frames_per_stream * NB_CIFS) % 64 == 0 && aligned16(a.soft, a.soft_stride) && (a.start_bit & 15) == 0 &&
-           (!a.hist_in || ((reinterpret_cast<uintptr_t>(a.hist_in) | size_t(a.nbits)) & 15) == 0) &&
-           (reinterpret_cast<uintptr_t>(a.out) & 3) == 0;
-}
-
-static size_t item_codewords(const LaneGroupItem &it) {
-    return size_t(it.args.n_streams) * it.args.frames_per_stream * NB_CIFS;      // FIC: 4 groups per frame as well
-}
-
-size_t lane_group_scratch_bytes(const LaneGroupItem *items, int n) {
-    size_t total = 0;
-    for (int i = 0; i < n; i++) total += ((item_codewords(items[i]) + 63) / 64) * 64 * size_t(items[i].code.nsteps) * sizeof(uint2);
-    return total + 512;
 }
 
 static int resident_cus() {
@@ -879,145 +760,130 @@ static int resident_cus() {
     return n;
 }
 
-hipError_t launch_lane_group(const LaneGroupItem *items, int n, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid) {
-    if (n <= 0) return hipSuccess;
-    if (!sc.base || sc.bytes < lane_group_scratch_bytes(items, n)) return hipErrorInvalidValue;
-    char *p = static_cast<char *>(sc.base);
-    for (int i0 = 0; i0 < n; i0 += LANE_GROUP_MAX) {
-        LaneEntryPack pack{};
-        pack.n = std::min(LANE_GROUP_MAX, n - i0);
-        int max_nwords = 0;
-        for (int i = 0; i < pack.n; i++) {
-            const LaneGroupItem &it = items[i0 + i];
-            const MscArgs &a = it.args;
-            if (!it.tables.fused_desc || !it.tables.fused_tiles || !lane_supported(it.code.nsteps)) return hipErrorInvalidValue;
-            LaneEntry &e = pack.e[i];
-            e.n_codewords = int(item_codewords(it));
-            if (it.is_fic) {
-                // the FIC as one more entry (make_fic_src: no interleaving, never a history row)
-                if (!aligned16(a.soft, a.soft_stride) || (reinterpret_cast<uintptr_t>(a.out) & 3)) return hipErrorInvalidValue;
-                e.src = make_fic_src(a.soft, a.soft_stride, e.n_codewords);
-            } else {
-                if (!lane_group_fusable(a)) return hipErrorInvalidValue;
-                e.src = make_msc_src(a);
-            }
-            e.desc = it.tables.fused_desc;
-            e.tiles = it.tables.fused_tiles;
-            e.prbs = it.code.prbs_bytes;
-            e.out = a.out;
-            e.crc_ok = it.is_fic ? it.crc_ok : nullptr;
-            e.dec = reinterpret_cast<uint2 *>(p);
-            e.nsteps = it.code.nsteps;
-            e.first_group = pack.total_groups;
-            e.groups = (e.n_codewords + 63) / 64;
-            pack.total_groups += e.groups;
-            p += size_t(e.groups) * 64 * size_t(e.nsteps) * sizeof(uint2);
-            if (lane_tile_fits(e.nsteps)) max_nwords = std::max(max_nwords, (e.nsteps - 6) >> 5);
-        }
-        const unsigned fgrid = unsigned((pack.total_groups + 3) / 4);
-        const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + LSrcMsc::PRE) * FPITCH, 3);
-        {   // every wave resident at once (<= 2 per SIMD) and entries of different lengths: the longest go first
-            int longest = 0, shortest = 0x7fffffff;
-            for (int i = 0; i < pack.n; i++) { longest = std::max(longest, pack.e[i].nsteps); shortest = std::min(shortest, pack.e[i].nsteps); }
-            pack.prio_nsteps = (pack.total_groups <= 2 * 4 * resident_cus() && longest > shortest) ? longest : 0;
-        }
-        const bool timed = mid && i0 + LANE_GROUP_MAX >= n;
-        hipLaunchKernelGGL(lane_forward_grouped_kernel, dim3(fgrid), dim3(256), lds, s, pack);
-        if (timed) (void)hipEventRecord(mid[0], s);
-        const size_t tb_lds = size_t(64) * (max_nwords | 1) * 4;
-        hipLaunchKernelGGL(lane_traceback_grouped_kernel, dim3(unsigned(pack.total_groups)), dim3(64), tb_lds, s, pack);
-        if (timed) (void)hipEventRecord(mid[1], s);
-    }
-    return hipGetLastError();
-}
-
-static size_t item_groups(const LaneGroupItem &it) { return (item_codewords(it) + 63) / 64; }
-
 // the table as it is uploaded: [n] entries, then the groups' entry numbers, rounded up to whole entries
-static size_t ragged_table_slots(const LaneGroupItem *items, int n) {
+static size_t ragged_table_slots(const LaneItem *items, int n) {
     size_t groups = 0;
-    for (int i = 0; i < n; i++) groups += item_groups(items[i]);
+    for (int i = 0; i < n; i++) groups += lane_item_groups(items[i]);
     return size_t(n) + (groups * sizeof(int32_t) + sizeof(RaggedEntry) - 1) / sizeof(RaggedEntry);
 }
-size_t lane_ragged_table_bytes(const LaneGroupItem *items, int n) { return ragged_table_slots(items, n) * sizeof(RaggedEntry); }
+size_t lane_table_bytes(const LaneItem *items, int n) { return ragged_table_slots(items, n) * sizeof(RaggedEntry); }
 
-hipError_t launch_lane_ragged(const LaneGroupItem *items, int n, const LaneScratch &sc, void *d_table, size_t table_bytes,
-                              hipStream_t s, hipEvent_t *mid) {
-    if (n <= 0) return hipSuccess;
+// the plan's entries into the device table (uploaded on `s`), forward pass and traceback over it
+static hipError_t launch_by_table(const LaneItem *items, const LanePlan &plan, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid) {
+    const int n = int(plan.e.size());
     const size_t slots = ragged_table_slots(items, n);
-    if (n > 65535 || !sc.base || sc.bytes < lane_group_scratch_bytes(items, n) || !d_table || table_bytes < slots * sizeof(RaggedEntry) ||
-        (reinterpret_cast<uintptr_t>(d_table) & 15))
-        return hipErrorInvalidValue;
-    // Dispatch order: workgroups start in grid order, so the longest codewords go first and the short ones fill the end of the
-    // launch (a long wave started last would run on alone).  Every entry works on buffers of its own: the order changes no result.
-    std::vector<int> order(size_t(n), 0);
-    for (int i = 0; i < n; i++) order[size_t(i)] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].code.nsteps > items[b].code.nsteps; });
+    if (n > 65535 || sc.table_bytes < slots * sizeof(RaggedEntry) || (reinterpret_cast<uintptr_t>(sc.table) & 15)) return hipErrorInvalidValue;
     std::vector<RaggedEntry> host(slots);
     int32_t *entry_of_group = reinterpret_cast<int32_t *>(host.data() + n);
     auto address = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
-    char *p = static_cast<char *>(sc.base);
-    int total_groups = 0, max_nwords = 0, longest = 0, shortest = 0x7fffffff;
-    bool any_history = false;
     for (int k = 0; k < n; k++) {
-        const LaneGroupItem &it = items[order[size_t(k)]];
-        const MscArgs &a = it.args;
-        if (!it.tables.fused_desc || !it.tables.fused_tiles || !lane_supported(it.code.nsteps)) return hipErrorInvalidValue;
-        const int n_codewords = int(item_codewords(it));
-        LSrcMsc src;
-        if (it.is_fic) {
-            if (!aligned16(a.soft, a.soft_stride) || (reinterpret_cast<uintptr_t>(a.out) & 3)) return hipErrorInvalidValue;
-            src = make_fic_src(a.soft, a.soft_stride, n_codewords);
-        } else {
-            if (!lane_group_fusable(a)) return hipErrorInvalidValue;
-            src = make_msc_src(a);
-        }
+        const LaneEntry &le = plan.e[size_t(k)];
+        const LaneItem &it = items[plan.item[size_t(k)]];
         RaggedEntry e{};
-        e.soft = address(src.soft);
-        e.hist = address(src.hist);
-        e.desc = address(it.tables.fused_desc);
-        e.tiles = address(it.tables.fused_tiles);
-        e.prbs = address(it.code.prbs_bytes);
-        e.out = address(a.out);
-        e.crc_ok = it.is_fic ? address(it.crc_ok) : 0;
-        e.dec = address(p);
-        e.stride = src.stride;
-        e.hist_out = it.is_fic ? 0 : address(a.hist_out);
-        e.cifs_per_stream = src.cifs_per_stream;
-        e.base_off = src.base_off;
-        e.per_cif = src.per_cif;
-        e.nbits = src.nbits;
-        e.d_force = src.d_force;
-        e.nsteps = it.code.nsteps;
-        e.n_codewords = n_codewords;
-        e.first_group = total_groups;
+        e.soft = address(le.src.soft);
+        e.hist = address(le.src.hist);
+        e.desc = address(le.desc);
+        e.tiles = address(le.tiles);
+        e.prbs = address(le.prbs);
+        e.out = address(le.out);
+        e.crc_ok = address(le.crc_ok);
+        e.dec = address(le.dec);
+        e.stride = le.src.stride;
+        e.hist_out = it.kind == LaneItem::SUBCHANNEL ? address(it.args.hist_out) : 0;
+        e.cifs_per_stream = le.src.cifs_per_stream;
+        e.base_off = le.src.base_off;
+        e.per_cif = le.src.per_cif;
+        e.nbits = le.src.nbits;
+        e.d_force = le.src.d_force;
+        e.nsteps = le.nsteps;
+        e.n_codewords = le.n_codewords;
+        e.first_group = le.first_group;
         e.hist_vec16 = (e.hist_out & 15) == 0;
-        any_history = any_history || e.hist_out != 0;
-        const int groups = int(item_groups(it));
-        for (int g = 0; g < groups; g++) entry_of_group[total_groups + g] = k;
-        total_groups += groups;
-        p += size_t(groups) * 64 * size_t(e.nsteps) * sizeof(uint2);
-        if (lane_tile_fits(e.nsteps)) max_nwords = std::max(max_nwords, (e.nsteps - 6) >> 5);
-        longest = std::max(longest, e.nsteps);
-        shortest = std::min(shortest, e.nsteps);
+        for (int g = 0; g < le.groups; g++) entry_of_group[le.first_group + g] = k;
         host[size_t(k)] = e;
     }
-    if (total_groups == 0) return hipSuccess;
     // (pageable memory: the copy has left `host` when the call returns)
-    hipError_t err = hipMemcpyAsync(d_table, host.data(), slots * sizeof(RaggedEntry), hipMemcpyHostToDevice, s);
+    const hipError_t err = hipMemcpyAsync(sc.table, host.data(), slots * sizeof(RaggedEntry), hipMemcpyHostToDevice, s);
     if (err != hipSuccess) return err;
-    const RaggedEntry *table = static_cast<const RaggedEntry *>(d_table);
+    const RaggedEntry *table = static_cast<const RaggedEntry *>(sc.table);
     const int32_t *d_entry_of_group = reinterpret_cast<const int32_t *>(table + n);
-    const unsigned fgrid = unsigned((total_groups + 3) / 4);
-    const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + LSrcMsc::PRE) * FPITCH, 3);
-    // the priority rule of launch_lane_group: only where every wave is resident at once
-    const int prio_nsteps = (total_groups <= 2 * 4 * resident_cus() && longest > shortest) ? longest : 0;
-    hipLaunchKernelGGL(lane_forward_ragged_kernel, dim3(fgrid), dim3(256), lds, s, table, d_entry_of_group, total_groups, prio_nsteps);
+    const unsigned fgrid = unsigned((plan.total_groups + 3) / 4);
+    const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + SoftSrc::PRE) * FPITCH, 3);
+    hipLaunchKernelGGL(lane_forward_ragged_kernel, dim3(fgrid), dim3(256), lds, s, table, d_entry_of_group, plan.total_groups,
+                       plan.prio_nsteps);
     if (mid) (void)hipEventRecord(mid[0], s);
-    const size_t tb_lds = size_t(64) * (max_nwords | 1) * 4;
-    hipLaunchKernelGGL(lane_traceback_ragged_kernel, dim3(unsigned(total_groups)), dim3(64), tb_lds, s, table, d_entry_of_group);
+    hipLaunchKernelGGL(lane_traceback_ragged_kernel, dim3(unsigned(plan.total_groups)), dim3(64), size_t(64) * (plan.tile_nwords | 1) * 4,
+                       s, table, d_entry_of_group);
     if (mid) (void)hipEventRecord(mid[1], s);
-    if (any_history) hipLaunchKernelGGL(lane_history_ragged_kernel, dim3(RAGGED_HIST_BLOCKS, unsigned(n)), dim3(256), 0, s, table);
+    return hipSuccess;
+}
+
+hipError_t launch_lane(const LaneItem *items, int n, const LaneScratch &sc, hipStream_t s, hipEvent_t *mid, bool *mid_recorded) {
+    if (mid_recorded) *mid_recorded = false;
+    if (n <= 0) return hipSuccess;
+    if (!sc.base || sc.bytes < lane_scratch_bytes(items, n, sc.unfused)) return hipErrorInvalidValue;
+    bool any_history = false;
+    for (int i = 0; i < n; i++) {
+        if (!lane_supported(items[i].code.nsteps) || (reinterpret_cast<uintptr_t>(items[i].args.out) & 3)) return hipErrorInvalidValue;
+        any_history = any_history || (items[i].kind == LaneItem::SUBCHANNEL && items[i].args.hist_out);
+    }
+    const int per_launch = sc.table ? n : LANE_GROUP_MAX;
+    char *scratch = static_cast<char *>(sc.base);
+    LanePlan plan;
+    for (int i0 = 0; i0 < n; i0 += per_launch) {
+        const int m = std::min(per_launch, n - i0);
+        plan_lane_launch(items + i0, m, sc.unfused, sc.table != nullptr, scratch, 2 * 4 * resident_cus(), plan);
+        scratch = plan.scratch_end;
+        if (!plan.fused && (n != 1 || sc.table)) return hipErrorInvalidValue;
+        if (plan.total_groups == 0) continue;
+        hipEvent_t *ev = m == n ? mid : nullptr;                  // parts only of a list that is one forward and one traceback launch
+        if (sc.table) {
+            const hipError_t err = launch_by_table(items, plan, sc, s, ev);
+            if (err != hipSuccess) return err;
+            if (any_history) hipLaunchKernelGGL(lane_history_ragged_kernel, dim3(RAGGED_HIST_BLOCKS, unsigned(n)), dim3(256), 0, s,
+                                                static_cast<const RaggedEntry *>(sc.table));
+        } else {
+            LaneEntryPack pack{};
+            pack.n = m;
+            pack.total_groups = plan.total_groups;
+            pack.prio_nsteps = plan.prio_nsteps;
+            std::copy(plan.e.begin(), plan.e.end(), pack.e);
+            const unsigned fgrid = unsigned((pack.total_groups + 3) / 4);
+            const LaneItem &one = items[i0];
+            if (plan.fused && n == 1 && one.kind != LaneItem::SUBCHANNEL) {   // no look-back rows to stage: soft_source.hpp
+                const LaneEntry &e = pack.e[0];
+                const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * 64 * FPITCH, 3);
+                if (one.kind == LaneItem::FIC)
+                    hipLaunchKernelGGL(lane_forward_fused_kernel<LSrcFic>, dim3(fgrid), dim3(256), lds, s, LSrcFic{e.src.soft, e.src.stride},
+                                       e.desc, e.tiles, e.nsteps, e.groups, e.n_codewords, e.dec);
+                else
+                    hipLaunchKernelGGL(lane_forward_fused_kernel<LSrcPlain>, dim3(fgrid), dim3(256), lds, s, LSrcPlain{e.src.soft, e.src.nbits},
+                                       e.desc, e.tiles, e.nsteps, e.groups, e.n_codewords, e.dec);
+            } else if (plan.fused) {
+                const size_t lds = balanced_lds_bytes(fgrid, size_t(4) * (64 + SoftSrc::PRE) * FPITCH, 3);
+                hipLaunchKernelGGL(lane_forward_grouped_kernel, dim3(fgrid), dim3(256), lds, s, pack);
+            } else {                                              // one item: depuncture, then the forward pass on soft words
+                const LaneItem &it = items[0];
+                const LaneEntry &e = pack.e[0];
+                uint32_t *M = static_cast<uint32_t *>(sc.base);
+                hipLaunchKernelGGL(lane_prep_kernel, dim3(unsigned((e.nsteps + PREP_STEPS - 1) / PREP_STEPS), unsigned(e.groups)),
+                                   dim3(256), 0, s, e.src, it.tables.punct_idx, e.nsteps, e.n_codewords, int(lane_src_vec16(e.src)), M);
+                hipLaunchKernelGGL(lane_forward_kernel, dim3(fgrid), dim3(256), balanced_lds_bytes(fgrid, 0, 8), s, M, e.nsteps,
+                                   e.groups, e.dec);
+            }
+            if (ev) (void)hipEventRecord(ev[0], s);
+            hipLaunchKernelGGL(lane_traceback_grouped_kernel, dim3(unsigned(pack.total_groups)), dim3(64),
+                               size_t(64) * (plan.tile_nwords | 1) * 4, s, pack);
+            if (ev) (void)hipEventRecord(ev[1], s);
+        }
+        if (ev && mid_recorded) *mid_recorded = true;
+    }
+    if (!sc.table)
+        for (int i = 0; i < n; i++)
+            if (items[i].kind == LaneItem::SUBCHANNEL) {
+                const hipError_t err = launch_msc_history(items[i].args, s);
+                if (err != hipSuccess) return err;
+            }
     return hipGetLastError();
 }
 

@@ -37,6 +37,19 @@ def kernel_metadata(asm):
     return out
 
 
+def base_name(mangled):
+    """`_ZN4dabk12_GLOBAL__N_116lane_prep_kernelENS_7SoftSrcE...` -> `lane_prep_kernel`: the last length-prefixed component of
+    the nested name (template arguments and the parameter list come behind it)."""
+    m = re.match(r"_ZN", mangled)
+    pos, name = (m.end(), None) if m else (2, None)
+    while True:
+        m = re.compile(r"(\d+)").match(mangled, pos)
+        if not m:
+            return name
+        pos = m.end() + int(m.group(1))
+        name = mangled[m.end():pos]
+
+
 @pytest.fixture(scope="module")
 def ofdm_asm(tmp_path_factory):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -89,6 +102,14 @@ def test_the_scratch_free_claim_holds_for_the_decoders_too():
             assert md, obj
             for k, v in md.items():
                 assert v["vgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0, (obj, k, v)
+            if obj == "viterbi_lane_kernels.o":
+                # the lane decoder is seven kernels (one prep, one forward pass on soft words, and the forward / traceback
+                # (/ history) of the two transports) and the forward pass of a single item without interleaving, for the FIC
+                # and for plain codewords: no other copy per source type or call shape
+                base = sorted(base_name(k) for k in md)
+                assert base == sorted(["lane_prep_kernel", "lane_forward_kernel", "lane_forward_grouped_kernel",
+                                       "lane_traceback_grouped_kernel", "lane_forward_ragged_kernel", "lane_traceback_ragged_kernel",
+                                       "lane_history_ragged_kernel", "lane_forward_fused_kernel", "lane_forward_fused_kernel"]), base
 
 
 def test_lane_forward_pass_instruction_count_matches_the_bench_lines_constants(tmp_path):

@@ -8,6 +8,8 @@ This times the grouped forward + traceback pair on launch shapes that isolate th
     fic + msc           the bench's shape
     fic + msc + msc     3 waves per SIMD: what "FIC wave + two half-occupancy sub-channel waves" would issue (a wave's
                         instruction count does not depend on how many of its lanes hold a codeword)
+    plain               dabgpu_viterbi_dev on as many contiguous codewords as `msc` decodes, same profile (1542 steps, 3072
+                        punctured bits each): the single-item call on a source without interleaving
 usage: tools/lane_shapes.py [n_frames]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +22,10 @@ fib = torch.zeros((n, 12, 32), dtype=torch.uint8, device=dev); crc = torch.zeros
 E = 64; F = n // E
 a, b = dabgpu.subchannel(0, 64, level=3), dabgpu.subchannel(48, 64, level=3)
 oa = torch.zeros((E, F * 4, 192), dtype=torch.uint8, device=dev); ob = torch.zeros_like(oa)
+from dabgpu import synth
+mask = np.ascontiguousarray(synth.eep_mask(0, 3, 64)[0], np.uint8)
+n_plain = max(n * 4, 24576)
+punct = torch.randint(-127, 128, (n_plain, int(mask.sum())), dtype=torch.int8, device=dev); op = torch.zeros((n_plain, 192), dtype=torch.uint8, device=dev)
 ctx = dabgpu.Context(0, n, flags=dabgpu.FLAG_VITERBI_LANE); st = torch.cuda.Stream(); torch.cuda.set_stream(st); s = st.cuda_stream
 def t(fn, reps=10):
     for _ in range(3): fn()
@@ -34,6 +40,8 @@ rows = [
     ("msc + msc", lambda: ctx.msc_decode_multi_dev([a, b], P, NB, E, F, None, None, [oa.data_ptr(), ob.data_ptr()], s)),
     ("fic + msc", lambda: ctx.decode_frames_dev(P, NB, E, F, fib.data_ptr(), crc.data_ptr(), [a], None, None, [oa.data_ptr()], s)),
     ("fic + msc + msc", lambda: ctx.decode_frames_dev(P, NB, E, F, fib.data_ptr(), crc.data_ptr(), [a, b], None, None, [oa.data_ptr(), ob.data_ptr()], s)),
+    ("plain", lambda: dabgpu._check(ctx._lib.dabgpu_viterbi_dev(ctx._h, punct.data_ptr(), n_plain, mask.ctypes.data, mask.size // 4, op.data_ptr(), s),
+                                    "dabgpu_viterbi_dev")),
 ]
 res = {}
 for name, fn in rows:
