@@ -378,6 +378,7 @@ void dabgpu_destroy(dabgpu_ctx *ctx) {
     if (ctx->d_twiddle) (void)hipFree(ctx->d_twiddle);
     if (ctx->d_bin_of_n) (void)hipFree(ctx->d_bin_of_n);
     if (ctx->d_n_of_vj) (void)hipFree(ctx->d_n_of_vj);
+    for (auto &kv : ctx->run_queues) (void)hipFree(kv.second.d_pairs);
     if (ctx->d_prs_qt) (void)hipFree(ctx->d_prs_qt);
     if (ctx->d_sync_pairs) (void)hipFree(ctx->d_sync_pairs);
     if (ctx->d_sync_fs) (void)hipFree(ctx->d_sync_fs);

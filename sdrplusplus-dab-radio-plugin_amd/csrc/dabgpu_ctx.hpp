@@ -73,6 +73,17 @@ enum StageSlot {
 
 struct Pipeline;                         // dabgpu_pipeline.hip
 
+// The {next, done} pairs of the front end's run queue (dabk::RunQueue), a ring per stream the context's front-end calls
+// have been enqueued on: launches on one stream run in order, so a stream's launches may share its ring; launches on
+// different streams may be in flight together and never share a pair.  A launch takes the ring's next pair.  Zeroed when
+// the ring is made; every launch leaves its pair zeroed (the kernel's last wave), so no call clears anything.
+constexpr int QUEUE_RING = 8;
+constexpr int QUEUE_PAIR_STRIDE = 32;    // in 32-bit words: a pair per 128-byte line
+struct QueueRing {
+    unsigned *d_pairs = nullptr;
+    unsigned launches = 0;
+};
+
 // The de-interleaver rings of the sub-channels a state-keeping call decodes (dabgpu_decode_stream_frames: one stream;
 // dabgpu_pipe_submit: n_streams of them), kept on the device between calls and double-buffered: [n_streams][15][bits] a
 // side.  A call acquires the ring of every sub-channel it lists, decodes from in() to out() and commits.  A ring that
@@ -155,6 +166,7 @@ struct dabgpu_ctx {
     float2 *d_twiddle = nullptr;
     uint16_t *d_bin_of_n = nullptr;
     uint16_t *d_n_of_vj = nullptr;
+    std::map<hipStream_t, dabapi::QueueRing> run_queues;   // front-end run queues, by stream (dabapi::QueueRing)
     int8_t *d_prs_qt = nullptr;
     uint16_t *d_sync_pairs = nullptr;
     int n_sync_pairs = 0;

@@ -10,11 +10,17 @@ using namespace dabapi;
 
 namespace {
 
-// How a launch's frames are cut into runs of consecutive symbols (one run = one wavefront; 12 resident per CU).  A cut
-// costs one more transform and one more symbol read (the run's differential reference), so cuts are made only where they
-// buy balance: as many whole frames as fill the resident wave slots an integer number of times go first, uncut; the
-// frames behind them -- which alone would leave most slots idle for the length of a frame -- are cut into `parts`.
-// Cost model, in symbol transforms per wave slot: rounds x (symbols per item + 1).
+// How a launch's frames are cut into runs of consecutive symbols (one run = one item of the launch's queue; 12 wavefronts
+// resident per CU take them).  A cut costs one more transform and one more symbol read (the run's differential reference),
+// so cuts are made only where they buy balance: as many whole frames as fill the resident wave slots an integer number
+// of times go first, uncut; the frames behind them -- which alone would leave most slots idle for the length of a frame --
+// are cut into `parts`.  Cost model, in symbol transforms per wave slot: passes x (symbols per item + 1).
+// The model counts passes over the wave slots as if they began together.  They do not: the waves take items from a queue
+// as they finish, and after the whole frames they finish up to a whole item's length apart, so the launch ends when the
+// last of the cut items does.  Shorter ones end it sooner: the frames behind the whole ones are cut into at least
+// TAIL_MIN_PARTS.  Measured on 64 x 256 frames (profiles/front_end_queue.md; the model alone says 3): 3 parts 5.272 ms,
+// 4 parts 5.252 ms, 6 parts 5.224 ms per launch -- although 6 parts read 0.4 % more than 3.
+constexpr int TAIL_MIN_PARTS = 6;
 struct RunPlan {
     int uncut_frames, parts;
 };
@@ -35,11 +41,34 @@ RunPlan plan_runs(const dabgpu_ctx *ctx, int n_frames, int total_syms) {
     const long cost_all = uniform(n_frames, &p_all);
     const long whole = long(n_frames) / slots * slots;
     const long cost_mixed = whole / slots * (total_syms + 1) + uniform(long(n_frames) - whole, &p_tail);
-    if (whole > 0 && cost_mixed < cost_all) return RunPlan{int(whole), p_tail};
+    if (whole > 0 && cost_mixed < cost_all) return RunPlan{int(whole), std::max(p_tail, TAIL_MIN_PARTS)};
     return RunPlan{0, p_all};
 }
 
 dabk::OfdmTables ofdm_tables(const dabgpu_ctx *ctx) { return dabk::OfdmTables{ctx->d_twiddle, ctx->d_bin_of_n, ctx->d_n_of_vj}; }
+
+// The run queue of the next front-end launch on `s` (dabk::RunQueue, QueueRing): the next pair of the stream's ring, which
+// is made -- and zeroed on `s`, ahead of the launch -- the first time the stream is seen.
+int next_run_queue(dabgpu_ctx *ctx, hipStream_t s, dabk::RunQueue &q) {
+    auto it = ctx->run_queues.find(s);
+    if (it == ctx->run_queues.end()) {
+        // (a caller that keeps making streams: the rings of the ones it has dropped go once nothing can be using them)
+        if (ctx->run_queues.size() >= 64) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (auto &kv : ctx->run_queues) (void)hipFree(kv.second.d_pairs);
+            ctx->run_queues.clear();
+        }
+        QueueRing ring;
+        constexpr size_t bytes = sizeof(unsigned) * QUEUE_RING * QUEUE_PAIR_STRIDE;
+        if (hipMalloc(reinterpret_cast<void **>(&ring.d_pairs), bytes) != hipSuccess) return DABGPU_ERR_NOMEM;
+        if (hipMemsetAsync(ring.d_pairs, 0, bytes, s) != hipSuccess) { (void)hipFree(ring.d_pairs); return DABGPU_ERR_HIP; }
+        it = ctx->run_queues.emplace(s, ring).first;
+    }
+    QueueRing &ring = it->second;
+    q.pair = ring.d_pairs + size_t(ring.launches++ % QUEUE_RING) * QUEUE_PAIR_STRIDE;
+    q.wave_slots = ctx->wave_slots;
+    return DABGPU_OK;
+}
 dabk::SyncTables sync_tables(const dabgpu_ctx *ctx) {
     return dabk::SyncTables{ctx->d_twiddle, ctx->d_prs_qt, ctx->d_sync_pairs, ctx->n_sync_pairs, ctx->d_sync_fs};
 }
@@ -51,10 +80,13 @@ dabk::SyncTables sync_tables(const dabgpu_ctx *ctx) {
 int launch_front_end(dabgpu_ctx *ctx, dabk::OfdmArgs &a, int total_syms, TimerSlot timer, hipStream_t s) {
     const dabk::OfdmTables tab = ofdm_tables(ctx);
     if (!a.spectra) a.keep = ctx->d_keep;
+    dabk::RunQueue q{};
+    const int rc = next_run_queue(ctx, s, q);
+    if (rc) return rc;
     ScopedTimer tm(ctx, timer, s);
     const RunPlan plan = plan_runs(ctx, a.n_frames, total_syms);
     a.uncut_frames = plan.uncut_frames;
-    HIP_TRY(a.spectra ? dabk::launch_fft_symbols(tab, a, plan.parts, s) : dabk::launch_ofdm_demod(tab, a, plan.parts, s, ctx->iq_format));
+    HIP_TRY(a.spectra ? dabk::launch_fft_symbols(tab, a, plan.parts, q, s) : dabk::launch_ofdm_demod(tab, a, plan.parts, q, s, ctx->iq_format));
     return DABGPU_OK;
 }
 
@@ -299,8 +331,11 @@ int dabgpu_mover_frames_dev(dabgpu_ctx *ctx, const void *d_iq, size_t frame_stri
     if (reinterpret_cast<uintptr_t>(d_soft) & 15u) return DABGPU_ERR_ARG;
     if (n_frames == 0) return DABGPU_OK;
     const RunPlan plan = plan_runs(ctx, n_frames, NB_DATA_SYMBOLS);
+    hipStream_t s = pick_stream(ctx, stream);
+    dabk::RunQueue q{};
+    if ((rc = next_run_queue(ctx, s, q))) return rc;
     HIP_TRY(dabk::launch_geometry_mover(static_cast<const float2 *>(d_iq), frame_stride, n_frames, d_soft, plan.uncut_frames,
-                                        plan.parts, with_prefixes != 0, pick_stream(ctx, stream)));
+                                        plan.parts, with_prefixes != 0, q, s));
     return DABGPU_OK;
 }
 

@@ -15,6 +15,15 @@ struct OfdmTables {
     const uint16_t *n_of_vj;   // [12][64][2] data index of carrier registers 2jj, 2jj+1 of lane v (wave kernel)
 };
 
+// The run queue of ONE front-end launch.  A launch has at most wave_slots / 4 workgroups, all resident; each wave starts on
+// the item of its own number and takes every further one from pair[0]; pair[1] counts the waves that have left, and the
+// last one zeroes both words again.  `pair` must be zero when the launch starts, and no other launch that may run at the
+// same time may be given the same pair.
+struct RunQueue {
+    unsigned *pair;
+    int wave_slots;            // wavefronts of this kernel the device holds at once (12 per CU)
+};
+
 // Per-stream tracking state kept in device memory between launches (== dabgpu_stream_state, 64 bytes): the
 // frequency offsets OFDM_Demod shows through GetFineFrequencyOffset / GetCoarseFrequencyOffset
 // (/root/reference/src/render_radio_block.cpp:202-207), its frame counters, and -- what RUNNING_FINE_TIME_SYNC
@@ -74,9 +83,9 @@ struct OfdmArgs {
 // iq_format (IQ_*, iq_load.hpp; every launcher that reads samples takes it): a.iq / the iq pointers then hold the caller's
 // integer samples; strides and starts stay in complex samples.  The integer formats take the fused kernel without a
 // constellation output only, and the tracking pass in batch mode without a riding upload (hipErrorInvalidValue otherwise).
-hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s, int iq_format = 0);
+hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, const RunQueue &q, hipStream_t s, int iq_format = 0);
 // A2+A3 only; parts in 1..76.
-hipError_t launch_fft_symbols(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s);
+hipError_t launch_fft_symbols(const OfdmTables &t, const OfdmArgs &a, int parts, const RunQueue &q, hipStream_t s);
 // Fine-frequency loop and counters of the stream call, after the demodulation launch on the same stream:
 // per stream, fine -= beta * mean(arg cyc[frame][symbol]) / (2*pi*2048), wrapped to +-half a carrier; frame count;
 // L1 level of the stream's last frame (first 4096 samples) into the running average, counted as a desync when it
@@ -100,9 +109,9 @@ int copy_pieces_max();
 // reads `in` and writes `out` at the same time (streaming, both whole): the launch is slower when the two buffers
 // share an HBM domain -- what the placement helpers time
 hipError_t launch_placement_probe(const void *in, size_t in_bytes, void *out, size_t out_bytes, hipStream_t s);
-// the fused front end's loads and stores without its arithmetic, same run structure and occupancy (dabgpu_mover_frames_dev)
+// the fused front end's loads and stores without its arithmetic, same grid, queue, run structure and occupancy (dabgpu_mover_frames_dev)
 hipError_t launch_geometry_mover(const float2 *iq, size_t frame_stride, int n_frames, int8_t *soft, int uncut_frames, int parts,
-                                 bool prefixes, hipStream_t s);
+                                 bool prefixes, const RunQueue &q, hipStream_t s);
 // dd != 0: `cyc` holds the front end's dd4 output instead; the error is angle(-sum of all entries l >= 1) / (4 * 2 pi * 2552)
 // (dd_gate, dd_terms_per_frame: see dd_loop_error / TrackUpdateArgs)
 hipError_t launch_stream_update(StreamState *state, const float2 *cyc, const float2 *iq, size_t frame_stride,

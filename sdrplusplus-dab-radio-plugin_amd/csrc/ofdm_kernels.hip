@@ -25,7 +25,12 @@
 // tools/ubench/lds_conflict.hip, profiles/r02_ofdm_bound.md).  No workgroup barrier is needed after the tables are
 // loaded: a wave only talks to itself.  Soft bits are scattered as bytes into the (then idle) exchange buffer and
 // leave as three coalesced 16-byte stores per lane.
+//
+// A launch has no more workgroups than the device holds at once.  A wave starts on the run of its own number and takes
+// every further one from the launch's queue (a device counter, asked while the run's last symbol loads); what a run
+// derives from its number it derives per run, and no wave ever waits for another.
 #include <algorithm>
+#include <cstddef>
 
 #include "kernels.hpp"
 #include "dab_tables.hpp"
@@ -61,6 +66,22 @@ struct WaveLds {
                                      // as soft-bit staging                                    8 KB each
     float2 cyc[WAVES][32];           // cyclic-prefix correlations waiting to leave as one wide store  1 KB
 };   // 52 KB per 4-wave workgroup -> 3 workgroups = 12 waves per CU
+
+// The run queue of one launch: queue[0] counts the items taken beyond every wave's first, queue[1] the waves that have
+// left.  One lane asks; the answer is wave-uniform (a scalar register).
+__device__ __forceinline__ unsigned take_item(unsigned *queue, int lane) {
+    unsigned v = 0u;
+    if (lane == 0) v = atomicAdd(queue, 1u);
+    return unsigned(__builtin_amdgcn_readfirstlane(int(v)));
+}
+// Every wave of the launch comes here once, after its last answer from queue[0]; the last one to leave hands the pair
+// back zeroed, for the launch that takes it next.
+__device__ __forceinline__ void leave_queue(unsigned *queue, int lane) {
+    if (lane == 0 && atomicAdd(queue + 1, 1u) == gridDim.x * WAVES - 1u) {
+        queue[0] = 0u;
+        queue[1] = 0u;
+    }
+}
 
 __device__ __forceinline__ float2 cmul_k(float2 a, float c, float s) {   // a * (c + j*s)
     return make_float2(a.x * c - a.y * s, a.x * s + a.y * c);
@@ -122,8 +143,49 @@ __device__ __forceinline__ void fft8_odd_scaled(float2 *v, const float2 (&c)[4])
 __device__ __forceinline__ void lds_stores_done() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); }
 __device__ __forceinline__ void lds_loads_may_start() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 
+// What the start of a run derives its frame, its samples' start and its frequency correction from: OfdmArgs' fields of
+// these names and the cut.  A wave reads them from the kernel's argument segment again at the start of every run (through a
+// pointer the compiler cannot see through): held as arguments they would occupy ~20 scalar registers, with what is derived
+// from them, from a wave's first run to its last -- registers the symbol loop has no room for.
+struct RunSetup {
+    size_t frame_stride;
+    const float *freq_offset;
+    const AcquiredFrame *acq;
+    const StreamState *state;
+    int acq_per_stream, frames_per_stream, uncut_frames, parts;
+};
+typedef const __attribute__((address_space(4))) char *KernArgs;
+template <typename T>
+__device__ __forceinline__ T kernarg(KernArgs k, size_t offset) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(k + offset);
+}
+// (a pointer read this way is a number to the compiler: told to be one into global memory, so that loads through it stay
+// global loads)
+template <typename T>
+__device__ __forceinline__ const T *kernarg_global(KernArgs k, size_t offset) {
+    return (const T *)(const __attribute__((address_space(1))) T *)kernarg<uint64_t>(k, offset);
+}
+// the argument segment of ofdm_wave_kernel: OfdmTables, OfdmArgs, the cut
+constexpr size_t KARG_ARGS = sizeof(OfdmTables), KARG_PARTS = KARG_ARGS + sizeof(OfdmArgs);
+static_assert(sizeof(OfdmTables) % alignof(OfdmArgs) == 0 && sizeof(OfdmArgs) % alignof(OfdmArgs) == 0 && alignof(OfdmArgs) == 8,
+              "the arguments follow each other without padding");
+__device__ __forceinline__ RunSetup run_setup() {
+    KernArgs k = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    RunSetup r;
+    r.frame_stride = kernarg<size_t>(k, KARG_ARGS + offsetof(OfdmArgs, frame_stride));
+    r.freq_offset = kernarg_global<float>(k, KARG_ARGS + offsetof(OfdmArgs, freq_offset));
+    r.acq = kernarg_global<AcquiredFrame>(k, KARG_ARGS + offsetof(OfdmArgs, acq));
+    r.state = kernarg_global<StreamState>(k, KARG_ARGS + offsetof(OfdmArgs, state));
+    r.acq_per_stream = kernarg<int>(k, KARG_ARGS + offsetof(OfdmArgs, acq_per_stream));
+    r.frames_per_stream = kernarg<int>(k, KARG_ARGS + offsetof(OfdmArgs, frames_per_stream));
+    r.uncut_frames = kernarg<int>(k, KARG_ARGS + offsetof(OfdmArgs, uncut_frames));
+    r.parts = kernarg<int>(k, KARG_PARTS);
+    return r;
+}
+
 // frequency correction of frame `frame`, as the NCO's 32-bit phase increment per sample
-__device__ __forceinline__ uint32_t frame_dphi(const OfdmArgs &a, int frame) {
+__device__ __forceinline__ uint32_t frame_dphi(const RunSetup &a, int frame) {
     if (a.state) {
         const StreamState st = a.state[frame / a.frames_per_stream];
         return uint32_t(__double2ll_rn(double(st.fine_freq_offset + st.coarse_freq_offset) * 4294967296.0));
@@ -138,12 +200,13 @@ __device__ __forceinline__ uint32_t frame_dphi(const OfdmArgs &a, int frame) {
 // FMT: sample format (IQ_*, iq_load.hpp); the integer ones are converted to float right after their loads.  (A compile-time
 // switch as well: with the cs8 / cu8 difference as a kernel argument the cf32 instantiations' code would not stay as it is.)
 template <bool FFT_ONLY, bool WITH_DQPSK, bool SELECT = false, bool NCO = true, int FMT = IQ_CF32>
-__global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab, OfdmArgs a, int parts, int n_items) {
+__global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab, OfdmArgs a, int /* parts: run_setup() */, int n_items, unsigned *queue) {
     constexpr int FAM = iq_family(FMT);
     __shared__ WaveLds sm;
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
+    int lane = tid & 63;
     const int wave = tid >> 6;
+    // the tables, once in the workgroup's life
     for (int i = tid; i < NB_FFT; i += 64 * WAVES) {
         int m;                                                  // exponent of exp(-2*pi*i/2048)
         if (i < TW_E1) {
@@ -161,43 +224,54 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
     }
     for (int i = tid; i < 12 * 64; i += 64 * WAVES) sm.nidx[i] = reinterpret_cast<const uint32_t *>(tab.n_of_vj)[i];
     __syncthreads();
+    // The workgroups of a launch are all resident (launch_grid); a wave starts on item blockIdx.x * WAVES + wave and takes
+    // every further one from the launch's counter.  No wave waits for another.
+    const int n_started = __builtin_amdgcn_readfirstlane(int(gridDim.x) * WAVES);
     // The item is the same for all lanes of a wave; saying so keeps everything derived from it (frame pointers, the
     // symbol counter, the NCO increment) in SGPRs: -5 % VALU instructions, -8 % time.
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wave);
-    if (item >= n_items) return;
+    int item = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wave);
+    while (item < n_items) {
+    // (the lane number, opaque per run: what a run derives from it is derived again by the next one instead of being held in
+    // vector registers from a wave's first run to its last)
+    asm volatile("" : "+v"(lane));
+    lane &= 63;                                                 // (its range stays known: addresses formed from it stay 32-bit sums)
+    const RunSetup rs = run_setup();
     // whole frames first (one run each), then the cut ones: the launch ends on short items
-    int frame = item, part = 0;
-    if (item >= a.uncut_frames) {
-        const int j = item - a.uncut_frames;
-        frame = a.uncut_frames + j / parts;
-        part = j - (frame - a.uncut_frames) * parts;
-    } else {
-        parts = 1;
+    int frame = item, part = 0, parts = 1;
+    if (item >= rs.uncut_frames) {
+        const int j = item - rs.uncut_frames;
+        parts = rs.parts;
+        frame = rs.uncut_frames + j / parts;
+        part = j - (frame - rs.uncut_frames) * parts;
     }
+    int next_item = n_items;                                    // taken while the run's last symbol loads (below)
     const IqSrc<FAM> iq0 = iq_src<FAM>(a.iq, FMT);
-    IqSrc<FAM> fiq = iq0 + size_t(frame) * a.frame_stride;
+    IqSrc<FAM> fiq = iq0 + size_t(frame) * rs.frame_stride;
     // fused: data symbols (l_first, l_last]; l_first is only the differential reference
     const int l_first = FFT_ONLY ? (NB_FRAME_SYMBOLS * part) / parts : (NB_DATA_SYMBOLS * part) / parts;
     const int l_last = FFT_ONLY ? (NB_FRAME_SYMBOLS * (part + 1)) / parts - 1 : (NB_DATA_SYMBOLS * (part + 1)) / parts;
     uint32_t dphi_acq = 0u;
-    if (a.acq) {
+    if (rs.acq) {
         // frames found by the acquisition kernels: arbitrary (8-byte aligned) start inside their stream
-        const AcquiredFrame m = a.acq[frame];
+        const AcquiredFrame m = rs.acq[frame];
         if ((m.flags & 3) != 3) {
             if constexpr (!FFT_ONLY) {                        // not a demodulable frame: erased soft bits
                 uint4 *o = reinterpret_cast<uint4 *>(a.soft + size_t(frame) * NB_FRAME_BITS + size_t(l_first) * NB_SYM_BITS);
                 const int n16 = (l_last - l_first) * NB_SYM_BITS / 16;
-                for (int i = lane; i < n16; i += 64) st_stream(o + i, make_uint4(0u, 0u, 0u, 0u));
+                unsigned zero = 0u;                             // (made here: four registers of zeros are not kept for this across every run)
+                asm volatile("" : "+v"(zero));
+                for (int i = lane; i < n16; i += 64) st_stream(o + i, make_uint4(zero, zero, zero, zero));
             }
-            return;
+            item = n_started + int(take_item(queue, lane));
+            continue;
         }
-        fiq = iq0 + size_t(frame / a.acq_per_stream) * a.frame_stride + m.start;
+        fiq = iq0 + size_t(frame / rs.acq_per_stream) * rs.frame_stride + m.start;
         dphi_acq = uint32_t(__double2ll_rn(double(m.freq_offset) * 4294967296.0));
     }
     bool aligned16;                                             // (integer formats: every load pair aligned to its width)
     if constexpr (FAM == IQF_F32) aligned16 = (reinterpret_cast<uintptr_t>(fiq) & 15u) == 0;
     else aligned16 = fiq.pair_aligned();
-    const uint32_t dphi = a.acq ? dphi_acq : frame_dphi(a, frame);
+    const uint32_t dphi = rs.acq ? dphi_acq : frame_dphi(rs, frame);
     float2 *ex = sm.ex[wave];
     const float2 *tw = sm.tw;
 
@@ -242,6 +316,9 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
     for (int l = l_first; l <= l_last; l++) {
         const IqSrc<FAM> sym = fiq + size_t(l) * NB_SYM_PERIOD;
         const bool emit = FFT_ONLY || (l > l_first) || (l == 0);
+        // the run's last symbol: ask for the next item now, read the answer once this symbol's loads are under way
+        unsigned taken = 0u;
+        if (l == l_last && lane == 0) taken = atomicAdd(queue, 1u);
         // Lane roles, derived per iteration from an opaque copy of the lane number: every LDS address below is one or
         // two VALU ops from these, which is cheaper than letting LICM park ~60 loop-invariant addresses in VGPRs (spills).
         int li = lane;
@@ -262,6 +339,7 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
             if (ls > l_first) { const unsigned long long *kw = a.keep + 3 * (ls - 1); need |= (kw[0] | kw[1] | kw[2]) != 0ull; }
             if (ls < l_last) { const unsigned long long *kw = a.keep + 3 * ls; need |= (kw[0] | kw[1] | kw[2]) != 0ull; }
             if (!need) {
+                if (l == l_last) next_item = n_started + __builtin_amdgcn_readfirstlane(int(taken));
                 if ((a.cyc && emit) || (dd && l == 0)) {
                     float2 acc = make_float2(0.f, 0.f);
                     const IqSrc<FAM> cp = sym + 2 * (lane - 4);
@@ -337,6 +415,7 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
                 x1[n1] = ld_stream(rows + 128 * n1 + 1);
             }
         }
+        if (l == l_last) next_item = n_started + __builtin_amdgcn_readfirstlane(int(taken));
         __builtin_amdgcn_sched_barrier(0);
         // ---- cyclic-prefix correlation on raw samples: CP pair c = lane-4+64*i <-> row 12+i of this lane ----
         // (decision-directed mode: of the PRS only -- its angle picks the branch of the fourth-power estimate, 4.1)
@@ -563,6 +642,9 @@ __global__ __launch_bounds__(64 * WAVES, 3) void ofdm_wave_kernel(OfdmTables tab
             st_stream(a.dd4 + size_t(frame) * NB_FRAME_SYMBOLS + l_first + 1 + i,
                       i == nrun - 1 ? make_float2(sx, sy) : make_float2(0.f, 0.f));
     }
+    item = next_item;
+    }
+    leave_queue(queue, lane);
 }
 
 // One 1024-thread workgroup per stream.  Restated by oracle.py stream_update() for the parity test.
@@ -710,59 +792,72 @@ __global__ __launch_bounds__(256) void placement_probe_kernel(const char *in, ch
 }  // namespace
 
 namespace {
-// The fused front end's memory geometry without its arithmetic (dabgpu_mover_frames_dev): the same items (whole frames
-// first, then frames cut into `parts` runs), one wavefront per item, per symbol of the run sixteen 16-byte loads per lane
-// from the useful part (PREFIXES: four more covering the cyclic prefix; else the prefix of symbol 0 only), per data symbol
-// three 16-byte stores per lane; streaming accesses, the same 52 KB of LDS per 4-wave workgroup.
+// The fused front end's memory geometry without its arithmetic (dabgpu_mover_frames_dev): the same grid of resident
+// workgroups, the same queue and items (whole frames first, then frames cut into `parts` runs), one wavefront per run, per
+// symbol of the run sixteen 16-byte loads per lane from the useful part (PREFIXES: four more covering the cyclic prefix; else
+// the prefix of symbol 0 only), per data symbol three 16-byte stores per lane; streaming accesses, the same 52 KB of LDS per
+// 4-wave workgroup.
 template <bool PREFIXES>
 __global__ __launch_bounds__(64 * WAVES, 3) void geometry_mover_kernel(const float2 *iq, size_t frame_stride, int8_t *soft,
-                                                                        int uncut_frames, int parts, int n_items) {
+                                                                        int uncut_frames, int parts_cut, int n_items, unsigned *queue) {
     __shared__ char occupancy[sizeof(WaveLds)];
     const int lane = threadIdx.x & 63;
     if (n_items < 0) occupancy[threadIdx.x] = 1;               // (never: keeps the array)
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
-    if (item >= n_items) return;
-    int frame = item, part = 0;
-    if (item >= uncut_frames) {
-        const int j = item - uncut_frames;
-        frame = uncut_frames + j / parts;
-        part = j - (frame - uncut_frames) * parts;
-    } else {
-        parts = 1;
-    }
-    const float2 *fiq = iq + size_t(frame) * frame_stride;
-    const int l_first = (NB_DATA_SYMBOLS * part) / parts, l_last = (NB_DATA_SYMBOLS * (part + 1)) / parts;
-    uint4 acc = make_uint4(1u, 2u, 3u, 4u);
-    for (int l = l_first; l <= l_last; l++) {
-        const float2 *sym = fiq + size_t(l) * NB_SYM_PERIOD;
-        const uint4 *rows = reinterpret_cast<const uint4 *>(sym + NB_CP) + lane;
-        uint4 v[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) v[i] = ld_stream(rows + 64 * i);
-        if (PREFIXES ? (l > l_first || l == 0) : l == 0) {
-            const uint4 *cp = reinterpret_cast<const uint4 *>(sym + 2 * (lane - 4));
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (i > 0 || lane >= 4) { const uint4 c = ld_stream(cp + 64 * i); acc.x += c.x; acc.y ^= c.y; acc.z += c.z; acc.w ^= c.w; }
+    const int n_started = __builtin_amdgcn_readfirstlane(int(gridDim.x) * WAVES);
+    int item = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    while (item < n_items) {
+        uint4 acc = make_uint4(1u, 2u, 3u, 4u);                // (per run: what is written does not depend on which wave ran it)
+        int frame = item, part = 0, parts = 1;
+        if (item >= uncut_frames) {
+            const int j = item - uncut_frames;
+            parts = parts_cut;
+            frame = uncut_frames + j / parts;
+            part = j - (frame - uncut_frames) * parts;
         }
+        const float2 *fiq = iq + size_t(frame) * frame_stride;
+        const int l_first = (NB_DATA_SYMBOLS * part) / parts, l_last = (NB_DATA_SYMBOLS * (part + 1)) / parts;
+        int next_item = n_items;
+        for (int l = l_first; l <= l_last; l++) {
+            unsigned taken = 0u;
+            if (l == l_last && lane == 0) taken = atomicAdd(queue, 1u);
+            const float2 *sym = fiq + size_t(l) * NB_SYM_PERIOD;
+            const uint4 *rows = reinterpret_cast<const uint4 *>(sym + NB_CP) + lane;
+            uint4 v[16];
 #pragma unroll
-        for (int i = 0; i < 16; i++) { acc.x += v[i].x; acc.y ^= v[i].y; acc.z += v[i].z; acc.w ^= v[i].w; }
-        if (l > l_first) {
-            uint4 *o = reinterpret_cast<uint4 *>(soft + size_t(frame) * NB_FRAME_BITS + size_t(l - 1) * NB_SYM_BITS) + lane;
-            st_stream(o, acc); st_stream(o + 64, acc); st_stream(o + 128, acc);
+            for (int i = 0; i < 16; i++) v[i] = ld_stream(rows + 64 * i);
+            if (l == l_last) next_item = n_started + __builtin_amdgcn_readfirstlane(int(taken));
+            if (PREFIXES ? (l > l_first || l == 0) : l == 0) {
+                const uint4 *cp = reinterpret_cast<const uint4 *>(sym + 2 * (lane - 4));
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i > 0 || lane >= 4) { const uint4 c = ld_stream(cp + 64 * i); acc.x += c.x; acc.y ^= c.y; acc.z += c.z; acc.w ^= c.w; }
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) { acc.x += v[i].x; acc.y ^= v[i].y; acc.z += v[i].z; acc.w ^= v[i].w; }
+            if (l > l_first) {
+                uint4 *o = reinterpret_cast<uint4 *>(soft + size_t(frame) * NB_FRAME_BITS + size_t(l - 1) * NB_SYM_BITS) + lane;
+                st_stream(o, acc); st_stream(o + 64, acc); st_stream(o + 128, acc);
+            }
         }
+        item = next_item;
     }
+    leave_queue(queue, lane);
+}
+
+// Every front-end launch: as many 4-wave workgroups as the items need, and never more than are resident at once
+dim3 launch_grid(int items, const RunQueue &q) {
+    return dim3(unsigned(std::min((items + WAVES - 1) / WAVES, std::max(q.wave_slots / WAVES, 1))));
 }
 }  // namespace
 
 hipError_t launch_geometry_mover(const float2 *iq, size_t frame_stride, int n_frames, int8_t *soft, int uncut_frames, int parts,
-                                 bool prefixes, hipStream_t s) {
+                                 bool prefixes, const RunQueue &q, hipStream_t s) {
     if (n_frames <= 0) return hipSuccess;
-    if (parts <= 0 || parts > NB_DATA_SYMBOLS || uncut_frames < 0 || uncut_frames > n_frames) return hipErrorInvalidValue;
+    if (parts <= 0 || parts > NB_DATA_SYMBOLS || uncut_frames < 0 || uncut_frames > n_frames || !q.pair) return hipErrorInvalidValue;
     const int items = uncut_frames + (n_frames - uncut_frames) * parts;
-    const dim3 grid(unsigned((items + WAVES - 1) / WAVES)), block(64 * WAVES);
-    if (prefixes) hipLaunchKernelGGL(geometry_mover_kernel<true>, grid, block, 0, s, iq, frame_stride, soft, uncut_frames, parts, items);
-    else hipLaunchKernelGGL(geometry_mover_kernel<false>, grid, block, 0, s, iq, frame_stride, soft, uncut_frames, parts, items);
+    const dim3 grid = launch_grid(items, q), block(64 * WAVES);
+    if (prefixes) hipLaunchKernelGGL(geometry_mover_kernel<true>, grid, block, 0, s, iq, frame_stride, soft, uncut_frames, parts, items, q.pair);
+    else hipLaunchKernelGGL(geometry_mover_kernel<false>, grid, block, 0, s, iq, frame_stride, soft, uncut_frames, parts, items, q.pair);
     return hipGetLastError();
 }
 
@@ -850,14 +945,14 @@ hipError_t launch_stream_update(StreamState *state, const float2 *cyc, const flo
     return hipGetLastError();
 }
 
-hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s, int iq_format) {
+hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, const RunQueue &q, hipStream_t s, int iq_format) {
     if (a.n_frames <= 0) return hipSuccess;
     if (parts <= 0 || parts > NB_DATA_SYMBOLS) return hipErrorInvalidValue;
     if (a.state && a.frames_per_stream <= 0) return hipErrorInvalidValue;
-    if (a.uncut_frames < 0 || a.uncut_frames > a.n_frames) return hipErrorInvalidValue;
+    if (a.uncut_frames < 0 || a.uncut_frames > a.n_frames || !q.pair) return hipErrorInvalidValue;
     const int items = a.uncut_frames + (a.n_frames - a.uncut_frames) * parts;
     const bool nco = a.freq_offset != nullptr || a.acq != nullptr || a.state != nullptr;
-    const dim3 grid(unsigned((items + WAVES - 1) / WAVES)), block(64 * WAVES);
+    const dim3 grid = launch_grid(items, q), block(64 * WAVES);
     OfdmArgs b = a;
     if (a.dqpsk) b.keep = nullptr;      // the constellation output covers every symbol: a selection is ignored there
     if (iq_format != IQ_CF32) {
@@ -865,9 +960,9 @@ hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, 
         if (b.dqpsk || !iq_format_valid(iq_format)) return hipErrorInvalidValue;
 #define DABK_INT_FE(SEL, NCO_)                                                                                          \
         do {                                                                                                               \
-            if (iq_format == IQ_CS16) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS16>), grid, block, 0, s, t, b, parts, items); \
-            else if (iq_format == IQ_CS8) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS8>), grid, block, 0, s, t, b, parts, items); \
-            else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CU8>), grid, block, 0, s, t, b, parts, items);     \
+            if (iq_format == IQ_CS16) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS16>), grid, block, 0, s, t, b, parts, items, q.pair); \
+            else if (iq_format == IQ_CS8) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CS8>), grid, block, 0, s, t, b, parts, items, q.pair); \
+            else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, SEL, NCO_, IQ_CU8>), grid, block, 0, s, t, b, parts, items, q.pair);     \
         } while (0)
         if (b.keep) { if (nco) DABK_INT_FE(true, true); else DABK_INT_FE(true, false); }
         else { if (nco) DABK_INT_FE(false, true); else DABK_INT_FE(false, false); }
@@ -875,27 +970,27 @@ hipError_t launch_ofdm_demod(const OfdmTables &t, const OfdmArgs &a, int parts, 
         return hipGetLastError();
     }
     if (b.dqpsk) {
-        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, true>), grid, block, 0, s, t, b, parts, items);
-        else hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, false>), grid, block, 0, s, t, b, parts, items);
+        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, true>), grid, block, 0, s, t, b, parts, items, q.pair);
+        else hipLaunchKernelGGL((ofdm_wave_kernel<false, true, false, false>), grid, block, 0, s, t, b, parts, items, q.pair);
     } else if (b.keep) {
-        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, true, true>), grid, block, 0, s, t, b, parts, items);
-        else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, true, false>), grid, block, 0, s, t, b, parts, items);
+        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, true, true>), grid, block, 0, s, t, b, parts, items, q.pair);
+        else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, true, false>), grid, block, 0, s, t, b, parts, items, q.pair);
     } else {
-        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, false, true>), grid, block, 0, s, t, b, parts, items);
-        else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, false, false>), grid, block, 0, s, t, b, parts, items);
+        if (nco) hipLaunchKernelGGL((ofdm_wave_kernel<false, false, false, true>), grid, block, 0, s, t, b, parts, items, q.pair);
+        else hipLaunchKernelGGL((ofdm_wave_kernel<false, false, false, false>), grid, block, 0, s, t, b, parts, items, q.pair);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_fft_symbols(const OfdmTables &t, const OfdmArgs &a, int parts, hipStream_t s) {
+hipError_t launch_fft_symbols(const OfdmTables &t, const OfdmArgs &a, int parts, const RunQueue &q, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
     if (parts <= 0 || parts > NB_FRAME_SYMBOLS) return hipErrorInvalidValue;
     if (a.state && a.frames_per_stream <= 0) return hipErrorInvalidValue;
-    if (a.uncut_frames < 0 || a.uncut_frames > a.n_frames) return hipErrorInvalidValue;
+    if (a.uncut_frames < 0 || a.uncut_frames > a.n_frames || !q.pair) return hipErrorInvalidValue;
     const int items = a.uncut_frames + (a.n_frames - a.uncut_frames) * parts;
-    const dim3 grid(unsigned((items + WAVES - 1) / WAVES)), block(64 * WAVES);
-    if (a.freq_offset || a.state) hipLaunchKernelGGL((ofdm_wave_kernel<true, false, false, true>), grid, block, 0, s, t, a, parts, items);
-    else hipLaunchKernelGGL((ofdm_wave_kernel<true, false, false, false>), grid, block, 0, s, t, a, parts, items);
+    const dim3 grid = launch_grid(items, q), block(64 * WAVES);
+    if (a.freq_offset || a.state) hipLaunchKernelGGL((ofdm_wave_kernel<true, false, false, true>), grid, block, 0, s, t, a, parts, items, q.pair);
+    else hipLaunchKernelGGL((ofdm_wave_kernel<true, false, false, false>), grid, block, 0, s, t, a, parts, items, q.pair);
     return hipGetLastError();
 }
 

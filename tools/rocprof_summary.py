@@ -43,7 +43,7 @@ def main():
         # (the ones before are the untimed settling and warm-up calls, which run slower: first touch, clocks ramping)
         trace = src.replace("_kernel_stats.csv", "_kernel_trace.csv")
         try:
-            d = launch_durations(trace, "ofdm_wave_kernel<false, false, false, true>")
+            d = launch_durations(trace, "ofdm_wave_kernel<false, false, false, true")      # (+ the sample format, cf32)
             if d:
                 f.write("# ofdm_wave_kernel<false,false,false,true> per launch, ms: %s\n" % " ".join("%.3f" % x for x in d))
                 for k in (10, 20):
