@@ -1419,6 +1419,125 @@ size_t dabgpu_dabplus_carry_bytes(int bitrate_kbps);
 int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entries, int n_entries, int n_cifs, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Dynamic labels: the text every followed DAB+ service shows ("now playing"),  */
+/* from the programme-associated data (PAD) of its access units -- what the     */
+/* reference prints as channel.GetDynamicLabel() for every audio channel        */
+/*   (/root/reference/src/render_radio_block.cpp:425-427, 470-472).             */
+/* PAD travels in a data stream element, the first syntactic element of the     */
+/* access unit, byte-aligned: no AAC is decoded.  Runs behind                   */
+/* dabgpu_dabplus_follow_dev on the same stream, on what that call left on the   */
+/* device.  One wave per entry, one launch.          */
+/*                                                                              */
+/* Not read: MOT / slideshow and X-PAD application types other than 1, 2, 3,     */
+/* 12, 13 (1, 12, 13 are stepped over); DL Plus tags (the command's CRC is        */
+/* checked, its body dropped); PAD of layer-II frames.  No audio is decoded.      */
+/* Charset 0 (EBU Latin) labels come out as bytes; no table translates them.      */
+/*                                                                              */
+/* THE CONTRACT of one entry in one call (EN 300 401 clauses 7.4.2 - 7.4.5,       */
+/* TS 102 563 clause 5.4, every ambiguity decided; one implementation,            */
+/* include/dabgpu_pad_walk.h, serves the kernel, the host twin and the mirror).   */
+/*                                                                              */
+/* Order and loss.  n = n_superframes of d_follow, clamped to 0 ..                */
+/* max_superframes.  Access units (AUs) are visited super-frame k = 0 .. n-1,      */
+/* then a = 0 .. num_aus-1 (num_aus above 7 counts as 7).  Every visited AU        */
+/* counts in aus.  A super-frame with firecode_ok == 0 or num_aus <= 0 is visited   */
+/* as ONE lost AU (how many it carried is not known).  Else AU a is LOST when bit   */
+/* a of au_crc_mask is clear, or when b = au_start[a], e = au_start[a+1] are not     */
+/* 0 <= b, b + 2 < e <= 110 s.  A lost AU counts in aus_lost and drops the           */
+/* continuation context and any open data group.                                    */
+/*                                                                              */
+/* Locating PAD.  len = e - b - 2 (without the AU CRC).  len < 2 or                */
+/* (au[0] >> 5) != 4: no PAD, nothing changes.  Else n = au[1], the payload p       */
+/* begins at o = 2; if au[1] == 255 then n += au[2], o = 3.  n < 2 or o + n > len    */
+/* (an escape with len == 2 included): pad_malformed++, context and group           */
+/* dropped.  F-PAD = p[n-2], p[n-1].  (p[n-2] >> 6) != 0: nothing changes.           */
+/* ind = (p[n-2] >> 4) & 3, ci = (p[n-1] >> 1) & 1; ind 0 or 3: nothing changes.      */
+/* X-PAD logical byte i = p[n-3-i], avail = n - 2 of them.  An AU that delivers       */
+/* at least one sub-field counts in aus_with_xpad.                                    */
+/*                                                                              */
+/* Short X-PAD (ind 1): avail < 4 is malformed.  With ci: byte 0 is a content         */
+/* indicator (CI), type = & 0x1F, then 3 data bytes; it counts as a list of one        */
+/* sub-field of length 4.  Without: 4 data bytes of the continued type.                */
+/* Variable X-PAD (ind 2), with ci: up to four CI bytes, length index >> 5 into         */
+/* {4, 6, 8, 12, 16, 24, 32, 48}, type & 0x1F; type 0 ends the list (its byte is         */
+/* consumed); type 31 consumes one more byte (the extended type) and its sub-field       */
+/* is skipped by length; the sub-fields follow in list order; a CI or extended-type      */
+/* byte at or beyond avail, or list plus sub-fields longer than avail: malformed,        */
+/* nothing of the field is used.  The list first sets the continued type to none.        */
+/* Without ci: one sub-field of the continued type, as long as the last sub-field         */
+/* of the most recent list, clamped to avail.                                             */
+/* Continued type: 3 after a sub-field of type 2 or 3, 13 after 12 or 13, none after      */
+/* anything else.  A CI-less field with no continued type counts in fields_ignored        */
+/* and delivers nothing.  Types other than 2 and 3 are skipped.                           */
+/*                                                                              */
+/* DLS data group.  A type-2 sub-field drops an open group and opens a new one; a          */
+/* type-3 sub-field appends to an open one and is ignored without.  Bytes are taken         */
+/* one by one.  With 2 bytes the length is known: b0 = T(1) F(1) L(1) C(1) field1(4),        */
+/* b1 = field2(4) field3(4).  C = 0: 2 + (field1 + 1) + 2.  C = 1, field1 = 1 (clear): 4.     */
+/* C = 1, field1 = 2 (DL Plus): 2 + (field3 + 1) + 2.  Any other command: the group is         */
+/* dropped, commands_ignored++.  With all its bytes the group closes; what is left of           */
+/* the sub-field is ignored.  CRC: the FIB's (CCITT 0x1021, start 0xFFFF, complemented)          */
+/* over all but the last two bytes, sent big-endian: groups_ok++ or groups_crc_failed++.          */
+/* A DL Plus group with a good CRC counts in groups_ok and in commands_ignored.                   */
+/*                                                                              */
+/* Segments.  A text group (C = 0) with F = 1 is segment 0 and field2 its charset; else            */
+/* its number is field2 & 7.  L marks the last segment (of several, the most recent).               */
+/* A T that differs from the assembly's empties the assembly and becomes its T.  A                   */
+/* segment overwrites its slot.  When segment 0, a last segment m and every one between               */
+/* are there: the label is their concatenation (at most 128 bytes), labels_completed++;                */
+/* if length, charset or bytes differ from the current label it is replaced and                        */
+/* changes++; toggle = T either way; the assembly is emptied, T kept.  A clear command                  */
+/* empties the assembly and zeroes the label record; changes++ if its length was not 0.                 */
+/* Text bytes behind length are 0.                                                                     */
+/*                                                                              */
+/* The state record (context, open group, assembly, current label) is opaque; a record                  */
+/* this library did not write (a field out of its range) is a fresh start.                              */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_pad_label {
+    int32_t length;             /* 0 .. 128                                                           */
+    int32_t charset;            /* 0 .. 15 (EN 300 401 clause 5.2.2.2: 15 = UTF-8, 6 = UCS-2, 0 = EBU Latin) */
+    int32_t toggle;             /* T of the label completed last                                      */
+    int32_t reserved;
+    uint8_t text[128];
+} dabgpu_pad_label;
+
+typedef struct dabgpu_pad_result {          /* counts of THIS call */
+    int32_t aus, aus_lost, aus_with_xpad, pad_malformed, fields_ignored;
+    int32_t groups_ok, groups_crc_failed, commands_ignored, labels_completed, changes;
+    int32_t reserved[6];
+} dabgpu_pad_result;
+
+typedef struct dabgpu_pad_entry {           /* HOST array, one per followed sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_data;      /* the follow entry's d_data: [max_superframes] rows of >= 110*s bytes          */
+    size_t data_stride;         /* >= 110*s                                                                    */
+    const dabgpu_superframe_status *d_status;     /* the follow entry's d_status                                */
+    const dabgpu_dabplus_follow_result *d_follow; /* its d_result: n_superframes is READ ON THE DEVICE           */
+    int32_t bitrate_kbps;       /* multiple of 8, 8 .. 512                                                      */
+    int32_t max_superframes;    /* rows that exist; n_superframes is clamped to it                               */
+    const void *d_state_in;     /* dabgpu_pad_state_bytes() on a 16-byte boundary; NULL or all zero = fresh start */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    dabgpu_pad_label *d_label;  /* the label after this call (also kept in the state)                            */
+    dabgpu_pad_result *d_result;
+} dabgpu_pad_entry;
+
+size_t dabgpu_pad_state_bytes(void);
+
+/* entries [n_entries] (HOST).  No host synchronisation: n_superframes is read on the device, behind the follow call on
+ * the same stream.  Everything is checked before anything is enqueued, so a refused call leaves every output as it was:
+ * DABGPU_ERR_ARG for a NULL context or table, a negative count, a bit rate outside 8 .. 512 or no multiple of 8, a negative
+ * max_superframes, data_stride < 110*s, a NULL pointer other than d_state_in, a state record off its 16-byte boundary,
+ * d_state_in and d_state_out that are equal or overlap, d_status, d_follow, d_label or d_result off a 4-byte boundary. */
+int dabgpu_pad_labels_dev(dabgpu_ctx *ctx, const dabgpu_pad_entry *entries, int n_entries, void *stream);
+/* the same table with HOST pointers, the same checks, the same walk: no context, no GPU */
+int dabgpu_pad_labels_host(const dabgpu_pad_entry *entries, int n_entries);
+/* The label's text as a NUL-terminated UTF-8 string in out[cap]: -> its length in bytes (>= 0).  Charset 15 (UTF-8: copied
+ * after validation -- no stray or missing continuation byte, overlong form, surrogate, code point above U+10FFFF, or NUL)
+ * and charset 6 (UCS-2 big-endian; an odd length, a surrogate or a NUL is refused).  DABGPU_ERR_PROFILE for any other
+ * charset, DABGPU_ERR_ARG for text that is not valid in its charset, a NULL pointer, cap < 1 or a length outside 0 .. 128,
+ * DABGPU_ERR_CAPACITY when cap is too small for the text and its NUL.  A refused call writes nothing. */
+int dabgpu_pad_label_utf8(const dabgpu_pad_label *label, char *out, int cap);
+
+/* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */
 /* Replaces the `viterbi` package (/root/reference/CMakeLists.txt:53-54).     */
 /* punct     [n_codewords][n_punct] int8 punctured soft bits                   */

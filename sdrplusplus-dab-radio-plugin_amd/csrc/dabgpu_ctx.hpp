@@ -1,7 +1,7 @@
 // dabgpu_ctx.hpp -- the context behind the opaque dabgpu_ctx handle and the helpers the translation units of the C ABI
 // share (dabgpu_api.hip: context, tables, timing, stream state; dabgpu_ofdm_api.hip: front end, synchronisation,
 // acquisition, tracking; dabgpu_measure_api.hip: TII, CIR, reception quality; dabgpu_decode_api.hip: channel decoder;
-// dabgpu_eti_api.hip: ETI(NI) output; dabgpu_mod_api.hip: ETI(NI) to IQ; dabgpu_placement.hip: frame buffers;
+// dabgpu_eti_api.hip: ETI(NI) output; dabgpu_pad_api.hip: dynamic labels; dabgpu_mod_api.hip: ETI(NI) to IQ; dabgpu_placement.hip: frame buffers;
 // dabgpu_pipeline.hip: the host-fed ring; decode_plan.hpp: what the decoder's entry points share).  Internal to libdabgpu.
 #pragma once
 #include "../../include/dabgpu.h"
@@ -68,6 +68,7 @@ enum StageSlot {
     STAGE_MOD_CUM = 11,     // ... and running quarter turns, one pair of bit planes per data symbol
     STAGE_ENSEMBLES = 12,   // dabgpu_decode_ensembles_dev: the entry table of the ragged grouped lane launch
     STAGE_DABPLUS = 13,     // dabgpu_dabplus_follow_dev: the entry table and the plans of the align / follow launches
+    STAGE_PAD = 14,         // dabgpu_pad_labels_dev: the entry table
     STAGE_SLOTS
 };
 

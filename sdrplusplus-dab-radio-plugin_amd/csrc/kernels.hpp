@@ -354,6 +354,26 @@ size_t follow_table_bytes(int n_entries);
 hipError_t launch_dabplus_follow(const FollowEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes,
                                  hipStream_t stream);
 
+// ---- dynamic labels from PAD (pad_kernels.hip) -----------------------------------
+// dabgpu_pad_labels_dev: one entry per followed DAB+ sub-channel, uploaded as a table; one wave per entry walks the access
+// units the follow call left on the device (include/dabgpu_pad_walk.h is the walk) and writes the state record, the label
+// and the counters.  n_superframes is read from the follow call's result record on the device.
+struct alignas(16) PadEntry {
+    uint64_t data;             // [max_superframes][data_stride], rows of 110 s bytes
+    uint64_t data_stride;
+    uint64_t status;           // [max_superframes] SuperframeStatus
+    uint64_t follow;           // one FollowResult
+    uint64_t state_in;         // dabgpu_pad::State or 0
+    uint64_t state_out;
+    uint64_t label;            // dabgpu_pad::Label
+    uint64_t result;           // dabgpu_pad::Counters
+    int32_t s;                 // bitrate / 8
+    int32_t max_superframes;
+    int32_t reserved[2];
+};
+// `entries`: HOST array (copied to d_table on `stream` before the kernel); every pointer checked by the caller
+hipError_t launch_pad_labels(const PadEntry *entries, int n_entries, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

@@ -53,6 +53,7 @@ EXPORTS = [
     "dabgpu_eti_streams_from_frame", "dabgpu_mod_default_cfg", "dabgpu_mod_state_bytes", "dabgpu_modulate_eti_dev",
     "dabgpu_decode_ensembles_dev", "dabgpu_fig_subchannels",
     "dabgpu_dabplus_follow_dev", "dabgpu_dabplus_carry_bytes", "dabgpu_fig_audio_components",
+    "dabgpu_pad_state_bytes", "dabgpu_pad_labels_dev", "dabgpu_pad_labels_host", "dabgpu_pad_label_utf8",
 ]
 
 ABI_VERSION = 6
@@ -129,6 +130,16 @@ DABPLUS_FOLLOW_RESULT_DTYPE = np.dtype([("n_superframes", np.int32), ("phase", n
                                         ("dropped", np.int32), ("raw_hits", np.int32), ("held", np.int32),
                                         ("reserved", np.int32, (2,))])
 assert DABPLUS_FOLLOW_RESULT_DTYPE.itemsize == 32
+#: dabgpu_pad_label: the dynamic label of one followed DAB+ service (text bytes behind `length` are zero)
+PAD_LABEL_DTYPE = np.dtype([("length", np.int32), ("charset", np.int32), ("toggle", np.int32), ("reserved", np.int32),
+                            ("text", np.uint8, (128,))])
+assert PAD_LABEL_DTYPE.itemsize == 144
+#: dabgpu_pad_result: what one entry of pad_labels_dev / pad_labels_host counted in one call
+PAD_RESULT_DTYPE = np.dtype([(n, np.int32) for n in (
+    "aus", "aus_lost", "aus_with_xpad", "pad_malformed", "fields_ignored", "groups_ok", "groups_crc_failed",
+    "commands_ignored", "labels_completed", "changes")] + [("reserved", np.int32, (6,))])
+assert PAD_RESULT_DTYPE.itemsize == 64
+PAD_CHARSET_EBU_LATIN, PAD_CHARSET_UCS2, PAD_CHARSET_UTF8 = 0, 6, 15
 #: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
 AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
                                   ("primary", np.int32), ("reserved", np.int32, (3,))])
@@ -194,6 +205,14 @@ class DabplusEntry(C.Structure):
     """dabgpu_dabplus_entry: one followed DAB+ sub-channel of Context.dabplus_follow_dev (device addresses)."""
     _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
                 ("d_carry_out", C.c_void_p), ("d_data", C.c_void_p), ("d_status", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+class PadEntry(C.Structure):
+    """dabgpu_pad_entry: one followed DAB+ sub-channel of Context.pad_labels_dev (device addresses) or pad_labels_host
+    (host addresses): the follow entry's d_data / d_status / d_result, the state records, the label and the counters."""
+    _fields_ = [("d_data", C.c_void_p), ("data_stride", C.c_size_t), ("d_status", C.c_void_p), ("d_follow", C.c_void_p),
+                ("bitrate_kbps", C.c_int32), ("max_superframes", C.c_int32), ("d_state_in", C.c_void_p),
+                ("d_state_out", C.c_void_p), ("d_label", C.c_void_p), ("d_result", C.c_void_p)]
 
 
 class AudioComponent(C.Structure):
@@ -466,6 +485,11 @@ def load_library(path):
     L.dabgpu_dabplus_follow_dev.argtypes = [vp, C.POINTER(DabplusEntry), i, i, vp]
     L.dabgpu_dabplus_carry_bytes.restype = C.c_size_t
     L.dabgpu_dabplus_carry_bytes.argtypes = [i]
+    L.dabgpu_pad_state_bytes.restype = C.c_size_t
+    L.dabgpu_pad_state_bytes.argtypes = []
+    L.dabgpu_pad_labels_dev.argtypes = [vp, C.POINTER(PadEntry), i, vp]
+    L.dabgpu_pad_labels_host.argtypes = [C.POINTER(PadEntry), i]
+    L.dabgpu_pad_label_utf8.argtypes = [vp, C.c_char_p, i]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -680,6 +704,30 @@ def fig_audio_components(fib, crc_ok, max_out=64):
 def dabplus_carry_bytes(bitrate_kbps):
     """Bytes of one carry record of Context.dabplus_follow_dev (0 for a bit rate it refuses)."""
     return int(lib().dabgpu_dabplus_carry_bytes(bitrate_kbps))
+
+
+def pad_state_bytes():
+    """Bytes of one state record of Context.pad_labels_dev / pad_labels_host (all zero = a fresh start)."""
+    return int(lib().dabgpu_pad_state_bytes())
+
+
+def pad_labels_host(entries):
+    """Context.pad_labels_dev on HOST memory (entries: PadEntry with host addresses): the same checks and the same walk,
+    no context and no GPU."""
+    n = len(entries)
+    arr = (PadEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_pad_labels_host(arr, n), "dabgpu_pad_labels_host")
+
+
+def pad_label_utf8(label):
+    """The text of one PAD_LABEL_DTYPE record as str: charset 15 (UTF-8, validated) and 6 (UCS-2 big-endian); any other
+    charset raises DabGpuError with status -5, text that is not valid in its charset -1."""
+    rec = np.ascontiguousarray(np.asarray(label, PAD_LABEL_DTYPE).reshape(-1)[:1])
+    buf = C.create_string_buffer(400)
+    n = lib().dabgpu_pad_label_utf8(rec.ctypes.data, buf, len(buf))
+    if n < 0:
+        raise DabGpuError(n, "dabgpu_pad_label_utf8")
+    return buf.raw[:n].decode("utf-8")
 
 
 # ------------------------------------------------------------------ context
@@ -1189,6 +1237,14 @@ class Context:
         n = len(entries)
         arr = (DabplusEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_dabplus_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dabplus_follow_dev")
+
+    def pad_labels_dev(self, entries, stream=None):
+        """Dynamic labels of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list of
+        PadEntry (device addresses).  Per entry: d_label (PAD_LABEL_DTYPE), d_result (PAD_RESULT_DTYPE, counts of this call)
+        and d_state_out, to be passed as d_state_in of the next call."""
+        n = len(entries)
+        arr = (PadEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_pad_labels_dev(self._h, arr, n, stream), "dabgpu_pad_labels_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

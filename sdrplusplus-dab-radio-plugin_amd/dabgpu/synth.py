@@ -574,9 +574,11 @@ def firecode16(data):
     return crc
 
 
-def build_superframe(rng, bitrate, dac_rate=1, sbr=0, channel_mode=1, ps=0, cuts=None):
+def build_superframe(rng, bitrate, dac_rate=1, sbr=0, channel_mode=1, ps=0, cuts=None, bodies=None):
     """-> (sf uint8[120*s], au_start list with the end appended, list of AU payloads incl. CRC).
-    cuts: the start addresses of access units 1 .. n-1 (default: drawn at random)."""
+    cuts: the start addresses of access units 1 .. n-1 (default: drawn at random).
+    bodies: per access unit, the bytes its body begins with (au_body: a data stream element carrying PAD) or None; the
+    random body is drawn as without, then its beginning is overwritten, so the draws do not depend on `bodies`."""
     s = bitrate // 8
     size = 110 * s
     num_aus = {(0, 1): 2, (1, 1): 3, (0, 0): 4, (1, 0): 6}[(dac_rate, sbr)]
@@ -596,6 +598,10 @@ def build_superframe(rng, bitrate, dac_rate=1, sbr=0, channel_mode=1, ps=0, cuts
     aus = []
     for a in range(num_aus):
         body = rng.integers(0, 256, starts[a + 1] - starts[a] - 2, dtype=np.uint8)
+        if bodies is not None and bodies[a] is not None:
+            head = np.frombuffer(bytes(bodies[a]), np.uint8)
+            assert head.size <= body.size, "access unit %d has %d bytes, its PAD element %d" % (a, body.size, head.size)
+            body[:head.size] = head
         c = crc16(body)
         au = np.concatenate([body, np.array([c >> 8, c & 0xFF], np.uint8)])
         sf[starts[a]:starts[a + 1]] = au
@@ -605,6 +611,139 @@ def build_superframe(rng, bitrate, dac_rate=1, sbr=0, channel_mode=1, ps=0, cuts
     for j in range(s):
         sf[size + j::s] = rs_parity(sf[j:size:s])
     return sf, starts, aus
+
+
+# ----------------------------------------------------------------------------- PAD: dynamic label (EN 300 401 7.4, TS 102 563 5.4)
+# The transmit side of the dynamic label, from the clauses: label -> segments (data groups with toggle, first / last flags
+# and CRC) -> X-PAD sub-fields, short or variable -> PAD (X-PAD bytes in reverse order, then F-PAD) -> data stream element
+# -> the beginning of an access unit's body (build_superframe's `bodies`).
+XPAD_LENGTHS = (4, 6, 8, 12, 16, 24, 32, 48)
+XPAD_DLS_START, XPAD_DLS_CONT = 2, 3
+CHARSET_EBU_LATIN, CHARSET_UCS2, CHARSET_UTF8 = 0, 6, 15
+
+
+def dls_group(b0, b1, body=b""):
+    """one DLS data group: the two prefix bytes, the body, the CRC (the FIB's, big-endian)"""
+    g = bytes([b0 & 0xFF, b1 & 0xFF]) + bytes(body)
+    c = crc16(g)
+    return g + bytes([c >> 8, c & 0xFF])
+
+
+def dls_segment(data, number, toggle, first, last, charset=CHARSET_UTF8):
+    """segment `number` of a label: 1 .. 16 bytes; the first one carries the charset where the others carry their number"""
+    data = bytes(data)
+    assert 1 <= len(data) <= 16 and 0 <= number <= 7
+    b0 = (toggle << 7) | (int(first) << 6) | (int(last) << 5) | (len(data) - 1)
+    return dls_group(b0, ((charset if first else number) & 0x0F) << 4, data)
+
+
+def dls_segments(text, toggle=0, charset=CHARSET_UTF8, seg_bytes=16):
+    """the label's bytes (at most 128; at most 8 segments) cut into segments of seg_bytes -> list of data groups"""
+    text = bytes(text)
+    assert 1 <= len(text) <= 128 and 1 <= seg_bytes <= 16
+    parts = [text[i:i + seg_bytes] for i in range(0, len(text), seg_bytes)]
+    assert len(parts) <= 8
+    return [dls_segment(part, m, toggle, m == 0, m == len(parts) - 1, charset) for m, part in enumerate(parts)]
+
+
+def dls_command(command, toggle=0, body=b""):
+    """a command group: 1 = clear (no body), 2 = DL Plus (1 .. 16 bytes of body), anything else for a receiver to ignore"""
+    b0 = (toggle << 7) | 0x10 | (command & 0x0F)
+    if command == 2:
+        assert 1 <= len(body) <= 16
+        return dls_group(b0, (len(body) - 1) & 0x0F, body)
+    return dls_group(b0, 0, body)
+
+
+def xpad_variable(subfields, end_marker=True):
+    """variable-size X-PAD with content indicators: subfields = [(type, data)] or [(31, extended type, data)], at most four,
+    every data a length of XPAD_LENGTHS -> the logical bytes: the list (closed by the end marker when shorter than four and
+    asked for), then the data"""
+    assert 1 <= len(subfields) <= 4
+    out, tail = [], b""
+    for sf in subfields:
+        typ, data = sf[0], bytes(sf[-1])
+        out.append((XPAD_LENGTHS.index(len(data)) << 5) | (typ & 0x1F))
+        if typ == 31:
+            out.append(sf[1] & 0xFF)
+        tail += data
+    if len(subfields) < 4 and end_marker:
+        out.append(0)
+    return bytes(out) + tail
+
+
+def xpad_short(data, app_type=None):
+    """short X-PAD: with a content indicator (app_type) 3 data bytes, without 4"""
+    data = bytes(data)
+    if app_type is None:
+        assert len(data) == 4
+        return data
+    assert len(data) == 3
+    return bytes([app_type & 0x1F]) + data
+
+
+def pad_field(xpad, ind, ci, n=None, fpad_type=0):
+    """PAD of n bytes (default: no more than needed): the X-PAD logical bytes in reverse order in front of the two F-PAD
+    bytes; what n leaves over lies in front of them (logical bytes behind the field's own)"""
+    xpad = bytes(xpad)
+    n = len(xpad) + 2 if n is None else n
+    assert n >= len(xpad) + 2
+    fpad = bytes([(fpad_type << 6) | (ind << 4), (int(ci) << 1)])
+    return bytes(n - 2 - len(xpad)) + xpad[::-1] + fpad
+
+
+def dse(pad, tag=0, escape=None):
+    """the data stream element that carries PAD: id 4, instance tag, no alignment flag, count (with the escape byte from
+    255 bytes on), the bytes"""
+    pad = bytes(pad)
+    assert len(pad) <= 510
+    if escape is None:
+        escape = len(pad) >= 255
+    assert escape == (len(pad) >= 255), "the escape byte is there exactly from 255 bytes on"
+    head = bytes([(4 << 5) | ((tag & 0x0F) << 1)])
+    return head + (bytes([255, len(pad) - 255]) if escape else bytes([len(pad)])) + pad
+
+
+def dls_subfields(group, lengths, first_type=XPAD_DLS_START):
+    """a data group cut into sub-fields of the given lengths (the last one filled up with zeros): [(type, data)] -- the
+    first of type 2, the others of type 3; as many as the group needs"""
+    group, out, at, k = bytes(group), [], 0, 0
+    while at < len(group):
+        n = lengths[min(k, len(lengths) - 1)]
+        part = group[at:at + n]
+        out.append((first_type if k == 0 else XPAD_DLS_CONT, part + bytes(n - len(part))))
+        at += n
+        k += 1
+    return out
+
+
+def dls_pads(groups, length_index=None, ci_less=False, before=(), after=(), end_marker=True, n=None):
+    """One PAD field per access unit for a sequence of data groups, one DLS sub-field per access unit.
+    length_index None: short X-PAD (the first access unit of a group has the content indicator and 3 bytes, the others are
+    CI-less with 4).  Else variable X-PAD with sub-fields of XPAD_LENGTHS[length_index]; ci_less: the continuation
+    sub-fields go without a list; before / after: other applications' sub-fields [(type, data)] around the DLS one in
+    every list (a CI-less field continues the LAST sub-field of the list, so `after` and ci_less exclude each other)."""
+    assert not (ci_less and after)
+    pads = []
+    for g in groups:
+        if length_index is None:
+            g = bytes(g)
+            pads.append(pad_field(xpad_short(g[:3] + bytes(3 - len(g[:3])), XPAD_DLS_START), 1, 1, n))
+            for at in range(3, len(g), 4):
+                part = g[at:at + 4]
+                pads.append(pad_field(xpad_short(part + bytes(4 - len(part))), 1, 0, n))
+            continue
+        for k, (typ, data) in enumerate(dls_subfields(g, [XPAD_LENGTHS[length_index]])):
+            if k and ci_less:
+                pads.append(pad_field(data, 2, 0, n))
+            else:
+                pads.append(pad_field(xpad_variable(list(before) + [(typ, data)] + list(after), end_marker), 2, 1, n))
+    return pads
+
+
+def au_body(pad, tag=0):
+    """what an access unit's body begins with to carry this PAD (build_superframe's `bodies`); None for no PAD"""
+    return None if pad is None else dse(pad, tag)
 
 
 # ----------------------------------------------------------------------------- FIGs (EN 300 401 clauses 5.2, 6, 8)
@@ -779,11 +918,13 @@ class ServiceEnsemble:
     FIC made of FIG 0/0, 0/1, 0/2, 1/0, 1/1.  services = [(label, sid, subchannel_id, option, level, bitrate,
     start_cu), ...].  n_frames must be a multiple of 5 so that whole super-frames (5 logical frames) tile."""
 
-    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True):
+    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True, bodies=None):
         """dab_services: DAB (MPEG layer II) services on UEP sub-channels, [(label, sid, subchannel_id, uep_index,
         start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body).
         extras=False leaves the rotation to the labels alone (FIG 0/0, 0/1, 0/2, 0/10 and one label per CIF): what
-        four services leave room for in three FIBs."""
+        four services leave room for in three FIBs.
+        bodies: per DAB+ service (or None), per super-frame, build_superframe's `bodies`: what the access units begin
+        with (PAD); the random draws do not depend on it."""
         assert n_frames % 5 == 0
         rng = np.random.default_rng(seed)
         self.n_frames, self.eid, self.label, self.services = n_frames, eid, label, services
@@ -791,11 +932,12 @@ class ServiceEnsemble:
         cifs = rng.integers(0, 2, size=(R, NB_CIF_BITS), dtype=np.uint8)
         self.masks, self.sizes, self.msc_bytes, self.superframes, self.aus = [], [], [], [], []
         self.subchannels = []
-        for (lab, sid, scid, option, level, bitrate, start_cu) in services:
+        for n_sv, (lab, sid, scid, option, level, bitrate, start_cu) in enumerate(services):
             mask, size_cu = eep_mask(option, level, bitrate)
             sfs, aus = [], []
-            for _ in range(R // 5):
-                sf, starts, au = build_superframe(rng, bitrate, dac_rate=1, sbr=1, channel_mode=1, ps=0)
+            for q in range(R // 5):
+                sf, starts, au = build_superframe(rng, bitrate, dac_rate=1, sbr=1, channel_mode=1, ps=0,
+                                                  bodies=bodies[n_sv][q] if bodies is not None and bodies[n_sv] is not None else None)
                 sfs.append(sf); aus.append(au)
             data = np.concatenate(sfs).reshape(R, bitrate * 3)
             coded = np.stack([msc_encode_lf(data[r], mask) for r in range(R)])

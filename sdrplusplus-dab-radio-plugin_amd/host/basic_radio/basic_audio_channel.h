@@ -4,6 +4,7 @@
 // in basic_dab_plus_channel.h.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <string_view>
 #include "basic_radio/basic_slideshow.h"
 #include "dab/database/dab_database_entities.h"
@@ -36,14 +37,17 @@ public:
     virtual ~Basic_Audio_Channel() = default;
     // which concrete channel this is (the GUI dispatches on it, /root/reference/src/render_radio_block.cpp:480-487)
     virtual AudioServiceType GetType() const = 0;
-    // programme-associated text needs the audio decoder's PAD extraction: never set here
-    std::string_view GetDynamicLabel() const { return {}; }
+    // programme-associated text (/root/reference/src/render_radio_block.cpp:425-427, 470-472): the label's bytes as sent,
+    // in the charset the service uses.  A DAB+ channel reads it from the PAD in front of its access units, without an audio
+    // decoder (basic_dab_plus_channel.cpp); a layer-II channel has none.  Read under BasicRadio::GetMutex() like the rest.
+    std::string_view GetDynamicLabel() const { return m_dynamic_label; }
     Basic_Audio_Controls &GetControls() { return m_controls; }
     // slideshows come out of the audio decoder's PAD as well: always empty (render_radio_block.cpp:591)
     Basic_Slideshow_Manager &GetSlideshowManager() { return m_slideshows; }
     Observable<BasicAudioParams, tcb::span<const uint8_t>> &OnAudioData() { return m_obs_audio; }
 
 protected:
+    std::string m_dynamic_label;
     Basic_Audio_Controls m_controls;
     Basic_Slideshow_Manager m_slideshows;
     Observable<BasicAudioParams, tcb::span<const uint8_t>> m_obs_audio;

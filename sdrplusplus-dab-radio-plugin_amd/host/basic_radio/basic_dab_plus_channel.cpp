@@ -20,6 +20,7 @@ void Basic_DAB_Plus_Channel::Process(tcb::span<const uint8_t> lf) {
         // not aligned (or a lost super-frame): slide by one logical frame and try again with the next one
         m_firecode_error = true;
         m_synced = false;
+        dabgpu_pad::walk_au(m_pad, m_pad_counts, nullptr, -1);        // whatever PAD was being collected has a hole now
         std::memmove(m_window.data(), m_window.data() + m_lf_bytes, 4 * m_lf_bytes);
         m_frames_in_window = 4;
         return;
@@ -39,8 +40,15 @@ void Basic_DAB_Plus_Channel::Process(tcb::span<const uint8_t> lf) {
     m_header.mpeg_surround = mpeg_surround_from_config(h & 7);
     m_header.nb_access_units = uint8_t(st.num_aus);
     bool au_error = false;
-    for (int a = 0; a < st.num_aus; a++) {
+    const bool read_pad = m_controls.GetIsDecodeData();
+    for (int a = 0; a < st.num_aus && a < 7; a++) {
         m_total_aus++;
+        if (read_pad) {
+            int at = 0;
+            const int len = dabgpu_pad::au_span(st.firecode_ok, st.num_aus, st.au_crc_mask, st.au_start[a], st.au_start[a + 1], a,
+                                                m_bitrate / 8, &at);
+            dabgpu_pad::walk_au(m_pad, m_pad_counts, m_data.data() + at, len);
+        }
         if (!((st.au_crc_mask >> a) & 1)) {
             au_error = true;
             m_total_au_errors++;
@@ -54,4 +62,5 @@ void Basic_DAB_Plus_Channel::Process(tcb::span<const uint8_t> lf) {
             m_obs_au.Notify(a, st.num_aus, tcb::span<const uint8_t>(m_data.data() + b, size_t(e - b)));
     }
     m_au_error = au_error;
+    if (read_pad) m_dynamic_label.assign(reinterpret_cast<const char *>(m_pad.label.text), size_t(m_pad.label.length));
 }

@@ -4,7 +4,8 @@
 // hands out the access units.  Mirrors what the GUI reads from the reference's Basic_DAB_Plus_Channel:
 // GetSuperFrameHeader(), IsFirecodeError(), IsRSError(), IsAUError(), IsCodecError(), GetDynamicLabel()
 // (/root/reference/src/render_radio_block.cpp:410-437).  AAC decoding itself is not part of the path, so
-// IsCodecError() is always false and GetDynamicLabel() empty; the access units leave through OnAccessUnit().
+// IsCodecError() is always false; the access units leave through OnAccessUnit().  GetDynamicLabel() is read from the
+// PAD in front of every access unit by the walk the GPU batch call runs (include/dabgpu_pad_walk.h), here on the host.
 #pragma once
 #include <cstdint>
 #include <string_view>
@@ -12,6 +13,7 @@
 #include "basic_radio/basic_audio_channel.h"
 #include "dab/audio/aac_frame_processor.h"
 #include "dabgpu.h"
+#include "dabgpu_pad_walk.h"
 #include "utility/gpu_buffers.h"
 
 struct SuperFrameHeader {                  // TS 102 563 clause 5.2; fields as the GUI prints them
@@ -39,6 +41,9 @@ public:
     int GetTotalSuperFrames() const { return m_total_superframes; }
     int GetTotalAccessUnits() const { return m_total_aus; }
     int GetTotalAccessUnitErrors() const { return m_total_au_errors; }
+    // charset of GetDynamicLabel() (EN 300 401 clause 5.2.2.2: 15 = UTF-8, 6 = UCS-2, 0 = EBU Latin) and what the walk counted
+    int GetDynamicLabelCharset() const { return m_pad.label.charset; }
+    const dabgpu_pad::Counters &GetPadCounters() const { return m_pad_counts; }
     const Subchannel &GetSubchannel() const { return m_subchannel; }
 
 private:
@@ -56,4 +61,6 @@ private:
     bool m_firecode_error = true, m_rs_error = false, m_au_error = false;
     int m_total_superframes = 0, m_total_aus = 0, m_total_au_errors = 0;
     Observable<int, int, tcb::span<const uint8_t>> m_obs_au;
+    dabgpu_pad::State m_pad{};             // all zero: a fresh start
+    dabgpu_pad::Counters m_pad_counts{};
 };

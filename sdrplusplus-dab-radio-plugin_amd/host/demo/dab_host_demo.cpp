@@ -168,10 +168,14 @@ int main(int argc, char **argv) {
                 auto *ch = dynamic_cast<Basic_DAB_Plus_Channel *>(radio->Get_Audio_Channel(sc.id));
                 if (!ch) continue;
                 const auto &h = ch->GetSuperFrameHeader();
-                std::fprintf(f, "channel subchannel=%d superframes=%d aus=%d au_errors=%d rate=%u sbr=%d stereo=%d firecode_error=%d rs_error=%d\n",
+                std::fprintf(f, "channel subchannel=%d superframes=%d aus=%d au_errors=%d rate=%u sbr=%d stereo=%d firecode_error=%d rs_error=%d",
                              sc.id, ch->GetTotalSuperFrames(), ch->GetTotalAccessUnits(), ch->GetTotalAccessUnitErrors(),
                              h.sampling_rate, int(h.is_spectral_band_replication), int(h.is_stereo), int(ch->IsFirecodeError()),
                              int(ch->IsRSError()));
+                // the dynamic label as the GUI reads it (render_radio_block.cpp:425-427), its bytes in hex
+                std::fprintf(f, " label_charset=%d label=", ch->GetDynamicLabelCharset());
+                for (const char v : ch->GetDynamicLabel()) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
+                std::fprintf(f, "\n");
             }
             std::fclose(f);
         }
