@@ -189,7 +189,13 @@ def _branch_signs():
 
 
 _SIGNS = _branch_signs()
-_SHIFT = np.arange(64, dtype=np.uint64)
+# the same numbers with less work: a branch's four signs are one of 16 patterns, so a step's 128 branch metrics are 16
+# sums, each used by eight branches (_SIGNS16[:, _PATTERN[b]] is column b of _SIGNS)
+_SIGNS16 = np.array([[2 * ((v >> (3 - k)) & 1) - 1 for v in range(16)] for k in range(4)], np.int64)
+_PATTERN = np.array([int("".join("1" if s > 0 else "0" for s in _SIGNS[:, b]), 2) for b in range(128)])
+assert (_SIGNS16[:, _PATTERN] == _SIGNS).all()
+_PATTERN0, _PATTERN1 = _PATTERN[0::2].copy(), _PATTERN[1::2].copy()
+assert np.dtype(np.uint64).byteorder in "=<" and np.little_endian       # (viterbi packs 64 decisions into a word)
 
 DOCUMENTED = "older-bit-1 only when strictly larger"    # the rule the kernels and the oracle state
 OPPOSITE = "older-bit-1 also on a tie"
@@ -222,6 +228,13 @@ class Decoded:
             self._cache[rule] = (bits, tied, s)
         return self._cache[rule]
 
+    def lanes(self, idx):
+        """The codewords idx of the batch as a Decoded of their own (what was traced back already is kept)."""
+        sub = Decoded(self.nsteps, self.best[idx], self._dec[:, idx], self._tie[:, idx],
+                      None if self.excursion is None else self.excursion[idx], None if self.spread is None else self.spread[idx], self.period)
+        sub._cache = {rule: tuple(x[idx] for x in traced) for rule, traced in self._cache.items()}
+        return sub
+
     def bits(self, rule=DOCUMENTED):
         """One maximum-likelihood information sequence [B][nsteps - 6] under a stated tie rule."""
         bits, _, start = self._trace(rule)
@@ -248,7 +261,7 @@ def viterbi(mother, stats=True, period=12):
     mother = np.atleast_2d(np.asarray(mother)).astype(np.int64)
     B = mother.shape[0]
     nsteps = mother.shape[1] // 4
-    soft = mother.reshape(B, nsteps, 4)
+    soft = np.ascontiguousarray(mother.reshape(B, nsteps, 4).transpose(1, 0, 2))    # [nsteps][B][4]
     m = np.full((B, 64), NEG_INF, np.int64)
     m[:, 0] = 0
     dec = np.zeros((nsteps, B), np.uint64)
@@ -257,14 +270,14 @@ def viterbi(mother, stats=True, period=12):
     spread = np.zeros(B, np.int64)
     ref0 = np.zeros(B, np.int64)
     for t in range(nsteps):
-        bm = soft[:, t, :] @ _SIGNS                                                 # [B][128]
-        c0 = m[:, _PRED0] + bm[:, 0::2]
-        c1 = m[:, _PRED1] + bm[:, 1::2]
+        bm = soft[t] @ _SIGNS16                                                     # [B][16]
+        c0 = m[:, _PRED0] + bm[:, _PATTERN0]                                        # [B][64]: = soft[t] @ _SIGNS[:, 0::2]
+        c1 = m[:, _PRED1] + bm[:, _PATTERN1]
         d = c1 > c0
         e = (c1 == c0) & (c0 > NEG_INF // 2)
         m = np.where(d, c1, c0)
-        dec[t] = (d.astype(np.uint64) << _SHIFT).sum(axis=1, dtype=np.uint64)
-        tie[t] = (e.astype(np.uint64) << _SHIFT).sum(axis=1, dtype=np.uint64)
+        dec[t] = np.packbits(d.ravel(), bitorder="little").view(np.uint64)           # bit n: the decision of state n
+        tie[t] = np.packbits(e.ravel(), bitorder="little").view(np.uint64)
         if stats:
             u = t + 1                                                               # m is now m_u
             hi = m.max(axis=1)
@@ -288,6 +301,22 @@ def metric_of(out_bytes, mother, dispersed=False):
         bits = bits ^ prbs(bits.shape[1])[None, :]
     code = conv_encode(bits).astype(np.int64) * 2 - 1
     return (code * np.atleast_2d(np.asarray(mother)).astype(np.int64)).sum(axis=1)
+
+
+def assert_decoder(got_bytes, mother, d, dispersed, what):
+    """The judgement the decoder tests share, on every codeword and in this order so that a failure names its kind:
+    1. metric_of(bytes) == best, the output is A maximum-likelihood sequence; 2. the bytes are those of the documented
+    tie rule (a failure with 1 passing is a tie-rule difference).  d: Decoded of `mother`."""
+    got_bytes = np.asarray(got_bytes).reshape(d.best.size, -1)
+    metric = metric_of(got_bytes, mother, dispersed)
+    bad = np.flatnonzero(metric != d.best)
+    assert bad.size == 0, "%s: NOT maximum-likelihood on %d of %d codewords, first %d: metric %d, best %d (excursion %d)" % (
+        what, bad.size, d.best.size, bad[0], metric[bad[0]], d.best[bad[0]], -1 if d.excursion is None else d.excursion[bad[0]])
+    bits = d.bits(DOCUMENTED)
+    want = np.packbits(bits ^ prbs(bits.shape[1])[None, :] if dispersed else bits, axis=1)[:, :got_bytes.shape[1]]
+    bad = np.flatnonzero((got_bytes != want).any(axis=1))
+    assert bad.size == 0, "%s: maximum-likelihood but not the documented tie rule's bytes on %d codewords, first %d (unique: %s)" % (
+        what, bad.size, bad[0], bool(d.unique[bad[0]]))
 
 
 # ------------------------------------------------------------------------------------------------ FIC and MSC

@@ -584,18 +584,7 @@ def test_signal_families_have_unique_optima():
 
 
 # ================================================================================================ CPU: the oracle
-def _assert_decoder(got_bytes, mother, d, dispersed, what):
-    """Assertions 1 and 2 of the module's docstring on every codeword."""
-    got_bytes = np.asarray(got_bytes).reshape(d.best.size, -1)
-    metric = R.metric_of(got_bytes, mother, dispersed)
-    bad = np.flatnonzero(metric != d.best)
-    assert bad.size == 0, "%s: NOT maximum-likelihood on %d of %d codewords, first %d: metric %d, best %d (excursion %d)" % (
-        what, bad.size, d.best.size, bad[0], metric[bad[0]], d.best[bad[0]], d.excursion[bad[0]])
-    bits = d.bits(R.DOCUMENTED)
-    want = np.packbits(bits ^ R.prbs(bits.shape[1])[None, :] if dispersed else bits, axis=1)[:, :got_bytes.shape[1]]
-    bad = np.flatnonzero((got_bytes != want).any(axis=1))
-    assert bad.size == 0, "%s: maximum-likelihood but not the documented tie rule's bytes on %d codewords, first %d (unique: %s)" % (
-        what, bad.size, bad[0], bool(d.unique[bad[0]]))
+_assert_decoder = R.assert_decoder                       # (shared with test_decoder_profiles.py)
 
 
 def _oracle_plain(mother):
@@ -658,11 +647,11 @@ def test_gpu_headroom_at_the_lane_kernels_batch_shapes(ctx, n):
     pick = np.arange(n) % 257                            # 257 is prime to 64: the lanes of a group all differ
     got = ctx.viterbi(soft[pick], mask)
     if n <= 257:
-        sub = R.Decoded(d.nsteps, d.best[pick], d._dec[:, pick], d._tie[:, pick], d.excursion[pick], d.spread[pick], d.period)
+        sub = d.lanes(pick)
         _assert_decoder(got, mother[pick], sub, False, "headroom, %d codewords" % n)
     else:
         assert (got == got[pick]).all(), "equal inputs, different lanes, different bytes"
-        sub = R.Decoded(d.nsteps, d.best[:257], d._dec[:, :257], d._tie[:, :257], d.excursion[:257], d.spread[:257], d.period)
+        sub = d.lanes(np.arange(257))
         _assert_decoder(got[:257], mother[:257], sub, False, "headroom, first 257 of %d codewords" % n)
         _assert_decoder(got[n - 257:][np.argsort(pick[n - 257:])], mother[:257], sub, False, "headroom, last 257 of %d codewords" % n)
 

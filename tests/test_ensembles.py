@@ -111,6 +111,8 @@ def assert_same(a, b, what):
 
 
 def assert_oracle(batch, got):
+    """Every soft bit of these batches keeps the transmitted sign, so equal bytes cannot show a lost or misplaced soft bit;
+    test_decoder_profiles.py runs the by-table launch on inputs that can."""
     ofib, ook = E.oracle_fic(batch.soft)
     assert (got.fib == ofib).all() and (got.ok == ook).all()
     for s, m in enumerate(batch.plexes):

@@ -59,6 +59,8 @@ def test_oracle_decodes_what_the_transmitter_sent(index):
 @pytest.mark.gpu
 @pytest.mark.parametrize("index", CASES)
 def test_gpu_uep_subchannel_bit_exact(ctx, index):
+    """Signal at 8 dB: the code corrects a soft bit a wrong table entry loses, so "bit exact" here cannot show one;
+    test_decoder_profiles.py holds every UEP row on every decoder path to inputs that can."""
     start = 3 if index != 63 else 448
     n_frames = 5
     e = synth.Ensemble(seed=500 + index, n_frames=n_frames, uep_index=index, start_cu=start)
