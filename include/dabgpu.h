@@ -1428,8 +1428,8 @@ int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entri
 /* dabgpu_dabplus_follow_dev on the same stream, on what that call left on the   */
 /* device.  One wave per entry, one launch.          */
 /*                                                                              */
-/* Not read: MOT / slideshow and X-PAD application types other than 1, 2, 3,     */
-/* 12, 13 (1, 12, 13 are stepped over); DL Plus tags (the command's CRC is        */
+/* Not read here: X-PAD application types 1, 12, 13 are stepped over (the         */
+/* slideshow call below reads them); DL Plus tags (the command's CRC is           */
 /* checked, its body dropped); PAD of layer-II frames.  No audio is decoded.      */
 /* Charset 0 (EBU Latin) labels come out as bytes; no table translates them.      */
 /*                                                                              */
@@ -1536,6 +1536,167 @@ int dabgpu_pad_labels_host(const dabgpu_pad_entry *entries, int n_entries);
  * charset, DABGPU_ERR_ARG for text that is not valid in its charset, a NULL pointer, cap < 1 or a length outside 0 .. 128,
  * DABGPU_ERR_CAPACITY when cap is too small for the text and its NUL.  A refused call writes nothing. */
 int dabgpu_pad_label_utf8(const dabgpu_pad_label *label, char *out, int cap);
+
+/* ------------------------------------------------------------------------ */
+/* Slideshow: the MOT objects every followed DAB+ service sends in X-PAD -- what  */
+/* the reference shows in the "Slideshow" tab of every audio channel              */
+/*   (its src/render_radio_block.cpp:309-382, 589-593).                           */
+/* Runs behind dabgpu_dabplus_follow_dev on the same stream, beside                */
+/* dabgpu_pad_labels_dev, on the same inputs.  One     */
+/* wave per entry, one launch.  The X-PAD field walk (locating PAD, F-PAD, short   */
+/* and variable X-PAD, the CI list, continuation, the continued type) is the        */
+/* label call's, the same code (include/dabgpu_pad_walk.h, walk_fields); the sink   */
+/* is include/dabgpu_mot_walk.h.  Counters aus .. fields_ignored mean what they     */
+/* mean there.                                                                      */
+/*                                                                                */
+/* Not read: FIG 0/13 user application signalling (X-PAD types 12 / 13 are taken    */
+/* as MOT as given); MOT directory mode (data group types 6, 7); scrambled bodies   */
+/* (type 5) and CA parameters; packet-mode MOT; PAD of layer-II frames.  The         */
+/* image is not decoded; the device does not look at the content type.               */
+/*                                                                                */
+/* THE CONTRACT of one entry in one call (EN 300 401 clauses 5.3.3, 7.4.5.1;          */
+/* EN 301 234 clauses 5.1, 5.2, 6.1; every ambiguity decided).                        */
+/*                                                                                */
+/* Order and loss: exactly the label call's.  A lost AU or a malformed PAD drops      */
+/* the continued type, an armed length and any open X-PAD data group.  It does        */
+/* not drop the object assembly.                                                      */
+/*                                                                                */
+/* Type 1 (data group length indicator).  A sub-field of fewer than 4 bytes (the       */
+/* 3 bytes of short X-PAD with a CI): lengths_ignored++.  Else bytes 0, 1 = rfa(2)     */
+/* length(14), bytes 2, 3 = the FIB's CRC over bytes 0, 1, big-endian: good arms        */
+/* next_length = length, lengths_ok++; bad: lengths_ignored++, nothing changes.         */
+/*                                                                                */
+/* Type 12 drops an open group and consumes the armed length: none armed:               */
+/* groups_no_length++, no group; a length below 4: groups_malformed++, no group;         */
+/* else a group of that many bytes opens.  Type 13 appends to an open group and is       */
+/* ignored without one.  Of a sub-field, min(its length, what the group lacks) bytes     */
+/* are taken; the rest is padding.  With all its bytes the group closes.                 */
+/*                                                                                */
+/* Closing a group (b0 = its first byte; end = length - 2), first match wins:             */
+/*   CRC flag (b0 & 0x40) clear, or CRC (the FIB's, over all but the last two bytes,      */
+/*     sent big-endian) bad                              -> groups_crc_failed++           */
+/*   data group type (b0 & 0x0F) not 3 (MOT header) or 4 (body) -> groups_ignored_type++  */
+/*   o = 2, + 2 with the extension flag (b0 & 0x80)                                       */
+/*   segment flag (b0 & 0x20) clear, or o + 2 > end      -> groups_malformed++            */
+/*   last = bit 7, number n = 15 bits of the two bytes at o; o += 2                        */
+/*   user access flag (b0 & 0x10) clear                  -> groups_no_transport_id++      */
+/*   o + 1 > end                                         -> groups_malformed++            */
+/*   ua = byte at o; o += 1; transport id flag (ua & 0x10) clear -> groups_no_transport_id++ */
+/*   li = ua & 0x0F; li < 2 or o + li + 2 > end          -> groups_malformed++            */
+/*   transport id = 16 bits at o; o += li (the end-user address is stepped over)            */
+/*   z = 13 bits of the two bytes at o (MOT segmentation header); o += 2                    */
+/*   z != end - o                                        -> groups_malformed++            */
+/*   else groups_ok++ and the segment (part = header | body, id, n, last, z bytes) is used. */
+/* Continuity and repetition indices and the repetition count are not looked at.            */
+/*                                                                                */
+/* Assembly: one object per entry.  For a used segment, first match wins:                    */
+/*   id equals the id of the object completed last      -> groups_repeated++, dropped       */
+/*   no assembly, or id differs from the assembly's: the assembly is emptied, id is its id   */
+/*   the assembly is marked too large                    -> dropped                          */
+/*   n >= 32 (header) / 256 (body)                       -> objects_too_large++, marked      */
+/*   not last: z == 0, or the part's segment size S is known and z != S, or the part's last  */
+/*     segment is known and n >= it                      -> groups_malformed++               */
+/*   last: n > 0 and S not known                         -> segments_early_last++, dropped   */
+/*   last: a last segment of another number or length is known, or S known and z > S, or a   */
+/*     segment above n is present                        -> groups_malformed++               */
+/*   at = n * S (S = z for the first non-last segment; 0 when not known).  at + z beyond      */
+/*     1024 (header) / body_capacity (body)              -> objects_too_large++, marked      */
+/*   S is set (not last) or the last segment and its length noted; then segment n present:    */
+/*     segments_repeated++, not overwritten; else placed at `at`: segments_placed++.          */
+/* Marked too large, the object is ignored until the transport id changes.                     */
+/*                                                                                */
+/* Completion, when segments 0 .. last of header AND body are present.  The header core        */
+/* is the first 7 header bytes: body_size(28) header_size(13) content_type(6) subtype(9).      */
+/* Fewer than 7 header bytes, header_size != assembled header bytes or body_size !=             */
+/* assembled body bytes: objects_mismatched++, the assembly is emptied (no id).  Else            */
+/* objects_completed++, the id becomes that of the object completed last, the assembly is        */
+/* emptied, and the object goes to slot slides_written of THIS call:                             */
+/* d_slides + slot * slide_stride holds a dabgpu_mot_slide, the header bytes, the body bytes;    */
+/* slides_written++.  No slot left (max_slides) or 32 + header + body > slide_stride:            */
+/* slides_dropped++ instead.  Bytes of a slot behind the object, and slots not written, are       */
+/* left as they were.                                                                            */
+/*                                                                                */
+/* The state record is opaque; a record this library did not write for an arena of this           */
+/* size is a fresh start.  The arena belongs to the state: the same memory, untouched by          */
+/* anyone else, goes into the next call.                                                         */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_mot_slide {           /* in front of every slide in its slot */
+    int32_t transport_id;
+    int32_t content_type, content_subtype;  /* of the header core; 2 = image (subtype 1 JFIF, 3 PNG)                 */
+    int32_t header_bytes, body_bytes;       /* the MOT header follows the record, the body follows the header          */
+    int32_t superframe, au;                 /* where in this call the object completed                                 */
+    int32_t reserved;
+} dabgpu_mot_slide;
+
+typedef struct dabgpu_mot_result {          /* counts of THIS call */
+    int32_t aus, aus_lost, aus_with_xpad, pad_malformed, fields_ignored;
+    int32_t lengths_ok, lengths_ignored, groups_no_length;
+    int32_t groups_ok, groups_crc_failed, groups_ignored_type, groups_no_transport_id, groups_malformed, groups_repeated;
+    int32_t segments_placed, segments_repeated, segments_early_last;
+    int32_t objects_completed, objects_mismatched, objects_too_large;
+    int32_t slides_written, slides_dropped;
+    int32_t xpad_bytes;                     /* X-PAD bytes taken into data groups                                      */
+    int32_t object_bytes;                   /* bytes placed into the assembly plus bytes written to slots               */
+    int32_t reserved[8];
+} dabgpu_mot_result;
+
+typedef struct dabgpu_mot_entry {           /* HOST array, one per followed sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_data;      /* as dabgpu_pad_entry                                                          */
+    size_t data_stride;
+    const dabgpu_superframe_status *d_status;
+    const dabgpu_dabplus_follow_result *d_follow;
+    int32_t bitrate_kbps;
+    int32_t max_superframes;
+    const void *d_state_in;     /* dabgpu_mot_state_bytes() on a 16-byte boundary; NULL or all zero = fresh start */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    void *d_arena;              /* 16-byte boundary; updated in place                                            */
+    size_t arena_bytes;         /* >= dabgpu_mot_arena_bytes(0); what is beyond it is body_capacity (at most 256 * 8191) */
+    uint8_t *d_slides;          /* [max_slides] slots, 16-byte boundary; may be NULL with max_slides == 0          */
+    size_t slide_stride;        /* a multiple of 16, >= 32                                                       */
+    int32_t max_slides;         /* max_slides * slide_stride < 2^31                                              */
+    int32_t reserved;
+    dabgpu_mot_result *d_result;
+} dabgpu_mot_entry;
+
+size_t dabgpu_mot_state_bytes(void);
+/* the smallest arena for objects whose body has up to body_capacity bytes (0 for more than 256 * 8191) */
+size_t dabgpu_mot_arena_bytes(size_t body_capacity);
+
+/* entries [n_entries] (HOST).  No host synchronisation: n_superframes is read on the device, behind the follow call on
+ * the same stream.  Everything is checked before anything is enqueued, so a refused call leaves every output as it was:
+ * DABGPU_ERR_ARG for a NULL context or table, a negative count, a bit rate outside 8 .. 512 or no multiple of 8, a negative
+ * max_superframes, data_stride < 110*s, a NULL pointer other than d_state_in (and d_slides with max_slides == 0), a state
+ * record, the arena or d_slides off its 16-byte boundary, d_state_in and d_state_out that are equal or overlap, d_status,
+ * d_follow or d_result off a 4-byte boundary, arena_bytes < dabgpu_mot_arena_bytes(0), a negative max_slides, and with
+ * max_slides > 0 a slide_stride below 32 or no multiple of 16, or max_slides * slide_stride >= 2^31. */
+int dabgpu_mot_slides_dev(dabgpu_ctx *ctx, const dabgpu_mot_entry *entries, int n_entries, void *stream);
+/* the same table with HOST pointers, the same checks, the same walk: no context, no GPU */
+int dabgpu_mot_slides_host(const dabgpu_mot_entry *entries, int n_entries);
+
+/* The MOT header of a slide (EN 301 234 clause 6, TS 101 499 clause 6.2), host side. */
+typedef struct dabgpu_mot_text {
+    int32_t length;             /* -1: the parameter is not there; else 0 .. 255                                 */
+    uint8_t bytes[256];         /* bytes behind length are zero                                                  */
+} dabgpu_mot_text;
+
+typedef struct dabgpu_mot_header {
+    int32_t body_size, header_size, content_type, content_subtype;        /* the header core                    */
+    int32_t n_params, n_unknown;    /* parameters in the header extension; those of them not named below          */
+    int32_t name_charset;           /* ContentName 0x0C: the charset nibble of its first byte; -1 = no name        */
+    int32_t has_trigger, trigger_now;   /* TriggerTime 0x05; now: its validity bit is clear                        */
+    uint32_t trigger_time;          /* its first four bytes, big-endian                                            */
+    int32_t has_expire, expire_now; /* ExpireTime 0x04, likewise                                                   */
+    uint32_t expire_time;
+    int32_t has_category, category_id, slide_id;                            /* CategoryID/SlideID 0x25            */
+    dabgpu_mot_text name, category_title /* 0x26 */, click_through_url /* 0x27 */, alternative_location_url /* 0x28 */;
+} dabgpu_mot_header;
+
+/* header[n]: n must equal the core's header_size.  Parameters by PLI: 0 no data, 1 one byte, 2 four bytes, 3 a length of
+ * 7 bits, or of 15 when the first length byte's top bit is set.  Unknown parameters are stepped over by length.  Of a
+ * parameter that comes twice the later one holds.  DABGPU_ERR_ARG for NULL, n < 7, header_size != n, a parameter that
+ * runs past the header, a ContentName without its charset byte, a time of fewer than 4 bytes, a CategoryID/SlideID of
+ * fewer than 2; DABGPU_ERR_CAPACITY for a text longer than 255 bytes.  A refused call writes nothing. */
+int dabgpu_mot_header_parse(const uint8_t *header, int n, dabgpu_mot_header *out);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

@@ -5,6 +5,9 @@
  * walk_au() below.  Plain C++17, header-only, no allocation, no table in memory; every function is __host__ __device__
  * under hipcc and inline otherwise.
  *
+ * The X-PAD field walk itself (walk_fields: locating the PAD, F-PAD, short and variable X-PAD, the content-indicator list,
+ * continuation without one) is a template over its sink; the label's sink is below, the slideshow's in dabgpu_mot_walk.h.
+ *
  * walk_au takes ONE access unit -- its bytes without the AU CRC, or "lost" -- and a state record, and updates the state
  * (continuation context, open data group, segment assembly, current label) and the counters.  It reads nothing outside
  * [au, au + len), whatever the bytes say.  The decisions the standards leave open, as taken here:
@@ -201,17 +204,32 @@ DABGPU_PAD_FN void subfield(State &st, Counters &c, int type, const uint8_t *xpa
             drop_group(st);
         }
     }
-    st.cont_type = (type == 2 || type == 3) ? 3 : (type == 12 || type == 13) ? 13 : 0;
 }
+
+/* what a CI-less field behind a sub-field of this type continues with */
+DABGPU_PAD_FN uint8_t continued_type(int type) { return (type == 2 || type == 3) ? 3 : (type == 12 || type == 13) ? 13 : 0; }
 
 DABGPU_PAD_FN int subfield_length(int index) { return ((index & 1) ? 6 : 4) << (index >> 1); }
 
-/* au: the access unit without its CRC, len >= 0 bytes; len < 0: the access unit is lost (au is not read) */
-DABGPU_PAD_FN void walk_au(State &st, Counters &c, const uint8_t *au, int len) {
+/* one sub-field to the sink; its type names what a CI-less field behind it continues */
+template <class Sink> DABGPU_PAD_FN void field(Sink &sink, int type, const uint8_t *xpad_end, int at, int len) {
+    sink.subfield(type, xpad_end, at, len);
+    sink.st.cont_type = continued_type(type);
+}
+
+/* The X-PAD field walk of one access unit, for any sink (the label's below, the slideshow's in dabgpu_mot_walk.h): locating
+ * the PAD, F-PAD, short and variable X-PAD, the content-indicator list, continuation without one.  A sink has
+ *   st: a state record with cont_type and last_len;  c: counters with aus, aus_lost, aus_with_xpad, pad_malformed,
+ *   fields_ignored;  drop_context(): no continued type, no open data group;
+ *   subfield(type, xpad_end, at, len): `len` logical bytes from logical byte `at`, logical byte i = xpad_end[-i].
+ * au: the access unit without its CRC, len >= 0 bytes; len < 0: the access unit is lost (au is not read) */
+template <class Sink> DABGPU_PAD_FN void walk_fields(Sink &sink, const uint8_t *au, int len) {
+    auto &st = sink.st;
+    auto &c = sink.c;
     c.aus++;
     if (len < 0) {
         c.aus_lost++;
-        drop_context(st);
+        sink.drop_context();
         return;
     }
     if (len < 2 || (au[0] >> 5) != 4) return;                         /* no data stream element in front: no PAD */
@@ -219,7 +237,7 @@ DABGPU_PAD_FN void walk_au(State &st, Counters &c, const uint8_t *au, int len) {
     if (n == 255) {
         if (len < 3) {
             c.pad_malformed++;
-            drop_context(st);
+            sink.drop_context();
             return;
         }
         n += au[2];
@@ -227,7 +245,7 @@ DABGPU_PAD_FN void walk_au(State &st, Counters &c, const uint8_t *au, int len) {
     }
     if (n < 2 || o + n > len) {
         c.pad_malformed++;
-        drop_context(st);
+        sink.drop_context();
         return;
     }
     const uint8_t *p = au + o;
@@ -236,72 +254,89 @@ DABGPU_PAD_FN void walk_au(State &st, Counters &c, const uint8_t *au, int len) {
     const int ind = (f0 >> 4) & 3, ci = (f1 >> 1) & 1, avail = n - 2;
     if (ind == 0 || ind == 3) return;
     const uint8_t *x = p + n - 3;                                     /* logical byte i = x[-i], i < avail */
+    /* the sub-fields of this field: 8 bits of length and 8 of type each, packed; they go to the sink from ONE place below */
+    uint32_t lens = 0, types = 0;
+    int count = 0, at = 0, last_after = -1;                           /* last_after: last_len behind the field; -1 = as it is */
     if (ind == 1) {
         if (avail < 4) {
             c.pad_malformed++;
-            drop_context(st);
+            sink.drop_context();
             return;
         }
         if (ci) {
-            subfield(st, c, x[0] & 0x1F, x, 1, 3);
-            st.last_len = 4;
+            types = x[0] & 0x1F;
+            lens = 3;
+            at = 1;
+            last_after = 4;
         } else if (st.cont_type) {
-            subfield(st, c, st.cont_type, x, 0, 4);
+            types = st.cont_type;
+            lens = 4;
         } else {
             c.fields_ignored++;
             return;
         }
-        c.aus_with_xpad++;
-        return;
-    }
-    if (!ci) {
+        count = 1;
+    } else if (!ci) {
         if (!st.cont_type) {
             c.fields_ignored++;
             return;
         }
-        subfield(st, c, st.cont_type, x, 0, st.last_len < avail ? st.last_len : avail);
-        c.aus_with_xpad++;
-        return;
-    }
-    /* the list: up to four content indicators, 8 bits of length and 8 of type each, packed */
-    uint32_t lens = 0, types = 0;
-    int count = 0, at = 0, total = 0;
-    bool bad = false;
-    for (int k = 0; k < 4; k++) {
-        if (at >= avail) {
-            bad = true;
-            break;
-        }
-        const uint8_t v = x[-at];
-        at++;
-        const int type = v & 0x1F;
-        if (type == 0) break;
-        if (type == 31) {
+        types = st.cont_type;
+        lens = uint32_t(st.last_len < avail ? st.last_len : avail);
+        count = 1;
+    } else {
+        /* the list: up to four content indicators */
+        int total = 0;
+        bool bad = false;
+        for (int k = 0; k < 4; k++) {
             if (at >= avail) {
                 bad = true;
                 break;
             }
-            at++;                                                     /* the extended type: its sub-field is skipped */
+            const uint8_t v = x[-at];
+            at++;
+            const int type = v & 0x1F;
+            if (type == 0) break;
+            if (type == 31) {
+                if (at >= avail) {
+                    bad = true;
+                    break;
+                }
+                at++;                                                 /* the extended type: its sub-field is skipped */
+            }
+            const int l = subfield_length(v >> 5);
+            lens |= uint32_t(l) << (8 * k);
+            types |= uint32_t(type) << (8 * k);
+            total += l;
+            count++;
         }
-        const int l = subfield_length(v >> 5);
-        lens |= uint32_t(l) << (8 * k);
-        types |= uint32_t(type) << (8 * k);
-        total += l;
-        count++;
+        if (bad || at + total > avail) {
+            c.pad_malformed++;
+            sink.drop_context();
+            return;
+        }
+        st.cont_type = 0;
+        if (count) last_after = int((lens >> (8 * (count - 1))) & 0xFF);
     }
-    if (bad || at + total > avail) {
-        c.pad_malformed++;
-        drop_context(st);
-        return;
-    }
-    st.cont_type = 0;
     for (int k = 0; k < count; k++) {
         const int l = (lens >> (8 * k)) & 0xFF, type = (types >> (8 * k)) & 0xFF;
-        subfield(st, c, type, x, at, l);
-        st.last_len = uint8_t(l);
+        field(sink, type, x, at, l);
         at += l;
     }
+    if (last_after >= 0) st.last_len = uint8_t(last_after);
     if (count) c.aus_with_xpad++;
+}
+
+/* the label's sink, and the walk under the name it has always had */
+struct LabelSink {
+    State &st;
+    Counters &c;
+    DABGPU_PAD_FN void drop_context() { dabgpu_pad::drop_context(st); }
+    DABGPU_PAD_FN void subfield(int type, const uint8_t *xpad_end, int at, int len) { dabgpu_pad::subfield(st, c, type, xpad_end, at, len); }
+};
+DABGPU_PAD_FN void walk_au(State &st, Counters &c, const uint8_t *au, int len) {
+    LabelSink k{st, c};
+    walk_fields(k, au, len);
 }
 
 /* How many access units of a super-frame are visited: one, lost, when firecode_ok == 0 or num_aus <= 0 (how many it

@@ -69,6 +69,7 @@ enum StageSlot {
     STAGE_ENSEMBLES = 12,   // dabgpu_decode_ensembles_dev: the entry table of the ragged grouped lane launch
     STAGE_DABPLUS = 13,     // dabgpu_dabplus_follow_dev: the entry table and the plans of the align / follow launches
     STAGE_PAD = 14,         // dabgpu_pad_labels_dev: the entry table
+    STAGE_MOT = 15,         // dabgpu_mot_slides_dev: the entry table
     STAGE_SLOTS
 };
 

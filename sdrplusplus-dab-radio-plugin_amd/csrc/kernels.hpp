@@ -374,6 +374,29 @@ struct alignas(16) PadEntry {
 // `entries`: HOST array (copied to d_table on `stream` before the kernel); every pointer checked by the caller
 hipError_t launch_pad_labels(const PadEntry *entries, int n_entries, void *d_table, size_t table_bytes, hipStream_t stream);
 
+// ---- slideshow objects from X-PAD (mot_kernels.hip) -------------------------------
+// dabgpu_mot_slides_dev: the same table idea; one wave per entry runs the control walk of include/dabgpu_mot_walk.h in
+// lane 0 and executes its copy orders with all 64 lanes.
+struct alignas(16) MotEntry {
+    uint64_t data;             // [max_superframes][data_stride], rows of 110 s bytes
+    uint64_t data_stride;
+    uint64_t status;           // [max_superframes] SuperframeStatus
+    uint64_t follow;           // one FollowResult
+    uint64_t state_in;         // dabgpu_mot::State or 0
+    uint64_t state_out;
+    uint64_t arena;            // dabgpu_mot::arena_bytes(body_capacity), updated in place
+    uint64_t slides;           // [max_slides][slide_stride]
+    uint64_t result;           // dabgpu_mot::Counters
+    uint32_t slide_stride;
+    int32_t max_slides;
+    int32_t body_capacity;
+    int32_t s;                 // bitrate / 8
+    int32_t max_superframes;
+    int32_t reserved;
+};
+// `entries`: HOST array (copied to d_table on `stream` before the kernel); every pointer checked by the caller
+hipError_t launch_mot_slides(const MotEntry *entries, int n_entries, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

@@ -54,6 +54,7 @@ EXPORTS = [
     "dabgpu_decode_ensembles_dev", "dabgpu_fig_subchannels",
     "dabgpu_dabplus_follow_dev", "dabgpu_dabplus_carry_bytes", "dabgpu_fig_audio_components",
     "dabgpu_pad_state_bytes", "dabgpu_pad_labels_dev", "dabgpu_pad_labels_host", "dabgpu_pad_label_utf8",
+    "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
 ]
 
 ABI_VERSION = 6
@@ -140,6 +141,18 @@ PAD_RESULT_DTYPE = np.dtype([(n, np.int32) for n in (
     "commands_ignored", "labels_completed", "changes")] + [("reserved", np.int32, (6,))])
 assert PAD_RESULT_DTYPE.itemsize == 64
 PAD_CHARSET_EBU_LATIN, PAD_CHARSET_UCS2, PAD_CHARSET_UTF8 = 0, 6, 15
+#: dabgpu_mot_slide: the record in front of every slide in its slot (then header_bytes of MOT header, then body_bytes of body)
+MOT_SLIDE_DTYPE = np.dtype([(n, np.int32) for n in (
+    "transport_id", "content_type", "content_subtype", "header_bytes", "body_bytes", "superframe", "au", "reserved")])
+assert MOT_SLIDE_DTYPE.itemsize == 32
+#: dabgpu_mot_result: what one entry of mot_slides_dev / mot_slides_host counted in one call
+MOT_COUNTERS = ("aus", "aus_lost", "aus_with_xpad", "pad_malformed", "fields_ignored", "lengths_ok", "lengths_ignored", "groups_no_length",
+                "groups_ok", "groups_crc_failed", "groups_ignored_type", "groups_no_transport_id", "groups_malformed", "groups_repeated",
+                "segments_placed", "segments_repeated", "segments_early_last", "objects_completed", "objects_mismatched",
+                "objects_too_large", "slides_written", "slides_dropped", "xpad_bytes", "object_bytes")
+MOT_RESULT_DTYPE = np.dtype([(n, np.int32) for n in MOT_COUNTERS] + [("reserved", np.int32, (8,))])
+assert MOT_RESULT_DTYPE.itemsize == 128
+MOT_CONTENT_IMAGE = 2
 #: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
 AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
                                   ("primary", np.int32), ("reserved", np.int32, (3,))])
@@ -213,6 +226,28 @@ class PadEntry(C.Structure):
     _fields_ = [("d_data", C.c_void_p), ("data_stride", C.c_size_t), ("d_status", C.c_void_p), ("d_follow", C.c_void_p),
                 ("bitrate_kbps", C.c_int32), ("max_superframes", C.c_int32), ("d_state_in", C.c_void_p),
                 ("d_state_out", C.c_void_p), ("d_label", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+class MotEntry(C.Structure):
+    """dabgpu_mot_entry: one followed DAB+ sub-channel of Context.mot_slides_dev (device addresses) or mot_slides_host (host
+    addresses): the follow entry's d_data / d_status / d_result, the state records, the arena, the slide slots, the counters."""
+    _fields_ = [("d_data", C.c_void_p), ("data_stride", C.c_size_t), ("d_status", C.c_void_p), ("d_follow", C.c_void_p),
+                ("bitrate_kbps", C.c_int32), ("max_superframes", C.c_int32), ("d_state_in", C.c_void_p),
+                ("d_state_out", C.c_void_p), ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_slides", C.c_void_p),
+                ("slide_stride", C.c_size_t), ("max_slides", C.c_int32), ("reserved", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class MotText(C.Structure):
+    _fields_ = [("length", C.c_int32), ("bytes", C.c_uint8 * 256)]
+
+
+class MotHeader(C.Structure):
+    """dabgpu_mot_header: what mot_header_parse reads from the MOT header of a slide"""
+    _fields_ = [("body_size", C.c_int32), ("header_size", C.c_int32), ("content_type", C.c_int32), ("content_subtype", C.c_int32),
+                ("n_params", C.c_int32), ("n_unknown", C.c_int32), ("name_charset", C.c_int32), ("has_trigger", C.c_int32),
+                ("trigger_now", C.c_int32), ("trigger_time", C.c_uint32), ("has_expire", C.c_int32), ("expire_now", C.c_int32),
+                ("expire_time", C.c_uint32), ("has_category", C.c_int32), ("category_id", C.c_int32), ("slide_id", C.c_int32),
+                ("name", MotText), ("category_title", MotText), ("click_through_url", MotText), ("alternative_location_url", MotText)]
 
 
 class AudioComponent(C.Structure):
@@ -490,6 +525,13 @@ def load_library(path):
     L.dabgpu_pad_labels_dev.argtypes = [vp, C.POINTER(PadEntry), i, vp]
     L.dabgpu_pad_labels_host.argtypes = [C.POINTER(PadEntry), i]
     L.dabgpu_pad_label_utf8.argtypes = [vp, C.c_char_p, i]
+    L.dabgpu_mot_state_bytes.restype = C.c_size_t
+    L.dabgpu_mot_state_bytes.argtypes = []
+    L.dabgpu_mot_arena_bytes.restype = C.c_size_t
+    L.dabgpu_mot_arena_bytes.argtypes = [C.c_size_t]
+    L.dabgpu_mot_slides_dev.argtypes = [vp, C.POINTER(MotEntry), i, vp]
+    L.dabgpu_mot_slides_host.argtypes = [C.POINTER(MotEntry), i]
+    L.dabgpu_mot_header_parse.argtypes = [vp, i, C.POINTER(MotHeader)]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -728,6 +770,41 @@ def pad_label_utf8(label):
     if n < 0:
         raise DabGpuError(n, "dabgpu_pad_label_utf8")
     return buf.raw[:n].decode("utf-8")
+
+
+def mot_state_bytes():
+    """Bytes of one state record of Context.mot_slides_dev / mot_slides_host (all zero = a fresh start)."""
+    return int(lib().dabgpu_mot_state_bytes())
+
+
+def mot_arena_bytes(body_capacity):
+    """Bytes of the smallest arena for slides whose body has up to body_capacity bytes (0: more than the call supports)."""
+    return int(lib().dabgpu_mot_arena_bytes(body_capacity))
+
+
+def mot_slides_host(entries):
+    """Context.mot_slides_dev on HOST memory (entries: MotEntry with host addresses): the same checks and the same walk,
+    no context and no GPU."""
+    n = len(entries)
+    arr = (MotEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_mot_slides_host(arr, n), "dabgpu_mot_slides_host")
+
+
+def mot_header_parse(header):
+    """The MOT header of a slide (bytes) -> dict: the header core, and of the header extension name (bytes), name_charset,
+    trigger / expire ("now", the first four bytes as int, or None), category_id, slide_id, category_title, click_through_url,
+    alternative_location_url (bytes, None where the parameter is not there), n_params, n_unknown."""
+    raw = np.frombuffer(bytes(header), np.uint8)
+    out = MotHeader()
+    _check(lib().dabgpu_mot_header_parse(raw.ctypes.data if raw.size else None, raw.size, C.byref(out)), "dabgpu_mot_header_parse")
+    text = lambda t: None if t.length < 0 else bytes(t.bytes[:t.length])
+    when = lambda has, now, t: None if not has else "now" if now else int(t)
+    return dict(body_size=out.body_size, header_size=out.header_size, content_type=out.content_type, content_subtype=out.content_subtype,
+                n_params=out.n_params, n_unknown=out.n_unknown, name=text(out.name), name_charset=out.name_charset if out.name.length >= 0 else None,
+                trigger=when(out.has_trigger, out.trigger_now, out.trigger_time), expire=when(out.has_expire, out.expire_now, out.expire_time),
+                category_id=out.category_id if out.has_category else None, slide_id=out.slide_id if out.has_category else None,
+                category_title=text(out.category_title), click_through_url=text(out.click_through_url),
+                alternative_location_url=text(out.alternative_location_url))
 
 
 # ------------------------------------------------------------------ context
@@ -1245,6 +1322,15 @@ class Context:
         n = len(entries)
         arr = (PadEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_pad_labels_dev(self._h, arr, n, stream), "dabgpu_pad_labels_dev")
+
+    def mot_slides_dev(self, entries, stream=None):
+        """Slideshow objects of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list
+        of MotEntry (device addresses).  Per entry: completed objects in the slots of d_slides (MOT_SLIDE_DTYPE, the MOT
+        header, the body), d_result (MOT_RESULT_DTYPE, counts of this call), d_state_out, to be passed as d_state_in of the
+        next call, and d_arena, which goes into the next call as it is."""
+        n = len(entries)
+        arr = (MotEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_mot_slides_dev(self._h, arr, n, stream), "dabgpu_mot_slides_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

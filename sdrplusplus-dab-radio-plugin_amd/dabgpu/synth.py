@@ -722,9 +722,11 @@ def dls_pads(groups, length_index=None, ci_less=False, before=(), after=(), end_
     length_index None: short X-PAD (the first access unit of a group has the content indicator and 3 bytes, the others are
     CI-less with 4).  Else variable X-PAD with sub-fields of XPAD_LENGTHS[length_index]; ci_less: the continuation
     sub-fields go without a list; before / after: other applications' sub-fields [(type, data)] around the DLS one in
-    every list (a CI-less field continues the LAST sub-field of the list, so `after` and ci_less exclude each other)."""
+    every list (a CI-less field continues the LAST sub-field of the list, so `after` and ci_less exclude each other);
+    either may be a callable, PAD index -> sub-fields (those of mot_fields: one PAD for a label and a slide)."""
     assert not (ci_less and after)
     pads = []
+    at_pad = lambda fields: list(fields(len(pads)) if callable(fields) else fields)    # (a callable: PAD index -> sub-fields)
     for g in groups:
         if length_index is None:
             g = bytes(g)
@@ -737,13 +739,218 @@ def dls_pads(groups, length_index=None, ci_less=False, before=(), after=(), end_
             if k and ci_less:
                 pads.append(pad_field(data, 2, 0, n))
             else:
-                pads.append(pad_field(xpad_variable(list(before) + [(typ, data)] + list(after), end_marker), 2, 1, n))
+                pads.append(pad_field(xpad_variable(at_pad(before) + [(typ, data)] + at_pad(after), end_marker), 2, 1, n))
     return pads
 
 
 def au_body(pad, tag=0):
     """what an access unit's body begins with to carry this PAD (build_superframe's `bodies`); None for no PAD"""
     return None if pad is None else dse(pad, tag)
+
+
+# ----------------------------------------------------------------------------- PAD: slideshow (MOT in X-PAD)
+# The transmit side of the slideshow, from the clauses: object -> MOT header (core + parameters, EN 301 234 6.1, 6.2;
+# TS 101 499 6.2) and body -> segments with their segmentation header (EN 301 234 5.1) -> MSC data groups with session
+# header and CRC (EN 300 401 5.3.3) -> X-PAD sub-fields: the data group length indicator (type 1), then the group in
+# sub-fields of type 12 (start) and 13 (continuation) (EN 300 401 7.4.5.1).
+XPAD_DGLI, XPAD_MOT_START, XPAD_MOT_CONT = 1, 12, 13
+MOT_DG_HEADER, MOT_DG_BODY = 3, 4
+MOT_CONTENT_NAME, MOT_TRIGGER_TIME, MOT_EXPIRE_TIME = 0x0C, 0x05, 0x04
+MOT_CATEGORY_SLIDE_ID, MOT_CATEGORY_TITLE, MOT_CLICK_THROUGH_URL, MOT_ALTERNATIVE_LOCATION_URL = 0x25, 0x26, 0x27, 0x28
+
+
+def mot_param(param_id, data=b"", pli=None, long_length=None):
+    """one header extension parameter: PLI 0 / 1 / 2 for no / one / four data bytes, else PLI 3 with a length of 7 bits, or
+    of 15 (long_length; default from 128 bytes on).  pli = 3 forces the length form on short data."""
+    data = bytes(data)
+    if pli is None:
+        pli = {0: 0, 1: 1, 4: 2}.get(len(data), 3)
+    assert {0: len(data) == 0, 1: len(data) == 1, 2: len(data) == 4, 3: len(data) < 32768}[pli]
+    head = bytes([(pli << 6) | (param_id & 0x3F)])
+    if pli < 3:
+        return head + data
+    if long_length is None:
+        long_length = len(data) >= 128
+    assert long_length or len(data) < 128
+    return head + (bytes([0x80 | (len(data) >> 8), len(data) & 0xFF]) if long_length else bytes([len(data)])) + data
+
+
+def mot_time(mjd_day=None, hours=0, minutes=0):
+    """the four bytes of a short-form time: validity(1) MJD(17) rfu(2) UTC flag(1) = 0, hours(5) minutes(6); None = "now":
+    validity clear and every other bit zero"""
+    if mjd_day is None:
+        return bytes(4)
+    v = (1 << 31) | ((mjd_day & 0x1FFFF) << 14) | ((hours & 0x1F) << 6) | (minutes & 0x3F)
+    return v.to_bytes(4, "big")
+
+
+def mot_header(body_size, content_type, content_subtype, params=(), header_size=None):
+    """header core (BodySize 28, HeaderSize 13, ContentType 6, ContentSubType 9 bits) and the header extension
+    (params: encoded by mot_param); header_size: what the core says (default: the truth)"""
+    ext = b"".join(bytes(p) for p in params)
+    size = 7 + len(ext) if header_size is None else header_size
+    assert body_size < 1 << 28 and size < 1 << 13
+    core = (body_size << 28) | (size << 15) | ((content_type & 0x3F) << 9) | (content_subtype & 0x1FF)
+    return core.to_bytes(7, "big") + ext
+
+
+def slide_header(body_size, name, subtype=1, charset=CHARSET_UTF8, trigger="now", extra=()):
+    """the MOT header of a slide: an image (content type 2; subtype 1 JFIF, 3 PNG) with its ContentName and TriggerTime"""
+    params = [mot_param(MOT_CONTENT_NAME, bytes([charset << 4]) + bytes(name))]
+    if trigger is not None:
+        params.append(mot_param(MOT_TRIGGER_TIME, mot_time() if trigger == "now" else bytes(trigger)))
+    return mot_header(body_size, 2, subtype, params + list(extra))
+
+
+def mot_segments(data, seg_size):
+    """an object part cut into segments of seg_size (the last one shorter or equal; one empty segment for no bytes)"""
+    data = bytes(data)
+    assert 1 <= seg_size <= 8191
+    return [data[i:i + seg_size] for i in range(0, len(data), seg_size)] or [b""]
+
+
+def msc_data_group(dg_type, data, tid=None, segment=None, continuity=0, repetition=0, extension=None, end_user=b"",
+                   crc=True, user_access=None):
+    """one MSC data group: header (extension flag, CRC flag, segment flag, user access flag, type; continuity and
+    repetition index; the extension field), session header (segment = (number, last); user access field with transport
+    id and end-user address), the data field, the CRC (the FIB's, big-endian).  user_access: default when tid is given;
+    True with tid None sends the field with its transport id flag clear."""
+    if user_access is None:
+        user_access = tid is not None
+    b0 = ((extension is not None) << 7) | (int(crc) << 6) | ((segment is not None) << 5) | (int(user_access) << 4) | (dg_type & 0x0F)
+    g = bytes([b0, ((continuity & 0x0F) << 4) | (repetition & 0x0F)])
+    if extension is not None:
+        g += int(extension).to_bytes(2, "big")
+    if segment is not None:
+        number, last = segment
+        g += ((int(last) << 15) | (number & 0x7FFF)).to_bytes(2, "big")
+    if user_access:
+        end_user = bytes(end_user)
+        li = (2 if tid is not None else 0) + len(end_user)
+        assert li <= 15
+        g += bytes([((tid is not None) << 4) | li]) + (int(tid).to_bytes(2, "big") if tid is not None else b"") + end_user
+    g += bytes(data)
+    if crc:
+        c = crc16(g)
+        g += bytes([c >> 8, c & 0xFF])
+    return g
+
+
+def mot_group(dg_type, tid, number, last, segment, repetition_count=0, size=None, **kw):
+    """a MOT segment in its data group: the segmentation header (RepetitionCount 3, SegmentSize 13 bits; size: what it
+    says, default the truth) in front of the segment"""
+    segment = bytes(segment)
+    size = len(segment) if size is None else size
+    return msc_data_group(dg_type, (((repetition_count & 7) << 13) | (size & 0x1FFF)).to_bytes(2, "big") + segment, tid,
+                          (number, last), **kw)
+
+
+def mot_object_groups(tid, header, body, seg_size, header_seg_size=None, **kw):
+    """the data groups of one object in header mode: the header's segments (type 3), then the body's (type 4)"""
+    out = []
+    for dg_type, part, size in ((MOT_DG_HEADER, header, header_seg_size or max(len(header), 1)), (MOT_DG_BODY, body, seg_size)):
+        segs = mot_segments(part, size)
+        out += [mot_group(dg_type, tid, n, n == len(segs) - 1, seg, continuity=n, **kw) for n, seg in enumerate(segs)]
+    return out
+
+
+def dgli(length, good=True):
+    """the data group length indicator: rfa(2) length(14), the CRC over these two bytes"""
+    assert 0 <= length < 1 << 14
+    b = bytes([length >> 8, length & 0xFF])
+    c = crc16(b) ^ (0 if good else 0x0100)
+    return b + bytes([c >> 8, c & 0xFF])
+
+
+def mot_fields(groups, length_index, with_length=True, per_au=1):
+    """-> per access unit the X-PAD sub-fields [(type, data)] that carry these data groups: in a group's first access unit
+    the length indicator (type 1, 4 bytes) and a start sub-field (type 12), then continuation sub-fields (type 13), each
+    of XPAD_LENGTHS[length_index] bytes, the last one filled up with zeros; per_au: sub-fields of a group per access unit
+    (the length indicator counts as one)"""
+    n, out = XPAD_LENGTHS[length_index], []
+    for g in groups:
+        g = bytes(g)
+        subs = [(XPAD_DGLI, dgli(len(g)))] if with_length else []
+        for k, at in enumerate(range(0, len(g), n)):
+            part = g[at:at + n]
+            subs.append((XPAD_MOT_CONT if k else XPAD_MOT_START, part + bytes(n - len(part))))
+        if per_au == 1 and with_length:
+            subs[:2] = [subs[:2]]                                        # (the indicator travels with the start sub-field)
+            out += [f if isinstance(f, list) else [f] for f in subs]
+        else:
+            out += [subs[i:i + per_au] for i in range(0, len(subs), per_au)]
+    return out
+
+
+def merge_fields(*streams):
+    """per access unit, the sub-fields of several applications side by side in one list, in the order given (a stream
+    that has ended adds nothing)"""
+    return [sum((list(s[k]) for s in streams if k < len(s)), []) for k in range(max(len(s) for s in streams))]
+
+
+def dls_fields(groups, length_index):
+    """dls_pads' sub-fields without their PAD: per access unit [(type, data)], for merge_fields"""
+    return [[f] for g in groups for f in dls_subfields(g, [XPAD_LENGTHS[length_index]])]
+
+
+def fields_pads(fields, ci_less=False, n=None, end_marker=True):
+    """one variable X-PAD field per access unit from its sub-fields (at most four); None where there are none.  ci_less: an
+    access unit with ONE sub-field of a continuation type (3, 13) that continues the last sub-field of the list before it,
+    with the same length, goes without a list."""
+    pads, prev = [], None
+    for f in fields:
+        if not f:
+            pads.append(None)
+            prev = None
+            continue
+        cont = {XPAD_DLS_START: XPAD_DLS_CONT, XPAD_DLS_CONT: XPAD_DLS_CONT, XPAD_MOT_START: XPAD_MOT_CONT, XPAD_MOT_CONT: XPAD_MOT_CONT}
+        if ci_less and prev is not None and len(f) == 1 and f[0][0] == cont.get(prev[0]) and len(f[0][1]) == len(prev[1]):
+            pads.append(pad_field(f[0][1], 2, 0, n))
+        else:
+            pads.append(pad_field(xpad_variable(f, end_marker), 2, 1, n))
+        prev = f[-1]
+    return pads
+
+
+def mot_pads(groups, length_index, ci_less=False, before=(), after=(), n=None, with_length=True, end_marker=True, per_au=1):
+    """One PAD field per access unit for a sequence of MOT data groups (mot_fields).  before / after: other applications'
+    sub-fields around them in every list -- fixed [(type, data)], or per access unit (dls_fields(...): a label beside the
+    slide); ci_less: the continuation sub-fields go without a list where they stand alone."""
+    own = mot_fields(groups, length_index, with_length, per_au)
+    side = lambda f: [list(f)] * len(own) if (not f or isinstance(f[0], tuple)) else [list(x) for x in f]
+    return fields_pads(merge_fields(side(before), own, side(after)), ci_less, n, end_marker)
+
+
+def pack_pads(sizes, mot_groups, dls_groups, dls_index=0):
+    """One PAD per access unit, as large as the unit has room for: a label sub-field of XPAD_LENGTHS[dls_index] bytes in front while the label
+    lasts, then the length indicator and sub-fields of the slide's current data group, the largest that fit.
+    sizes: bytes of every access unit with its CRC -> PAD per unit (None: no room), sub-fields left over"""
+    mot = [bytes(g) for g in mot_groups]
+    dls = [f[0] for f in dls_fields(dls_groups, dls_index)]
+    pads, at = [], 0                                                  # at: bytes of mot[0] already sent
+    for size in sizes:
+        room = min(size - 2 - 3 - 2 - 4, 190)                         # CRC, element header, F-PAD, content indicators
+        fields = []
+        if dls and room >= XPAD_LENGTHS[dls_index]:
+            fields.append(dls.pop(0))
+            room -= XPAD_LENGTHS[dls_index]
+        if mot and at == 0 and room >= 8 and len(fields) <= 2:
+            fields.append((XPAD_DGLI, dgli(len(mot[0]))))
+            room -= 4
+        while mot and len(fields) < 4 and room >= 4 and (at > 0 or (fields and fields[-1][0] == XPAD_DGLI)):
+            left = len(mot[0]) - at
+            fit = [n for n in XPAD_LENGTHS if n <= room]
+            n = min([m for m in fit if m >= left] or [fit[-1]])
+            part = mot[0][at:at + n]
+            fields.append((XPAD_MOT_CONT if at else XPAD_MOT_START, part + bytes(n - len(part))))
+            room -= n
+            at += n
+            if at >= len(mot[0]):
+                mot.pop(0)
+                at = 0
+                break
+        pads.append(pad_field(xpad_variable(fields), 2, 1) if fields else None)
+    return pads, len(mot) + len(dls)
 
 
 # ----------------------------------------------------------------------------- FIGs (EN 300 401 clauses 5.2, 6, 8)

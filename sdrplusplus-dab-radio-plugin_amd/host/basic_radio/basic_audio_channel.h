@@ -42,7 +42,7 @@ public:
     // decoder (basic_dab_plus_channel.cpp); a layer-II channel has none.  Read under BasicRadio::GetMutex() like the rest.
     std::string_view GetDynamicLabel() const { return m_dynamic_label; }
     Basic_Audio_Controls &GetControls() { return m_controls; }
-    // slideshows come out of the audio decoder's PAD as well: always empty (render_radio_block.cpp:591)
+    // slideshows come out of the PAD as well: a DAB+ channel fills it (basic_dab_plus_channel.cpp), a layer-II channel does not
     Basic_Slideshow_Manager &GetSlideshowManager() { return m_slideshows; }
     Observable<BasicAudioParams, tcb::span<const uint8_t>> &OnAudioData() { return m_obs_audio; }
 

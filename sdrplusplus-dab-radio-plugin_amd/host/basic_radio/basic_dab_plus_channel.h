@@ -6,6 +6,8 @@
 // (/root/reference/src/render_radio_block.cpp:410-437).  AAC decoding itself is not part of the path, so
 // IsCodecError() is always false; the access units leave through OnAccessUnit().  GetDynamicLabel() is read from the
 // PAD in front of every access unit by the walk the GPU batch call runs (include/dabgpu_pad_walk.h), here on the host.
+// The slideshow comes the same way: the MOT walk of include/dabgpu_mot_walk.h runs beside the label walk, its copy orders
+// executed by a loop, and every completed image object becomes a Basic_Slideshow of GetSlideshowManager().
 #pragma once
 #include <cstdint>
 #include <string_view>
@@ -13,6 +15,7 @@
 #include "basic_radio/basic_audio_channel.h"
 #include "dab/audio/aac_frame_processor.h"
 #include "dabgpu.h"
+#include "dabgpu_mot_walk.h"
 #include "dabgpu_pad_walk.h"
 #include "utility/gpu_buffers.h"
 
@@ -44,6 +47,7 @@ public:
     // charset of GetDynamicLabel() (EN 300 401 clause 5.2.2.2: 15 = UTF-8, 6 = UCS-2, 0 = EBU Latin) and what the walk counted
     int GetDynamicLabelCharset() const { return m_pad.label.charset; }
     const dabgpu_pad::Counters &GetPadCounters() const { return m_pad_counts; }
+    const dabgpu_mot::Counters &GetMotCounters() const { return m_mot_counts; }     // (slides_written: of the last access unit)
     const Subchannel &GetSubchannel() const { return m_subchannel; }
 
 private:
@@ -63,4 +67,12 @@ private:
     Observable<int, int, tcb::span<const uint8_t>> m_obs_au;
     dabgpu_pad::State m_pad{};             // all zero: a fresh start
     dabgpu_pad::Counters m_pad_counts{};
+    // the slideshow: state, arena and the slots of one access unit (at most one object completes per sub-field)
+    static constexpr int MOT_BODY_CAPACITY = 256 * 1024, MOT_SLOTS = 4;
+    void WalkMot(const uint8_t *au, int len);
+    void AddSlide(const uint8_t *slot);
+    dabgpu_mot::State m_mot{};
+    dabgpu_mot::Counters m_mot_counts{};
+    dabgpu_mot::Call m_mot_call{};
+    std::vector<uint8_t> m_mot_arena, m_mot_slides;
 };

@@ -176,6 +176,15 @@ int main(int argc, char **argv) {
                 std::fprintf(f, " label_charset=%d label=", ch->GetDynamicLabelCharset());
                 for (const char v : ch->GetDynamicLabel()) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
                 std::fprintf(f, "\n");
+                // the slides as the GUI's "Slideshow" tab lists them (render_radio_block.cpp:309-382), the image in hex
+                auto slides_lock = std::scoped_lock(ch->GetSlideshowManager().GetSlideshowsMutex());
+                for (const auto &slide : ch->GetSlideshowManager().GetSlideshows()) {
+                    std::fprintf(f, "slide subchannel=%d tid=%u name=", sc.id, unsigned(slide->transport_id));
+                    for (const char v : slide->name) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
+                    std::fprintf(f, " bytes=%zu body=", slide->image_data.size());
+                    for (const uint8_t v : slide->image_data) std::fprintf(f, "%02x", unsigned(v));
+                    std::fprintf(f, "\n");
+                }
             }
             std::fclose(f);
         }
