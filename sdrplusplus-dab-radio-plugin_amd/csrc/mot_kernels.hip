@@ -11,6 +11,7 @@
 
 #include "../../include/dabgpu_mot_walk.h"
 #include "kernels.hpp"
+#include "wave_copy.hpp"
 
 namespace dabk {
 namespace {
@@ -23,28 +24,6 @@ constexpr int MOT_AU_BYTES = 528;       // tag, count, escape count and at most 
 
 static_assert(sizeof(mot::State) % 16 == 0 && sizeof(mot::Counters) % 4 == 0, "copied by words");
 static_assert(sizeof(SuperframeStatus) == 64 && sizeof(FollowResult) == 32, "records of the follow call");
-
-// len bytes from src to dst (global memory, no overlap) by the whole wave: 16-byte accesses where both run on the same
-// 16-byte phase, 4-byte ones where on the same 4-byte phase, else a byte a lane -- coalesced either way
-template <class W> __device__ __forceinline__ void wave_copy_as(uint8_t *dst, const uint8_t *src, int len, int lane) {
-    constexpr int B = int(sizeof(W));
-    int head = int((B - (reinterpret_cast<uintptr_t>(dst) & (B - 1))) & (B - 1));
-    head = head < len ? head : len;
-    if (lane < head) dst[lane] = src[lane];
-    const int words = (len - head) / B;
-    const W *s = reinterpret_cast<const W *>(src + head);
-    W *d = reinterpret_cast<W *>(dst + head);
-    for (int i = lane; i < words; i += 64) d[i] = s[i];
-    const int done = head + words * B;
-    if (done + lane < len) dst[done + lane] = src[done + lane];       // (fewer than B <= 16 bytes are left)
-}
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, int len, int lane) {
-    const unsigned phase = unsigned(reinterpret_cast<uintptr_t>(dst) ^ reinterpret_cast<uintptr_t>(src));
-    if (!(phase & 15)) wave_copy_as<uint4>(dst, src, len, lane);
-    else if (!(phase & 3)) wave_copy_as<uint32_t>(dst, src, len, lane);
-    else
-        for (int i = lane; i < len; i += 64) dst[i] = src[i];
-}
 
 __global__ __launch_bounds__(64) void mot_slides_kernel(const MotEntry *table) {
     __shared__ mot::State st;

@@ -229,7 +229,8 @@ class DeviceMemory:
 
 def call(mem, specs, mutate=None, refused=False):
     """One call on buffers laid out in one allocation, every region between sentinel bytes.  specs: dicts {s, data [rows][110 s],
-    status [rows], n (what d_follow says), max_sf (default: the rows), state (bytes or None = NULL), stride}.  After the call
+    status [rows], n (what d_follow says), max_sf (default: the rows), state (bytes or None = NULL), stride, data_off (the
+    data rows begin that many bytes, below 16, off their 256-byte boundary)}.  After the call
     nothing but the state-out, label and result regions may have changed (none at all for a refused call).
     -> per entry (label record, result record, state bytes)"""
     size, lay = 0, []
@@ -243,7 +244,8 @@ def call(mem, specs, mutate=None, refused=False):
     nb = dabgpu.pad_state_bytes()
     for sp in specs:
         rows, stride = len(sp["data"]), sp.get("stride", 110 * sp["s"])
-        lay.append(dict(data=take(max(rows, 1) * stride), status=take(max(rows, 1) * 64), follow=take(32),
+        assert 0 <= sp.get("data_off", 0) < 16
+        lay.append(dict(data=take(max(rows, 1) * stride + 16) + sp.get("data_off", 0), status=take(max(rows, 1) * 64), follow=take(32),
                         sin=take(nb) if sp.get("state") is not None else None, sout=take(nb), label=take(144), result=take(64)))
     image = np.full(size + GAP, FILL, np.uint8)
     for sp, L in zip(specs, lay):

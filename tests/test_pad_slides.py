@@ -38,15 +38,66 @@ def obj(tid, body, name, seg, hseg=None, extra=(), **kw):
 
 
 class Scenario:
-    def __init__(self, name, pads, slides=(), counts=None, damage=None, max_slides=4, slide_stride=None):
+    def __init__(self, name, pads, slides=(), counts=None, damage=None, max_slides=4, slide_stride=None, rows=None):
         """slides: (transport id, header, body) of the objects the scenario completes, in order; counts: counters of the
-        scenario that the reference must report (a subset); damage(status rows of the scenario): reception losses"""
+        scenario that the reference must report (a subset); damage(status rows of the scenario): reception losses;
+        rows(s) -> (data, status): super-frames laid out by hand (unit_rows) in the place of `pads`"""
         self.name, self.pads, self.slides, self.counts, self.damage = name, pads, list(slides), counts or {}, damage
-        self.max_slides, self.slide_stride = max_slides, slide_stride
+        self.max_slides, self.slide_stride, self.rows = max_slides, slide_stride, rows
 
 
 def sent(*objs):
     return [(tid, o[0], o[1]) for tid, o in objs]
+
+
+def sized_object(tid, hbytes, bbytes, seed, seg=2048, hseg=2048):
+    """an object whose header has exactly hbytes >= 16 (an unknown parameter fills it up): in its slot the body begins
+    32 + hbytes bytes in"""
+    name = synth.mot_param(synth.MOT_CONTENT_NAME, b"\xf0cap")
+    header = synth.mot_header(bbytes, 2, 1, [name, synth.mot_param(0x3A, bytes(hbytes - 7 - len(name) - 3), pli=3, long_length=True)])
+    assert len(header) == hbytes
+    body = image(bbytes, seed)
+    return header, body, synth.mot_object_groups(tid, header, body, seg, hseg)
+
+
+def placed_object(tid, size, last, eu0, eu1, seed):
+    """an object whose body is one segment of `size` bytes and a last one of `last`, in data groups whose end-user address has
+    eu0 and eu1 bytes: the segments lie 9 + eu bytes into the group buffer and go to body offsets 0 and `size`"""
+    body = image(size + last, seed)
+    header = synth.slide_header(len(body), b"placed %x" % tid)
+    groups = [synth.mot_group(3, tid, 0, True, header), synth.mot_group(4, tid, 0, False, body[:size], end_user=bytes(eu0)),
+              synth.mot_group(4, tid, 1, True, body[size:], end_user=bytes(eu1), continuity=1)]
+    return header, body, groups
+
+
+NO_AUDIO = b"\x21\x00\x00"                                            # an access unit with a channel pair element in front
+
+
+def unit(fields, n=None, behind=b""):
+    """an access unit laid out by hand: the data stream element whose PAD of n bytes (default: no more than needed) carries
+    these sub-fields [(type, data)], and what follows the element"""
+    return synth.dse(synth.fields_pads([fields], n=n)[0]) + bytes(behind)
+
+
+def unit_rows(units, claim=None, first=11):
+    """Scenario(rows=): super-frames whose access units are given byte for byte, at most seven each (bytes without the CRC,
+    or (bytes, what lies behind them where the CRC would be: at most 2 bytes)); they lie back to back from byte `first`;
+    claim: what num_aus says (default: the truth).  What a data part holds besides is 0xEE."""
+    def rows(s):
+        data, status = np.full((len(units), 110 * s), 0xEE, np.uint8), np.zeros(len(units), P.STATUS_DTYPE)
+        for k, us in enumerate(units):
+            at, starts = first, [first]
+            for u in us:
+                au, behind = u if isinstance(u, tuple) else (u, b"")
+                assert len(au) >= 1 and len(behind) <= 2
+                data[k, at:at + len(au) + len(behind)] = np.frombuffer(bytes(au) + bytes(behind), np.uint8)
+                at += len(au) + 2
+                starts.append(at)
+            assert at <= 110 * s and len(us) <= 7
+            status[k]["firecode_ok"], status[k]["num_aus"], status[k]["au_crc_mask"] = 1, claim or len(us), (1 << len(us)) - 1
+            status[k]["au_start"][:len(starts)] = starts
+        return data, status
+    return rows
 
 
 def _streams():
@@ -169,9 +220,65 @@ def _streams():
     pads = mp(groups, 4, after=synth.dls_fields(LABEL_GROUPS[0] + LABEL_GROUPS[1], 1))
     S["chunks"] = dict(s=8, num_aus=3, seed=42, body_capacity=512, scenarios=[
         Scenario("objects across every boundary", pads, sent((0xB00, ch[0]), (0xB01, ch[1]), (0xB02, ch[2])), dict(groups_repeated=2))])
+    # M, N: s = 24, six access units: the directed copies (csrc/wave_copy.hpp; the census of test_pad_device_edges.py counts
+    # what they reach).  A segment goes from group offset 9 + (end-user address bytes) to a body offset that is a multiple of
+    # the segment size; a completed object's header goes to byte 32 of its slot, its body behind the header.
+    mv = [placed_object(0xC00 + i, *a, 110 + i) for i, a in enumerate([
+        (1039, 17, 7, 6), (1041, 16, 7, 8), (1009, 62, 7, 8), (41, 8, 7, 0),                         # 16-byte accesses
+        (259, 254, 3, 2), (261, 7, 11, 0), (10, 5, 3, 5),                                           # 4-byte accesses
+        (70, 9, 1, 3),                      # a byte a lane where source and destination are two bytes apart (mod 4)
+        (6, 1, 3, 1), (25, 3, 7, 0)])]      # len < head on either; last, so that what a copy writes beyond them stays in the arena
+    S["moves"] = dict(s=24, num_aus=6, seed=43, body_capacity=2048, slots=12, scenarios=[
+        Scenario("segments moved by 16-byte words", mp(sum((o[2] for o in mv[:4]), []), 7, per_au=4), sent(*[(0xC00 + i, mv[i]) for i in range(4)]),
+                 dict(groups_ok=12, segments_placed=12, slides_written=4), slide_stride=2048),
+        Scenario("segments moved by 4-byte words; segments shorter than their head", mp(sum((o[2] for o in mv[4:]), []), 7, per_au=4),
+                 sent(*[(0xC00 + i, mv[i]) for i in range(4, 10)]), dict(groups_ok=18, segments_placed=18, slides_written=6), max_slides=6, slide_stride=2048)])
+    sl = [sized_object(0xD00 + i, hb, bb, 130 + i) for i, (hb, bb) in enumerate([
+        (16, 15), (32, 1009), (48, 1024), (64, 1055),                                               # the body by 16-byte words
+        (20, 3), (24, 5), (28, 252), (36, 257), (40, 263),                                          # ... by 4-byte words
+        (17, 70), (18, 70)])]                                 # ... a byte a lane, two trips: one and two bytes apart (mod 4)
+    S["slotcopies"] = dict(s=24, num_aus=6, seed=44, body_capacity=2048, slots=12, scenarios=[
+        Scenario("objects into their slots: %s" % what, mp(sum((o[2] for o in sl[a:b]), []), 7, per_au=4), sent(*[(0xD00 + i, sl[i]) for i in range(a, b)]),
+                 dict(groups_ok=2 * (b - a), slides_written=b - a), max_slides=b - a, slide_stride=2048)
+        for what, a, b in (("16-byte words", 0, 4), ("4-byte words", 4, 9), ("bytes", 9, 11))])
+    # O, P: s = 32, access units laid out by hand: what the kernels fetch of a data stream element (the window `need`)
+    lab = lambda text, toggle: [f[0] for f in synth.dls_fields(synth.dls_segments(text, toggle), 5)]
+    grp = lambda g: synth.mot_fields([g], 7)[0]
+    w0, w1 = obj(0xE00, image(21, 150), b"w0", 64), obj(0xE01, image(75, 151), b"w1", 30)
+    assert all(len(g) <= 48 for g in w0[2] + w1[2]) and len(w1[2]) == 4
+    l0, l1 = lab(WINDOW_TEXT[0], 0), lab(WINDOW_TEXT[1], 1)
+    assert len(l0) == 2 and len(l1) == 2
+    counts = [bytes([0x80, 0]), bytes([0x80, 1, 0x20]) + bytes(3), bytes([0x80, 2, 0x20, 0x02]), bytes([0x80, 3, 0x00, 0x20, 0x02]) + bytes(2),
+              unit([l0[0]] + grp(w0[2][0]), 253, bytes(5)), unit([l0[1]] + grp(w0[2][1]), 254)]
+    escapes = [unit([l1[0]] + grp(w1[2][0]), 255), NO_AUDIO, unit(grp(w1[2][1]), 256, bytes(7)), unit(grp(w1[2][2]), 509, bytes(1)), NO_AUDIO,
+               unit([l1[1]] + grp(w1[2][3]), 510)]
+    assert [len(u) for u in counts[4:]] == [260, 256] and [len(escapes[i]) for i in (0, 2, 3, 5)] == [258, 266, 513, 513] and escapes[5][1:3] == b"\xff\xff"
+    S["window"] = dict(s=32, num_aus=6, seed=45, body_capacity=256, scenarios=[
+        Scenario("element counts 0, 1, 2, 3, 253, 254", None, sent((0xE00, w0)), dict(pad_malformed=3, groups_ok=2, aus=6), rows=unit_rows([counts])),
+        Scenario("escape bytes 0, 1, 254, 255; a unit that ends with its element of 513 bytes", None, sent((0xE01, w1)),
+                 dict(pad_malformed=0, groups_ok=4, aus=6), rows=unit_rows([escapes]))])
+    # the stale row: slot a of one super-frame holds a valid unit (a label segment and a data group, whole), slot a of the next
+    # one begins with the same bytes and is (i) a byte short of its count, (ii) cut behind the count 255, (iii) without the
+    # element's tag; a = 0 and the last unit visited -- the seventh, of nine claimed, or the sixth with a seventh claimed
+    stale = []
+    for i, (what, n, seven, spoil_unit, malformed) in enumerate([
+            ("a byte too short for its count", 100, True, lambda v: (v[:-1], v[-1:]), 2),
+            ("the count 255 and no escape byte", 300, True, lambda v: v[:2], 2),
+            ("no element tag in front of the same bytes", 100, True, lambda v: b"\x21" + v[1:], 0),
+            ("a byte too short, six units and a seventh claimed", 120, False, lambda v: (v[:-1], v[-1:]), 2)]):
+        o, text = obj(0xF00 + i, image(30, 160 + i), b"st%d" % i, 64), lab(STALE_TEXT[i], i & 1)
+        first, last = unit([text[0]] + grp(o[2][0]), n), unit([text[1]] + grp(o[2][1]), n)
+        assert len(text) == 2 and len(o[2]) == 2 and (n < 255 or first[1] == 255)
+        quiet = [NO_AUDIO] * (5 if seven else 4)
+        stale.append(Scenario("a stale row: " + what, None, sent((0xF00 + i, o)),
+                              dict(pad_malformed=malformed, groups_ok=2, slides_written=1, aus=14, aus_lost=0 if seven else 2),
+                              rows=unit_rows([[first] + quiet + [last], [spoil_unit(first)] + quiet + [spoil_unit(last)]], claim=9 if seven else 7)))
+    S["stale"] = dict(s=32, num_aus=6, seed=46, body_capacity=256, scenarios=stale)
     return S
 
 
+WINDOW_TEXT = [b"counts below the escape", b"and the escape byte itself"]
+STALE_TEXT = [b"stale row, one byte short", b"stale row, cut at the count", b"stale row, no element tag", b"stale row, the sixth unit"]
 LABEL_TEXT = [b"Now: a slide beside this label", b"and another one"]
 LABEL_GROUPS = [synth.dls_segments(LABEL_TEXT[0], 0), synth.dls_segments(LABEL_TEXT[1], 1)]
 STREAMS = _streams()
@@ -184,13 +291,14 @@ def built_streams(built):
     for name, spec in STREAMS.items():
         datas, stats, bounds, at = [], [], [], 0
         for k, sc in enumerate(spec["scenarios"]):
-            d, st = superframes(spec["seed"] * 100 + k, spec["s"], spec["num_aus"], sc.pads)
+            d, st = sc.rows(spec["s"]) if sc.rows else superframes(spec["seed"] * 100 + k, spec["s"], spec["num_aus"], sc.pads)
             if sc.damage:
                 sc.damage(st)
             datas.append(d); stats.append(st)
             bounds.append((sc, at, at + len(d)))
             at += len(d)
-        out[name] = dict(s=spec["s"], body_capacity=spec["body_capacity"], data=np.concatenate(datas), status=np.concatenate(stats), bounds=bounds)
+        out[name] = dict(s=spec["s"], body_capacity=spec["body_capacity"], data=np.concatenate(datas), status=np.concatenate(stats), bounds=bounds,
+                         slots=spec.get("slots"))
         assert at <= 16, (name, at)
     return out
 
@@ -236,7 +344,7 @@ def stride_of(sp):
 def call(mem, specs, mutate=None, refused=False):
     """One call on buffers laid out in one allocation, every region between sentinel bytes.  specs: dicts {s, data, status, n,
     max_sf, state (bytes or None = NULL), arena (bytes or None = sentinel bytes), body_capacity, max_slides, slide_stride,
-    stride}.  After the call nothing but state-out, arena, result and the slots' written bytes may have changed (nothing at
+    stride, data_off (the data rows begin that many bytes, below 16, off their 256-byte boundary)}.  After the call nothing but state-out, arena, result and the slots' written bytes may have changed (nothing at
     all for a refused call).  -> per entry dict(slides [(record, header, body)], result, state, arena)"""
     size, lay = 0, []
 
@@ -251,7 +359,8 @@ def call(mem, specs, mutate=None, refused=False):
         rows, stride = len(sp["data"]), sp.get("stride", 110 * sp["s"])
         ab = dabgpu.mot_arena_bytes(sp["body_capacity"])
         assert ab == M.arena_bytes(sp["body_capacity"])
-        lay.append(dict(data=take(max(rows, 1) * stride), status=take(max(rows, 1) * 64), follow=take(32),
+        assert 0 <= sp.get("data_off", 0) < 16
+        lay.append(dict(data=take(max(rows, 1) * stride + 16) + sp.get("data_off", 0), status=take(max(rows, 1) * 64), follow=take(32),
                         sin=take(nb) if sp.get("state") is not None else None, sout=take(nb), arena=take(ab), ab=ab,
                         slides=take(max(sp.get("max_slides", 4), 1) * stride_of(sp)), result=take(128)))
     img = np.full(size + GAP, FILL, np.uint8)
@@ -269,6 +378,8 @@ def call(mem, specs, mutate=None, refused=False):
             img[L["arena"]:L["arena"] + L["ab"]] = sp["arena"]
     base = mem.load(img)
     assert base % 256 == 0
+    # (what the census of copy classes in test_pad_device_edges.py rests on: arena and slots on 16-byte boundaries)
+    assert all((base + L["arena"]) % 16 == 0 and (base + L["slides"]) % 16 == 0 and stride_of(sp) % 16 == 0 for sp, L in zip(specs, lay))
     entries = [dabgpu.MotEntry(base + L["data"], sp.get("stride", 110 * sp["s"]), base + L["status"], base + L["follow"], 8 * sp["s"],
                                sp.get("max_sf", len(sp["data"])), base + L["sin"] if L["sin"] is not None else None, base + L["sout"],
                                base + L["arena"], L["ab"], base + L["slides"], stride_of(sp), sp.get("max_slides", 4), 0, base + L["result"])
@@ -610,7 +721,7 @@ def ragged_specs(built_streams):
         ff = np.full((2, 110 * st["s"]), 0xFF, np.uint8)
         ffs = np.full(2 * 64, 0xFF, np.uint8).view(P.STATUS_DTYPE)
         specs.append(dict(s=st["s"], data=np.concatenate([st["data"], ff]), status=np.concatenate([st["status"], ffs]), n=n, body_capacity=st["body_capacity"],
-                          stride=110 * st["s"] + [0, 2, 16][e % 3], max_slides=[8, 2, 5][e % 3], slide_stride=8192 + 128 if st["body_capacity"] > 4096 else 2048))
+                          stride=110 * st["s"] + [0, 2, 16][e % 3], max_slides=st["slots"] or [8, 2, 5][e % 3], slide_stride=8192 + 128 if st["body_capacity"] > 4096 else 2048))
     return specs
 
 
