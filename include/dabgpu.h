@@ -1167,6 +1167,10 @@ typedef struct dabgpu_eti_history {    /* DEVICE memory, per stream, 1504 bytes 
     int32_t next_count;                /* CIF count of the first CIF of the next call                */
     int32_t valid;                     /* how many of the 15 slots hold a CIF (the newest ones); 0:  */
                                        /* nothing here, next_count included                          */
+                                       /* A record the library did not write is read like this: valid */
+                                       /* below 0 counts as 0, above 15 as 15; next_count is taken as  */
+                                       /* an unsigned 32-bit number modulo 5000 (-1 counts as 2295).   */
+                                       /* No value of either makes a call read outside the record.     */
     int32_t reserved[2];
 } dabgpu_eti_history;
 

@@ -124,6 +124,17 @@ def fig0_0_count(fib, crc_ok):
 WARMUP, FIB_CRC, NO_ANCHOR, COUNT_MISMATCH = 1, 2, 4, 8
 
 
+def history_of_record(fib, crc_ok, next_count, valid):
+    """The history a dabgpu_eti_history record stands for, whatever the caller left in it (include/dabgpu.h, the record's
+    comment): `valid` below 0 counts as 0 and above 15 as 15, the newest `valid` of the 15 slots hold a CIF, next_count is
+    the int32 read as unsigned (write_stream takes it modulo 5000) and means nothing when valid is 0.
+    fib [15][96], crc_ok [15][3] -> the dict write_stream takes."""
+    import numpy as np
+    n = min(max(int(valid), 0), 15)
+    return {"fibs": [np.array(fib[j], np.uint8).reshape(3, 32) for j in range(15 - n, 15)],
+            "crc_ok": [np.array(crc_ok[j], np.uint8).reshape(3) for j in range(15 - n, 15)], "next_count": int(next_count) & 0xFFFFFFFF}
+
+
 def write_stream(streams, fibs, crc_ok, data, history=None, cif_start=None):
     """What one call on one ensemble stream must write.  fibs [n_cif][3][32] and crc_ok [n_cif][3] of this call's CIFs,
     data {stream id: [n_cif][bytes]} as the decoder aligns them (entry t belongs to CIF t - 15).  history: None or
@@ -140,7 +151,7 @@ def write_stream(streams, fibs, crc_ok, data, history=None, cif_start=None):
         base = (fig0_0_count(fibs[anchor][0], 1) - anchor) % 5000
     else:
         no_anchor = True
-        base = history["next_count"] % 5000 if history and old_f else 0
+        base = (int(history["next_count"]) & 0xFFFFFFFF) % 5000 if history and old_f else 0   # the record's int32 read as unsigned
     _, length = frame_length(streams)
     frames, status = [], []
     for t in range(n_cif):

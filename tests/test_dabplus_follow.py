@@ -286,12 +286,28 @@ def fctx(built):
 IN_FILL, DATA_FILL, GAP = 0xC9, 0xA7, 64
 
 
+def held_of(sp):
+    """the frames the spec's carry record holds, as the call reads the record"""
+    if sp.get("carry") is None:
+        return 0
+    held = int(np.asarray(sp["carry"][:16], np.uint8).view("<i4")[1])
+    return held if 0 <= held <= 4 else 0
+
+
+def decoy_count(sp, n_cifs):
+    """the lanes of the last 64-frame block of the entry's held + n_cifs frames that have no frame"""
+    return -(held_of(sp) + n_cifs) % 64
+
+
 def call(ctx, specs, n_cifs, mutate=None, refused=False):
     """One follow call on device buffers laid out in one allocation, every region between sentinel bytes.
     specs: dicts {s, frames [n_cifs][24 s], carry (bytes of the record, or None = NULL), stride, shift (bytes the input is
     moved off its 256-byte boundary)}.  The whole allocation after the call must equal the allocation before it with the
     reference's outputs written in -- data rows and status records of the emitted super-frames only, the result record, the
     whole carry record -- or, for a call that must be refused (`mutate` spoils the table), the allocation before it.
+    A spec's `decoy` (eleven bytes that pass F.raw_hit) is written where the frames behind the entry's last one would begin, at
+    in + n_cifs stride, in + (n_cifs + 1) stride, ... for every lane the last 64-frame block of held + n_cifs frames leaves
+    idle (decoy_count): inside the allocation, and nothing of the reference's outputs knows of them.
     -> per entry (data [n_sf][110 s], status [n_sf], result record, carry_out bytes) as the GPU wrote them."""
     import torch
     max_sf = (n_cifs + 4) // 5
@@ -306,7 +322,8 @@ def call(ctx, specs, n_cifs, mutate=None, refused=False):
     for sp in specs:
         s = sp["s"]
         stride = sp.get("stride", 24 * s)
-        lay.append({"in": take(max(n_cifs - 1, 0) * stride + 24 * s, sp.get("shift", 0)),
+        n_decoys = decoy_count(sp, n_cifs) if sp.get("decoy") is not None else 0
+        lay.append({"in": take(max(n_cifs + n_decoys - 1, 0) * stride + 24 * s, sp.get("shift", 0)),
                     "cin": take(F.carry_bytes(s)) if sp.get("carry") is not None else None, "cout": take(F.carry_bytes(s)),
                     "data": take(max_sf * 110 * s, sp.get("shift", 0)), "status": take(max_sf * 64), "result": take(32)})
     before = np.full(size + GAP, DATA_FILL, np.uint8)
@@ -318,6 +335,12 @@ def call(ctx, specs, n_cifs, mutate=None, refused=False):
         before[L["in"]:L["in"] + max(n_cifs - 1, 0) * stride + 24 * s] = rng.integers(0, 256, max(n_cifs - 1, 0) * stride + 24 * s, dtype=np.uint8)
         for i in range(n_cifs):
             before[L["in"] + i * stride:L["in"] + i * stride + 24 * s] = frames[i]
+        if sp.get("decoy") is not None:
+            decoy = np.asarray(sp["decoy"], np.uint8)
+            assert decoy.shape == (11,) and F.raw_hit(decoy)
+            for i in range(n_cifs, n_cifs + decoy_count(sp, n_cifs)):
+                before[L["in"] + i * stride:L["in"] + i * stride + 24 * s] = rng.integers(0, 256, 24 * s, dtype=np.uint8)
+                before[L["in"] + i * stride:L["in"] + i * stride + 11] = decoy
         if L["cin"] is not None:
             before[L["cin"]:L["cin"] + F.carry_bytes(s)] = sp["carry"]
     t = torch.from_numpy(before).cuda()

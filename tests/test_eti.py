@@ -252,14 +252,26 @@ def _dev(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def run_eti(ctx, streams, fib, ok, outs, history=None, cif_start=None, want_history=True):
+def _dev_shifted(torch, a, shift):
+    """`a` on the device, `shift` bytes behind a 256-byte boundary"""
+    a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    room = torch.full((a.size + 256,), 0xEE, dtype=torch.uint8, device="cuda")
+    assert room.data_ptr() % 256 == 0
+    view = room[shift:shift + a.size]
+    view.copy_(torch.from_numpy(a))
+    return view
+
+
+def run_eti(ctx, streams, fib, ok, outs, history=None, cif_start=None, want_history=True, out_shift=0):
     """eti_frames_dev on host arrays: fib [n_streams][n_cif][3][32], ok [n_streams][n_cif][3], outs[i] [n_streams][n_cif]
-    [bytes] in the order of `streams` -> eti [n_streams][n_cif][6144], status, history (numpy)."""
+    [bytes] in the order of `streams` -> eti [n_streams][n_cif][6144], status, history (numpy).  out_shift: the bytes every
+    d_out pointer lies behind a 256-byte boundary (8: aligned as the contract asks and no further)."""
     import torch
     n_streams, n_cif = fib.shape[:2]
     plan = dabgpu.eti_layout(streams)
     d_fib, d_ok = _dev(torch, fib), _dev(torch, ok)
-    d_outs = [_dev(torch, o) for o in outs]
+    d_outs = [_dev_shifted(torch, o, out_shift) if out_shift else _dev(torch, o) for o in outs]
+    assert all(o.data_ptr() % 256 == out_shift for o in d_outs if o.numel())
     d_eti = torch.zeros((n_streams, n_cif, 6144), dtype=torch.uint8, device="cuda")
     d_status = torch.zeros((n_streams, n_cif, 8), dtype=torch.uint8, device="cuda")
     d_hin = None if history is None else _dev(torch, history.view(np.uint8).reshape(n_streams, -1))
