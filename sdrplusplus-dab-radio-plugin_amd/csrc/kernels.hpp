@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "wave_plan.hpp"
+
 namespace dabk {
 
 // ---- OFDM front end (ofdm_kernels.hip) -------------------------------------
@@ -445,16 +447,14 @@ struct WaveFicItem {
     int n_frames;
     uint8_t *fib, *crc_ok;
 };
-bool wave_group_supported(int nsteps);
+// (wave_group_supported: wave_plan.hpp)
 // true when `n_waves` codewords whose longest takes `max_nsteps` trellis steps are all resident at once (LDS per wave x
 // waves <= the chip's LDS): a grouped launch then finishes with its longest codeword instead of queueing kinds up
 bool wave_group_one_round(int max_nsteps, long n_waves);
 hipError_t launch_msc_decode_group(const WaveGroupItem *items, int n, hipStream_t s, const WaveFicItem *fic = nullptr);
 
 // ---- large-batch variant: one codeword per lane (viterbi_lane_kernels.hip, lane_plan.hpp) ----
-// Whole phase cycles and whole 32-bit output words; any length (a codeword whose output tile does not fit into LDS
-// writes its words directly, lane_traceback_body).
-inline bool lane_supported(int nsteps) { return nsteps >= 38 && nsteps % 6 == 0 && ((nsteps - 6) & 31) == 0; }
+// (lane_supported: wave_plan.hpp)
 // per-profile tables of the lane kernels: punct_idx [4*nsteps] (punctured index of each mother bit, -1 = erased);
 // fused_desc [4*nsteps] and fused_tiles [2*ceil(nsteps/24)] from build_lane_fused_tables (may be null: prep path)
 struct LaneTables {
@@ -694,14 +694,6 @@ hipError_t launch_mod_tii(const int8_t *prs_qt, int main_id, int sub_id, float2 
 hipError_t init_viterbi_kernel_attributes();
 hipError_t init_lane_kernel_attributes();
 
-// LDS bytes one codeword needs in the first (fallback) wave-per-codeword kernel
-inline size_t viterbi_wave_lds_bytes(int nsteps) { return size_t(nsteps) * 12 + 64; }
-// largest trellis the wave-per-codeword kernels take: it must fit one CU's 160 KB of LDS (8 B/step for DAB codeword
-// lengths) and its mother-bit positions 16 bits (CodeTables::mother_pos) -- about 680 kbit/s.  Longer codewords go to
-// the lane kernels, which keep survivors in HBM.
-inline bool viterbi_fits(int nsteps) {
-    const bool rot = nsteps >= 102 && (nsteps - 6) % 96 == 0;
-    return 4 * size_t(nsteps) <= 65535 && (rot ? size_t(nsteps) * 8 + 4096 : viterbi_wave_lds_bytes(nsteps)) <= 160 * 1024;
-}
+// (viterbi_wave_lds_bytes, viterbi_fits: wave_plan.hpp)
 
 }  // namespace dabk

@@ -22,7 +22,6 @@ using namespace dab;
 
 namespace {
 
-constexpr int WAVES_PER_WG = 4;
 constexpr int WGV = 64 * WAVES_PER_WG;
 
 __device__ __forceinline__ int parity32(unsigned x) { return __popc(x) & 1; }
@@ -269,35 +268,7 @@ __device__ __forceinline__ unsigned transpose32(unsigned x, int lane) {
     return transpose_round<1>(x, lane);
 }
 
-// The per-wave LDS slab of the rot kernel (host and device agree through this one function).
-//   survivors: one 8-byte slot per trellis step t (bit l = lane l's r of the step: flip bit q or not), at slot t + (t - 6) / seg_steps
-//              for t >= 6 -- one slot of skew per traceback segment, so that the lanes of the traceback, each reading
-//              its own segment, spread over the LDS banks (segments are 12..48 slots long: unskewed, 8- to 16-way conflicts)
-//   mother:    the depunctured codeword, consumed from a region that starts half-way up the survivors' final extent: a
-//              survivor row is only written after the codeword bytes it overlaps have been read (4 B/step consumed vs
-//              8 B/step produced); the skew slots are added to the offset
-//   out6:      the decoded bits, six per byte;  zero: six all-zero slots (what the traceback reads above the last step:
-//              nothing flips)
-struct RotLayout {
-    int seg_cycles;       // six-step phase cycles per traceback lane
-    int seg_steps;        // = 6 * seg_cycles
-    int n_lanes;          // lanes that own a segment
-    int mother_off, mother_bytes, out6_off, zero_off, total;
-};
-__host__ __device__ inline RotLayout rot_layout(int nsteps) {
-    RotLayout L;
-    const int groups = (nsteps - 6) / 6;
-    L.seg_cycles = (groups + 63) / 64;
-    L.seg_steps = 6 * L.seg_cycles;
-    L.n_lanes = (groups + L.seg_cycles - 1) / L.seg_cycles;
-    const int skew_slots = (nsteps - 6) / L.seg_steps + 2;
-    L.mother_off = 128 * ((nsteps - 6) / 32 + 1) + ((8 * skew_slots + 255) & ~255);
-    L.mother_bytes = (4 * nsteps + 255) & ~255;
-    L.out6_off = L.mother_off + L.mother_bytes;
-    L.zero_off = L.out6_off + ((groups + 255) & ~255);
-    L.total = L.zero_off + 256;                                   // (the survivors end below out6_off)
-    return L;
-}
+// (the per-wave LDS slab of the rot kernel: RotLayout / rot_layout of wave_plan.hpp, host and device agree through it)
 constexpr int ROT_WARM_CYCLES = 16;                                // 96 steps run in before a lane's own segment
 
 // One wavefront decodes codeword `cw` in its LDS slab (every wave of the workgroup must call it: it contains
@@ -591,7 +562,6 @@ __device__ __forceinline__ void msc_history_body(const MscArgs &a, size_t first,
 // with its own profile and length, in ONE launch -- one wavefront (= one workgroup) per codeword, the entry table by
 // value in the kernel arguments.  A whole multiplex is then three launches (FIC, sub-channels, history rings)
 // instead of one pair per sub-channel queueing up behind each other on the stream.
-constexpr int WAVE_GROUP_MAX = 24;
 struct WaveEntry {
     FetchMsc fetch;
     CodeTables code;
@@ -600,7 +570,6 @@ struct WaveEntry {
     int n_streams;                    // (with fetch: everything the entry's history ring update needs)
     int8_t *hist_out;
 };
-constexpr int HIST_BLOCKS = 32;       // workgroups per entry that write its history ring, behind the decoding ones
 struct WaveEntryPack {
     int n;
     int n_dec;                        // workgroups that decode (FIC + sub-channel codewords); the rest update history rings
@@ -646,8 +615,6 @@ struct HistoryPack {
     MscArgs a[WAVE_GROUP_MAX];
 };
 
-inline size_t viterbi_rot_lds_bytes(int nsteps) { return size_t(rot_layout(nsteps).total); }
-
 __global__ void msc_history_kernel(MscArgs a) {
     msc_history_body(a, size_t(blockIdx.x) * blockDim.x + threadIdx.x, size_t(gridDim.x) * blockDim.x);
 }
@@ -660,18 +627,12 @@ template <class Fetch, Tail TAIL>
 hipError_t launch_wave(Fetch f, const CodeTables &c, int n_codewords, uint8_t *out, uint8_t *crc_ok,
                        hipStream_t s) {
     if (n_codewords <= 0) return hipSuccess;
-    if (!viterbi_fits(c.nsteps) || !c.mother_pos) return hipErrorInvalidValue;     // longer codewords: lane kernels only
-    const bool rot = c.nsteps >= 102 && (c.nsteps - 6) % 96 == 0 && viterbi_rot_lds_bytes(c.nsteps) <= 160 * 1024;
-    const size_t per_wave = rot ? viterbi_rot_lds_bytes(c.nsteps) : viterbi_wave_lds_bytes(c.nsteps);
-    int lds_per_wave = int((per_wave + 255) & ~size_t(255));
-    // 4 waves per workgroup normally; long codewords (high bit rates) need more LDS per wave -> fewer waves
-    int waves = WAVES_PER_WG;
-    while (waves > 1 && size_t(lds_per_wave) * waves > 160 * 1024) waves >>= 1;
-    size_t lds = size_t(lds_per_wave) * waves;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const WaveLaunchPlan p = plan_wave_launch(c.nsteps);       // (wave_plan.hpp: kernel, LDS per wave, waves per workgroup)
+    if (!p.ok || !c.mother_pos) return hipErrorInvalidValue;   // longer codewords: lane kernels only
+    const int lds_per_wave = p.lds_per_wave, waves = p.waves;
     const unsigned grid = unsigned((n_codewords + waves - 1) / waves);
-    lds = balanced_lds_bytes(grid, lds, 8);
-    if (rot)
+    const size_t lds = balanced_lds_bytes(grid, p.lds, 8);
+    if (p.rot)
         hipLaunchKernelGGL((viterbi_rot_kernel<Fetch, TAIL>), dim3(grid), dim3(64 * waves), lds, s, f, c, n_codewords, out,
                            crc_ok, lds_per_wave);
     else
@@ -692,10 +653,6 @@ hipError_t allow_full_lds() {
 
 }  // namespace
 
-bool wave_group_supported(int nsteps) {
-    return nsteps >= 102 && (nsteps - 6) % 96 == 0 && viterbi_fits(nsteps) && viterbi_rot_lds_bytes(nsteps) <= 160 * 1024;
-}
-
 static unsigned cu_count() {
     static const unsigned n_cu = [] {
         int dev = 0;
@@ -709,8 +666,7 @@ static unsigned cu_count() {
 }
 
 bool wave_group_one_round(int max_nsteps, long n_waves) {
-    const size_t lds = (viterbi_rot_lds_bytes(max_nsteps) + 255) & ~size_t(255);
-    return n_waves >= 0 && size_t(n_waves) <= size_t(cu_count()) * (size_t(160 * 1024) / lds);
+    return wave_group_fits_one_round(max_nsteps, n_waves, cu_count());
 }
 
 hipError_t launch_msc_decode_group(const WaveGroupItem *items, int n, hipStream_t s, const WaveFicItem *fic) {
@@ -728,7 +684,7 @@ hipError_t launch_msc_decode_group(const WaveGroupItem *items, int n, hipStream_
             pack.fic_code = fic->code;
             pack.fib = fic->fib;
             pack.crc_ok = fic->crc_ok;
-            lds = (viterbi_rot_lds_bytes(fic->code.nsteps) + 255) & ~size_t(255);
+            lds = wave_group_lds_bytes(fic->code.nsteps);
         }
         for (int i = 0; i < m; i++) {
             const WaveGroupItem &it = items[i0 + i];
@@ -741,15 +697,13 @@ hipError_t launch_msc_decode_group(const WaveGroupItem *items, int n, hipStream_
             pack.e[i].n_streams = a.n_streams;
             pack.e[i].hist_out = a.hist_out;
             total += a.n_streams * a.frames_per_stream * NB_CIFS;
-            lds = std::max(lds, (viterbi_rot_lds_bytes(it.code.nsteps) + 255) & ~size_t(255));
+            lds = std::max(lds, wave_group_lds_bytes(it.code.nsteps));
             hp.a[i] = a;
             if (a.hist_out) hist_items = std::max(hist_items, size_t(a.n_streams) * 15 * a.nbits);
         }
         if (total + pack.n_fic <= 0) continue;
         pack.n_dec = total + pack.n_fic;
-        // small rings (the plugin's one stream) ride in the decoding launch; large ones keep a launch of their own, whose
-        // 256-thread workgroups move bytes faster than 64-thread ones sharing CUs with the decoder
-        const bool ride = hist_items > 0 && hist_items <= size_t(1) << 20;
+        const bool ride = wave_history_rides(hist_items);       // (small rings ride in the decoding launch: wave_plan.hpp)
         hipLaunchKernelGGL(viterbi_rot_grouped_kernel, dim3(unsigned(pack.n_dec + (ride ? m * HIST_BLOCKS : 0))), dim3(64), lds, s, pack);
         if (hist_items && !ride)
             hipLaunchKernelGGL(msc_history_grouped_kernel, dim3(unsigned(std::min<size_t>((hist_items + 255) / 256, 256)), unsigned(m)),

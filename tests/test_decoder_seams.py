@@ -1,0 +1,858 @@
+"""The channel decoder on both sides of every kernel-selection seam (rows A8-A12 and f-2 of tests/README.md).
+
+The decoder is a family of kernels chosen by codeword length and batch size: viterbi_rot_kernel with 4, 2 or 1 codewords a
+workgroup, the non-rotating viterbi_wave_kernel, the small-batch grouped wave launch, the lane kernels with an LDS output
+tile or with direct stores.  Every switch-over is a comparison against a constant next to a hardware limit (160 KiB of LDS
+per CU, the 16-bit position table, 2^20 history bytes), and the lengths next to those constants are the decoder's largest
+legal requests.  CENSUS lists every such comparison as the source writes it, the two adjacent values, and the GPU test that
+runs each.  The values are not restated here by hand: tools/decoder_plan_table.hip (plain C++ over csrc/wave_plan.hpp and
+csrc/lane_plan.hpp, built and run under the host sanitizers by test_census) prints the path of every legal length, and the
+CPU part asserts that the table changes exactly at the census's values.
+
+`-m gpu`: every case bit for bit through decoder_reference.assert_decoder (maximum likelihood by metric, then the documented
+tie rule), history_out exact, outputs between sentinel bytes, and the path asserted by the means the library gives: the
+forced-family flags, the timer's slots and parts, returned statuses.  Inputs: tests/decoder_seams.py."""
+import ctypes as C
+import functools
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+import collections
+
+import numpy as np
+import pytest
+
+import decoder_profiles as P
+import decoder_reference as R
+import decoder_seams as S
+from conftest import make_ctx
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sdrplusplus-dab-radio-plugin_amd", "csrc")
+TESTS = os.path.join(ROOT, "tests")
+FB = S.NB_FRAME_BITS
+LDS_PER_CU = 160 * 1024                                  # the hardware limit every request is held to
+ERR_CAPACITY = -6
+
+
+def _report(line):
+    print("\n[decoder_seams] " + line)
+
+
+# ============================================================================================================ the tool
+Row = collections.namedtuple("Row", "bitrate nsteps path waves lds seg_cycles n_lanes group group_lds lane tile_lds")
+
+
+@functools.lru_cache(maxsize=None)
+def plan_table(sanitize=True):
+    """Build tools/decoder_plan_table.hip as a stand-alone host program, run it, parse what it prints.  sanitize: under
+    ASan and UBSan, which is how the CPU part (test_census) runs it; the tests marked gpu take their thresholds from a
+    plain build of the same program: no sanitizer runs in a GPU test.
+    -> {"const": {name: int}, "dab": {bitrate: Row}, "plain": {nsteps: Row}}"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.fail("hipcc not found: the decoder's plan table cannot be built")
+    tmp = tempfile.mkdtemp(prefix="decoder_plan_table")
+    try:
+        exe = os.path.join(tmp, "decoder_plan_table")
+        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if sanitize else []
+        subprocess.check_call([hipcc, "-std=c++17", "--offload-arch=gfx950"] + san +
+                              ["-I" + CSRC, os.path.join(ROOT, "tools", "decoder_plan_table.hip"), "-o", exe], cwd=tmp)
+        run = subprocess.run([exe], capture_output=True, text=True, cwd=tmp)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
+    lines = run.stdout.splitlines()
+    assert lines[-1] == "decoder plan ok", lines[-5:]
+    t = {"const": {}, "dab": {}, "plain": {}}
+    for l in lines[:-1]:
+        f = l.split()
+        if f[0] == "const":
+            t["const"][f[1]] = int(f[2])
+        else:
+            r = Row(int(f[1]), int(f[2]), f[3], *[int(x) for x in f[4:]])
+            t[f[0]][r.bitrate if f[0] == "dab" else r.nsteps] = r
+    assert sorted(t["dab"]) == list(range(8, 1729, 8)) and sorted(t["plain"]) == list(range(38, 20001, 2))
+    assert all(r.nsteps == 24 * b + 6 for b, r in t["dab"].items())
+    return t
+
+
+def plain_legal(n):
+    """lengths dabgpu_viterbi takes as an argument: whole bytes of information bits"""
+    return n >= 14 and (n - 6) % 8 == 0
+
+
+def rot_length(n):
+    return (n - 6) % 96 == 0
+
+
+# ============================================================================================================ the census
+_T = "test_decoder_seams.py::"
+_MSC_ALL = [_T + "test_gpu_msc_decode_wave_family", _T + "test_gpu_msc_decode_lane_fused", _T + "test_gpu_msc_decode_lane_prep",
+            _T + "test_gpu_wave_decode_frames_with_the_fic", _T + "test_gpu_lane_decode_frames_with_the_fic"]
+_PLAIN = _T + "test_gpu_plain_viterbi_on_both_sides"
+#: One row per path-selection predicate.  lines: the comparison as the source writes it (file, text), every line that
+#: takes part.  seams: (table of the tool, last value on one side, first on the other).  values: each adjacent value and
+#: the GPU test case (with its parameter) that runs it.  tests: every GPU test that runs both sides.  path: how the case
+#: shows which path it took, or why it cannot.
+CENSUS = [
+    dict(id="waves per workgroup",
+         lines=[("wave_plan.hpp", "while (p.waves > 1 && size_t(p.lds_per_wave) * p.waves > 160 * 1024) p.waves >>= 1;")],
+         seams=[("dab", 200, 208), ("dab", 408, 416), ("plain rot", 4806, 4902), ("plain rot", 9798, 9894), ("plain wave", 3406, 3414),
+                ("plain wave", 6814, 6830)],
+         values=dict([("%d kbit/s" % b, _MSC_ALL[0] + "[eep3A-%d#0]" % b) for b in (200, 208, 408, 416)] +
+                     [("%d steps" % n, _PLAIN + "[%d]" % n) for n in (4806, 4902, 9798, 9894, 3406, 3414, 6814, 6830)]),
+         tests=_MSC_ALL[:1] + [_PLAIN],
+         path="the wave family is forced by DABGPU_FLAG_VITERBI_WAVE; the waves per workgroup leave no trace a call can read: the tool's "
+              "table says which the length takes, and plain codewords n = 1, 2, 3, 5, 9 give workgroups with inactive waves at 4 and at 2"),
+    dict(id="viterbi_fits",
+         lines=[("wave_plan.hpp", "return 4 * size_t(nsteps) <= 65535 && (rot ? size_t(nsteps) * 8 + 4096 : viterbi_wave_lds_bytes(nsteps)) <= 160 * 1024;"),
+                ("wave_plan.hpp", "if (!viterbi_fits(nsteps)) return p;"),
+                ("viterbi_kernels.hip", "if (!p.ok || !c.mother_pos) return hipErrorInvalidValue;"),
+                ("wave_plan.hpp", "inline bool wave_group_supported(int nsteps) { return wave_rot_length(nsteps) && viterbi_fits(nsteps); }"),
+                ("dabgpu_decode_api.hip", "if (!dabk::wave_group_supported(dc->prof.nsteps)) { group = false; break; }"),
+                ("dabgpu_decode_api.hip", "const bool too_long = !dabk::viterbi_fits(dc->prof.nsteps);"),
+                ("dabgpu_decode_api.hip", "if (too_long) return DABGPU_ERR_CAPACITY;"),
+                ("dabgpu_decode_api.hip", "if (too_long && !dabk::lane_supported(nsteps)) return DABGPU_ERR_CAPACITY;"),
+                ("dabgpu_decode_api.hip", "if (!dabk::lane_supported(it.code.nsteps)) return 1;")],
+         seams=[("dab", 680, 688), ("plain rot", 16326, 16422), ("plain wave", 13646, 13654)],
+         values=dict([("%d kbit/s" % b, _MSC_ALL[0] + "[eep3A-%d#0]" % b) for b in (680, 688)] +
+                     [("%d kbit/s with the FIC" % b, _MSC_ALL[3] + "[eep3A-%d#0]" % b) for b in (680, 688)] +
+                     [("%d steps" % n, _PLAIN + "[%d]" % n) for n in (16326, 16422, 13646, 13654)]),
+         tests=_MSC_ALL[:1] + [_MSC_ALL[3], _PLAIN],
+         path="status and timer slots: with the wave family forced a longer sub-channel goes to the lane kernels (include/dabgpu.h, "
+              "DABGPU_FLAG_VITERBI_WAVE: 'those go per lane') and returns DABGPU_OK; in dabgpu_decode_frames_dev it leaves the grouped wave "
+              "launch, which shows as one timed slot per sub-channel and one for the FIC; a plain length the lane kernels do not take "
+              "returns DABGPU_ERR_CAPACITY and writes nothing"),
+    dict(id="lane_tile_fits",
+         lines=[("lane_plan.hpp", "if (lane_tile_fits(e.nsteps)) plan.tile_nwords = std::max(plan.tile_nwords, (e.nsteps - 6) >> 5);"),
+                ("lane_plan.hpp", "return size_t(64) * size_t(((nsteps - 6) >> 5) | 1) * 4 <= size_t(150) * 1024;")],
+         seams=[("dab", 792, 800)],
+         values=dict([("%d kbit/s" % b, _MSC_ALL[1] + "[eep3A-%d#0]" % b) for b in (792, 800)] +
+                     [("%d kbit/s, prep kernel" % b, _MSC_ALL[2] + "[eep3A-%d#0]" % b) for b in (792, 800)] +
+                     [("%d kbit/s with the FIC" % b, _MSC_ALL[4] + "[eep3A-%d#0]" % b) for b in (792, 800)] +
+                     [("792 and 800 kbit/s by table", _T + "test_gpu_table_launch_with_a_tile_and_a_direct_entry")]),
+         tests=_MSC_ALL + [_T + "test_gpu_table_launch_with_a_tile_and_a_direct_entry", _T + "test_gpu_lane_entry_counts"],
+         path="the lane family is forced by DABGPU_FLAG_VITERBI_LANE (and by the length itself); tile or direct stores leave no trace a "
+              "call can read: the tool's table says which"),
+    dict(id="rot",
+         lines=[("wave_plan.hpp", "return nsteps >= 102 && (nsteps - 6) % 96 == 0 && viterbi_rot_lds_bytes(nsteps) <= 160 * 1024;"),
+                ("wave_plan.hpp", "const size_t per_wave = p.rot ? viterbi_rot_lds_bytes(nsteps) : viterbi_wave_lds_bytes(nsteps);"),
+                ("viterbi_kernels.hip", "if (p.rot)")],
+         seams=[],                                          # every 96 steps: lengths 6 mod 96 and not, see test_census
+         values=dict([("%d steps, 6 mod 96" % n, _PLAIN + "[%d]" % n) for n in (4806, 4902, 9798, 9894, 16326)] +
+                     [("%d steps, not" % n, _PLAIN + "[%d]" % n) for n in (3406, 3414, 6814, 6830, 13646)]),
+         tests=[_PLAIN],
+         path="no trace a call can read; lengths that are 6 mod 96 and lengths that are not, at every seam of either kernel. "
+              "`nsteps >= 102` excludes only nsteps = 6, which dabgpu_viterbi refuses (nsteps < 14)"),
+    dict(id="rot_layout",
+         lines=[("wave_plan.hpp", "L.seg_cycles = (groups + 63) / 64;"), ("wave_plan.hpp", "L.n_lanes = (groups + L.seg_cycles - 1) / L.seg_cycles;")],
+         seams=[],                                          # extremes, see ROT_LAYOUT_EXTREMES
+         values={"8 kbit/s": "test_decoder_profiles.py::test_gpu_msc_decode_of_every_profile[198]",
+                 "24 kbit/s": "test_decoder_profiles.py::test_gpu_msc_decode_of_every_profile[582]",
+                 "504 kbit/s": _MSC_ALL[0] + "[eep3A-504#0]", "520 kbit/s": _MSC_ALL[0] + "[eep3A-520#0]", "680 kbit/s": _MSC_ALL[0] + "[eep3A-680#0]"},
+         tests=[_T + "test_gpu_msc_decode_wave_family", "test_decoder_profiles.py::test_gpu_msc_decode_of_every_profile"],
+         path="the wave family is forced; 8 and 24 kbit/s are in the profile sweep (test_decoder_profiles.py)"),
+    dict(id="ride",
+         lines=[("wave_plan.hpp", "inline bool wave_history_rides(size_t hist_items) { return hist_items > 0 && hist_items <= size_t(1) << 20; }"),
+                ("viterbi_kernels.hip", "const bool ride = wave_history_rides(hist_items);"),
+                ("viterbi_kernels.hip", "hipLaunchKernelGGL(viterbi_rot_grouped_kernel, dim3(unsigned(pack.n_dec + (ride ? m * HIST_BLOCKS : 0))), dim3(64), lds, s, pack);"),
+                ("viterbi_kernels.hip", "if (hist_items && !ride)")],
+         seams=[("ring bytes", 4 * 15 * 64 * 273, 73 * 15 * 64 * 15)],
+         values={"1 048 320 bytes": _T + "test_gpu_history_rings_that_ride_and_that_do_not[4-(1,2,416)]",
+                 "1 051 200 bytes": _T + "test_gpu_history_rings_that_ride_and_that_do_not[73-(1,4,32)]",
+                 "3 streams x 360 CU": _T + "test_gpu_history_rings_that_ride_and_that_do_not[3-(0,3,480)]",
+                 "3 streams x 366 CU": _T + "test_gpu_history_rings_that_ride_and_that_do_not[3-(0,3,488)]"},
+         tests=[_T + "test_gpu_history_rings_that_ride_and_that_do_not"],
+         path="one timed slot either way: not visible; the CPU part holds the cases' ring sizes to the tool's RIDE_MAX_BYTES"),
+    dict(id="WAVE_GROUP_MAX",
+         lines=[("wave_plan.hpp", "constexpr int WAVE_GROUP_MAX = 24;"), ("viterbi_kernels.hip", "for (int i0 = 0; i0 < n; i0 += WAVE_GROUP_MAX) {"),
+                ("viterbi_kernels.hip", "if (fic && i0 == 0 && fic->n_frames > 0) {")],
+         seams=[("entries", 24, 25)],
+         values={"24 entries": _T + "test_gpu_wave_entry_counts[24]", "25 entries": _T + "test_gpu_wave_entry_counts[25]"},
+         tests=[_T + "test_gpu_wave_entry_counts"],
+         path="one timed slot either way: not visible"),
+    dict(id="LANE_GROUP_MAX",
+         lines=[("viterbi_lane_kernels.hip", "constexpr int LANE_GROUP_MAX = 16;"), ("viterbi_lane_kernels.hip", "const int per_launch = sc.table ? n : LANE_GROUP_MAX;"),
+                ("viterbi_lane_kernels.hip", "for (int i0 = 0; i0 < n; i0 += per_launch) {"),
+                ("viterbi_lane_kernels.hip", "hipEvent_t *ev = m == n ? mid : nullptr;")],
+         seams=[("entries", 16, 17)],
+         values={"16 entries": _T + "test_gpu_lane_entry_counts[16]", "17 entries": _T + "test_gpu_lane_entry_counts[17]"},
+         tests=[_T + "test_gpu_lane_entry_counts"],
+         path="timer parts: a list that is one pack leaves them, two packs leave none"),
+    dict(id="LANE_MIN_CODEWORDS",
+         lines=[("dabgpu_ctx.hpp", "constexpr int LANE_MIN_CODEWORDS = 24576;"),
+                ("dabgpu_decode_api.hip", "return (ctx->lane_mode < 0 && n_codewords >= LANE_MIN_CODEWORDS) ? 1 : 0;"),
+                ("dabgpu_decode_api.hip", "const int policy = lane_policy(ctx, by_table ? long(LANE_MIN_CODEWORDS) : total_cw, too_long);")],
+         seams=[("codewords", 24575, 24576)],
+         values={"24 575 and 24 576 codewords": _T + "test_gpu_plain_codewords_at_the_lane_threshold"},
+         tests=[_T + "test_gpu_plain_codewords_at_the_lane_threshold"],
+         path="plain codewords are not timed: not visible"),
+    dict(id="wave_group_one_round",
+         lines=[("wave_plan.hpp", "return n_waves >= 0 && size_t(n_waves) <= size_t(n_cu) * (size_t(160 * 1024) / lds);"),
+                ("dabgpu_decode_api.hip", "if (group && plan.n == 1 && !dabk::wave_group_one_round(std::max(items[0].code.nsteps, ctx->fic.prof.nsteps), 2 * cw_each))")],
+         seams=[],                                          # depends on the device's CU count
+         values={"F frames": _T + "test_gpu_fic_with_one_sub_channel_at_the_last_resident_frame_count[last resident]",
+                 "F + 1 frames": _T + "test_gpu_fic_with_one_sub_channel_at_the_last_resident_frame_count[one more]"},
+         tests=[_T + "test_gpu_fic_with_one_sub_channel_at_the_last_resident_frame_count"],
+         path="timer slots: grouped, the FIC has none of its own"),
+]
+#: rot_layout: bit rate -> (seg_cycles, n_lanes, last segment whole); where each runs
+ROT_LAYOUT_EXTREMES = {8: (1, 32, True), 24: (2, 48, True), 504: (32, 63, True), 520: (33, 64, False), 680: (43, 64, False)}
+
+_FUNCTIONS = {"launch_wave": "viterbi_kernels.hip", "launch_msc_decode_group": "viterbi_kernels.hip", "launch_lane": "viterbi_lane_kernels.hip",
+              "decode_lane": "dabgpu_decode_api.hip", "decode_subchannels": "dabgpu_decode_api.hip", "msc_decode_one": "dabgpu_decode_api.hip",
+              "plan_lane_launch": "lane_plan.hpp", "lane_item_fusable": "lane_plan.hpp", "plan_wave_launch": "wave_plan.hpp"}
+_DS, _LO, _GL, _DP, _LC, _EN = ("test_decoder_status.py::", "test_lane_one_path.py::", "test_gpu_lane.py::", "test_decoder_profiles.py::",
+                                "test_long_codewords.py::", "test_ensembles.py::")
+_ENTRIES = "the entry count: 1 (msc_decode_dev), 3 (the pairs with the FIC), 16 | 17, 24 | 25"
+#: every other `if` / `?:` / `while` / `for` of those functions that compares a length, a count or a byte size: the test that holds it
+CHECKED_ELSEWHERE = {
+    # loops over the entries of a list: their trip count is the entry count
+    "for (int i = 0; i < m; i++) {": _T + "test_gpu_wave_entry_counts",
+    "for (int i = 0; i < n; i++) {": _T + "test_gpu_lane_entry_counts",
+    "for (int i = 0; i < n; i++)": _T + "test_gpu_lane_entry_counts",
+    "for (const dabk::LaneItem &it : items) {": _T + "test_gpu_lane_entry_counts",
+    "for (const dabk::LaneItem &it : items)": _T + "test_gpu_lane_entry_counts",
+    "for (int i = 0; group && i < plan.n; i++) {": _T + "test_gpu_wave_entry_counts",
+    "for (int i = 0; i < plan.n; i++) {": _T + "test_gpu_wave_decode_frames_with_the_fic",
+    "for (int i = 0; i < n; i++) plan.item[size_t(i)] = i;": _T + "test_gpu_lane_entry_counts",
+    "for (int k = 0; k < n; k++) {": _T + "test_gpu_lane_entry_counts",
+    "if (n_codewords <= 0) return hipSuccess;": _LC + "test_every_entry_point_accepts_empty_batches",
+    "if (n <= 0) return hipSuccess;": _LC + "test_every_entry_point_accepts_empty_batches",
+    "if (total + pack.n_fic <= 0) continue;": _LC + "test_every_entry_point_accepts_empty_batches",
+    "if (plan.total_groups == 0) continue;": _LC + "test_every_entry_point_accepts_empty_batches",
+    "if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;": _LC + "test_every_entry_point_accepts_empty_batches",
+    "if (plan.fused && n == 1 && one.kind != LaneItem::SUBCHANNEL) {": _LO + "test_plain_codewords_as_a_pack_of_one",
+    "if (!dabk::lane_item_fusable(it)) return 1;": _EN + "test_shapes_that_do_not_qualify_give_the_same_bytes",
+    "if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));": _EN + "test_one_call_decodes_every_ensembles_own_plan",
+    "bool group = plan.n >= 1 && plan.n + (d_fib ? 1 : 0) >= 2 && lane_policy(ctx, cw_each, false) == 0 && d_soft && n_streams > 0 &&":
+        _GL + "test_decode_frames_equals_separate_calls",
+    "if (!ctx || !d_soft || !d_out || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;": _DS + "test_single_fault_status",
+    "if (soft_stride < size_t(NB_FRAME_BITS) && size_t(n_streams) * frames_per_stream > 1) return DABGPU_ERR_ARG;": _DS + "test_single_fault_status",
+    "e.dec = reinterpret_cast<uint2 *>(scratch + (fused ? 0 : words * 4));": _DP + "test_gpu_msc_decode_of_every_profile",
+    "scratch += words * (fused ? 8 : 12);": _DP + "test_gpu_fused_decode_frames_of_every_stream",
+    "plan.prio_nsteps = (plan.total_groups <= resident_groups && longest > shortest) ? longest : 0;":
+        _GL + "test_bench_shape_grouped_launch_equals_the_oracle_on_noise",
+}
+#: ... those no call through the ABI reaches, so that no test can hold them: the launchers' own guards behind a caller that
+#: has asked the same question (line -> why)
+UNREACHABLE = {
+    "if (!wave_group_supported(fic->code.nsteps)) return hipErrorInvalidValue;": "the FIC has 774 steps",
+    "if (!wave_group_supported(it.code.nsteps)) return hipErrorInvalidValue;":
+        "decode_subchannels asks wave_group_supported of every entry before it builds the list",
+    "if (!sc.base || sc.bytes < lane_scratch_bytes(items, n, sc.unfused)) return hipErrorInvalidValue;":
+        "decode_lane sizes the scratch with the same lane_scratch_bytes before the launch",
+    "if (!lane_supported(items[i].code.nsteps) || (reinterpret_cast<uintptr_t>(items[i].args.out) & 3)) return hipErrorInvalidValue;":
+        "decode_lane asks lane_supported of every item first (the other half compares an alignment, no size)",
+    "if (!plan.fused && (n != 1 || sc.table)) return hipErrorInvalidValue;":
+        "decode_lane sends several items, or a table, only when every item is fusable and the context is not unfused",
+    "if (too_long && !dabk::lane_supported(dc->prof.nsteps)) return DABGPU_ERR_CAPACITY;":
+        "every EEP and UEP length is 96 k + 6, which the lane kernels take (test_decoder_status.py's docstring)",
+}
+#: ... and those that compare no size: pointers, flags, kinds, statuses
+NOT_A_SIZE = [
+    "if (a.hist_out) hist_items = std::max(hist_items, size_t(a.n_streams) * 15 * a.nbits);", "if (mid_recorded) *mid_recorded = false;",
+    "if (sc.table) {", "if (err != hipSuccess) return err;", "if (any_history) hipLaunchKernelGGL(lane_history_ragged_kernel, dim3(RAGGED_HIST_BLOCKS, unsigned(n)), dim3(256), 0, s,", "if (one.kind == LaneItem::FIC)",
+    "} else if (plan.fused) {", "if (ev) (void)hipEventRecord(ev[0], s);", "if (ev) (void)hipEventRecord(ev[1], s);",
+    "if (ev && mid_recorded) *mid_recorded = true;", "if (!sc.table)", "if (items[i].kind == LaneItem::SUBCHANNEL) {",
+    "if (policy == 0) return 1;", "if (!single) {", "if (ctx->lane_unfused) return 1;",
+    "if (!lane_scratch(ctx, dabk::lane_scratch_bytes(items.data(), n, ctx->lane_unfused), s, &rc))",
+    "return rc ? rc : (single && policy == 2) ? DABGPU_ERR_NOMEM : 1;", "if (by_table) {", "if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &lsc.table)) return 1;",
+    "if (timer >= 0) tm.emplace(ctx, timer, s);", "const hipError_t e = dabk::launch_lane(items.data(), n, lsc, s, (tm && !single) ? tm->mids() : nullptr, &parts);", "if (tm && parts) tm->mids_recorded();",
+    "return e == hipSuccess ? 0 : DABGPU_ERR_HIP;", "it.args = msc_args(plan.sc[i], d_soft, soft_stride, n_streams, frames_per_stream, d_history_in ? d_history_in[i] : nullptr,",
+    "d_history_out ? d_history_out[i] : nullptr, d_out[i]);", "d_history_in ? d_history_in[i] : nullptr, d_history_out ? d_history_out[i] : nullptr,",
+    "if (it.args.hist_in && it.args.hist_in == it.args.hist_out) return DABGPU_ERR_ARG;", "if (group) {", "HIP_TRY(dabk::launch_msc_decode_group(items.data(), int(items.size()), s, d_fib ? &fic : nullptr));", "if (d_fib) {",
+    "if (rc) return rc;", "if (d_history_in && d_history_in == d_history_out) return DABGPU_ERR_ARG;", "if (!dc && (rc = lookup_code(ctx, sc, &dc))) return rc;",
+    "if ((rc = decode_lane(ctx, {msc_item(dc, a)}, too_long, TIMER_MSC, false, stream)) <= 0) return rc;", "if (longest_first)",
+    "e.crc_ok = it.kind == LaneItem::FIC ? it.crc_ok : nullptr;",
+]
+
+
+def _function_body(src, fn):
+    m = re.search(r"^[^\n;{}]*\b%s\([^;{]*\)\s*\{" % fn, src, re.M)
+    assert m, fn
+    i, depth = m.end(), 1
+    while depth:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+    return src[m.start():i]
+
+
+def _param_ids(test):
+    """The ids pytest gives the cases of "module.py::function", from the function's own parametrize mark."""
+    import importlib
+    mod, fn = test.split("::")
+    marks = [m for m in getattr(getattr(importlib.import_module(mod[:-3]), fn), "pytestmark", []) if m.name == "parametrize"]
+    assert len(marks) == 1, test
+    names, values = marks[0].args[0], list(marks[0].args[1])
+    ids = marks[0].kwargs.get("ids") or str
+    if "," in names:
+        return ["-".join(ids(v) for v in row) for row in values]
+    return [ids(v) for v in values]
+
+
+def _seams_of(rows, key):
+    """[(last, first)] wherever key(row) changes between neighbours of the sorted table `rows` {value: Row}"""
+    vals = sorted(rows)
+    return [(a, b) for a, b in zip(vals, vals[1:]) if key(rows[a]) != key(rows[b])]
+
+
+def test_census():
+    t = plan_table()
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted({f for row in CENSUS for f, _ in row["lines"]} | set(_FUNCTIONS.values()))}
+    readme = open(os.path.join(TESTS, "README.md")).read()
+    for row in CENSUS:
+        for f, line in row["lines"]:
+            assert line in src[f], (row["id"], f, line)
+        for test in row["tests"]:
+            mod, fn = test.split("::")
+            assert re.search(r"^def %s\(" % re.escape(fn), open(os.path.join(TESTS, mod)).read(), re.M), test
+            assert "`%s`" % test in readme, "tests/README.md does not name " + test
+        for value, case in row["values"].items():                                  # each value's own case: the test and its parameter
+            test, _, param = case.partition("[")
+            assert test in row["tests"], (row["id"], case)
+            if param:
+                assert param[:-1] in _param_ids(test), (row["id"], value, case)
+        for _, a, b in row["seams"]:                                                # both sides of every seam have a case
+            assert all(str(v) in " ".join(row["values"]).replace(" ", "") for v in (a, b)), (row["id"], a, b)
+        assert "`%s`" % row["lines"][0][1] in readme, "tests/README.md does not list " + row["lines"][0][1]
+    census = {kind: sorted((a, b) for row in CENSUS for k, a, b in row["seams"] if k == kind) for kind in
+              ("dab", "plain rot", "plain wave", "ring bytes", "entries", "codewords")}
+
+    # ---- sub-channels: the table changes path, waves per workgroup, grouped launch or tile exactly at the census's values
+    dab = t["dab"]
+    assert _seams_of(dab, lambda r: (r.path, r.waves, r.group, r.tile_lds > 0)) == census["dab"]
+    assert [(dab[a].path, dab[a].waves, dab[b].path, dab[b].waves) for a, b in census["dab"]] == [
+        ("rot", 4, "rot", 2), ("rot", 2, "rot", 1), ("rot", 1, "lane_tile", 0), ("lane_tile", 0, "lane_direct", 0)]
+    assert all(r.lane for r in dab.values())                                        # every sub-channel length: the lane kernels take it
+    assert all(r.group == (r.path == "rot") for r in dab.values())
+    assert {b for b, r in dab.items() if r.path == "rot"} == set(range(8, 681, 8))
+    # ---- plain codewords: the lengths dabgpu_viterbi takes, rot lengths (6 mod 96) and the others apart
+    plain = {n: r for n, r in t["plain"].items() if plain_legal(n)}
+    rot = {n: r for n, r in plain.items() if rot_length(n)}
+    wave = {n: r for n, r in plain.items() if not rot_length(n)}
+    assert all(r.path in ("rot", "lane_tile", "lane_direct") for r in rot.values()) and all(r.path in ("wave", "refused") for r in wave.values())
+    assert all(r.lane == rot_length(n) for n, r in plain.items() if n >= 38)
+    rot_seams = _seams_of(rot, lambda r: (r.path, r.waves))
+    assert rot_seams[:3] == census["plain rot"] and rot_seams[3:] == [(19110, 19206)]   # (the last: lane_tile_fits, run as 792 | 800 kbit/s)
+    assert _seams_of(wave, lambda r: (r.path, r.waves)) == census["plain wave"]
+    assert [(wave[a].waves, wave[b].waves) for a, b in census["plain wave"]] == [(4, 2), (2, 1), (1, 0)] and wave[13654].path == "refused"
+    assert min(wave) == 38 and wave[38].waves == 4 and rot[102].path == "rot"       # nothing changes below: `nsteps >= 102` is nsteps != 6
+    # every DAB length is a plain rot length with the same answers
+    assert all(rot[r.nsteps][2:] == r[2:] for r in dab.values() if r.nsteps <= 20000)
+    # ---- the largest requests
+    worst = max(list(dab.values()) + list(t["plain"].values()), key=lambda r: max(r.lds, r.group_lds, r.tile_lds))
+    assert max(worst.lds, worst.group_lds, worst.tile_lds) <= LDS_PER_CU
+    legal = list(dab.values()) + list(plain.values())
+    assert max(r.lds for r in legal) == LDS_PER_CU and wave[3406].lds == wave[6814].lds == wave[13646].lds == LDS_PER_CU
+    assert (dab[200].lds, dab[408].lds, dab[680].lds, dab[792].tile_lds) == (162816, 162816, 134912, 152320)
+    assert max(r.tile_lds for r in legal) == rot[19110].tile_lds == 152832
+    _report("largest dynamic LDS requests: launch_wave %d B (plain 3 406 / 6 814 / 13 646 steps), rot kernel %d B (200 and 408 kbit/s), "
+            "lane traceback tile %d B (plain 19 110 steps; %d B at 792 kbit/s)" % (LDS_PER_CU, dab[200].lds, rot[19110].tile_lds, dab[792].tile_lds))
+    # ---- rot_layout
+    for b, (seg, lanes, whole) in ROT_LAYOUT_EXTREMES.items():
+        groups = (dab[b].nsteps - 6) // 6
+        assert (dab[b].seg_cycles, dab[b].n_lanes, lanes * seg == groups) == (seg, lanes, whole), b
+    grouped = [r for r in dab.values() if r.group]
+    assert {r.seg_cycles for r in grouped} == set(range(1, 44)) and (min(r.n_lanes for r in grouped), max(r.n_lanes for r in grouped)) == (32, 64)
+    assert all(dab[b].seg_cycles == (b + 15) // 16 for b in dab if dab[b].group)    # a step at every 16 kbit/s
+    ran = {k[2] for k in S.MAIN + S.WAVE_ONLY} | {P.profile(k).nbytes // 3 for k in P.PROFILES}
+    assert set(ROT_LAYOUT_EXTREMES) <= ran
+    # ---- history rings, entry counts, the batch threshold: the cases sit where the tool and the source put the threshold
+    ride_max = t["const"]["RIDE_MAX_BYTES"]
+    sizes = {(n, key): S.ring_bytes(n, key) for n, key in S.RINGS}                  # the largest ring of the list, as the launcher takes it
+    assert all(v == n * 15 * 64 * S.profile(key + (0,)).size_cu for (n, key), v in sizes.items())   # ... is the named sub-channel's
+    assert sorted(sizes.values()) == [3 * 15 * 64 * 360, 4 * 15 * 64 * 273, 73 * 15 * 64 * 15, 3 * 15 * 64 * 366]
+    assert census["ring bytes"] == [(max(v for v in sizes.values() if v <= ride_max), min(v for v in sizes.values() if v > ride_max))]
+    # no legal list comes closer: ring bytes are 960 x streams x CU, and no product of a stream count with a size in CU that a
+    # sub-channel of the grouped launch can have is 1093 or 1094 (1095 = 73 streams x 15 CU, EEP 4-B at 32 kbit/s)
+    cu = {R.eep_profile(o, lv, b).size_cu for o, step in ((0, 8), (1, 32)) for lv in (1, 2, 3, 4) for b in range(step, 681, step)}
+    cu |= {R.uep_profile(i).size_cu for i in range(64)}
+    products = {n * c for c in cu for n in range(1, 1100 // c + 1)}
+    assert 1092 in products and 1095 in products and not products & {1093, 1094} and 960 * 1092 <= ride_max < 960 * 1093
+    assert all(dab[key[2]].group for _, key in S.RINGS)
+    assert census["entries"] == [(16, 17), (24, 25)] and t["const"]["WAVE_GROUP_MAX"] == 24
+    assert int(re.search(r"constexpr int LANE_GROUP_MAX = (\d+);", src["viterbi_lane_kernels.hip"]).group(1)) == 16
+    assert max(len(lst) for lst in P.streams()) >= 25 and len(S.MANY) == 17 and sum(S.profile(k).size_cu for k in S.MANY) <= 864
+    assert census["codewords"] == [(24575, 24576)]
+    assert int(re.search(r"constexpr int LANE_MIN_CODEWORDS = (\d+);", src["dabgpu_ctx.hpp"]).group(1)) == 24576
+    # ---- every sub-channel case is adjacent to its seam, and the GPU tests' parameters are the census's values
+    assert sorted(S.SEAM_RATES) == sorted({v for a, b in census["dab"] for v in (a, b)}) and S.LANE_RATES == (504, 520)
+    assert sorted(PLAIN_LENGTHS) == sorted({v for k in ("plain rot", "plain wave") for a, b in census[k] for v in (a, b)})
+    # ---- no comparison of a length, a count or a byte size in the launch functions is left out
+    # (whole lines, comments and indentation apart: a new short condition cannot hide inside a listed longer one)
+    listed = set([line for row in CENSUS for _, line in row["lines"]] + list(CHECKED_ELSEWHERE) + list(UNREACHABLE) + NOT_A_SIZE)
+    found = set()
+    for fn, f in _FUNCTIONS.items():
+        for raw in _function_body(src[f], fn).splitlines():
+            code = raw.split("//")[0].strip()
+            if re.search(r"\bif \(|\bwhile \(|\bfor \(| \? ", code):
+                assert code in listed, (fn, code)
+                found.add(code)
+    stale = (set(CHECKED_ELSEWHERE) | set(UNREACHABLE) | set(NOT_A_SIZE)) - found
+    assert not stale, stale                                                        # nothing listed that the functions no longer hold
+    assert not (set(CHECKED_ELSEWHERE) & set(UNREACHABLE)) and all(UNREACHABLE.values())
+    for line, test in CHECKED_ELSEWHERE.items():
+        assert any(line in s for s in src.values()), line
+        mod, fn = test.split("::")
+        assert re.search(r"^def %s\(" % re.escape(fn), open(os.path.join(TESTS, mod)).read(), re.M), test
+    for line in NOT_A_SIZE:
+        assert any(line in s for s in src.values()), line
+
+
+def test_builder_takes_nothing_from_the_code_under_test():
+    src = open(os.path.join(TESTS, "decoder_seams.py")).read()
+    imports = sorted(l.strip() for l in src.splitlines() if l.strip().startswith(("import ", "from ")))
+    assert imports == ["import decoder_reference as R", "import functools", "import numpy as np"], imports
+
+
+def test_streams_deinterleave_to_the_codewords():
+    """The reference's time_deinterleave over a built stream gives back the 16 codewords, history_out is the last 15 rows and
+    equals history_in, a run that is no whole period continues the cycle, 12 of 16 codewords are noise."""
+    for key in S.MAIN[:2] + ((1, 4, 800, 0),):
+        p = S.profile(key)
+        frames = S.stream_frames(S.pair(key))
+        sub = frames[:, R.NB_FIC_BITS:].reshape(16, R.NB_CIF_BITS)[:, 64 * 3:64 * (3 + p.size_cu)]
+        assert (sub == S.period(key)).all()
+        lf, hist = R.time_deinterleave(sub, S.history(key))
+        assert (lf == S.codewords(key)).all() and (hist == S.history(key)).all()
+        rows, h5 = S.cifs_of(key, 20)
+        lf5, hist5 = R.time_deinterleave(rows, S.history(key))
+        assert (lf5 == S.codewords(key)[np.arange(20) % 16]).all() and (hist5 == h5).all() and (h5 == rows[-15:]).all()
+        c = S.codewords(key)
+        assert len(np.unique(c[10:])) <= 16 and np.abs(c[4:10].astype(int)).max() > 120 and len(S.NOISE) == 12
+        assert (frames[:, :R.NB_FIC_BITS] == S.fic_noise()).all() and np.abs(frames[:, R.NB_FIC_BITS:R.NB_FIC_BITS + 64 * 3].astype(int)).max() > 100
+        _, d = S.ref(key)
+        assert d.unique[list(S.SIGNAL)].all(), S.name(key)                          # signal at 8 dB: one optimum
+
+
+@pytest.mark.parametrize("key", S.MAIN, ids=S.name)
+def test_structural_mutants_are_rejected(key):
+    """By the reference alone, as test_decoder_profiles.py does for the sweep: a decoder that reads the sub-channel one bit
+    late and one that shifts the tail's puncturing vector by one return bytes the assertion rejects on the 12 noise
+    codewords.  (A single lost soft bit is a matter of shares, which that file's study measures: up to 5 % of such mutants
+    pass there, and here the last kept bit of the 200 kbit/s codewords can be lost unseen, so it is no hard condition.)"""
+    p = S.profile(key)
+    noise = list(S.NOISE)
+    frames = S.stream_frames(S.pair(key))
+    cifs = frames[:, R.NB_FIC_BITS:].reshape(16, R.NB_CIF_BITS)[:, 64 * 3 + 1:64 * (3 + p.size_cu) + 1]
+    late = R.time_deinterleave(cifs, cifs[1:])[0][noise]
+    mutants = {"one bit late": R.depuncture(late, p.mask),
+               "tail shifted": R.depuncture(S.codewords(key)[noise], np.concatenate([p.mask[:-24], np.roll(R.V_TAIL, 1)]))}
+    got = P.reference_bytes(np.concatenate(list(mutants.values())))
+    mother, d = S.ref(key)
+    for i, kind in enumerate(mutants):
+        with pytest.raises(AssertionError):
+            R.assert_decoder(got[12 * i:12 * (i + 1)], mother[noise], d.lanes(np.array(noise)), True, kind)
+
+
+@pytest.mark.parametrize("nsteps", sorted({S.profile(k).nsteps for k in S.all_keys()}))
+def test_oracle_on_every_sub_channel_input(built, nsteps):
+    from oracle import oracle as O
+    for k in S.all_keys():
+        p = S.profile(k)
+        if p.nsteps != nsteps:
+            continue
+        mother, d = S.ref(k)
+        rows = np.concatenate([S.history(k), S.period(k)])
+        got = np.stack([O.msc_decode_lf(O.time_deinterleave(rows[t:t + 16])[:p.kept], p.mask, p.nsteps) for t in range(16)])
+        R.assert_decoder(got, mother, d, True, "oracle, " + S.name(k))
+
+
+PLAIN_LENGTHS = (3406, 3414, 4806, 4902, 6814, 6830, 9798, 9894, 13646, 13654, 16326, 16422)
+PLAIN_COUNTS = (1, 2, 3, 5, 9)
+
+
+@pytest.mark.parametrize("nsteps", [n for n in PLAIN_LENGTHS if n != 13654])
+def test_oracle_on_every_plain_input(built, nsteps):
+    from oracle import oracle as O
+    for kind, (mother, d) in S.plain_ref(nsteps).items():
+        got = np.stack([np.packbits(O.viterbi(m.astype(np.int8))) for m in mother])
+        R.assert_decoder(got, mother, d, False, "oracle, %d steps, %s" % (nsteps, kind))
+
+
+# ================================================================================================================ GPU
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.array(a)).to(torch.device("cuda", 0))     # (a copy: the builder's arrays are read-only)
+
+
+class Guarded:
+    """n bytes of device memory between two 64-byte runs of sentinel bytes, the payload 0xA5 as well"""
+
+    def __init__(self, n, dtype=np.uint8):
+        import torch
+        self.n, self.dtype = int(n), dtype
+        self.buf = torch.full((self.n + 128,), 0xA5, dtype=torch.uint8, device=torch.device("cuda", 0))
+        self.ptr = self.buf.data_ptr() + 64
+        assert self.ptr % 16 == 0
+
+    def get(self):
+        h = self.buf.cpu().numpy()
+        assert (h[:64] == 0xA5).all() and (h[64 + self.n:] == 0xA5).all(), "written outside the output"
+        return h[64:64 + self.n].view(self.dtype)
+
+    def untouched(self):
+        return bool((self.buf.cpu().numpy() == 0xA5).all())
+
+
+def _sc(key, start):
+    import dabgpu
+    p = S.profile(key)
+    sc = dabgpu.subchannel(start, key[2], level=key[1], eep_type=key[0])
+    assert sc.length == p.size_cu and sc.bitrate_kbps * 3 == p.nbytes and sc.start_address == start
+    return sc
+
+
+def _slots(c, which):
+    import dabgpu
+    try:
+        return c.mean_kernel_ms(which)[1]
+    except dabgpu.DabGpuError:
+        return 0
+
+
+def _assert_periods(out, key, n_cw, what):
+    """out [n_cw][nbytes] of a cyclic run: codeword t is codeword t mod 16, the first 16 (or fewer) through the assertion"""
+    mother, d = S.ref(key)
+    got = out.reshape(n_cw, -1)
+    first = min(n_cw, 16)
+    assert (got == got[np.arange(n_cw) % 16]).all(), "%s: the copies of a codeword differ, %s" % (what, S.name(key))
+    R.assert_decoder(got[:first], mother[:first], d.lanes(np.arange(first)), True, "%s, %s" % (what, S.name(key)))
+
+
+def _assert_fic(fib, ok, n_frames, what):
+    ref = S.fic_ref()
+    f, o = fib.reshape(n_frames, 4, 96), ok.reshape(n_frames, 12)
+    assert (f == f[np.arange(n_frames) % 4]).all() and (o == o[np.arange(n_frames) % 4]).all(), what
+    first = min(n_frames, 4)
+    R.assert_decoder(f[:first].reshape(-1, 96), ref.mother[:4 * first], ref.decoded.lanes(np.arange(4 * first)), True, what + ", FIC")
+    assert (o[:first] == ref.crc_ok[:first]).all(), what
+
+
+@functools.lru_cache(maxsize=4)
+def _frames_dev(entries, fps):
+    return _dev(np.tile(S.stream_frames(entries), (fps // 4, 1)))
+
+
+@pytest.fixture(scope="module")
+def wave_ctx(built):
+    c = make_ctx(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def lane_ctx(built):
+    c = make_ctx(1)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def prep_ctx(built):
+    c = make_ctx(1, unfused=True)
+    yield c
+    c.close()
+
+
+def _msc_one(c, key, fps, what):
+    """dabgpu_msc_decode_dev of the pair's first sub-channel, one stream of fps frames: one timed slot, no parts"""
+    p = S.profile(key)
+    soft = _frames_dev(S.pair(key), fps)
+    hin = _dev(S.history(key))
+    out, hout = Guarded(4 * fps * p.nbytes), Guarded(15 * 64 * p.size_cu, np.int8)
+    assert all(x % 16 == 0 for x in (soft.data_ptr(), hin.data_ptr(), out.ptr, hout.ptr)) and (4 * fps) % 16 == 0
+    c.set_timing(True)
+    try:
+        c.msc_decode_dev(_sc(key, 3), soft.data_ptr(), FB, 1, fps, hin.data_ptr(), hout.ptr, out.ptr, None)
+        c.sync()
+        assert (_slots(c, 2), _slots(c, 4)) == (1, 0), what
+    finally:
+        c.set_timing(False)
+    _assert_periods(out.get(), key, 4 * fps, what)
+    assert (hout.get().reshape(15, -1) == S.history(key)).all(), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", S.MAIN + S.WAVE_ONLY, ids=S.name)
+def test_gpu_msc_decode_wave_family(wave_ctx, key):
+    """DABGPU_FLAG_VITERBI_WAVE, four frames: viterbi_rot_kernel with 4 | 2 | 1 codewords a workgroup at 200 | 208 and 408 | 416
+    kbit/s (workgroups of 162 816 B at 200 and 408), 63 | 64 traceback lanes at 504 | 520, its last length at 680; at 688 and
+    above the context's flag does not hold ('those go per lane', include/dabgpu.h): DABGPU_OK and the lane kernels' bytes."""
+    _msc_one(wave_ctx, key, 4, "wave family, msc_decode_dev")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", S.MAIN, ids=S.name)
+def test_gpu_msc_decode_lane_fused(lane_ctx, key):
+    """DABGPU_FLAG_VITERBI_LANE, sixteen frames = one whole group, everything on 16 bytes: the fused forward pass; the
+    traceback through its LDS tile up to 792 kbit/s (152 320 B), with direct stores at 800."""
+    _msc_one(lane_ctx, key, 16, "lane family, fused, msc_decode_dev")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", S.MAIN, ids=S.name)
+def test_gpu_msc_decode_lane_prep(prep_ctx, key):
+    """The same call with DABGPU_FLAG_LANE_UNFUSED: lane_prep_kernel, lane_forward_kernel, the same traceback."""
+    _msc_one(prep_ctx, key, 16, "lane family, prep kernel, msc_decode_dev")
+
+
+def _decode_frames_pair(c, key, fps, what):
+    """dabgpu_decode_frames_dev: the FIC, the sub-channel and the 64 kbit/s one behind it.  -> (msc slots, parts, fic slots)"""
+    entries = S.pair(key)
+    soft = _frames_dev(entries, fps)
+    hin = [_dev(S.history(k)) for k, _ in entries]
+    outs = [Guarded(4 * fps * S.profile(k).nbytes) for k, _ in entries]
+    houts = [Guarded(15 * 64 * S.profile(k).size_cu, np.int8) for k, _ in entries]
+    fib, ok = Guarded(fps * 12 * 32), Guarded(fps * 12)
+    c.set_timing(True)
+    try:
+        c.decode_frames_dev(soft.data_ptr(), FB, 1, fps, fib.ptr, ok.ptr, [_sc(k, s) for k, s in entries], [h.data_ptr() for h in hin],
+                            [h.ptr for h in houts], [o.ptr for o in outs], None)
+        c.sync()
+        seen = (_slots(c, 2), _slots(c, 4), _slots(c, 1))
+    finally:
+        c.set_timing(False)
+    for (k, _), o, h in zip(entries, outs, houts):
+        _assert_periods(o.get(), k, 4 * fps, what)
+        assert (h.get().reshape(15, -1) == S.history(k)).all(), (what, S.name(k))
+    _assert_fic(fib.get(), ok.get(), fps, what)
+    return seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", S.MAIN + S.WAVE_ONLY, ids=S.name)
+def test_gpu_wave_decode_frames_with_the_fic(wave_ctx, key):
+    """The small-batch grouped wave launch, four frames: the FIC's, the sub-channel's and a 64 kbit/s sub-channel's codewords in
+    one launch whose LDS is the longest codeword's slab (one timed slot, none for the FIC), up to 680 kbit/s; at 688 the list
+    leaves the grouped launch: the FIC alone and one call per sub-channel (two slots and one)."""
+    seen = _decode_frames_pair(wave_ctx, key, 4, "wave family, decode_frames_dev")
+    assert seen == ((1, 0, 0) if plan_table(False)["dab"][key[2]].group else (2, 0, 1)), seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", S.MAIN, ids=S.name)
+def test_gpu_lane_decode_frames_with_the_fic(lane_ctx, key):
+    """The grouped lane launch, sixteen frames: three entries by value, the tile sized by the longest entry whose tile fits
+    (at 800 kbit/s that is the 64 kbit/s entry's, while the 800 writes directly).  One timed slot with its parts."""
+    assert _decode_frames_pair(lane_ctx, key, 16, "lane family, decode_frames_dev") == (1, 1, 0)
+
+
+@pytest.mark.gpu
+def test_gpu_table_launch_with_a_tile_and_a_direct_entry(built):
+    """dabgpu_decode_ensembles_dev by table: three streams whose one sub-channel each -- 792, 800 and 64 kbit/s -- starts at CU 0.
+    The launch's tile is sized by the 792 (152 320 B) while the 800 writes directly."""
+    from test_ensembles import took_the_grouped_launch
+    keys = [lst[0] for lst in S.TABLE]
+    soft = _dev(np.concatenate([np.tile(S.stream_frames(((k, 0),)), (4, 1)) for k in keys]))
+    hin = [_dev(S.history(k)) for k in keys]
+    outs = [Guarded(64 * S.profile(k).nbytes) for k in keys]
+    houts = [Guarded(15 * 64 * S.profile(k).size_cu, np.int8) for k in keys]
+    fib, ok = Guarded(48 * 12 * 32), Guarded(48 * 12)
+    c = make_ctx(None, max_frames=64)
+    try:
+        c.set_timing(True)
+        c.decode_ensembles_dev(soft.data_ptr(), FB, 3, 16, fib.ptr, ok.ptr, [[_sc(k, 0)] for k in keys], [[h.data_ptr()] for h in hin],
+                               [[h.ptr] for h in houts], [[o.ptr] for o in outs], None)
+        c.sync()
+        assert took_the_grouped_launch(c)
+    finally:
+        c.close()
+    for k, o, h in zip(keys, outs, houts):
+        _assert_periods(o.get(), k, 64, "decode_ensembles_dev")
+        assert (h.get().reshape(15, -1) == S.history(k)).all(), S.name(k)
+    f, o = fib.get().reshape(3, 16 * 12 * 32), ok.get().reshape(3, 16 * 12)
+    for s in range(3):
+        _assert_fic(f[s], o[s], 16, "decode_ensembles_dev, stream %d" % s)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_streams,key", S.RINGS, ids=lambda v: str(v).replace(" ", ""))
+def test_gpu_history_rings_that_ride_and_that_do_not(wave_ctx, n_streams, key):
+    """The grouped wave launch on n streams x one frame: the largest ring of the list is 3 x 15 x 23 040 bytes (rides),
+    4 x 15 x 17 472 = 1 048 320 (the last size that rides), 73 x 15 x 960 = 1 051 200 (the first size any legal list has that
+    gets a launch of its own) or 3 x 15 x 23 424 (the first with three streams).  Bytes and history_out exact on both sides;
+    which side a case is on is held to the tool on the CPU."""
+    t = plan_table(False)
+    ring = S.ring_bytes(n_streams, key)
+    assert ring == n_streams * 15 * 64 * S.profile(key + (0,)).size_cu
+    assert (ring <= t["const"]["RIDE_MAX_BYTES"]) == (n_streams in (3, 4) and key[2] != 488) and t["dab"][key[2]].group
+    lists = [S.ring_stream(key, s) for s in range(n_streams)]
+    soft = _dev(np.concatenate([S.stream_frames(lst)[:1] for lst in lists]))
+    hin = [_dev(np.stack([S.history(lists[s][i][0]) for s in range(n_streams)])) for i in range(2)]
+    sizes = [S.profile(lists[0][i][0]) for i in range(2)]
+    outs = [Guarded(n_streams * 4 * p.nbytes) for p in sizes]
+    houts = [Guarded(n_streams * 15 * 64 * p.size_cu, np.int8) for p in sizes]
+    fib, ok = Guarded(n_streams * 12 * 32), Guarded(n_streams * 12)
+    wave_ctx.set_timing(True)
+    try:
+        wave_ctx.decode_frames_dev(soft.data_ptr(), FB, n_streams, 1, fib.ptr, ok.ptr, [_sc(k, s) for k, s in lists[0]], [h.data_ptr() for h in hin],
+                                   [h.ptr for h in houts], [o.ptr for o in outs], None)
+        wave_ctx.sync()
+        assert (_slots(wave_ctx, 2), _slots(wave_ctx, 4), _slots(wave_ctx, 1)) == (1, 0, 0)
+    finally:
+        wave_ctx.set_timing(False)
+    for i in range(2):
+        got, hist = outs[i].get().reshape(n_streams, 4, -1), houts[i].get().reshape(n_streams, 15, -1)
+        for s in range(n_streams):
+            k = lists[s][i][0]
+            _assert_periods(got[s], k, 4, "rings, stream %d" % s)
+            assert (hist[s] == S.cifs_of(k, 4)[1]).all(), (s, S.name(k))
+    f, o = fib.get().reshape(n_streams, -1), ok.get().reshape(n_streams, -1)
+    for s in range(n_streams):
+        _assert_fic(f[s], o[s], 1, "rings, stream %d" % s)
+
+
+def _entry_stream():
+    return max(range(len(P.streams())), key=lambda s: len(P.streams()[s]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [24, 25])
+def test_gpu_wave_entry_counts(wave_ctx, n):
+    """24 and 25 sub-channels with the FIC on one frame (the first entries of the profile sweep's 31-entry stream): one pack
+    of the grouped wave launch, and two, the FIC with the first only."""
+    s = _entry_stream()
+    entries = P.streams()[s][:n]
+    assert len(entries) == n
+    soft = _dev(P.stream_frames(s)[:1])
+    hin = [_dev(P.history(k)) for k, _ in entries]
+    outs = [Guarded(4 * P.profile(k).nbytes) for k, _ in entries]
+    houts = [Guarded(15 * 64 * P.profile(k).size_cu, np.int8) for k, _ in entries]
+    fib, ok = Guarded(12 * 32), Guarded(12)
+    import dabgpu
+    scs = [dabgpu.uep_subchannel(k[1], st) if k[0] == "uep" else dabgpu.subchannel(st, k[3], level=k[2], eep_type=k[1]) for k, st in entries]
+    wave_ctx.set_timing(True)
+    try:
+        wave_ctx.decode_frames_dev(soft.data_ptr(), FB, 1, 1, fib.ptr, ok.ptr, scs, [h.data_ptr() for h in hin], [h.ptr for h in houts],
+                                   [o.ptr for o in outs], None)
+        wave_ctx.sync()
+        assert (_slots(wave_ctx, 2), _slots(wave_ctx, 1)) == (1, 0)
+    finally:
+        wave_ctx.set_timing(False)
+    for (k, _), o, h in zip(entries, outs, houts):
+        mother, d = P.ref(k)
+        R.assert_decoder(o.get().reshape(4, -1), mother[:4], d.lanes(np.arange(4)), True, "%d entries, %s" % (n, P.name(k)))
+        assert (h.get().reshape(15, -1) == np.concatenate([P.history(k), P.period(k)[:4]])[-15:]).all(), P.name(k)
+    ref = P.fic_ref(s)
+    R.assert_decoder(fib.get().reshape(4, 96), ref.mother[:4], ref.decoded.lanes(np.arange(4)), True, "%d entries, FIC" % n)
+    assert (ok.get() == ref.crc_ok[0]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [16, 17])
+def test_gpu_lane_entry_counts(lane_ctx, n):
+    """dabgpu_msc_decode_multi_dev, lane kernels, sixteen frames: the 800 kbit/s entry (direct stores) and fifteen or sixteen
+    8 kbit/s entries: one pack by value (timer parts) and two (none)."""
+    entries = S.many_stream(16)[:n]
+    soft = _frames_dev(S.many_stream(16), 16)
+    hin = [_dev(S.history(k)) for k, _ in entries]
+    outs = [Guarded(64 * S.profile(k).nbytes) for k, _ in entries]
+    houts = [Guarded(15 * 64 * S.profile(k).size_cu, np.int8) for k, _ in entries]
+    lane_ctx.set_timing(True)
+    try:
+        lane_ctx.msc_decode_multi_dev([_sc(k, s) for k, s in entries], soft.data_ptr(), FB, 1, 16, [h.data_ptr() for h in hin],
+                                      [h.ptr for h in houts], [o.ptr for o in outs], None)
+        lane_ctx.sync()
+        assert (_slots(lane_ctx, 2), _slots(lane_ctx, 4)) == (1, 1 if n <= 16 else 0)
+    finally:
+        lane_ctx.set_timing(False)
+    for (k, _), o, h in zip(entries, outs, houts):
+        _assert_periods(o.get(), k, 64, "%d entries" % n)
+        assert (h.get().reshape(15, -1) == S.history(k)).all(), S.name(k)
+
+
+@pytest.mark.gpu
+def test_gpu_plain_codewords_at_the_lane_threshold(built):
+    """24 575 and 24 576 plain 774-step codewords (the FIC's mask) from one input buffer, default selection: the wave kernels
+    below LANE_MIN_CODEWORDS, the lane kernels from it.  The inputs are test_decoder_reference.py's 774-step family (its
+    saturated headroom family has 606 steps and cannot give this length): 63 of its 64 codewords, 63 prime to 64, so that a
+    lane sees every one."""
+    import test_decoder_reference as TDR
+    mask, punct, _ = TDR.long_case(774, "real")
+    mother, d = TDR.long_ref(774, "real")
+    pick = np.arange(24576) % 63
+    buf = np.ascontiguousarray(punct[pick])
+    sub = d.lanes(np.arange(63))
+    c = make_ctx(None)
+    try:
+        for n in (24575, 24576):
+            got = c.viterbi(buf[:n], mask)
+            assert (got == got[pick[:n]]).all(), "equal inputs, different lanes, different bytes"
+            R.assert_decoder(got[:63], mother[:63], sub, False, "first 63 of %d codewords" % n)
+            R.assert_decoder(got[n - 63:][np.argsort(pick[n - 63:n])], mother[:63], sub, False, "last 63 of %d codewords" % n)
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", ["last resident", "one more"])
+def test_gpu_fic_with_one_sub_channel_at_the_last_resident_frame_count(built, side):
+    """The FIC with ONE 64 kbit/s sub-channel: one launch while all 8 F codewords are resident at once, F from the device's
+    CU count and the tool's LDS slab; two launches at F + 1.  Four distinct frames tiled, against the exact reference."""
+    import torch
+    t = plan_table(False)
+    key = S.ONE_ROUND
+    lds = max(t["dab"][key[2]].group_lds, t["plain"][774].group_lds)
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    F = n_cu * (LDS_PER_CU // lds) // 8 + (side == "one more")
+    _report("the FIC with one sub-channel, %s: %d frames on %d CUs, %d B of LDS a codeword" % (side, F, n_cu, lds))
+    entries = ((key, 5),)
+    soft = _dev(np.tile(S.stream_frames(entries), ((F + 3) // 4, 1))[:F])
+    p = S.profile(key)
+    hin = _dev(S.history(key))
+    out, hout = Guarded(4 * F * p.nbytes), Guarded(15 * 64 * p.size_cu, np.int8)
+    fib, ok = Guarded(F * 12 * 32), Guarded(F * 12)
+    c = make_ctx(None, max_frames=8)
+    try:
+        c.set_timing(True)
+        c.decode_frames_dev(soft.data_ptr(), FB, 1, F, fib.ptr, ok.ptr, [_sc(key, 5)], [hin.data_ptr()], [hout.ptr], [out.ptr], None)
+        c.sync()
+        assert (_slots(c, 2), _slots(c, 1)) == ((1, 0) if side == "last resident" else (1, 1)), (F, n_cu, lds)
+    finally:
+        c.close()
+    _assert_periods(out.get(), key, 4 * F, "%d frames" % F)
+    assert (hout.get().reshape(15, -1) == S.cifs_of(key, 4 * F)[1]).all()
+    _assert_fic(fib.get(), ok.get(), F, "%d frames" % F)
+
+
+def _viterbi_dev(c, punct, n, mask, nsteps, out):
+    import torch
+    torch.cuda.synchronize()
+    m = np.ascontiguousarray(mask, np.uint8)
+    return c._lib.dabgpu_viterbi_dev(c._h, C.c_void_p(punct.data_ptr()), n, m.ctypes.data_as(C.c_void_p), nsteps, C.c_void_p(out.ptr), None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nsteps", PLAIN_LENGTHS)
+def test_gpu_plain_viterbi_on_both_sides(wave_ctx, lane_ctx, nsteps):
+    """dabgpu_viterbi_dev with the wave family forced, at PI 1, PI 24 and unpunctured, n = 1, 2, 3, 5, 9 codewords (workgroups
+    with inactive waves at 4 and at 2 codewords a workgroup).  viterbi_wave_kernel: 3 406 | 3 414 (4 | 2), 6 814 | 6 830 (2 | 1),
+    13 646 | 13 654 (its largest request, 160 KiB exactly | DABGPU_ERR_CAPACITY, nothing written).  viterbi_rot_kernel on plain
+    codewords: 4 806 | 4 902, 9 798 | 9 894, 16 326 | 16 422 (its last length | the lane kernels).  Lengths the lane kernels
+    take run on them as well."""
+    row = plan_table(False)["plain"][nsteps]
+    assert plain_legal(nsteps) and (row.path in ("rot", "lane_tile")) == rot_length(nsteps)
+    nbytes = (nsteps - 6) // 8
+    for kind in S.PLAIN_MASKS:
+        mask = S.plain_mask(nsteps, kind)
+        if row.path == "refused":
+            punct = _dev(np.zeros((2, int(mask.sum())), np.int8))
+            out = Guarded(2 * nbytes)
+            assert _viterbi_dev(wave_ctx, punct, 2, mask, nsteps, out) == ERR_CAPACITY
+            wave_ctx.sync()
+            assert out.untouched()
+            continue
+        punct = _dev(S.plain_case(nsteps, kind))
+        mother, d = S.plain_ref(nsteps)[kind]
+        for name, c in (("wave", wave_ctx),) + ((("lane", lane_ctx),) if row.lane else ()):
+            for n in PLAIN_COUNTS:
+                out = Guarded(n * nbytes)
+                assert _viterbi_dev(c, punct, n, mask, nsteps, out) == 0
+                c.sync()
+                R.assert_decoder(out.get().reshape(n, nbytes), mother[:n], d.lanes(np.arange(n)), False,
+                                 "%s family, %d steps, %s, %d codewords" % (name, nsteps, kind, n))
