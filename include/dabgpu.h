@@ -1434,7 +1434,8 @@ int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entri
 /*                                                                              */
 /* Not read here: X-PAD application types 1, 12, 13 are stepped over (the         */
 /* slideshow call below reads them); DL Plus tags (the command's CRC is           */
-/* checked, its body dropped); PAD of layer-II frames.  No audio is decoded.      */
+/* checked, its body dropped).  No audio is decoded.  (Layer-II frames reach      */
+/* this call through dabgpu_mp2_follow_dev below.)                                */
 /* Charset 0 (EBU Latin) labels come out as bytes; no table translates them.      */
 /*                                                                              */
 /* THE CONTRACT of one entry in one call (EN 300 401 clauses 7.4.2 - 7.4.5,       */
@@ -1555,8 +1556,8 @@ int dabgpu_pad_label_utf8(const dabgpu_pad_label *label, char *out, int cap);
 /*                                                                                */
 /* Not read: FIG 0/13 user application signalling (X-PAD types 12 / 13 are taken    */
 /* as MOT as given); MOT directory mode (data group types 6, 7); scrambled bodies   */
-/* (type 5) and CA parameters; packet-mode MOT; PAD of layer-II frames.  The         */
-/* image is not decoded; the device does not look at the content type.               */
+/* (type 5) and CA parameters; packet-mode MOT.  The image is not decoded; the       */
+/* device does not look at the content type.                                         */
 /*                                                                                */
 /* THE CONTRACT of one entry in one call (EN 300 401 clauses 5.3.3, 7.4.5.1;          */
 /* EN 301 234 clauses 5.1, 5.2, 6.1; every ambiguity decided).                        */
@@ -1701,6 +1702,78 @@ typedef struct dabgpu_mot_header {
  * runs past the header, a ContentName without its charset byte, a time of fewer than 4 bytes, a CategoryID/SlideID of
  * fewer than 2; DABGPU_ERR_CAPACITY for a text longer than 255 bytes.  A refused call writes nothing. */
 int dabgpu_mot_header_parse(const uint8_t *header, int n, dabgpu_mot_header *out);
+
+/* ------------------------------------------------------------------------ */
+/* Following every DAB (MPEG layer II) sub-channel of a batch to checked frames  */
+/* and their PAD on the device -- what stands behind the audio parameters and    */
+/* the dynamic label the reference shows for a layer-II channel                   */
+/*   (/root/reference/src/render_radio_block.cpp:439-486).                        */
+/* The other audio kind of dabgpu_fig_audio_components (ascty == 0).  One entry   */
+/* per followed sub-channel; one call takes the n_cifs logical frames every       */
+/* entry's decode call produced and two launches: one wave per entry finds the    */
+/* sampling rate and the pairing phase, then one lane per frame checks header     */
+/* and ISO CRC and whole waves lift the PAD into rows.  The rows, their status    */
+/* and d_follow are what dabgpu_pad_labels_dev and dabgpu_mot_slides_dev read:     */
+/* point their entries at d_rows / d_status / d_follow with bitrate_kbps =         */
+/* DABGPU_MP2_PAD_KBPS, data_stride >= DABGPU_MP2_ROW_BYTES and max_superframes    */
+/* = n_cifs + 1, in the same table as the DAB+ entries. */
+/*                                                                              */
+/* THE CONTRACT -- header, ISO CRC, ScF-CRC bytes, the PAD row, rate and phase,    */
+/* the carry record -- stands at the top of include/dabgpu_mp2_frame.h, the one     */
+/* implementation the kernels, the host twin and the host mirror run.  In short:    */
+/* a frame with a valid header and a good ISO CRC over bit allocation and SCFSI     */
+/* becomes one pseudo access unit whose data stream element holds its X-PAD and     */
+/* F-PAD (au_crc_mask = 1); any other slot is one lost access unit                  */
+/* (au_crc_mask = 0, a row of zeros).  Frames without the ISO CRC (protection       */
+/* bit 1) are counted and deliver no PAD.  The ScF-CRC bytes are stepped over, not   */
+/* checked.  No audio is decoded.                                                   */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_MP2_ROW_BYTES 220
+#define DABGPU_MP2_PAD_KBPS 16
+
+typedef struct dabgpu_mp2_result {
+    int32_t id;                 /* 1 = MPEG-1 (48 kHz), 0 = LSF (24 kHz), -1 = no rate found                 */
+    int32_t sample_rate;        /* 48000, 24000 or 0                                                         */
+    int32_t bitrate_kbps;       /* the entry's, 0 with no rate                                               */
+    int32_t mode;               /* 0 stereo, 1 joint stereo, 2 dual channel, 3 single channel; -1 = no valid header seen */
+    int32_t phase;              /* first frame of F that starts a row; -1 = no rate                           */
+    int32_t held;               /* logical frames in carry_out, 0 or 1                                        */
+    int32_t synced;             /* what carry_out says                                                       */
+    int32_t hits;               /* valid headers of either ID among the frames of F                           */
+    /* counts of THIS call */
+    int32_t frames;             /* rows emitted = header_errors + frames_no_crc + crc_failed + good frames     */
+    int32_t header_errors, crc_failed, frames_no_crc;
+    int32_t dropped;            /* logical frames of F that belong to no row and are not carried               */
+    int32_t reserved[3];
+} dabgpu_mp2_result;
+
+typedef struct dabgpu_mp2_entry {           /* HOST array, one per followed sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_in;        /* [n_cifs][in_stride] logical frames: the d_out[j] of the decode calls            */
+    size_t in_stride;           /* >= bitrate*3                                                                    */
+    int32_t bitrate_kbps;       /* multiple of 8, 8 .. 384                                                         */
+    const void *d_carry_in;     /* dabgpu_mp2_carry_bytes(bitrate) bytes on a 16-byte boundary, or NULL = fresh start; */
+                                /* a record this library did not write (all zero included) is a fresh start too     */
+    void *d_carry_out;          /* same size and alignment; != d_carry_in; overlaps nothing else of the call        */
+    uint8_t *d_rows;            /* [n_cifs + 1][DABGPU_MP2_ROW_BYTES]                                              */
+    dabgpu_superframe_status *d_status;      /* [n_cifs + 1]                                                       */
+    dabgpu_dabplus_follow_result *d_follow;  /* one record: n_superframes = rows emitted, phase, synced, dropped,   */
+                                             /* raw_hits = hits, held -- what the PAD entries' d_follow points at   */
+    dabgpu_mp2_result *d_result;             /* one record                                                         */
+} dabgpu_mp2_entry;
+
+/* bytes of one carry record: a 16-byte header and one logical frame of bitrate*3 bytes, rounded up to 16; 0 for a bit
+ * rate the follow call refuses */
+size_t dabgpu_mp2_carry_bytes(int bitrate_kbps);
+
+/* entries [n_entries] (HOST), any mix of bit rates; n_cifs logical frames per entry.  Everything is checked before anything
+ * is enqueued, so a refused call leaves every output as it was: DABGPU_ERR_ARG for a NULL context or table, negative counts,
+ * n_cifs above 2^28 (frame indices and row offsets stay within 32 bits),
+ * a bit rate outside 8 .. 384 or no multiple of 8, in_stride < bitrate*3, a NULL pointer other than d_carry_in (d_in may be
+ * NULL with n_cifs = 0), a carry record off its 16-byte boundary, d_carry_in and d_carry_out that are equal or overlap,
+ * d_status, d_follow or d_result off a 4-byte boundary.  No host synchronisation. */
+int dabgpu_mp2_follow_dev(dabgpu_ctx *ctx, const dabgpu_mp2_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_mp2_follow_host(const dabgpu_mp2_entry *entries, int n_entries, int n_cifs);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

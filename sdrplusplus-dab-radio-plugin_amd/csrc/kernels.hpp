@@ -399,6 +399,30 @@ struct alignas(16) MotEntry {
 // `entries`: HOST array (copied to d_table on `stream` before the kernel); every pointer checked by the caller
 hipError_t launch_mot_slides(const MotEntry *entries, int n_entries, void *d_table, size_t table_bytes, hipStream_t stream);
 
+// ---- following layer-II sub-channels (mp2_kernels.hip) ----------------------------
+// dabgpu_mp2_follow_dev: one entry per followed DAB (MPEG layer II) sub-channel, uploaded as a table; the rate kernel (one
+// wave per entry) checks every logical frame's header, chooses sampling rate and pairing phase, writes the entry's plan
+// behind the table, both result records and the carry record; the frame kernel (one lane per frame, 64 frames a workgroup)
+// checks header and ISO CRC and lifts the PAD into rows (include/dabgpu_mp2_frame.h is the contract and the code).
+struct alignas(16) Mp2Entry {
+    uint64_t in;               // [n_cifs][in_stride] logical frames of 3 B bytes
+    uint64_t carry_in;         // carry record or 0
+    uint64_t carry_out;
+    uint64_t rows;             // [n_cifs + 1][220]
+    uint64_t status;           // [n_cifs + 1] SuperframeStatus
+    uint64_t follow;           // one FollowResult
+    uint64_t result;           // one dabgpu_mp2::Result
+    uint64_t in_stride;
+    int32_t bitrate;           // B, kbit/s
+    int32_t reserved[3];
+};
+struct alignas(16) Mp2Plan {
+    int32_t rate, phase, n_rows, held;
+};
+size_t mp2_table_bytes(int n_entries);
+// `entries`: HOST array (copied to d_table on `stream` before the kernels); every pointer checked by the caller
+hipError_t launch_mp2_follow(const Mp2Entry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

@@ -54,6 +54,7 @@ EXPORTS = [
     "dabgpu_decode_ensembles_dev", "dabgpu_fig_subchannels",
     "dabgpu_dabplus_follow_dev", "dabgpu_dabplus_carry_bytes", "dabgpu_fig_audio_components",
     "dabgpu_pad_state_bytes", "dabgpu_pad_labels_dev", "dabgpu_pad_labels_host", "dabgpu_pad_label_utf8",
+    "dabgpu_mp2_carry_bytes", "dabgpu_mp2_follow_dev", "dabgpu_mp2_follow_host",
     "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
 ]
 
@@ -141,6 +142,13 @@ PAD_RESULT_DTYPE = np.dtype([(n, np.int32) for n in (
     "commands_ignored", "labels_completed", "changes")] + [("reserved", np.int32, (6,))])
 assert PAD_RESULT_DTYPE.itemsize == 64
 PAD_CHARSET_EBU_LATIN, PAD_CHARSET_UCS2, PAD_CHARSET_UTF8 = 0, 6, 15
+#: dabgpu_mp2_result: what one entry of Context.mp2_follow_dev / mp2_follow_host found and counted in one call
+MP2_RESULT_DTYPE = np.dtype([(n, np.int32) for n in (
+    "id", "sample_rate", "bitrate_kbps", "mode", "phase", "held", "synced", "hits", "frames", "header_errors", "crc_failed",
+    "frames_no_crc", "dropped")] + [("reserved", np.int32, (3,))])
+assert MP2_RESULT_DTYPE.itemsize == 64
+#: a row of the layer-II follow call, and the bit rate the PAD / slideshow entries name for such rows (110 * 16 / 8 = 220)
+MP2_ROW_BYTES, MP2_PAD_KBPS = 220, 16
 #: dabgpu_mot_slide: the record in front of every slide in its slot (then header_bytes of MOT header, then body_bytes of body)
 MOT_SLIDE_DTYPE = np.dtype([(n, np.int32) for n in (
     "transport_id", "content_type", "content_subtype", "header_bytes", "body_bytes", "superframe", "au", "reserved")])
@@ -218,6 +226,14 @@ class DabplusEntry(C.Structure):
     """dabgpu_dabplus_entry: one followed DAB+ sub-channel of Context.dabplus_follow_dev (device addresses)."""
     _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
                 ("d_carry_out", C.c_void_p), ("d_data", C.c_void_p), ("d_status", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+class Mp2Entry(C.Structure):
+    """dabgpu_mp2_entry: one followed DAB (MPEG layer II) sub-channel of Context.mp2_follow_dev (device addresses) or
+    mp2_follow_host (host addresses)."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
+                ("d_carry_out", C.c_void_p), ("d_rows", C.c_void_p), ("d_status", C.c_void_p), ("d_follow", C.c_void_p),
+                ("d_result", C.c_void_p)]
 
 
 class PadEntry(C.Structure):
@@ -525,6 +541,10 @@ def load_library(path):
     L.dabgpu_pad_labels_dev.argtypes = [vp, C.POINTER(PadEntry), i, vp]
     L.dabgpu_pad_labels_host.argtypes = [C.POINTER(PadEntry), i]
     L.dabgpu_pad_label_utf8.argtypes = [vp, C.c_char_p, i]
+    L.dabgpu_mp2_carry_bytes.restype = C.c_size_t
+    L.dabgpu_mp2_carry_bytes.argtypes = [i]
+    L.dabgpu_mp2_follow_dev.argtypes = [vp, C.POINTER(Mp2Entry), i, i, vp]
+    L.dabgpu_mp2_follow_host.argtypes = [C.POINTER(Mp2Entry), i, i]
     L.dabgpu_mot_state_bytes.restype = C.c_size_t
     L.dabgpu_mot_state_bytes.argtypes = []
     L.dabgpu_mot_arena_bytes.restype = C.c_size_t
@@ -759,6 +779,19 @@ def pad_labels_host(entries):
     n = len(entries)
     arr = (PadEntry * max(n, 1))(*entries)
     _check(lib().dabgpu_pad_labels_host(arr, n), "dabgpu_pad_labels_host")
+
+
+def mp2_carry_bytes(bitrate_kbps):
+    """Bytes of one carry record of Context.mp2_follow_dev / mp2_follow_host (0 for a bit rate they refuse)."""
+    return int(lib().dabgpu_mp2_carry_bytes(bitrate_kbps))
+
+
+def mp2_follow_host(entries, n_cifs):
+    """Context.mp2_follow_dev on HOST memory (entries: Mp2Entry with host addresses): the same checks and the same code,
+    include/dabgpu_mp2_frame.h; no context, no GPU."""
+    n = len(entries)
+    arr = (Mp2Entry * max(n, 1))(*entries)
+    _check(lib().dabgpu_mp2_follow_host(arr, n, n_cifs), "dabgpu_mp2_follow_host")
 
 
 def pad_label_utf8(label):
@@ -1314,6 +1347,15 @@ class Context:
         n = len(entries)
         arr = (DabplusEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_dabplus_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dabplus_follow_dev")
+
+    def mp2_follow_dev(self, entries, n_cifs, stream=None):
+        """Follows DAB (MPEG layer II) sub-channels to checked frames and PAD rows on the device: entries is a list of Mp2Entry
+        (device addresses), n_cifs the logical frames every entry's d_in holds.  Per entry: d_rows [n_cifs + 1][MP2_ROW_BYTES],
+        d_status (SUPERFRAME_STATUS_DTYPE), d_follow (DABPLUS_FOLLOW_RESULT_DTYPE: what PadEntry / MotEntry.d_follow point at,
+        with bitrate_kbps = MP2_PAD_KBPS), d_result (MP2_RESULT_DTYPE).  No host synchronisation."""
+        n = len(entries)
+        arr = (Mp2Entry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_mp2_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_mp2_follow_dev")
 
     def pad_labels_dev(self, entries, stream=None):
         """Dynamic labels of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list of

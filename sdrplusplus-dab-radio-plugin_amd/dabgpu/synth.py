@@ -748,6 +748,96 @@ def au_body(pad, tag=0):
     return None if pad is None else dse(pad, tag)
 
 
+# ----------------------------------------------------------------------------- DAB (MPEG layer II) audio frames
+# The transmit side of include/dabgpu_mp2_frame.h, from the clauses: header (ISO 11172-3 2.4.1.3), CRC, bit allocation and
+# SCFSI (2.4.1.4 - 2.4.1.6, Annex B table B.2), then a random body, the ScF-CRC bytes and the PAD at the frame's end
+# (EN 300 401 7.3.1.5, 7.4.1).
+MP2_RATES_48K = (0, 32, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384)
+MP2_RATES_24K = (0, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160)
+MP2_STEREO, MP2_JOINT, MP2_DUAL, MP2_MONO = 0, 1, 2, 3
+_MP2_NBAL_48K_SMALL = [4] * 2 + [3] * 6
+_MP2_NBAL_48K_LARGE = [4] * 11 + [3] * 12 + [2] * 4
+_MP2_NBAL_24K = [4] * 4 + [3] * 7 + [2] * 19
+
+
+def _mp2_crc_table():
+    t = []
+    for v in range(256):
+        r = v << 8
+        for _ in range(8):
+            r = ((r << 1) ^ 0x8005) & 0xFFFF if r & 0x8000 else (r << 1) & 0xFFFF
+        t.append(r)
+    return t
+
+
+_MP2_CRC_TABLE = _mp2_crc_table()
+
+
+def mp2_crc(bits):
+    """the ISO 11172-3 CRC-16 (0x8005, start 0xFFFF) over a list of bits: whole bytes through the table, the rest by shifts"""
+    crc, n = 0xFFFF, len(bits) // 8 * 8
+    for at in range(0, n, 8):
+        v = int("".join(str(int(b)) for b in bits[at:at + 8]), 2)
+        crc = ((crc << 8) & 0xFFFF) ^ _MP2_CRC_TABLE[(crc >> 8) ^ v]
+    for b in bits[n:]:
+        crc = ((crc << 1) & 0xFFFF) ^ (0x8005 if ((crc >> 15) ^ int(b)) & 1 else 0)
+    return crc
+
+
+def mp2_scf_crc_bytes(bitrate, mode, lsf):
+    per_channel = bitrate if mode == MP2_MONO else bitrate // 2
+    return 4 if lsf or per_channel >= 56 else 2
+
+
+def mp2_frame(rng, bitrate, mode=MP2_STEREO, mode_ext=0, lsf=False, pad=None, crc=True, silent_bands=0.25):
+    """One layer-II audio frame as a DAB sub-channel of `bitrate` kbit/s carries it: 3 * bitrate bytes at 48 kHz, 6 * bitrate
+    (two logical frames) at 24 kHz (lsf) -- header, a correct ISO CRC (crc=False: protection bit 1, no CRC), random bit
+    allocation (a share of silent_bands of the fields zero), random SCFSI and body, and `pad` -- pad_field()'s bytes: the
+    X-PAD in reverse order, then the two F-PAD bytes -- at the frame's end: F-PAD last, four X-PAD bytes in front of it,
+    the rest in front of the ScF-CRC bytes.  None: the random body stands there."""
+    rates = MP2_RATES_24K if lsf else MP2_RATES_48K
+    assert bitrate in rates[1:], "no bit-rate index names %d kbit/s" % bitrate
+    if not lsf:                                                     # ISO 11172-3 2.4.2.3
+        assert not (bitrate in (32, 48, 56, 80) and mode != MP2_MONO) and not (bitrate in (224, 256, 320, 384) and mode == MP2_MONO)
+    L = (6 if lsf else 3) * bitrate
+    f = rng.integers(0, 256, size=L, dtype=np.uint8)
+    f[0] = 0xFF
+    f[1] = 0xF0 | ((0 if lsf else 1) << 3) | (2 << 1) | (0 if crc else 1)
+    f[2] = (rates.index(bitrate) << 4) | (1 << 2) | (int(f[2]) & 1)
+    f[3] = (mode << 6) | (mode_ext << 4) | (int(f[3]) & 0x0F)
+    channels = 1 if mode == MP2_MONO else 2
+    per_channel = bitrate // channels
+    nbal = _MP2_NBAL_24K if lsf else _MP2_NBAL_48K_SMALL if per_channel in (32, 48) else _MP2_NBAL_48K_LARGE
+    bound = min(4 * (mode_ext + 1), len(nbal)) if mode == MP2_JOINT else len(nbal)
+    bits, scfsi = [], 0
+    for sb, n in enumerate(nbal):
+        shared = channels == 2 and sb >= bound
+        for _ in range(1 if channels == 1 or shared else 2):
+            a = 0 if rng.random() < silent_bands else int(rng.integers(1, 1 << n))
+            bits += [(a >> (n - 1 - k)) & 1 for k in range(n)]
+            scfsi += (2 if shared else 1) * (a != 0)
+    bits += [int(b) for b in rng.integers(0, 2, size=2 * scfsi)]
+    if crc:
+        nbytes = (len(bits) + 7) // 8
+        stream = np.unpackbits(f[6:6 + nbytes])
+        stream[:len(bits)] = bits
+        f[6:6 + nbytes] = np.packbits(stream)
+        head = [int(b) for b in np.unpackbits(f[2:4])]
+        c = mp2_crc(head + bits)
+        f[4], f[5] = c >> 8, c & 0xFF
+    if pad is not None:
+        pad = bytes(pad)
+        c = mp2_scf_crc_bytes(bitrate, mode, lsf)
+        xpad = pad[:-2]
+        assert len(pad) >= 2 and len(xpad) <= min(196, L - 8 - c), "the PAD does not fit this frame"
+        xpad = bytes(max(0, 4 - len(xpad))) + xpad
+        f[L - 2:] = np.frombuffer(pad[-2:], np.uint8)
+        f[L - 6:L - 2] = np.frombuffer(xpad[-4:], np.uint8)
+        if len(xpad) > 4:
+            f[L - 6 - c - (len(xpad) - 4):L - 6 - c] = np.frombuffer(xpad[:-4], np.uint8)
+    return f
+
+
 # ----------------------------------------------------------------------------- PAD: slideshow (MOT in X-PAD)
 # The transmit side of the slideshow, from the clauses: object -> MOT header (core + parameters, EN 301 234 6.1, 6.2;
 # TS 101 499 6.2) and body -> segments with their segmentation header (EN 301 234 5.1) -> MSC data groups with session
@@ -1125,13 +1215,17 @@ class ServiceEnsemble:
     FIC made of FIG 0/0, 0/1, 0/2, 1/0, 1/1.  services = [(label, sid, subchannel_id, option, level, bitrate,
     start_cu), ...].  n_frames must be a multiple of 5 so that whole super-frames (5 logical frames) tile."""
 
-    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True, bodies=None):
+    def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True, bodies=None,
+                 dab_pads=None):
         """dab_services: DAB (MPEG layer II) services on UEP sub-channels, [(label, sid, subchannel_id, uep_index,
         start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body).
         extras=False leaves the rotation to the labels alone (FIG 0/0, 0/1, 0/2, 0/10 and one label per CIF): what
         four services leave room for in three FIBs.
         bodies: per DAB+ service (or None), per super-frame, build_superframe's `bodies`: what the access units begin
-        with (PAD); the random draws do not depend on it."""
+        with (PAD); the random draws do not depend on it.
+        dab_pads: per DAB service (or None), per logical frame, the PAD (pad_field's bytes, or None: F-PAD alone) of that frame: the
+        service then sends mp2_frame()s with the ISO CRC, 48 kHz (stereo, or single channel at the rates only that mode may
+        use), from a generator of their own; the draws of everything else do not depend on it."""
         assert n_frames % 5 == 0
         rng = np.random.default_rng(seed)
         self.n_frames, self.eid, self.label, self.services = n_frames, eid, label, services
@@ -1160,6 +1254,11 @@ class ServiceEnsemble:
             data[:, 0], data[:, 1] = 0xFF, 0xFD                     # sync, MPEG-1, layer II, no CRC
             data[:, 2] = (data[:, 2] & 0xF0) | 0x04                 # 48 kHz
             data[:, 3] &= 0x3F                                      # stereo
+            if dab_pads is not None and dab_pads[len(self.mp2_frames)] is not None:
+                pads, frng = dab_pads[len(self.mp2_frames)], np.random.default_rng([seed, scid])
+                mode = MP2_MONO if bitrate in (32, 48, 56, 80) else MP2_STEREO
+                data = np.stack([mp2_frame(frng, bitrate, mode=mode, pad=pads[r] if r < len(pads) and pads[r] is not None else bytes(2))
+                                 for r in range(R)])
             coded = np.stack([msc_encode_lf(data[r], mask) for r in range(R)])
             coded = np.concatenate([coded, np.zeros((R, size_cu * 64 - coded.shape[1]), np.uint8)], axis=1)
             cifs[:, start_cu * 64:(start_cu + size_cu) * 64] = time_interleave(coded, cyclic=True)

@@ -39,10 +39,11 @@ public:
     virtual AudioServiceType GetType() const = 0;
     // programme-associated text (/root/reference/src/render_radio_block.cpp:425-427, 470-472): the label's bytes as sent,
     // in the charset the service uses.  A DAB+ channel reads it from the PAD in front of its access units, without an audio
-    // decoder (basic_dab_plus_channel.cpp); a layer-II channel has none.  Read under BasicRadio::GetMutex() like the rest.
+    // decoder (basic_dab_plus_channel.cpp); a layer-II channel from the PAD at the end of its frames (basic_dab_channel.h).
+    // Read under BasicRadio::GetMutex() like the rest.
     std::string_view GetDynamicLabel() const { return m_dynamic_label; }
     Basic_Audio_Controls &GetControls() { return m_controls; }
-    // slideshows come out of the PAD as well: a DAB+ channel fills it (basic_dab_plus_channel.cpp), a layer-II channel does not
+    // slideshows come out of the PAD as well: a DAB+ channel fills it (basic_dab_plus_channel.cpp), a layer-II channel too
     Basic_Slideshow_Manager &GetSlideshowManager() { return m_slideshows; }
     Observable<BasicAudioParams, tcb::span<const uint8_t>> &OnAudioData() { return m_obs_audio; }
 

@@ -4,10 +4,20 @@
 // through GetAudioParams() (/root/reference/src/render_radio_block.cpp:439-460) and hands the frames to whoever
 // decodes MP2 (not part of the hot path; OnAudioData() never fires).  These services normally sit on UEP
 // sub-channels.
+// GetDynamicLabel() and the slideshow manager (/root/reference/src/render_radio_block.cpp:470-486) are read from the
+// frames' PAD without an audio decoder, by the code the GPU batch call dabgpu_mp2_follow_dev runs
+// (include/dabgpu_mp2_frame.h: header valid for the sub-channel's bit rate, ISO CRC over allocation and SCFSI, the PAD
+// lifted into a row) and the two walks behind it (basic_pad_reader.h).  Frame by frame there is no vote: a logical frame
+// with a valid 24 kHz header waits for its second half; if the next one has such a header too, the one that waited was
+// an orphan (a lost access unit) and the new one waits.  Frames without the ISO CRC (protection bit 1) deliver no PAD.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <optional>
+#include <vector>
 #include "basic_radio/basic_audio_channel.h"
+#include "basic_radio/basic_pad_reader.h"
+#include "dabgpu_mp2_frame.h"
 
 // what the GUI prints about a layer-II stream (/root/reference/src/render_radio_block.cpp:444-467): the names of the
 // reference's MP2 decoder front end; only the frame header is parsed here
@@ -38,6 +48,7 @@ public:
         const bool sync = lf[0] == 0xFF && (lf[1] & 0xF0) == 0xF0;
         const bool layer2 = ((lf[1] >> 1) & 3) == 2;
         const bool fs_ok = ((lf[2] >> 2) & 3) == 1;
+        if (m_controls.GetIsDecodeData()) ReadPad(lf);
         if (!(sync && layer2 && fs_ok)) {
             m_total_header_errors++;
             m_is_error = true;
@@ -61,12 +72,59 @@ public:
     int GetTotalFrames() const { return m_total_frames; }
     int GetTotalHeaderErrors() const { return m_total_header_errors; }
     const Subchannel &GetSubchannel() const { return m_subchannel; }
+    // what the PAD path counted: audio frames with a good ISO CRC | with a valid header and a bad one | without the CRC
+    int GetTotalCheckedFrames() const { return m_total_checked; }
+    int GetTotalCrcErrors() const { return m_total_crc_errors; }
+    int GetTotalFramesWithoutCrc() const { return m_total_no_crc; }
+    int GetDynamicLabelCharset() const { return m_pad ? m_pad->GetLabel().charset : 0; }
 
 private:
+    // one logical frame through the shared header: a 48 kHz frame, or a half of a 24 kHz one
+    void ReadPad(tcb::span<const uint8_t> lf) {
+        namespace mp2 = dabgpu_mp2;
+        const int lf_bytes = int(m_lf_bytes), B = lf_bytes / 3;
+        if (!mp2::bitrate_ok(B)) return;
+        const bool starts_24k = mp2::header_id(mp2::header_word(lf[0], lf[1], lf[2], lf[3]), B) == 0;
+        if (!m_half.empty() && !starts_24k) {
+            const mp2::TwoPart pair = {m_half.data(), lf.data(), lf_bytes};
+            AudioFrame(pair, 2 * lf_bytes, B, 0);
+            m_half.clear();
+            return;
+        }
+        if (!m_half.empty()) Lost();                                       // an orphan first half
+        if (starts_24k) {
+            m_half.assign(lf.begin(), lf.end());
+            return;
+        }
+        const mp2::TwoPart whole = {lf.data(), lf.data(), lf_bytes};
+        AudioFrame(whole, lf_bytes, B, 1);
+    }
+    void AudioFrame(const dabgpu_mp2::TwoPart &f, int L, int B, int id) {
+        namespace mp2 = dabgpu_mp2;
+        int c = 0;
+        const int kind = mp2::parse_frame(f, L, B, id, &c);
+        m_total_crc_errors += kind == mp2::FRAME_CRC_FAILED;
+        m_total_no_crc += kind == mp2::FRAME_NO_CRC;
+        if (kind != mp2::FRAME_GOOD) return Lost();
+        m_total_checked++;
+        const int x = mp2::xpad_bytes(L, c);
+        uint8_t row[mp2::ROW_BYTES];
+        for (int j = 0; j < mp2::ROW_BYTES; j++) row[j] = mp2::row_byte(f, L, c, x, j);
+        if (!m_pad) m_pad = std::make_unique<Basic_Pad_Reader>();
+        m_pad->Walk(row, x + 4, m_slideshows);                             // (the access unit without the two bytes that stand for its CRC)
+        const dabgpu_pad::Label &label = m_pad->GetLabel();
+        m_dynamic_label.assign(reinterpret_cast<const char *>(label.text), size_t(label.length));
+    }
+    void Lost() {
+        if (m_pad) m_pad->Walk(nullptr, -1, m_slideshows);                 // (before the first good frame there is nothing to drop)
+    }
     const Subchannel m_subchannel;
     const size_t m_lf_bytes;
     std::optional<MP2_Audio_Decoder::AudioParams> m_params;
     bool m_is_error = false;
     int m_total_frames = 0, m_total_header_errors = 0;
     Observable<tcb::span<const uint8_t>> m_obs_frame;
+    std::vector<uint8_t> m_half;           // the first logical frame of a 24 kHz frame, waiting for the second
+    std::unique_ptr<Basic_Pad_Reader> m_pad;
+    int m_total_checked = 0, m_total_crc_errors = 0, m_total_no_crc = 0;
 };

@@ -27,6 +27,7 @@ void Basic_DAB_Plus_Channel::WalkMot(const uint8_t *au, int len) {
     for (int k = 0; k < m_mot_counts.slides_written; k++) AddSlide(m_mot_slides.data() + size_t(k) * m_mot_call.slide_stride);
 }
 
+// (TWO PLACES: basic_pad_reader.h, Basic_Add_Slide, is this function for the layer-II channel; a change goes into both)
 void Basic_DAB_Plus_Channel::AddSlide(const uint8_t *slot) {
     int32_t rec[8];
     std::memcpy(rec, slot, sizeof rec);

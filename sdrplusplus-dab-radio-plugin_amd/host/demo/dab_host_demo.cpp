@@ -30,6 +30,22 @@
 
 static constexpr float SAMPLING_RATE_HZ = 2.048e6f;   // the offsets are in cycles per sample (src/render_radio_block.cpp:202)
 
+// the rest of a channel's line and its slide lines: the dynamic label as the GUI reads it (render_radio_block.cpp:425-427,
+// 470-472), its bytes in hex, then the slides as the "Slideshow" tab lists them (render_radio_block.cpp:309-382), the image in hex
+static void print_label_and_slides(std::FILE *f, int subchannel, Basic_Audio_Channel &ch, int charset) {
+    std::fprintf(f, " label_charset=%d label=", charset);
+    for (const char v : ch.GetDynamicLabel()) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
+    std::fprintf(f, "\n");
+    auto slides_lock = std::scoped_lock(ch.GetSlideshowManager().GetSlideshowsMutex());
+    for (const auto &slide : ch.GetSlideshowManager().GetSlideshows()) {
+        std::fprintf(f, "slide subchannel=%d tid=%u name=", subchannel, unsigned(slide->transport_id));
+        for (const char v : slide->name) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
+        std::fprintf(f, " bytes=%zu body=", slide->image_data.size());
+        for (const uint8_t v : slide->image_data) std::fprintf(f, "%02x", unsigned(v));
+        std::fprintf(f, "\n");
+    }
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s iq.cf32 out_prefix [chunk] [coarse] [bitrate start_cu level]\n", argv[0]);
@@ -160,9 +176,11 @@ int main(int argc, char **argv) {
             for (const auto &sc : subs) {
                 if (auto *mp2 = dynamic_cast<Basic_DAB_Channel *>(radio->Get_Audio_Channel(sc.id))) {
                     const auto &ap = mp2->GetAudioParams();
-                    std::fprintf(f, "channel subchannel=%d mp2_frames=%d header_errors=%d rate=%u stereo=%d\n", sc.id,
+                    std::fprintf(f, "channel subchannel=%d mp2_frames=%d header_errors=%d rate=%u stereo=%d checked_frames=%d crc_errors=%d", sc.id,
                                  mp2->GetTotalFrames(), mp2->GetTotalHeaderErrors(), ap ? ap->sample_rate : 0u,
-                                 ap ? int(ap->is_stereo) : 0);
+                                 ap ? int(ap->is_stereo) : 0, mp2->GetTotalCheckedFrames(), mp2->GetTotalCrcErrors());
+                    // label and slides of a layer-II service (render_radio_block.cpp:470-486), as for DAB+ below
+                    print_label_and_slides(f, sc.id, *mp2, mp2->GetDynamicLabelCharset());
                     continue;
                 }
                 auto *ch = dynamic_cast<Basic_DAB_Plus_Channel *>(radio->Get_Audio_Channel(sc.id));
@@ -172,19 +190,7 @@ int main(int argc, char **argv) {
                              sc.id, ch->GetTotalSuperFrames(), ch->GetTotalAccessUnits(), ch->GetTotalAccessUnitErrors(),
                              h.sampling_rate, int(h.is_spectral_band_replication), int(h.is_stereo), int(ch->IsFirecodeError()),
                              int(ch->IsRSError()));
-                // the dynamic label as the GUI reads it (render_radio_block.cpp:425-427), its bytes in hex
-                std::fprintf(f, " label_charset=%d label=", ch->GetDynamicLabelCharset());
-                for (const char v : ch->GetDynamicLabel()) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
-                std::fprintf(f, "\n");
-                // the slides as the GUI's "Slideshow" tab lists them (render_radio_block.cpp:309-382), the image in hex
-                auto slides_lock = std::scoped_lock(ch->GetSlideshowManager().GetSlideshowsMutex());
-                for (const auto &slide : ch->GetSlideshowManager().GetSlideshows()) {
-                    std::fprintf(f, "slide subchannel=%d tid=%u name=", sc.id, unsigned(slide->transport_id));
-                    for (const char v : slide->name) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
-                    std::fprintf(f, " bytes=%zu body=", slide->image_data.size());
-                    for (const uint8_t v : slide->image_data) std::fprintf(f, "%02x", unsigned(v));
-                    std::fprintf(f, "\n");
-                }
+                print_label_and_slides(f, sc.id, *ch, ch->GetDynamicLabelCharset());
             }
             std::fclose(f);
         }
