@@ -1726,7 +1726,8 @@ int dabgpu_mot_header_parse(const uint8_t *header, int n, dabgpu_mot_header *out
 /* F-PAD (au_crc_mask = 1); any other slot is one lost access unit                  */
 /* (au_crc_mask = 0, a row of zeros).  Frames without the ISO CRC (protection       */
 /* bit 1) are counted and deliver no PAD.  The ScF-CRC bytes are stepped over, not   */
-/* checked.  No audio is decoded.                                                   */
+/* checked.  No audio is decoded here: dabgpu_mp2_subbands_dev below takes the       */
+/* GOOD frames on to sub-band samples and audio levels.                             */
 /* ------------------------------------------------------------------------ */
 #define DABGPU_MP2_ROW_BYTES 220
 #define DABGPU_MP2_PAD_KBPS 16
@@ -1774,6 +1775,65 @@ size_t dabgpu_mp2_carry_bytes(int bitrate_kbps);
 int dabgpu_mp2_follow_dev(dabgpu_ctx *ctx, const dabgpu_mp2_entry *entries, int n_entries, int n_cifs, void *stream);
 /* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
 int dabgpu_mp2_follow_host(const dabgpu_mp2_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
+/* Layer-II services of a batch: sub-band samples and audio levels -- whether    */
+/* audio is on a layer-II channel and how loud, the question behind the           */
+/* reference's layer-II channel view (its src/render_radio_block.cpp:439-486).    */
+/* Behind dabgpu_mp2_follow_dev on the same stream, with no host synchronisation:  */
+/* every checked (GOOD) frame of every followed entry goes through the whole      */
+/* layer-II decoder except its last stage -- bit allocation, SCFSI, scale factors, */
+/* sample unpacking with the grouped code words, requantisation and scaling to     */
+/* the 36 x 32 sub-band samples of each channel -- one wave per frame, a lane per   */
+/* cell.  Each row of the follow call gets a level record (power and peak per      */
+/* channel); the sub-band samples themselves are optional.  The row count, the     */
+/* rate and the phase are read on the device from d_result, the held half of a     */
+/* 24 kHz frame from d_carry_in; rows at or beyond `frames` are not written.        */
+/*                                                                              */
+/* THE CONTRACT -- classes, SCFSI, scale factors, grouping, the value of a sample, */
+/* the end of the audio, the level record -- stands at the top of                   */
+/* include/dabgpu_mp2_audio.h, the one implementation the kernel, the host twin     */
+/* and the host mirror run.  The polyphase synthesis to PCM is NOT part of this     */
+/* (it needs the 512-tap window of ISO 11172-3 table B.3): power and peak are        */
+/* SUB-BAND-DOMAIN figures, where a full-scale sinusoid has a sub-band amplitude     */
+/* of about 1; how they map to PCM dBFS is a convention nobody here has measured.    */
+/* Silence is power == 0, or a threshold the caller chooses.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_mp2_level {
+    int32_t kind;               /* 0 decoded, 1 not a GOOD frame, 2 overrun: the audio would run into the ScF-CRC or the PAD */
+    int32_t channels;           /* 1 or 2; 0 when kind != 0 (as everything below)                            */
+    int32_t cells;              /* active (sub-band, channel) cells                                          */
+    int32_t scf63;              /* scale-factor indices sent that are the forbidden 63 (factor 0)            */
+    float power[2];             /* per channel: the sum of v^2 over its 36 x 32 values                       */
+    float peak[2];              /* per channel: max |v|, exact                                               */
+} dabgpu_mp2_level;
+
+typedef struct dabgpu_mp2_audio_result {
+    int32_t decoded, not_good, overrun;     /* rows of this call by kind; their sum = the follow call's frames */
+    int32_t silent;                         /* decoded frames with power[0] + power[1] == 0                    */
+    int32_t reserved[4];
+} dabgpu_mp2_audio_result;
+
+typedef struct dabgpu_mp2_audio_entry {     /* HOST array, one per followed sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_in;        /* the follow entry's d_in                                                         */
+    size_t in_stride;           /* >= bitrate*3                                                                    */
+    int32_t bitrate_kbps;       /* multiple of 8, 8 .. 384                                                         */
+    const void *d_carry_in;     /* the record the FOLLOW call READ (NULL as there), on a 16-byte boundary           */
+    const dabgpu_superframe_status *d_status;    /* what the follow call wrote: au_crc_mask says GOOD              */
+    const dabgpu_mp2_result *d_result;           /* what the follow call wrote: id, phase, frames                  */
+    dabgpu_mp2_level *d_levels;                  /* [n_cifs + 1]                                                   */
+    float *d_subbands;          /* NULL, or [n_cifs + 1][2][36][32] (channel, sample, sub-band) on a 16-byte boundary */
+    dabgpu_mp2_audio_result *d_audio;            /* one record, written whole by this call                         */
+} dabgpu_mp2_audio_entry;
+
+/* entries [n_entries] (HOST), any mix of bit rates; n_cifs as in the follow call.  Everything is checked before anything is
+ * enqueued, so a refused call leaves every output as it was: DABGPU_ERR_ARG for a NULL context or table, negative counts,
+ * n_cifs above 2^28, a bit rate outside 8 .. 384 or no multiple of 8, in_stride < bitrate*3, a NULL pointer other than
+ * d_carry_in and d_subbands (d_in may be NULL with n_cifs = 0), d_carry_in or d_subbands off a 16-byte boundary, d_status,
+ * d_result, d_levels or d_audio off a 4-byte boundary.  No host synchronisation. */
+int dabgpu_mp2_subbands_dev(dabgpu_ctx *ctx, const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

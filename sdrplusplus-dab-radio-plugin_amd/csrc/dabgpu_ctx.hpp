@@ -71,6 +71,7 @@ enum StageSlot {
     STAGE_PAD = 14,         // dabgpu_pad_labels_dev: the entry table
     STAGE_MOT = 15,         // dabgpu_mot_slides_dev: the entry table
     STAGE_MP2 = 16,         // dabgpu_mp2_follow_dev: the entry table and the plans of the rate / frame launches
+    STAGE_MP2_AUDIO = 17,   // dabgpu_mp2_subbands_dev: the entry table
     STAGE_SLOTS
 };
 

@@ -1,10 +1,12 @@
 // dabgpu_mp2_api.hip -- the C ABI of following DAB (MPEG layer II) sub-channels (include/dabgpu.h, "Following every DAB
-// (MPEG layer II) sub-channel"): the batch call on device memory and its twin on host memory (no context, no GPU: the same
-// code, include/dabgpu_mp2_frame.h).
+// (MPEG layer II) sub-channel") and of taking their checked frames on to sub-band samples and audio levels: each batch call
+// on device memory and its twin on host memory (no context, no GPU: the same code, include/dabgpu_mp2_frame.h and
+// include/dabgpu_mp2_audio.h).
 #include "dabgpu_ctx.hpp"
 
 #include <cstring>
 
+#include "../../include/dabgpu_mp2_audio.h"
 #include "../../include/dabgpu_mp2_frame.h"
 
 using namespace dabapi;
@@ -124,6 +126,100 @@ int dabgpu_mp2_follow_host(const dabgpu_mp2_entry *entries, int n_entries, int n
         fr.raw_hits = r.hits; fr.held = p.kept;
         std::memcpy(e.d_follow, &fr, sizeof fr);
         std::memcpy(e.d_result, &r, sizeof r);
+    }
+    return DABGPU_OK;
+}
+
+// ---- sub-band samples and audio levels (include/dabgpu.h, "Layer-II services of a batch: sub-band samples and audio levels")
+static_assert(sizeof(dabgpu_mp2_level) == sizeof(mp2::Level) && sizeof(dabgpu_mp2_audio_result) == sizeof(mp2::AudioResult),
+              "ABI structs mirror the header-only code's");
+
+// everything both calls refuse, before anything is done; fills the kernels' table when there is one
+static int mp2_audio_check(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs, dabk::Mp2AudioEntry *table) {
+    if (n_entries < 0 || n_cifs < 0 || n_cifs > (1 << 28) || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
+    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
+    for (int i = 0; i < n_entries; i++) {
+        const dabgpu_mp2_audio_entry &e = entries[i];
+        if (!mp2::bitrate_ok(e.bitrate_kbps)) return DABGPU_ERR_ARG;
+        if (e.in_stride < size_t(3) * size_t(e.bitrate_kbps)) return DABGPU_ERR_ARG;
+        if (n_cifs > 0 && !e.d_in) return DABGPU_ERR_ARG;
+        if (!e.d_status || !e.d_result || !e.d_levels || !e.d_audio) return DABGPU_ERR_ARG;
+        if ((addr(e.d_carry_in) | addr(e.d_subbands)) & 15) return DABGPU_ERR_ARG;
+        if ((addr(e.d_status) | addr(e.d_result) | addr(e.d_levels) | addr(e.d_audio)) & 3) return DABGPU_ERR_ARG;
+        if (!table) continue;
+        dabk::Mp2AudioEntry &t = table[i];
+        t.in = addr(e.d_in);
+        t.carry_in = addr(e.d_carry_in);
+        t.status = addr(e.d_status);
+        t.result = addr(e.d_result);
+        t.levels = addr(e.d_levels);
+        t.subbands = addr(e.d_subbands);
+        t.audio = addr(e.d_audio);
+        t.in_stride = e.in_stride;
+        t.bitrate = e.bitrate_kbps;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_mp2_subbands_dev(dabgpu_ctx *ctx, const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs, void *stream) {
+    if (!ctx) return DABGPU_ERR_ARG;
+    // everything is checked before anything is enqueued: a refused call leaves every output as it was
+    std::vector<dabk::Mp2AudioEntry> table(size_t(n_entries > 0 ? n_entries : 0), dabk::Mp2AudioEntry{});
+    const int bad = mp2_audio_check(entries, n_entries, n_cifs, table.data());
+    if (bad) return bad;
+    if (n_entries == 0) return DABGPU_OK;
+    DeviceGuard guard(ctx);
+    hipStream_t s = pick_stream(ctx, stream);
+    const size_t table_bytes = dabk::mp2_audio_table_bytes(n_entries);
+    // (growing the table must not race with a launch that still reads the old one)
+    if (ctx->stage_bytes[STAGE_MP2_AUDIO] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
+    void *d_table = nullptr;
+    const int rc = stage(ctx, STAGE_MP2_AUDIO, table_bytes, &d_table);
+    if (rc) return rc;
+    HIP_TRY(dabk::launch_mp2_subbands(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_MP2_AUDIO], s));
+    return DABGPU_OK;
+}
+
+int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs) {
+    const int bad = mp2_audio_check(entries, n_entries, n_cifs, nullptr);
+    if (bad) return bad;
+    for (int n = 0; n < n_entries; n++) {
+        const dabgpu_mp2_audio_entry &e = entries[n];
+        const int B = e.bitrate_kbps, lf = 3 * B;
+        mp2::AudioResult tally = {};
+        mp2::Result res;
+        std::memcpy(&res, e.d_result, sizeof res);
+        mp2::Carry cy = {0, 0, 0};
+        if (e.d_carry_in) {
+            int32_t h[4];
+            std::memcpy(h, e.d_carry_in, sizeof h);
+            cy = mp2::read_carry(h[0], h[1], h[2], h[3]);
+        }
+        if ((res.id == 0 || res.id == 1) && (res.phase == 0 || res.phase == 1)) {
+            const int per = res.id == 1 ? 1 : 2, L = per * lf;
+            const int fit = (cy.held + n_cifs - res.phase) / per, frames = res.frames < fit ? res.frames : fit;
+            auto frame = [&](int i) {
+                return i < cy.held ? static_cast<const uint8_t *>(e.d_carry_in) + mp2::CARRY_HEADER : e.d_in + size_t(i - cy.held) * e.in_stride;
+            };
+            for (int k = 0; k < frames; k++) {
+                mp2::TwoPart tp;
+                tp.a = frame(res.phase + per * k);
+                tp.b = per == 2 ? frame(res.phase + per * k + 1) : tp.a + lf;
+                tp.split = lf;
+                int32_t mask;
+                std::memcpy(&mask, reinterpret_cast<const int32_t *>(e.d_status + k) + 4, sizeof mask);
+                float *v = e.d_subbands ? e.d_subbands + size_t(k) * mp2::FRAME_VALUES : nullptr;
+                mp2::Level lv = mp2::empty_level(mp2::AUDIO_NOT_GOOD);
+                if (mask == 1) lv = mp2::decode_frame(tp, L, B, res.id, v);
+                else if (v) std::memset(v, 0, sizeof(float) * mp2::FRAME_VALUES);
+                std::memcpy(e.d_levels + k, &lv, sizeof lv);
+                tally.decoded += lv.kind == mp2::AUDIO_DECODED;
+                tally.not_good += lv.kind == mp2::AUDIO_NOT_GOOD;
+                tally.overrun += lv.kind == mp2::AUDIO_OVERRUN;
+                tally.silent += lv.kind == mp2::AUDIO_DECODED && lv.power[0] + lv.power[1] == 0.0f;
+            }
+        }
+        std::memcpy(e.d_audio, &tally, sizeof tally);
     }
     return DABGPU_OK;
 }

@@ -423,6 +423,26 @@ size_t mp2_table_bytes(int n_entries);
 // `entries`: HOST array (copied to d_table on `stream` before the kernels); every pointer checked by the caller
 hipError_t launch_mp2_follow(const Mp2Entry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
 
+// ---- layer-II frames to sub-band samples and audio levels (mp2_audio_kernels.hip) --
+// dabgpu_mp2_subbands_dev, behind the follow call: one wave per checked frame decodes bit allocation, SCFSI, scale factors
+// and samples a lane per cell (include/dabgpu_mp2_audio.h is the contract and the code); rows, rate and phase are read on the
+// device from what the follow call wrote.
+struct alignas(16) Mp2AudioEntry {
+    uint64_t in;               // [n_cifs][in_stride] logical frames of 3 B bytes
+    uint64_t carry_in;         // the carry record the follow call read, or 0
+    uint64_t status;           // [n_cifs + 1] SuperframeStatus the follow call wrote
+    uint64_t result;           // one dabgpu_mp2::Result the follow call wrote
+    uint64_t levels;           // [n_cifs + 1] dabgpu_mp2::Level
+    uint64_t subbands;         // 0, or [n_cifs + 1][2][36][32] float
+    uint64_t audio;            // one dabgpu_mp2::AudioResult
+    uint64_t in_stride;
+    int32_t bitrate;           // B, kbit/s
+    int32_t reserved[3];
+};
+size_t mp2_audio_table_bytes(int n_entries);
+// `entries`: HOST array (copied to d_table on `stream` before the kernels); every pointer checked by the caller
+hipError_t launch_mp2_subbands(const Mp2AudioEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

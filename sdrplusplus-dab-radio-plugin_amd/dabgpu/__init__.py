@@ -55,6 +55,7 @@ EXPORTS = [
     "dabgpu_dabplus_follow_dev", "dabgpu_dabplus_carry_bytes", "dabgpu_fig_audio_components",
     "dabgpu_pad_state_bytes", "dabgpu_pad_labels_dev", "dabgpu_pad_labels_host", "dabgpu_pad_label_utf8",
     "dabgpu_mp2_carry_bytes", "dabgpu_mp2_follow_dev", "dabgpu_mp2_follow_host",
+    "dabgpu_mp2_subbands_dev", "dabgpu_mp2_subbands_host",
     "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
 ]
 
@@ -149,6 +150,16 @@ MP2_RESULT_DTYPE = np.dtype([(n, np.int32) for n in (
 assert MP2_RESULT_DTYPE.itemsize == 64
 #: a row of the layer-II follow call, and the bit rate the PAD / slideshow entries name for such rows (110 * 16 / 8 = 220)
 MP2_ROW_BYTES, MP2_PAD_KBPS = 220, 16
+#: dabgpu_mp2_level: the audio level record of one row of Context.mp2_subbands_dev / mp2_subbands_host (sub-band domain)
+MP2_LEVEL_DTYPE = np.dtype([("kind", np.int32), ("channels", np.int32), ("cells", np.int32), ("scf63", np.int32),
+                            ("power", np.float32, (2,)), ("peak", np.float32, (2,))])
+assert MP2_LEVEL_DTYPE.itemsize == 32
+MP2_AUDIO_DECODED, MP2_AUDIO_NOT_GOOD, MP2_AUDIO_OVERRUN = 0, 1, 2
+#: dabgpu_mp2_audio_result: the rows of one entry in one call by kind, and the decoded ones whose power is zero
+MP2_AUDIO_RESULT_DTYPE = np.dtype([(n, np.int32) for n in ("decoded", "not_good", "overrun", "silent")] + [("reserved", np.int32, (4,))])
+assert MP2_AUDIO_RESULT_DTYPE.itemsize == 32
+#: the sub-band samples of one row: [channel][sample][sub-band] float32
+MP2_SUBBANDS_SHAPE = (2, 36, 32)
 #: dabgpu_mot_slide: the record in front of every slide in its slot (then header_bytes of MOT header, then body_bytes of body)
 MOT_SLIDE_DTYPE = np.dtype([(n, np.int32) for n in (
     "transport_id", "content_type", "content_subtype", "header_bytes", "body_bytes", "superframe", "au", "reserved")])
@@ -234,6 +245,15 @@ class Mp2Entry(C.Structure):
     _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
                 ("d_carry_out", C.c_void_p), ("d_rows", C.c_void_p), ("d_status", C.c_void_p), ("d_follow", C.c_void_p),
                 ("d_result", C.c_void_p)]
+
+
+class Mp2AudioEntry(C.Structure):
+    """dabgpu_mp2_audio_entry: one followed DAB (MPEG layer II) sub-channel of Context.mp2_subbands_dev (device addresses) or
+    mp2_subbands_host (host addresses): the follow entry's d_in / d_carry_in / d_status / d_result, the level records, the
+    optional sub-band samples, the counters."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("d_carry_in", C.c_void_p),
+                ("d_status", C.c_void_p), ("d_result", C.c_void_p), ("d_levels", C.c_void_p), ("d_subbands", C.c_void_p),
+                ("d_audio", C.c_void_p)]
 
 
 class PadEntry(C.Structure):
@@ -545,6 +565,8 @@ def load_library(path):
     L.dabgpu_mp2_carry_bytes.argtypes = [i]
     L.dabgpu_mp2_follow_dev.argtypes = [vp, C.POINTER(Mp2Entry), i, i, vp]
     L.dabgpu_mp2_follow_host.argtypes = [C.POINTER(Mp2Entry), i, i]
+    L.dabgpu_mp2_subbands_dev.argtypes = [vp, C.POINTER(Mp2AudioEntry), i, i, vp]
+    L.dabgpu_mp2_subbands_host.argtypes = [C.POINTER(Mp2AudioEntry), i, i]
     L.dabgpu_mot_state_bytes.restype = C.c_size_t
     L.dabgpu_mot_state_bytes.argtypes = []
     L.dabgpu_mot_arena_bytes.restype = C.c_size_t
@@ -792,6 +814,14 @@ def mp2_follow_host(entries, n_cifs):
     n = len(entries)
     arr = (Mp2Entry * max(n, 1))(*entries)
     _check(lib().dabgpu_mp2_follow_host(arr, n, n_cifs), "dabgpu_mp2_follow_host")
+
+
+def mp2_subbands_host(entries, n_cifs):
+    """Context.mp2_subbands_dev on HOST memory (entries: Mp2AudioEntry with host addresses): the same checks and the same
+    code, include/dabgpu_mp2_audio.h; no context, no GPU."""
+    n = len(entries)
+    arr = (Mp2AudioEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_mp2_subbands_host(arr, n, n_cifs), "dabgpu_mp2_subbands_host")
 
 
 def pad_label_utf8(label):
@@ -1356,6 +1386,16 @@ class Context:
         n = len(entries)
         arr = (Mp2Entry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_mp2_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_mp2_follow_dev")
+
+    def mp2_subbands_dev(self, entries, n_cifs, stream=None):
+        """Behind mp2_follow_dev on the same stream: decodes every checked frame of every entry (a list of Mp2AudioEntry, device
+        addresses, n_cifs as in the follow call) to sub-band samples -- everything of layer II but the synthesis filter.  Per
+        entry: d_levels [n_cifs + 1] (MP2_LEVEL_DTYPE; rows at or beyond the follow call's `frames` are not written),
+        d_subbands NULL or [n_cifs + 1] + MP2_SUBBANDS_SHAPE float32, d_audio (MP2_AUDIO_RESULT_DTYPE).  No host
+        synchronisation."""
+        n = len(entries)
+        arr = (Mp2AudioEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_mp2_subbands_dev(self._h, arr, n, n_cifs, stream), "dabgpu_mp2_subbands_dev")
 
     def pad_labels_dev(self, entries, stream=None):
         """Dynamic labels of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list of

@@ -838,6 +838,169 @@ def mp2_frame(rng, bitrate, mode=MP2_STEREO, mode_ext=0, lsf=False, pad=None, cr
     return f
 
 
+# The transmit side of include/dabgpu_mp2_audio.h: a frame whose whole audio part is chosen -- bit allocation, SCFSI, scale
+# factors and samples (ISO 11172-3 2.4.1.6, Annex B tables B.2a, B.2c and B.4; ISO 13818-3 table B.1) -- and the sub-band
+# values those choices mean.  Levels of allocation index 1, 2, ... per run of sub-bands:
+_MP2_LEVELS_48K_LARGE = ([[3] + [2 ** b - 1 for b in range(3, 17)]] * 3
+                         + [[3, 5, 7, 9] + [2 ** b - 1 for b in range(4, 14)] + [65535]] * 8
+                         + [[3, 5, 7, 9, 15, 31, 65535]] * 12 + [[3, 5, 65535]] * 4)
+_MP2_LEVELS_48K_SMALL = [[3, 5, 9] + [2 ** b - 1 for b in range(4, 16)]] * 2 + [[3, 5, 9, 15, 31, 63, 127]] * 6
+_MP2_LEVELS_24K = [[3, 5, 7, 9] + [2 ** b - 1 for b in range(4, 15)]] * 4 + [[3, 5, 9, 15, 31, 63, 127]] * 7 + [[3, 5, 9]] * 19
+_MP2_GROUPED_BITS = {3: 5, 5: 7, 9: 10}
+_MP2_SCF_PARTS = {0: (0, 1, 2), 1: (0, 0, 1), 2: (0, 0, 0), 3: (0, 1, 1)}     # SCFSI -> which index sent holds in each part
+
+
+def mp2_levels(bitrate, mode, lsf):
+    """levels[sb][a - 1] of the allocation table a frame of this rate and mode uses"""
+    per_channel = bitrate if mode == MP2_MONO else bitrate // 2
+    return _MP2_LEVELS_24K if lsf else _MP2_LEVELS_48K_SMALL if per_channel in (32, 48) else _MP2_LEVELS_48K_LARGE
+
+
+def mp2_field_bits(n):
+    """bits an active allocation field of n levels takes in one granule"""
+    return _MP2_GROUPED_BITS[n] if n in _MP2_GROUPED_BITS else 3 * (n + 1).bit_length() - 3
+
+
+def mp2_audio_bits(bitrate, mode, mode_ext, lsf, alloc, scfsi):
+    """(E, limit): the bit position behind the last sample of a frame with allocation indices alloc[ch][sb] and SCFSI
+    scfsi[ch][sb], and the position its audio must end in front of, 8 (L - 6 - c)"""
+    levels = mp2_levels(bitrate, mode, lsf)
+    channels, sblimit = (1 if mode == MP2_MONO else 2), len(levels)
+    bound = min(4 * (mode_ext + 1), sblimit) if mode == MP2_JOINT else sblimit
+    nbal = [len(l).bit_length() for l in levels]
+    E = 48
+    for sb in range(sblimit):
+        shared = channels == 2 and sb >= bound
+        for ch in range(channels):
+            a = int(alloc[0 if shared else ch][sb])
+            if not shared or ch == 0:
+                E += nbal[sb] + (12 * mp2_field_bits(levels[sb][a - 1]) if a else 0)
+            if a:
+                E += 2 + 6 * len(set(_MP2_SCF_PARTS[int(scfsi[ch][sb])]))
+    return E, 8 * ((6 if lsf else 3) * bitrate - 6 - mp2_scf_crc_bytes(bitrate, mode, lsf))
+
+
+def mp2_audio_pack(rng, bitrate, mode, mode_ext, lsf, alloc, scfsi, scf, samples, pad=None, codes=None, fit=True):
+    """The frame that says exactly this: allocation indices alloc[ch][sb] (a shared field is channel 0's), SCFSI
+    scfsi[ch][sb], scale-factor indices scf[ch][sb][part] (of which the frame sends those its SCFSI names: for SCFSI 1 the
+    indices of parts 0 and 2, for 2 that of part 0, for 3 those of parts 0 and 1) and samples[ch][t][sb] (integers 0 .. n - 1;
+    a shared field carries channel 0's) -- or, for a grouped field, codes[(g, sb, ch)] = the raw code word instead of its
+    three samples.  Header, ISO CRC, the audio from bit 48 on, random bytes behind it (rng), the PAD as mp2_frame lays it.
+    fit = False packs an audio part that runs past 8 (L - 6 - c), as far as the frame goes.
+    -> (frame uint8 [L], truth float64 [2][36][32]: what the frame's words mean, read as the frame sends them)"""
+    rates = MP2_RATES_24K if lsf else MP2_RATES_48K
+    assert bitrate in rates[1:]
+    L = (6 if lsf else 3) * bitrate
+    levels = mp2_levels(bitrate, mode, lsf)
+    channels, sblimit = (1 if mode == MP2_MONO else 2), len(levels)
+    bound = min(4 * (mode_ext + 1), sblimit) if mode == MP2_JOINT else sblimit
+    nbal = [len(l).bit_length() for l in levels]
+    E, limit = mp2_audio_bits(bitrate, mode, mode_ext, lsf, alloc, scfsi)
+    assert not fit or E <= limit, "the audio does not fit: %d bits in front of %d" % (E, limit)
+    f = rng.integers(0, 256, size=L, dtype=np.uint8)
+    f[0] = 0xFF
+    f[1] = 0xF0 | ((0 if lsf else 1) << 3) | (2 << 1)
+    f[2] = (rates.index(bitrate) << 4) | (1 << 2) | (int(f[2]) & 1)
+    f[3] = (mode << 6) | (mode_ext << 4) | (int(f[3]) & 0x0F)
+    bits = []
+
+    def put(v, n):
+        bits.extend((int(v) >> (n - 1 - k)) & 1 for k in range(n))
+
+    fields = [(sb, ch) for sb in range(sblimit) for ch in range(1 if channels == 1 or sb >= bound else 2)]
+    cells = [(sb, ch) for sb in range(sblimit) for ch in range(channels)]
+    index = lambda sb, ch: int(alloc[0 if channels == 2 and sb >= bound else ch][sb])
+    for sb, ch in fields:
+        put(index(sb, ch), nbal[sb])
+    active = [(sb, ch) for sb, ch in cells if index(sb, ch)]
+    for sb, ch in active:
+        put(scfsi[ch][sb], 2)
+    protected = len(bits)
+    for sb, ch in active:
+        parts = _MP2_SCF_PARTS[int(scfsi[ch][sb])]
+        for j in sorted(set(parts)):
+            put(scf[ch][sb][parts.index(j)], 6)
+    truth = np.zeros((2, 36, 32), np.float64)
+    for g in range(12):
+        for sb, ch in fields:
+            a = index(sb, ch)
+            if not a:
+                continue
+            n = levels[sb][a - 1]
+            if n in _MP2_GROUPED_BITS:
+                if codes is not None and (g, sb, ch) in codes:
+                    c = int(codes[(g, sb, ch)])
+                else:
+                    c = sum(int(samples[ch][3 * g + k][sb]) * n ** k for k in range(3))
+                put(c, _MP2_GROUPED_BITS[n])
+                s = [c % n, (c // n) % n, (c // (n * n)) % n]
+            else:
+                s = [int(samples[ch][3 * g + k][sb]) for k in range(3)]
+                for v in s:
+                    put(v, (n + 1).bit_length() - 1)
+            for to in ((0, 1) if channels == 2 and sb >= bound else (ch,)):
+                # (the index that holds in this part is the one SENT for it: parts that share an index share the first's)
+                parts = _MP2_SCF_PARTS[int(scfsi[to][sb])]
+                i = int(scf[to][sb][parts.index(parts[g // 4])])
+                factor = 0.0 if i == 63 else 2.0 ** (1.0 - i / 3.0)
+                for k in range(3):
+                    truth[to, 3 * g + k, sb] = (2 * s[k] + 1 - n) / n * factor
+    assert len(bits) == E - 48
+    bits = bits[:8 * (L - 6)]
+    nbytes = (len(bits) + 7) // 8
+    stream = np.unpackbits(f[6:6 + nbytes])
+    stream[:len(bits)] = bits
+    f[6:6 + nbytes] = np.packbits(stream)
+    c = mp2_crc([int(b) for b in np.unpackbits(f[2:4])] + bits[:protected])
+    f[4], f[5] = c >> 8, c & 0xFF
+    if pad is not None:
+        pad = bytes(pad)
+        c = mp2_scf_crc_bytes(bitrate, mode, lsf)
+        xpad = pad[:-2]
+        assert len(pad) >= 2 and len(xpad) <= min(196, L - 8 - c), "the PAD does not fit this frame"
+        xpad = bytes(max(0, 4 - len(xpad))) + xpad
+        f[L - 2:] = np.frombuffer(pad[-2:], np.uint8)
+        f[L - 6:L - 2] = np.frombuffer(xpad[-4:], np.uint8)
+        if len(xpad) > 4:
+            assert 8 * (L - 6 - c - (len(xpad) - 4)) >= min(E, limit), "the PAD would lie over the audio"
+            f[L - 6 - c - (len(xpad) - 4):L - 6 - c] = np.frombuffer(xpad[:-4], np.uint8)
+    return f, truth
+
+
+def mp2_audio_frame(rng, bitrate, mode=MP2_STEREO, mode_ext=0, lsf=False, pad=None, silent_bands=0.25, scf_range=(0, 63)):
+    """One layer-II audio frame with a whole audio part, and the truth: random allocation (a share of silent_bands of the
+    fields zero), SCFSI, scale-factor indices (scf_range, 63 excluded) and samples; the largest allocation indices are lowered
+    one at a time until the audio (and an X-PAD of more than four bytes) fits in front of L - 6 - c.
+    -> (frame uint8 [L], truth float64 [2][36][32]) as mp2_audio_pack."""
+    levels = mp2_levels(bitrate, mode, lsf)
+    channels, sblimit = (1 if mode == MP2_MONO else 2), len(levels)
+    bound = min(4 * (mode_ext + 1), sblimit) if mode == MP2_JOINT else sblimit
+    alloc = np.zeros((2, 32), np.int64)
+    for sb in range(sblimit):
+        for ch in range(channels):
+            if rng.random() >= silent_bands:
+                alloc[ch][sb] = rng.integers(1, len(levels[sb]) + 1)
+        if channels == 2 and sb >= bound:
+            alloc[1][sb] = alloc[0][sb]
+    scfsi = rng.integers(0, 4, size=(2, 32))
+    scf = rng.integers(scf_range[0], scf_range[1], size=(2, 32, 3))
+    room = 8 * max(0, len(bytes(pad)) - 2 - 4) if pad is not None else 0
+    while True:
+        E, limit = mp2_audio_bits(bitrate, mode, mode_ext, lsf, alloc, scfsi)
+        if E <= limit - room:
+            break
+        ch, sb = np.unravel_index(int(np.argmax(alloc)), alloc.shape)      # (the first of the largest)
+        alloc[ch][sb] -= 1
+        if channels == 2 and sb >= bound:
+            alloc[1][sb] = alloc[0][sb]
+    samples = np.zeros((2, 36, 32), np.int64)
+    for sb in range(sblimit):
+        for ch in range(channels):
+            if alloc[ch][sb]:
+                samples[ch, :, sb] = rng.integers(0, levels[sb][alloc[ch][sb] - 1], size=36)
+    return mp2_audio_pack(rng, bitrate, mode, mode_ext, lsf, alloc, scfsi, scf, samples, pad=pad)
+
+
 # ----------------------------------------------------------------------------- PAD: slideshow (MOT in X-PAD)
 # The transmit side of the slideshow, from the clauses: object -> MOT header (core + parameters, EN 301 234 6.1, 6.2;
 # TS 101 499 6.2) and body -> segments with their segmentation header (EN 301 234 5.1) -> MSC data groups with session

@@ -10,6 +10,9 @@
 // lifted into a row) and the two walks behind it (basic_pad_reader.h).  Frame by frame there is no vote: a logical frame
 // with a valid 24 kHz header waits for its second half; if the next one has such a header too, the one that waited was
 // an orphan (a lost access unit) and the new one waits.  Frames without the ISO CRC (protection bit 1) deliver no PAD.
+// GetAudioLevel() answers whether audio is on the channel and how loud: while audio decoding is enabled every good frame
+// goes through the serial decoder of include/dabgpu_mp2_audio.h (the code the GPU batch call dabgpu_mp2_subbands_dev runs a
+// lane per cell) to its sub-band samples' power and peak; the synthesis filter to PCM is not part of it.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -17,6 +20,7 @@
 #include <vector>
 #include "basic_radio/basic_audio_channel.h"
 #include "basic_radio/basic_pad_reader.h"
+#include "dabgpu_mp2_audio.h"
 #include "dabgpu_mp2_frame.h"
 
 // what the GUI prints about a layer-II stream (/root/reference/src/render_radio_block.cpp:444-467): the names of the
@@ -48,7 +52,9 @@ public:
         const bool sync = lf[0] == 0xFF && (lf[1] & 0xF0) == 0xF0;
         const bool layer2 = ((lf[1] >> 1) & 3) == 2;
         const bool fs_ok = ((lf[2] >> 2) & 3) == 1;
-        if (m_controls.GetIsDecodeData()) ReadPad(lf);
+        m_read_data = m_controls.GetIsDecodeData();
+        m_read_audio = m_controls.GetIsDecodeAudio();
+        if (m_read_data || m_read_audio) ReadPad(lf);
         if (!(sync && layer2 && fs_ok)) {
             m_total_header_errors++;
             m_is_error = true;
@@ -77,6 +83,8 @@ public:
     int GetTotalCrcErrors() const { return m_total_crc_errors; }
     int GetTotalFramesWithoutCrc() const { return m_total_no_crc; }
     int GetDynamicLabelCharset() const { return m_pad ? m_pad->GetLabel().charset : 0; }
+    // the level record of the last good frame seen while audio decoding was enabled (sub-band domain, include/dabgpu_mp2_audio.h)
+    const std::optional<dabgpu_mp2::Level> &GetAudioLevel() const { return m_level; }
 
 private:
     // one logical frame through the shared header: a 48 kHz frame, or a half of a 24 kHz one
@@ -91,7 +99,7 @@ private:
             m_half.clear();
             return;
         }
-        if (!m_half.empty()) Lost();                                       // an orphan first half
+        if (!m_half.empty() && m_read_data) Lost();                        // an orphan first half
         if (starts_24k) {
             m_half.assign(lf.begin(), lf.end());
             return;
@@ -103,6 +111,8 @@ private:
         namespace mp2 = dabgpu_mp2;
         int c = 0;
         const int kind = mp2::parse_frame(f, L, B, id, &c);
+        if (m_read_audio && kind == mp2::FRAME_GOOD) m_level = mp2::decode_frame(f, L, B, id, static_cast<float *>(nullptr));
+        if (!m_read_data) return;
         m_total_crc_errors += kind == mp2::FRAME_CRC_FAILED;
         m_total_no_crc += kind == mp2::FRAME_NO_CRC;
         if (kind != mp2::FRAME_GOOD) return Lost();
@@ -127,4 +137,6 @@ private:
     std::vector<uint8_t> m_half;           // the first logical frame of a 24 kHz frame, waiting for the second
     std::unique_ptr<Basic_Pad_Reader> m_pad;
     int m_total_checked = 0, m_total_crc_errors = 0, m_total_no_crc = 0;
+    bool m_read_data = false, m_read_audio = false;                       // the controls, as Process found them
+    std::optional<dabgpu_mp2::Level> m_level;
 };
