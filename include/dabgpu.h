@@ -1556,8 +1556,8 @@ int dabgpu_pad_label_utf8(const dabgpu_pad_label *label, char *out, int cap);
 /*                                                                                */
 /* Not read: FIG 0/13 user application signalling (X-PAD types 12 / 13 are taken    */
 /* as MOT as given); MOT directory mode (data group types 6, 7); scrambled bodies   */
-/* (type 5) and CA parameters; packet-mode MOT.  The image is not decoded; the       */
-/* device does not look at the content type.                                         */
+/* (type 5) and CA parameters.  The image is not decoded; the device does not look    */
+/* at the content type.  (MOT in packet mode: dabgpu_packet_slides_dev, below.)       */
 /*                                                                                */
 /* THE CONTRACT of one entry in one call (EN 300 401 clauses 5.3.3, 7.4.5.1;          */
 /* EN 301 234 clauses 5.1, 5.2, 6.1; every ambiguity decided).                        */
@@ -1834,6 +1834,131 @@ typedef struct dabgpu_mp2_audio_entry {     /* HOST array, one per followed sub-
 int dabgpu_mp2_subbands_dev(dabgpu_ctx *ctx, const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs, void *stream);
 /* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
 int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
+/* Packet-mode MOT services of a batch, to their slides, on the device -- what  */
+/* the reference renders for a data packet channel                              */
+/*   (its src/render_radio_block.cpp:533, 538-540, 592-593).                    */
+/* The third kind of service component beside DAB+ and layer II: TMId = 3.       */
+/* dabgpu_fig_packet_components (host) lists them; the caller picks those with   */
+/* DSCTy 60 (MOT) and DG flag 0 and gives one entry per (sub-channel, packet     */
+/* address) to dabgpu_packet_slides_dev, which runs behind                       */
+/* dabgpu_decode_ensembles_dev on the same stream, on the n_cifs logical frames  */
+/* that call wrote.  Two launches: a scan (one lane  */
+/* per 24-byte slot: packet CRCs, the chain of packets of every frame, a list    */
+/* of the followed ones) and a walk (one wave per entry: data groups, then the   */
+/* slideshow call's own closing, assembly and slot code).  The contract and the  */
+/* code are include/dabgpu_packet_walk.h.                                        */
+/*                                                                            */
+/* Not done: Reed-Solomon RS(204,188) correction of FEC frames (FEC packets are  */
+/* recognised and counted only; a later call may correct logical frames in front */
+/* of this one); MOT directory mode (data group types 6, 7); non-MOT packet data */
+/* (TPEG, SPI, Journaline); conditional access; FIG 0/13 user application        */
+/* signalling (the caller chooses DSCTy 60 / DG 0 from the component list).      */
+/*                                                                            */
+/* THE CONTRACT of one entry in one call (EN 300 401 clauses 5.3.2, 5.3.3; every  */
+/* ambiguity decided).                                                           */
+/*                                                                            */
+/* A logical frame of a sub-channel with bit rate R has 3 R bytes: S = R / 8      */
+/* slots of 24 bytes.  Packets do not straddle frames.  Scan of one frame:        */
+/* pos = 0; while pos < S, with h0 h1 h2 the bytes at 24 pos:                     */
+/*   L = (h0 >> 6) + 1 slots; addr = ((h0 & 3) << 8) | h1.  First match wins:     */
+/*   1. fec non-zero, addr == 1022, L == 1: packets_fec++, pos += 1 (no packet    */
+/*      CRC in these 24 bytes; not checked)                                       */
+/*   2. pos + L > S: slots_bad++, pos += 1                                        */
+/*   3. the FIB's CRC over the first 24 L - 2 bytes (x^16 + x^12 + x^5 + 1,       */
+/*      register all ones, complemented, sent big-endian) is not the last two:    */
+/*      slots_bad++, pos += 1 (the scan resynchronises at the next slot and does  */
+/*      not trust a length it could not check)                                    */
+/*   4. a good packet, pos += L: addr == 0: packets_padding++; addr != address:   */
+/*      packets_other++; else packets_followed++, and it is followed.             */
+/*                                                                            */
+/* Followed packets, in frame and position order: ci = (h0 >> 4) & 3,             */
+/* first = (h0 >> 3) & 1, last = (h0 >> 2) & 1, cmd = h2 >> 7, udl = h2 & 0x7F.   */
+/* "Dropped": an open group is forgotten and groups_unfinished++ (nothing when     */
+/* none is open).                                                                 */
+/*   a. a followed packet was seen before (this call or an earlier one) and       */
+/*      ci != (prev + 1) & 3: continuity_breaks++, dropped.  Then prev = ci.       */
+/*   b. udl > 24 L - 5: packets_malformed++, dropped; next packet.                 */
+/*   c. cmd: packets_command++; next packet (an open group stays).                 */
+/*   d. first: dropped; a new group opens empty, groups_opened++.  Not first and   */
+/*      none open: packets_orphan++; next packet.                                  */
+/*   e. have + udl > 16384: groups_too_long++, the group is forgotten (it is not   */
+/*      counted unfinished); next packet.                                          */
+/*   f. the udl bytes from offset 3 are appended; group_bytes += udl.              */
+/*   g. last: have < 4: mot.groups_malformed++, the group is forgotten.  Else the   */
+/*      group closes with length = have by "Closing a group" and "Assembly" of      */
+/*      dabgpu_mot_slides_dev, word for word (CRC flag clear: groups_crc_failed).   */
+/* A completed object goes to its slot as there: a dabgpu_mot_slide whose           */
+/* superframe = the index of the logical frame in this call and au = the slot       */
+/* position of the closing packet, then header and body.                            */
+/*                                                                            */
+/* cifs = n_cifs, slots = n_cifs S.  Of the embedded dabgpu_mot_result the fields    */
+/* only PAD gives (aus .. fields_ignored, lengths_*, groups_no_length, xpad_bytes)   */
+/* stay 0.  The state record is opaque (all zero = a fresh start; a record this      */
+/* library did not write for an arena of this size is one) and goes with the arena   */
+/* from call to call: a group or an object may span any number of calls.  No frame   */
+/* is carried.                                                                      */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_packet_component {
+    uint32_t sid; int32_t scid;            /* FIG 0/2 TMId = 3: SCId(12) P/S(1) CA(1)                      */
+    int32_t subchid, start_address;        /* FIG 0/3 SubChId joined through FIG 0/1                        */
+    int32_t packet_address;                /* FIG 0/3, 10 bits                                              */
+    int32_t dscty, dg_flag;                /* FIG 0/3: DSCTy(6) (60 = MOT), DG flag (0 = data groups used)  */
+    int32_t fec_scheme;                    /* FIG 0/14 for that SubChId (2 bits), 0 if none seen            */
+    int32_t primary, reserved[3];
+} dabgpu_packet_component;
+
+/* host only, the sister of dabgpu_fig_audio_components: the packet-mode components (FIG 0/2 TMId = 3, both P/D forms) of
+ * CRC-clean FIBs of ONE ensemble, current configuration of this ensemble (C/N = 0, OE = 0), joined through their SCId to
+ * FIG 0/3 -- SCId(12) Rfa(3) CAOrg flag(1), DG flag(1) Rfu(1) DSCTy(6), SubChId(6) packet address(10), CAOrg(16) only when
+ * its flag is set -- through the SubChId to FIG 0/1 (the start address) and to FIG 0/14 -- entries of SubChId(6) FEC
+ * scheme(2).  Sorted by (start address, packet address); each (SubChId, packet address) once (its first component); a
+ * component whose FIG 0/3 or whose sub-channel the same FIBs have not announced is left out.  *n receives the count;
+ * DABGPU_ERR_CAPACITY if max is too small (nothing written). */
+int dabgpu_fig_packet_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_packet_component *out, int max,
+                                 int *n);
+
+typedef struct dabgpu_packet_result {       /* counts of THIS call */
+    int32_t cifs, slots, slots_bad;
+    int32_t packets_fec, packets_padding, packets_other, packets_followed;
+    int32_t continuity_breaks, packets_malformed, packets_command, packets_orphan;
+    int32_t groups_opened, groups_unfinished, groups_too_long;
+    int32_t group_bytes;                    /* useful bytes taken into data groups                              */
+    int32_t reserved;
+    dabgpu_mot_result mot;                  /* from the closed group on                                         */
+} dabgpu_packet_result;
+
+typedef struct dabgpu_packet_entry {        /* HOST array, one per (sub-channel, packet address); every pointer DEVICE memory */
+    const uint8_t *d_in;        /* [n_cifs][in_stride] logical frames of 3 * bitrate_kbps bytes, any alignment; several
+                                 * entries may name the same frames                                               */
+    size_t in_stride;           /* >= 3 * bitrate_kbps                                                           */
+    int32_t bitrate_kbps;       /* a multiple of 8 in 8 .. 512                                                   */
+    int32_t address;            /* the packet address followed, 1 .. 1023                                        */
+    int32_t fec;                /* non-zero: the sub-channel carries FEC packets (the component's fec_scheme)    */
+    int32_t reserved;
+    const void *d_state_in;     /* dabgpu_packet_state_bytes() on a 16-byte boundary; NULL or all zero = fresh start */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    void *d_arena;              /* as dabgpu_mot_entry: 16-byte boundary, updated in place                       */
+    size_t arena_bytes;         /* >= dabgpu_mot_arena_bytes(0); what is beyond it is body_capacity              */
+    uint8_t *d_slides;          /* [max_slides] slots, 16-byte boundary; may be NULL with max_slides == 0          */
+    size_t slide_stride;        /* a multiple of 16, >= 32                                                       */
+    int32_t max_slides;         /* max_slides * slide_stride < 2^31                                              */
+    int32_t reserved2;
+    dabgpu_packet_result *d_result;
+} dabgpu_packet_entry;
+
+size_t dabgpu_packet_state_bytes(void);
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Everything is checked before anything is enqueued, so a refused call
+ * leaves every output as it was: DABGPU_ERR_ARG for a NULL context or table, a negative count, n_cifs outside 0 .. 2^24, a
+ * bit rate outside 8 .. 512 or no multiple of 8, in_stride < 3 * bitrate_kbps, an address outside 1 .. 1023, a NULL d_in with
+ * n_cifs > 0, a NULL pointer other than d_in, d_state_in (and d_slides with max_slides == 0), and for the state records, the
+ * arena, the slots and d_result what dabgpu_mot_slides_dev refuses; DABGPU_ERR_CAPACITY for a table whose scan would need
+ * 2^31 or more workgroups (n_entries times the frames of a call over the frames a wave takes, 64 / S). */
+int dabgpu_packet_slides_dev(dabgpu_ctx *ctx, const dabgpu_packet_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_packet_slides_host(const dabgpu_packet_entry *entries, int n_entries, int n_cifs);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

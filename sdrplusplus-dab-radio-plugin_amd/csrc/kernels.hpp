@@ -443,6 +443,38 @@ size_t mp2_audio_table_bytes(int n_entries);
 // `entries`: HOST array (copied to d_table on `stream` before the kernels); every pointer checked by the caller
 hipError_t launch_mp2_subbands(const Mp2AudioEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
 
+// ---- packet-mode MOT services to slides (packet_kernels.hip) -----------------------
+// dabgpu_packet_slides_dev: one entry per (sub-channel, packet address), uploaded as a table; the scan kernel (one lane per
+// 24-byte slot, 64 / S frames a wave) checks every candidate packet's CRC, resolves each frame's chain and writes one scan
+// record per frame behind the table; the walk kernel (one wave per entry) sums the records' counters, runs the control walk
+// of include/dabgpu_packet_walk.h in lane 0 over the followed packets alone and executes its copy orders with all 64 lanes.
+struct alignas(16) PacketEntry {
+    uint64_t in;               // [n_cifs][in_stride] logical frames of 24 s bytes
+    uint64_t in_stride;
+    uint64_t state_in;         // dabgpu_packet::State or 0
+    uint64_t state_out;
+    uint64_t arena;            // dabgpu_mot::arena_bytes(body_capacity), updated in place
+    uint64_t slides;           // [max_slides][slide_stride]
+    uint64_t result;           // dabgpu_packet::Counters
+    uint64_t records;          // [n_cifs] scan records of packet_record_words(s) words (filled in by the launch)
+    uint32_t slide_stride;
+    int32_t max_slides;
+    int32_t body_capacity;
+    int32_t s;                 // bitrate / 8
+    int32_t address;
+    int32_t fec;
+    int32_t reserved[2];
+};
+// A scan record: word 0 = followed packets n, word 1 = FEC | bad << 8 | padding << 16 | other << 24 (each <= 64), words 2, 3
+// zero, then n words pos | L << 8 | h0 << 16 | h2 << 24 (room for s)
+__host__ __device__ inline int packet_record_words(int s) { return 4 + s; }
+size_t packet_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs);
+// workgroups of the scan launch; 0 = nothing to scan
+uint64_t packet_scan_blocks(const PacketEntry *entries, int n_entries, int n_cifs);
+// `entries`: HOST array (its `records` are set here; copied to d_table on `stream` before the kernels); every pointer checked
+// by the caller
+hipError_t launch_packet_slides(PacketEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

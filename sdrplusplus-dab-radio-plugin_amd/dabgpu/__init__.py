@@ -57,6 +57,7 @@ EXPORTS = [
     "dabgpu_mp2_carry_bytes", "dabgpu_mp2_follow_dev", "dabgpu_mp2_follow_host",
     "dabgpu_mp2_subbands_dev", "dabgpu_mp2_subbands_host",
     "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
+    "dabgpu_fig_packet_components", "dabgpu_packet_state_bytes", "dabgpu_packet_slides_dev", "dabgpu_packet_slides_host",
 ]
 
 ABI_VERSION = 6
@@ -172,6 +173,19 @@ MOT_COUNTERS = ("aus", "aus_lost", "aus_with_xpad", "pad_malformed", "fields_ign
 MOT_RESULT_DTYPE = np.dtype([(n, np.int32) for n in MOT_COUNTERS] + [("reserved", np.int32, (8,))])
 assert MOT_RESULT_DTYPE.itemsize == 128
 MOT_CONTENT_IMAGE = 2
+#: dabgpu_packet_result: what one entry of packet_slides_dev / packet_slides_host counted in one call; `mot` is a
+#: MOT_RESULT_DTYPE record (from the closed data group on)
+PACKET_COUNTERS = ("cifs", "slots", "slots_bad", "packets_fec", "packets_padding", "packets_other", "packets_followed",
+                   "continuity_breaks", "packets_malformed", "packets_command", "packets_orphan", "groups_opened",
+                   "groups_unfinished", "groups_too_long", "group_bytes")
+PACKET_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_COUNTERS] + [("reserved", np.int32), ("mot", MOT_RESULT_DTYPE)])
+assert PACKET_RESULT_DTYPE.itemsize == 192
+#: dabgpu_packet_component: one packet-mode service component (fig_packet_components)
+PACKET_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("scid", np.int32), ("subchid", np.int32), ("start_address", np.int32),
+                                   ("packet_address", np.int32), ("dscty", np.int32), ("dg_flag", np.int32), ("fec_scheme", np.int32),
+                                   ("primary", np.int32), ("reserved", np.int32, (3,))])
+assert PACKET_COMPONENT_DTYPE.itemsize == 48
+DSCTY_MOT = 60
 #: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
 AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
                                   ("primary", np.int32), ("reserved", np.int32, (3,))])
@@ -271,6 +285,25 @@ class MotEntry(C.Structure):
                 ("bitrate_kbps", C.c_int32), ("max_superframes", C.c_int32), ("d_state_in", C.c_void_p),
                 ("d_state_out", C.c_void_p), ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_slides", C.c_void_p),
                 ("slide_stride", C.c_size_t), ("max_slides", C.c_int32), ("reserved", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class PacketEntry(C.Structure):
+    """dabgpu_packet_entry: one (sub-channel, packet address) of Context.packet_slides_dev (device addresses) or
+    packet_slides_host (host addresses): the logical frames the decode call wrote, the address followed, the state records,
+    the arena, the slide slots, the counters."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("address", C.c_int32),
+                ("fec", C.c_int32), ("reserved", C.c_int32), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
+                ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_slides", C.c_void_p), ("slide_stride", C.c_size_t),
+                ("max_slides", C.c_int32), ("reserved2", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class PacketComponent(C.Structure):
+    _fields_ = [("sid", C.c_uint32), ("scid", C.c_int32), ("subchid", C.c_int32), ("start_address", C.c_int32),
+                ("packet_address", C.c_int32), ("dscty", C.c_int32), ("dg_flag", C.c_int32), ("fec_scheme", C.c_int32),
+                ("primary", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+assert C.sizeof(PacketComponent) == PACKET_COMPONENT_DTYPE.itemsize
 
 
 class MotText(C.Structure):
@@ -574,6 +607,11 @@ def load_library(path):
     L.dabgpu_mot_slides_dev.argtypes = [vp, C.POINTER(MotEntry), i, vp]
     L.dabgpu_mot_slides_host.argtypes = [C.POINTER(MotEntry), i]
     L.dabgpu_mot_header_parse.argtypes = [vp, i, C.POINTER(MotHeader)]
+    L.dabgpu_fig_packet_components.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
+    L.dabgpu_packet_state_bytes.restype = C.c_size_t
+    L.dabgpu_packet_state_bytes.argtypes = []
+    L.dabgpu_packet_slides_dev.argtypes = [vp, C.POINTER(PacketEntry), i, i, vp]
+    L.dabgpu_packet_slides_host.argtypes = [C.POINTER(PacketEntry), i, i]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -783,6 +821,35 @@ def fig_audio_components(fib, crc_ok, max_out=64):
     n = C.c_int(0)
     _check(lib().dabgpu_fig_audio_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_audio_components")
     return [AudioComponent(a.sid, a.subchid, a.start_address, a.ascty, a.primary) for a in arr[:n.value]]
+
+
+def fig_packet_components(fib, crc_ok, max_out=64):
+    """The packet-mode service components one ensemble announces (FIG 0/2 TMId 3 joined to FIG 0/3, FIG 0/1 and FIG 0/14) in
+    its CRC-clean FIBs, each (sub-channel, packet address) once, sorted by (start address, packet address): fib
+    [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of PacketComponent (dscty 60 = MOT; no GPU needed)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    arr = (PacketComponent * max(max_out, 1))()
+    n = C.c_int(0)
+    _check(lib().dabgpu_fig_packet_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_packet_components")
+    return [PacketComponent(a.sid, a.scid, a.subchid, a.start_address, a.packet_address, a.dscty, a.dg_flag, a.fec_scheme, a.primary)
+            for a in arr[:n.value]]
+
+
+def packet_state_bytes():
+    """Bytes of one state record of Context.packet_slides_dev / packet_slides_host (all zero = a fresh start)."""
+    return int(lib().dabgpu_packet_state_bytes())
+
+
+def packet_slides_host(entries, n_cifs):
+    """Context.packet_slides_dev on HOST memory (entries: PacketEntry with host addresses): the same checks and the same
+    code, include/dabgpu_packet_walk.h; no context, no GPU."""
+    n = len(entries)
+    arr = (PacketEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_packet_slides_host(arr, n, n_cifs), "dabgpu_packet_slides_host")
 
 
 def dabplus_carry_bytes(bitrate_kbps):
@@ -1413,6 +1480,16 @@ class Context:
         n = len(entries)
         arr = (MotEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_mot_slides_dev(self._h, arr, n, stream), "dabgpu_mot_slides_dev")
+
+    def packet_slides_dev(self, entries, n_cifs, stream=None):
+        """Slideshow objects of packet-mode MOT components, behind decode_ensembles_dev on the same stream: entries is a list
+        of PacketEntry (device addresses), one per (sub-channel, packet address); n_cifs logical frames each.  Per entry:
+        completed objects in the slots of d_slides (MOT_SLIDE_DTYPE, the MOT header, the body), d_result
+        (PACKET_RESULT_DTYPE, counts of this call), d_state_out, to be passed as d_state_in of the next call, and d_arena,
+        which goes into the next call as it is.  No host synchronisation."""
+        n = len(entries)
+        arr = (PacketEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_packet_slides_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_slides_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

@@ -1207,6 +1207,88 @@ def pack_pads(sizes, mot_groups, dls_groups, dls_index=0):
 
 
 # ----------------------------------------------------------------------------- FIGs (EN 300 401 clauses 5.2, 6, 8)
+# Packet mode (EN 300 401 clause 5.3.2): a sub-channel of bit rate R carries logical frames of R / 8 slots of 24 bytes;
+# a packet is 1 .. 4 slots: length (2 bits) continuity index (2) first (1) last (1) address (10) command (1) useful data
+# length (7), the data field (useful bytes, then padding), the CRC (the FIB's, big-endian).  Data groups (msc_data_group)
+# travel cut into the useful bytes of packets of one address.
+PACKET_SLOT = 24
+PACKET_FEC_ADDRESS = 1022
+DSCTY_MOT = 60
+
+
+def packet(address, data, slots=None, ci=0, first=True, last=True, command=False, crc=True, udl=None, fill=0):
+    """one packet: slots (default: as few as hold the data) * 24 bytes; crc=False sends a wrong CRC; udl: what the header
+    says (default: the truth)"""
+    data = bytes(data)
+    if slots is None:
+        slots = max(1, -(-(len(data) + 5) // PACKET_SLOT))
+    room = PACKET_SLOT * slots - 5
+    assert 1 <= slots <= 4 and len(data) <= room and 0 <= address < 1024
+    n = len(data) if udl is None else udl
+    head = _bits((slots - 1, 2), (ci & 3, 2), (int(first), 1), (int(last), 1), (address, 10), (int(command), 1), (n, 7))
+    body = head + data + bytes([fill]) * (room - len(data))
+    c = crc16(body) ^ (0 if crc else 0x0040)
+    return body + bytes([c >> 8, c & 0xFF])
+
+
+def packetise(groups, address, sizes=(4,), ci=0):
+    """data groups -> packets of one address, continuity index from `ci`: each group in packets of sizes[k % len] slots
+    (k: the running packet number), the last one of a group as short as holds the rest; an empty group is one packet"""
+    out, k = [], 0
+    for g in groups:
+        g, at = bytes(g), 0
+        while True:
+            room = PACKET_SLOT * sizes[k % len(sizes)] - 5
+            rest = len(g) - at
+            final = rest <= room
+            take = rest if final else room
+            out.append(packet(address, g[at:at + take], None if final else sizes[k % len(sizes)], ci=ci + k, first=at == 0, last=final))
+            k += 1
+            at += take
+            if final:
+                break
+    return out
+
+
+def padding_packet(slots=1, fill=0x55):
+    """a padding packet: address 0, no useful data"""
+    return packet(0, b"", slots, fill=fill)
+
+
+def fec_packet(rng):
+    """24 bytes shaped like an FEC packet: one slot, address 1022, the other 21 bytes what RS parity would be (random): no
+    packet CRC"""
+    return _bits((0, 2), (int(rng.integers(0, 4)), 2), (0, 1), (0, 1), (PACKET_FEC_ADDRESS, 10)) + bytes(rng.integers(0, 256, 22, dtype=np.uint8))
+
+
+def packet_frames(bitrate, streams, n_frames=None):
+    """logical frames [n][3 * bitrate] uint8 of a packet-mode sub-channel: streams is a list of packet lists; a frame takes the
+    next packet of each stream in turn while it fits (a packet never straddles frames; order within a stream is kept), the
+    rest of the frame is padding packets.  n_frames: at least that many frames (of padding, behind the streams)"""
+    slots = bitrate // 8
+    assert bitrate % 8 == 0 and 1 <= slots <= 64
+    queues = [list(q) for q in streams]
+    assert all(len(p) % PACKET_SLOT == 0 and len(p) // PACKET_SLOT <= slots for q in queues for p in q)
+    frames = []
+    while any(queues) or len(frames) < (n_frames or 0):
+        frame, blocked = b"", [False] * len(queues)
+        while True:
+            moved = False
+            for i, q in enumerate(queues):
+                if q and not blocked[i]:
+                    if len(frame) + len(q[0]) <= PACKET_SLOT * slots:
+                        frame += q.pop(0)
+                        moved = True
+                    else:
+                        blocked[i] = True
+            if not moved:
+                break
+        while len(frame) < PACKET_SLOT * slots:
+            frame += padding_packet(min(4, slots - len(frame) // PACKET_SLOT))
+        frames.append(np.frombuffer(frame, np.uint8))
+    return np.stack(frames) if frames else np.zeros((0, 3 * bitrate), np.uint8)
+
+
 # What a multiplex says about itself in the FIC: enough for a receiver to find and decode its audio services
 # without being told anything (FIG 0/0 ensemble, 0/1 sub-channel organisation, 0/2 service organisation,
 # 1/0 ensemble label, 1/1 service labels).
@@ -1246,15 +1328,37 @@ def fig0_1(subchannels):
     return fig0(1, body)
 
 
-def fig0_2(services):
-    """services: dicts {sid (16 bit), components: [{subchannel, ascty, primary}]} (programme services, MSC stream audio)."""
+def fig0_2(services, pd=0):
+    """services: dicts {sid (16 bit; 32 with pd=1), components: [{subchannel, ascty, primary}]} (MSC stream audio) or
+    [{scid, primary}] (packet mode, TMId 3: the 12-bit service component identifier FIG 0/3 describes)."""
     body = b""
     for sv in services:
         comps = sv["components"]
-        body += _bits((sv["sid"], 16), (0, 1), (0, 3), (len(comps), 4))
+        body += _bits((sv["sid"], 32 if pd else 16), (0, 1), (0, 3), (len(comps), 4))
         for c in comps:
-            body += _bits((0, 2), (c["ascty"], 6), (c["subchannel"], 6), (1 if c.get("primary", True) else 0, 1), (0, 1))
-    return fig0(2, body)
+            if "scid" in c:
+                body += _bits((3, 2), (c["scid"], 12), (1 if c.get("primary", True) else 0, 1), (0, 1))
+            else:
+                body += _bits((0, 2), (c["ascty"], 6), (c["subchannel"], 6), (1 if c.get("primary", True) else 0, 1), (0, 1))
+    return fig0(2, body, pd=pd)
+
+
+def fig0_3(entries):
+    """Service component in packet mode (clause 6.3.2): dicts {scid, subchannel, address, dscty (default 60, MOT), dg_flag
+    (default 0: data groups are used), caorg (default None: no CAOrg field)}."""
+    body = b""
+    for e in entries:
+        caorg = e.get("caorg")
+        body += _bits((e["scid"], 12), (0, 3), (0 if caorg is None else 1, 1), (e.get("dg_flag", 0), 1), (0, 1), (e.get("dscty", DSCTY_MOT), 6),
+                      (e["subchannel"], 6), (e["address"], 10))
+        if caorg is not None:
+            body += _bits((caorg, 16))
+    return fig0(3, body)
+
+
+def fig0_14(entries):
+    """FEC sub-channel organisation (clause 6.2.2): [(subchannel_id, fec_scheme), ...]."""
+    return fig0(14, b"".join(_bits((scid, 6), (fec, 2)) for scid, fec in entries))
 
 
 def fig0_5(entries):
@@ -1379,7 +1483,7 @@ class ServiceEnsemble:
     start_cu), ...].  n_frames must be a multiple of 5 so that whole super-frames (5 logical frames) tile."""
 
     def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True, bodies=None,
-                 dab_pads=None):
+                 dab_pads=None, packet_services=()):
         """dab_services: DAB (MPEG layer II) services on UEP sub-channels, [(label, sid, subchannel_id, uep_index,
         start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body).
         extras=False leaves the rotation to the labels alone (FIG 0/0, 0/1, 0/2, 0/10 and one label per CIF): what
@@ -1388,7 +1492,11 @@ class ServiceEnsemble:
         with (PAD); the random draws do not depend on it.
         dab_pads: per DAB service (or None), per logical frame, the PAD (pad_field's bytes, or None: F-PAD alone) of that frame: the
         service then sends mp2_frame()s with the ISO CRC, 48 kHz (stereo, or single channel at the rates only that mode may
-        use), from a generator of their own; the draws of everything else do not depend on it."""
+        use), from a generator of their own; the draws of everything else do not depend on it.
+        packet_services: packet-mode data services on EEP sub-channels, [(label, sid, subchannel_id, option, level, bitrate,
+        start_cu, components, frames, fec_scheme), ...]: components = [(scid, packet address, dscty, dg_flag), ...] (FIG 0/2
+        TMId 3 and FIG 0/3; the first is the primary one), frames = 4 * n_frames logical frames (packet_frames), fec_scheme
+        non-zero announces FIG 0/14.  No random draw depends on them."""
         assert n_frames % 5 == 0
         rng = np.random.default_rng(seed)
         self.n_frames, self.eid, self.label, self.services = n_frames, eid, label, services
@@ -1427,12 +1535,27 @@ class ServiceEnsemble:
             cifs[:, start_cu * 64:(start_cu + size_cu) * 64] = time_interleave(coded, cyclic=True)
             self.mp2_frames.append(data)
             self.subchannels.append({"id": scid, "start": start_cu, "uep_index": uidx})
+        self.packet_services = list(packet_services)
+        packet_figs = []
+        for (lab, sid, scid, option, level, bitrate, start_cu, comps, frames, fec) in self.packet_services:
+            mask, size_cu = eep_mask(option, level, bitrate)
+            data = np.ascontiguousarray(frames, np.uint8)
+            assert data.shape == (R, bitrate * 3), (data.shape, R, bitrate)
+            coded = np.stack([msc_encode_lf(data[r], mask) for r in range(R)])
+            cifs[:, start_cu * 64:(start_cu + size_cu) * 64] = time_interleave(coded, cyclic=True)
+            self.subchannels.append({"id": scid, "start": start_cu, "option": option, "level": level, "size": size_cu})
+            packet_figs.append(fig0_3([{"scid": c[0], "subchannel": scid, "address": c[1], "dscty": c[2], "dg_flag": c[3]} for c in comps]))
+            if fec:
+                packet_figs.append(fig0_14([(scid, fec)]))
         sv = [{"sid": sid, "components": [{"subchannel": scid, "ascty": ASCTY_DABPLUS}]}
               for (lab, sid, scid, *_rest) in services]
         sv += [{"sid": sid, "components": [{"subchannel": scid, "ascty": ASCTY_DAB}]}
                for (lab, sid, scid, *_rest) in self.dab_services]
         labels = [fig1(0, eid, label)] + [fig1(1, sid, lab) for (lab, sid, *_rest) in services]
         labels += [fig1(1, sid, lab) for (lab, sid, *_rest) in self.dab_services]
+        sv += [{"sid": sid, "components": [{"scid": c[0], "primary": k == 0} for k, c in enumerate(comps)]}
+               for (lab, sid, _scid, _o, _l, _b, _s, comps, *_rest) in self.packet_services]
+        labels += [fig1(1, sid, lab) for (lab, sid, *_rest) in self.packet_services]
         # what else a multiplex says about itself (one of these per CIF, in rotation with the labels): country and
         # local time, component identifiers and labels, programme types, languages, a linkage set with its FM
         # alternative and that station's frequencies, the neighbouring ensemble carrying the first service
@@ -1454,6 +1577,7 @@ class ServiceEnsemble:
                 figs = [fig0_0(eid, 4 * f + c)]
                 figs += [fig0_1(self.subchannels[i:i + 6]) for i in range(0, len(self.subchannels), 6)]
                 figs += [fig0_2(sv[i:i + 5]) for i in range(0, len(sv), 5)]
+                figs += packet_figs
                 figs.append(labels[k % len(labels)]); k += 1
                 if c == 3:                                    # once per frame: date and time, advancing 96 ms
                     ms = 96 * f

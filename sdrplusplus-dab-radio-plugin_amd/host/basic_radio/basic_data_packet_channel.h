@@ -1,18 +1,105 @@
 // basic_radio/basic_data_packet_channel.h -- what BasicRadio::Get_Data_Packet_Channel returns
-// (/root/reference/src/render_radio_block.cpp:533, 593).  Packet-mode sub-channels (TMId 3) are not followed by this
-// receiver (data services are outside the hot path), so none is ever created; the type exists
-// for the callers that ask.
+// (the reference's src/render_radio_block.cpp:533, 538-540, 592-593): a packet-mode sub-channel (TMId 3) whose MOT
+// components are followed to their slides.  Process takes the sub-channel's logical frames; the scan and the walk are
+// include/dabgpu_packet_walk.h, the code the GPU batch call dabgpu_packet_slides_dev runs, here on the host with its copy
+// orders executed by a loop (no export of libdabgpu is called); every completed image object goes to the one slideshow
+// manager, through Basic_Add_Slide as an audio channel's do.  Up to four packet addresses (DSCTy 60, DG flag 0) of the
+// sub-channel are followed, each with a state record and an arena of its own.  FEC packets are counted, not corrected.
 #pragma once
+#include <cstdint>
+#include <memory>
+#include <vector>
+#include "basic_radio/basic_pad_reader.h"
 #include "basic_radio/basic_slideshow.h"
 #include "dab/database/dab_database_entities.h"
+#include "dabgpu_packet_walk.h"
+#include "utility/span.h"
 
 class Basic_Data_Packet_Channel {
 public:
-    explicit Basic_Data_Packet_Channel(const Subchannel &subchannel) : m_subchannel(subchannel) {}
+    static constexpr int MAX_ADDRESSES = 4;
+    explicit Basic_Data_Packet_Channel(const Subchannel &subchannel, int fec_scheme = 0) : m_subchannel(subchannel), m_fec(fec_scheme) {
+        m_call.body_capacity = BODY_CAPACITY;
+        m_call.max_slides = 1;                                         // (a packet closes at most one group: one object)
+        m_call.slide_stride = uint32_t(dabgpu_mot::RECORD_BYTES + dabgpu_mot::HEADER_CAP + BODY_CAPACITY);
+    }
     Basic_Slideshow_Manager &GetSlideshowManager() { return m_slideshows; }
     const Subchannel &GetSubchannel() const { return m_subchannel; }
+    void SetFecScheme(int fec_scheme) { m_fec = fec_scheme; }
+    int GetFecScheme() const { return m_fec; }
+
+    // a packet address (1 .. 1023) to follow from the next frame on: false for one out of range, and for a fifth
+    bool FollowAddress(int address) {
+        if (address < 1 || address > 1023) return false;
+        for (const auto &f : m_followers)
+            if (f->address == address) return true;
+        if (int(m_followers.size()) >= MAX_ADDRESSES) return false;
+        auto f = std::make_unique<Follower>();
+        f->address = address;
+        f->arena.resize(size_t(dabgpu_mot::arena_bytes(BODY_CAPACITY)));
+        dabgpu_packet::sanitize(f->state, BODY_CAPACITY);
+        m_followers.push_back(std::move(f));
+        if (m_slot.empty()) m_slot.resize(m_call.slide_stride);
+        return true;
+    }
+    int GetTotalAddresses() const { return int(m_followers.size()); }
+    int GetAddress(int i) const { return m_followers[size_t(i)]->address; }
+    // counts since the address was added (slides_written: of the last packet alone)
+    const dabgpu_packet::Counters &GetCounters(int i) const { return m_followers[size_t(i)]->counts; }
+    int GetTotalFrames() const { return m_total_frames; }
+    int GetTotalFramesIgnored() const { return m_total_ignored; }
+
+    // one logical frame of the sub-channel: 24 S bytes, S = bit rate / 8 in 1 .. 64 (any other size is counted and ignored)
+    void Process(tcb::span<const uint8_t> lf) {
+        namespace pkt = dabgpu_packet;
+        const int S = int(lf.size() / pkt::SLOT_BYTES);
+        if (lf.size() % pkt::SLOT_BYTES || S < 1 || S > pkt::MAX_SLOTS) {
+            m_total_ignored++;
+            return;
+        }
+        const uint8_t *frame = lf.data();
+        uint32_t verdicts[pkt::MAX_SLOTS];                             // one scan for every address
+        for (int pos = 0; pos < S; pos++) verdicts[pos] = pkt::slot_verdict(frame, S, pos, m_fec);
+        dabgpu_mot::Orders orders;
+        dabgpu_mot::Call call = m_call;
+        call.superframe = m_total_frames;
+        for (auto &f : m_followers) {
+            pkt::FrameTally t = {};
+            pkt::Counters &c = f->counts;
+            pkt::resolve_chain(
+                S, f->address, t, [&](int pos) { return verdicts[pos]; },
+                [&](int pos, int L) {
+                    const uint8_t *packet = frame + pkt::SLOT_BYTES * pos;
+                    call.au = pos;
+                    c.mot.slides_written = 0;                          // the slot is this packet's
+                    pkt::follow_packet(f->state, c, orders, call, packet, L);
+                    for (int i = 0; i < orders.n; i++) pkt::execute_order(orders.o[i], orders, packet, f->arena.data(), m_slot.data());
+                    if (c.mot.slides_written) Basic_Add_Slide(m_slideshows, m_slot.data());
+                });
+            c.cifs++;
+            c.slots += S;
+            c.packets_fec += t.fec;
+            c.slots_bad += t.bad;
+            c.packets_padding += t.padding;
+            c.packets_other += t.other;
+            c.packets_followed += t.followed;
+        }
+        m_total_frames++;
+    }
 
 private:
+    static constexpr int BODY_CAPACITY = 256 * 1024;
+    struct Follower {
+        int address = 0;
+        dabgpu_packet::State state{};      // all zero: a fresh start
+        dabgpu_packet::Counters counts{};
+        std::vector<uint8_t> arena;
+    };
     Subchannel m_subchannel;
+    int m_fec;
+    dabgpu_mot::Call m_call{};
+    std::vector<std::unique_ptr<Follower>> m_followers;
+    std::vector<uint8_t> m_slot;
     Basic_Slideshow_Manager m_slideshows;
+    int m_total_frames = 0, m_total_ignored = 0;
 };

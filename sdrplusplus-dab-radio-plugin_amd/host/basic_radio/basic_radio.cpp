@@ -104,6 +104,7 @@ void BasicRadio::Process(tcb::span<const viterbi_bit_t> buf) {
             m_obs_msc.Notify(int(i), lf);
             if (s.dab_plus) s.dab_plus->Process(lf);
             if (s.dab) s.dab->Process(lf);
+            if (s.packet) s.packet->Process(lf);
         }
     }
     LAP(3);
@@ -124,8 +125,87 @@ void BasicRadio::process_fibs_locked() {
         if (m_crc[i]) m_fic_parser.ProcessFIB(tcb::span<const uint8_t>(m_fib.data() + 32 * i, 32));
 }
 
-// Open every audio component whose sub-channel the FIC has described (called with the mutex held).
+// what the per-frame call needs to know of a sub-channel the FIC has described; false: a profile it cannot decode
+bool BasicRadio::describe_subchannel(::Subchannel &sub, dabgpu_subchannel &sc) {
+    sc = dabgpu_subchannel{};
+    if (sub.is_uep) {
+        // short form: bit rate, level and size come from the protection profile table
+        if (dabgpu_uep_subchannel(sub.uep_prot_index, sub.start_address, &sc) != DABGPU_OK) return false;
+        sub.length = uint16_t(sc.length);
+        return true;
+    }
+    if (sub.eep_prot_level > 3 || sub.length == 0) return false;
+    sc.start_address = sub.start_address;
+    sc.length = sub.length;
+    sc.protection_level = sub.eep_prot_level + 1;           // the ABI counts levels 1..4
+    sc.eep_type = sub.eep_type == EEP_Type::TYPE_B ? 1 : 0;
+    sc.bitrate_kbps = int(CalculateEEPBitrate(sub));
+    return sc.bitrate_kbps > 0;
+}
+
+// the index of the described sub-channel in the per-frame call, joining it if need be; negative: it cannot join.
+// A sub-channel registered by hand (AddSubchannel) that the FIC now announces with the same range and profile is
+// already open: the channel attaches to it instead of claiming the range twice
+int BasicRadio::open_subchannel(const dabgpu_subchannel &sc) {
+    for (size_t k = 0; k < m_subchannels.size(); k++) {
+        const dabgpu_subchannel &d = m_subchannels[k].desc;
+        if (d.start_address == sc.start_address && d.length == sc.length && d.bitrate_kbps == sc.bitrate_kbps &&
+            d.is_uep == sc.is_uep && d.eep_type == sc.eep_type && d.protection_level == sc.protection_level && !m_subchannels[k].dab_plus &&
+            !m_subchannels[k].dab && !m_subchannels[k].packet)
+            return int(k);
+    }
+    return add_subchannel_locked(sc);
+}
+
+// Open a data packet channel for every packet-mode component that carries MOT in data groups, once FIG 0/2, FIG 0/3 and
+// FIG 0/1 have all spoken; further addresses of an open sub-channel join its channel (up to four)
+void BasicRadio::update_packet_channels() {
+    size_t described = 0;
+    for (const auto &pc : m_database.packet_components) described += pc.has_service && pc.is_described;
+    for (auto &kv : m_packet_channels) kv.second->SetFecScheme(m_database.fec_scheme[kv.first & 63]);
+    if (described == m_seen_packet_described && !m_pending_packets) return;
+    m_pending_packets = false;
+    for (const auto &pc : m_database.packet_components) {
+        if (!pc.has_service || !pc.is_described || pc.dscty != 60 || pc.dg_flag) continue;
+        auto open = m_packet_channels.find(pc.subchannel_id);
+        if (open != m_packet_channels.end()) {
+            open->second->FollowAddress(pc.packet_address);
+            continue;
+        }
+        if (m_channels.count(pc.subchannel_id)) continue;       // (an audio channel has the sub-channel)
+        bool rejected = false;
+        for (auto id : m_rejected) rejected |= (id == pc.subchannel_id);
+        if (rejected) continue;
+        ::Subchannel *sub = nullptr;
+        for (auto &s : m_database.subchannels)
+            if (s.id == pc.subchannel_id) sub = &s;
+        if (!sub) {                                          // FIG 0/1 for it has not arrived yet
+            m_pending_packets = true;
+            continue;
+        }
+        dabgpu_subchannel sc{};
+        // (packets need whole slots: a bit rate that is a multiple of 8, at most 512)
+        const int idx = describe_subchannel(*sub, sc) && sc.bitrate_kbps % 8 == 0 && sc.bitrate_kbps <= 512 ? open_subchannel(sc) : -1;
+        if (idx < 0) {
+            m_rejected.push_back(sub->id);
+            m_total_unsupported++;
+            continue;
+        }
+        auto ch = std::make_unique<Basic_Data_Packet_Channel>(*sub, m_database.fec_scheme[sub->id & 63]);
+        ch->FollowAddress(pc.packet_address);
+        m_subchannels[size_t(idx)].packet = ch.get();
+        m_packet_channels.emplace(sub->id, std::move(ch));
+    }
+    m_seen_packet_described = described;
+}
+
+// Open every component whose sub-channel the FIC has described (called with the mutex held).
 void BasicRadio::update_channels_from_database() {
+    update_audio_channels();
+    update_packet_channels();
+}
+
+void BasicRadio::update_audio_channels() {
     if (m_database.service_components.size() == m_seen_components && !m_pending_components) return;
     m_pending_components = false;
     for (const auto &comp : m_database.service_components) {
@@ -145,33 +225,7 @@ void BasicRadio::update_channels_from_database() {
             continue;
         }
         dabgpu_subchannel sc{};
-        bool ok = false;
-        if (sub->is_uep) {
-            // short form: bit rate, level and size come from the protection profile table
-            ok = dabgpu_uep_subchannel(sub->uep_prot_index, sub->start_address, &sc) == DABGPU_OK;
-            if (ok) sub->length = uint16_t(sc.length);
-        } else if (sub->eep_prot_level <= 3 && sub->length > 0) {
-            const bool type_b = sub->eep_type == EEP_Type::TYPE_B;
-            sc.start_address = sub->start_address;
-            sc.length = sub->length;
-            sc.protection_level = sub->eep_prot_level + 1;       // the ABI counts levels 1..4
-            sc.eep_type = type_b ? 1 : 0;
-            sc.bitrate_kbps = int(CalculateEEPBitrate(*sub));
-            ok = sc.bitrate_kbps > 0;
-        }
-        int idx = -1;
-        if (ok) {
-            // a sub-channel registered by hand (AddSubchannel) that the FIC now announces with the same range and
-            // profile is already open: the audio channel attaches to it instead of claiming the range twice
-            for (size_t k = 0; k < m_subchannels.size() && idx < 0; k++) {
-                const dabgpu_subchannel &d = m_subchannels[k].desc;
-                if (d.start_address == sc.start_address && d.length == sc.length && d.bitrate_kbps == sc.bitrate_kbps &&
-                    d.is_uep == sc.is_uep && d.eep_type == sc.eep_type && d.protection_level == sc.protection_level && !m_subchannels[k].dab_plus &&
-                    !m_subchannels[k].dab)
-                    idx = int(k);
-            }
-            if (idx < 0) idx = add_subchannel_locked(sc);
-        }
+        const int idx = describe_subchannel(*sub, sc) ? open_subchannel(sc) : -1;
         if (idx < 0) {
             m_rejected.push_back(sub->id);
             m_total_unsupported++;

@@ -8,7 +8,9 @@
 // frame f+1 on.  The FIBs go through the FIG
 // parser into the database; every audio component found there (DAB+ or DAB, EEP or UEP sub-channel)
 // gets its sub-channel decoded and a Basic_DAB_Plus_Channel (8f-3) / Basic_DAB_Channel without being asked (On_Audio_Channel fires once per
-// channel, as in the reference).  Audio decoding is outside the path: channels hand out access units.
+// channel, as in the reference).  Audio decoding is outside the path: channels hand out access units.  A packet-mode
+// component that carries MOT in data groups (FIG 0/3: DSCTy 60, DG flag 0) gets its sub-channel decoded and a
+// Basic_Data_Packet_Channel that follows its packet address to slides.
 #pragma once
 #include <cstdint>
 #include <mutex>
@@ -47,8 +49,11 @@ public:
         auto it = m_channels.find(id);
         return it == m_channels.end() ? nullptr : it->second.get();
     }
-    // packet-mode data sub-channels are not followed (render_radio_block.cpp:533): never a channel
-    Basic_Data_Packet_Channel *Get_Data_Packet_Channel(subchannel_id_t) { return nullptr; }
+    // the channel of a packet-mode sub-channel with a MOT component (render_radio_block.cpp:533), nullptr for any other
+    Basic_Data_Packet_Channel *Get_Data_Packet_Channel(subchannel_id_t id) {
+        auto it = m_packet_channels.find(id);
+        return it == m_packet_channels.end() ? nullptr : it->second.get();
+    }
     // sub-channels listed in the FIC that cannot be decoded here (invalid profile, does not fit the CIF)
     int GetTotalUnsupportedSubchannels() const { return m_total_unsupported; }
     void SetAutoChannels(bool v) { m_auto_channels = v; }
@@ -75,7 +80,12 @@ private:
         PinnedBuffer<uint8_t> out;
         Basic_DAB_Plus_Channel *dab_plus = nullptr;   // set for sub-channels opened from the database
         Basic_DAB_Channel *dab = nullptr;
+        Basic_Data_Packet_Channel *packet = nullptr;
     };
+    bool describe_subchannel(::Subchannel &sub, dabgpu_subchannel &sc);
+    int open_subchannel(const dabgpu_subchannel &sc);
+    void update_audio_channels();
+    void update_packet_channels();
     void update_channels_from_database();
     void process_fibs_locked();
     int add_subchannel_locked(const dabgpu_subchannel &sc);
@@ -95,9 +105,12 @@ private:
     DAB_Database_Updater m_updater{m_database};
     FIC_Parser m_fic_parser{m_updater};
     std::map<subchannel_id_t, std::unique_ptr<Basic_Audio_Channel>> m_channels;
+    std::map<subchannel_id_t, std::unique_ptr<Basic_Data_Packet_Channel>> m_packet_channels;
     std::vector<subchannel_id_t> m_rejected;             // sub-channels we looked at and cannot open
     size_t m_seen_components = 0;
+    size_t m_seen_packet_described = 0;                  // packet components FIG 0/2 has named and FIG 0/3 described
     bool m_pending_components = false;                   // a component whose sub-channel is not described yet
+    bool m_pending_packets = false;                      // ... a packet component
     bool m_auto_channels = true;
     int m_total_unsupported = 0;
     int m_total_frames_lost = 0;

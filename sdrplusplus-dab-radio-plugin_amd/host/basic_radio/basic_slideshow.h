@@ -1,8 +1,8 @@
 // basic_radio/basic_slideshow.h -- the slideshow entities the GUI asks an audio or data channel for
 // (/root/reference/src/render_radio_block.cpp:309-340, 591-593).  MOT slideshows ride in the programme-associated data of
 // the audio frames or in packet-mode sub-channels.  A DAB+ channel fills its manager from the X-PAD of its access units
-// (basic_dab_plus_channel.cpp, the walk of include/dabgpu_mot_walk.h; no audio decoder is needed for it); packet-mode MOT
-// is not read, so a data channel's manager stays empty.
+// (basic_dab_plus_channel.cpp, the walk of include/dabgpu_mot_walk.h; no audio decoder is needed for it); a data packet
+// channel fills its manager from the packets of its sub-channel (basic_data_packet_channel.h, include/dabgpu_packet_walk.h).
 #pragma once
 #include <cstdint>
 #include <list>

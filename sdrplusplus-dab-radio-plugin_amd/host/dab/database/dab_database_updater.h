@@ -130,6 +130,10 @@ public:
     }
     void SetComponentLabel(ServiceComponent &c, const std::string &label) { set_string(c.label, label); }
     std::vector<ServiceComponent> &Components() { return m_db.service_components; }
+    std::vector<PacketComponent> &PacketComponents() { return m_db.packet_components; }
+    void SetFecScheme(subchannel_id_t id, uint8_t scheme) {
+        if (id < 64 && !m_db.fec_scheme[id]) m_db.fec_scheme[id] = scheme;
+    }
     void same(bool ok) { m_stats.nb_total++; if (!ok) m_stats.nb_conflicts++; }
     void changed() { m_stats.nb_total++; m_stats.nb_updates++; }
 

@@ -37,6 +37,9 @@ void FIC_Parser::fig0(const uint8_t *d, int n) {
     case 0: fig0_0(d + 1, n - 1); break;
     case 1: fig0_1(d + 1, n - 1); break;
     case 2: fig0_2(d + 1, n - 1, pd); break;
+    // packet mode: the current configuration of this ensemble alone (C/N = 0, OE = 0)
+    case 3: if (!(d[0] & 0xC0)) fig0_3(d + 1, n - 1); break;
+    case 14: if (!(d[0] & 0xC0)) fig0_14(d + 1, n - 1); break;
     case 5: fig0_5(d + 1, n - 1); break;
     case 6: fig0_6(d + 1, n - 1, pd); break;
     case 8: fig0_8(d + 1, n - 1, pd); break;
@@ -86,6 +89,43 @@ void FIC_Parser::fig0_1(const uint8_t *d, int n) {
     }
 }
 
+// the packet-mode component of that SCId, found or made (the list is capped as every list of the database is; nullptr
+// beyond the cap); these components have a list of their own and leave the statistics alone
+PacketComponent *FIC_Parser::packet_component(uint16_t scid) {
+    auto &list = m_updater.PacketComponents();
+    for (auto &c : list)
+        if (c.scid == scid) return &c;
+    if (list.size() >= DAB_Database_Updater::MAX_ENTITIES) return nullptr;
+    list.emplace_back();
+    list.back().scid = scid;
+    return &list.back();
+}
+
+// FIG 0/3 service component in packet mode: SCId(12) Rfa(3) CAOrg flag(1), DG flag(1) Rfu(1) DSCTy(6), SubChId(6) packet
+// address(10), CAOrg(16) only when its flag is set.  Written once, as every field of the database.
+void FIC_Parser::fig0_3(const uint8_t *d, int n) {
+    int i = 0;
+    while (i + 5 <= n) {
+        const uint16_t scid = uint16_t((d[i] << 4) | (d[i + 1] >> 4));
+        const int size = 5 + ((d[i + 1] & 1) ? 2 : 0);
+        if (i + size > n) return;
+        PacketComponent *c = packet_component(scid);
+        if (c && !c->is_described) {
+            c->is_described = true;
+            c->dg_flag = d[i + 2] >> 7;
+            c->dscty = d[i + 2] & 0x3F;
+            c->subchannel_id = subchannel_id_t(d[i + 3] >> 2);
+            c->packet_address = uint16_t(((d[i + 3] & 3) << 8) | d[i + 4]);
+        }
+        i += size;
+    }
+}
+
+// FIG 0/14 FEC sub-channel organisation: SubChId(6) FEC scheme(2) per entry
+void FIC_Parser::fig0_14(const uint8_t *d, int n) {
+    for (int i = 0; i < n; i++) m_updater.SetFecScheme(d[i] >> 2, d[i] & 3);
+}
+
 void FIC_Parser::fig0_2(const uint8_t *d, int n, bool pd) {
     const int idlen = pd ? 4 : 2;
     int i = 0;
@@ -98,7 +138,17 @@ void FIC_Parser::fig0_2(const uint8_t *d, int n, bool pd) {
         m_updater.GetService(sid, pd);
         for (int c = 0; c < nc; c++, i += 2) {
             const uint8_t b0 = d[i], b1 = d[i + 1];
-            if ((b0 >> 6) != 0) continue;                   // only MSC stream audio is followed
+            if ((b0 >> 6) == 3) {                           // packet mode: SCId(12) P/S(1) CA(1)
+                PacketComponent *pc = packet_component(uint16_t(((b0 & 0x3F) << 6) | (b1 >> 2)));
+                if (pc && !pc->has_service) {
+                    pc->has_service = true;
+                    pc->service_id = sid;
+                    pc->service_id_32 = pd;
+                    pc->is_primary = (b1 & 2) != 0;
+                }
+                continue;
+            }
+            if ((b0 >> 6) != 0) continue;                   // stream data and FIDC are not followed
             bool is_new;
             ServiceComponent &sc = m_updater.GetServiceComponent(sid, b1 >> 2, &is_new);
             const auto ascty = static_cast<AudioServiceType>(b0 & 0x3F);     // 0 = DAB, 63 = DAB+, others kept as sent

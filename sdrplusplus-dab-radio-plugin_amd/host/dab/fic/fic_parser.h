@@ -25,6 +25,9 @@ private:
     void fig0_0(const uint8_t *d, int n);
     void fig0_1(const uint8_t *d, int n);
     void fig0_2(const uint8_t *d, int n, bool pd);
+    void fig0_3(const uint8_t *d, int n);
+    void fig0_14(const uint8_t *d, int n);
+    PacketComponent *packet_component(uint16_t scid);
     void fig0_5(const uint8_t *d, int n);
     void fig0_6(const uint8_t *d, int n, bool pd);
     void fig0_8(const uint8_t *d, int n, bool pd);

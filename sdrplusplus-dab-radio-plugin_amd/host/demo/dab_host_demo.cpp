@@ -32,18 +32,20 @@ static constexpr float SAMPLING_RATE_HZ = 2.048e6f;   // the offsets are in cycl
 
 // the rest of a channel's line and its slide lines: the dynamic label as the GUI reads it (render_radio_block.cpp:425-427,
 // 470-472), its bytes in hex, then the slides as the "Slideshow" tab lists them (render_radio_block.cpp:309-382), the image in hex
+static void print_slide(std::FILE *f, int subchannel, const Basic_Slideshow &slide) {
+    std::fprintf(f, "slide subchannel=%d tid=%u name=", subchannel, unsigned(slide.transport_id));
+    for (const char v : slide.name) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
+    std::fprintf(f, " bytes=%zu body=", slide.image_data.size());
+    for (const uint8_t v : slide.image_data) std::fprintf(f, "%02x", unsigned(v));
+    std::fprintf(f, "\n");
+}
+
 static void print_label_and_slides(std::FILE *f, int subchannel, Basic_Audio_Channel &ch, int charset) {
     std::fprintf(f, " label_charset=%d label=", charset);
     for (const char v : ch.GetDynamicLabel()) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
     std::fprintf(f, "\n");
     auto slides_lock = std::scoped_lock(ch.GetSlideshowManager().GetSlideshowsMutex());
-    for (const auto &slide : ch.GetSlideshowManager().GetSlideshows()) {
-        std::fprintf(f, "slide subchannel=%d tid=%u name=", subchannel, unsigned(slide->transport_id));
-        for (const char v : slide->name) std::fprintf(f, "%02x", unsigned(uint8_t(v)));
-        std::fprintf(f, " bytes=%zu body=", slide->image_data.size());
-        for (const uint8_t v : slide->image_data) std::fprintf(f, "%02x", unsigned(v));
-        std::fprintf(f, "\n");
-    }
+    for (const auto &slide : ch.GetSlideshowManager().GetSlideshows()) print_slide(f, subchannel, *slide);
 }
 
 int main(int argc, char **argv) {
@@ -174,6 +176,21 @@ int main(int argc, char **argv) {
             auto subs = db.subchannels;
             std::sort(subs.begin(), subs.end(), [](const Subchannel &a, const Subchannel &b) { return a.id < b.id; });
             for (const auto &sc : subs) {
+                if (auto *data = radio->Get_Data_Packet_Channel(sc.id)) {
+                    // a packet-mode sub-channel (render_radio_block.cpp:533-540, 592-593): its addresses, then its slides
+                    std::fprintf(f, "packet subchannel=%d frames=%d fec=%d addresses=%d", sc.id, data->GetTotalFrames(), data->GetFecScheme(),
+                                 data->GetTotalAddresses());
+                    for (int a = 0; a < data->GetTotalAddresses(); a++) {
+                        const auto &c = data->GetCounters(a);
+                        std::fprintf(f, " address=%d followed=%d slots_bad=%d continuity_breaks=%d groups_ok=%d groups_crc_failed=%d groups_repeated=%d objects=%d",
+                                     data->GetAddress(a), c.packets_followed, c.slots_bad, c.continuity_breaks, c.mot.groups_ok, c.mot.groups_crc_failed,
+                                     c.mot.groups_repeated, c.mot.objects_completed);
+                    }
+                    std::fprintf(f, "\n");
+                    auto slides_lock = std::scoped_lock(data->GetSlideshowManager().GetSlideshowsMutex());
+                    for (const auto &slide : data->GetSlideshowManager().GetSlideshows()) print_slide(f, sc.id, *slide);
+                    continue;
+                }
                 if (auto *mp2 = dynamic_cast<Basic_DAB_Channel *>(radio->Get_Audio_Channel(sc.id))) {
                     const auto &ap = mp2->GetAudioParams();
                     std::fprintf(f, "channel subchannel=%d mp2_frames=%d header_errors=%d rate=%u stereo=%d checked_frames=%d crc_errors=%d", sc.id,
