@@ -1850,9 +1850,10 @@ int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entrie
 /* slideshow call's own closing, assembly and slot code).  The contract and the  */
 /* code are include/dabgpu_packet_walk.h.                                        */
 /*                                                                            */
-/* Not done: Reed-Solomon RS(204,188) correction of FEC frames (FEC packets are  */
-/* recognised and counted only; a later call may correct logical frames in front */
-/* of this one); MOT directory mode (data group types 6, 7); non-MOT packet data */
+/* Reed-Solomon RS(204,188) correction of FEC frames is a call of its own in      */
+/* front of this one, dabgpu_packet_fec_dev (below): this call recognises and     */
+/* counts FEC packets and reads what that one wrote, unchanged.  Not done: MOT    */
+/* directory mode (data group types 6, 7); non-MOT packet data                   */
 /* (TPEG, SPI, Journaline); conditional access; FIG 0/13 user application        */
 /* signalling (the caller chooses DSCTy 60 / DG 0 from the component list).      */
 /*                                                                            */
@@ -1959,6 +1960,101 @@ size_t dabgpu_packet_state_bytes(void);
 int dabgpu_packet_slides_dev(dabgpu_ctx *ctx, const dabgpu_packet_entry *entries, int n_entries, int n_cifs, void *stream);
 /* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
 int dabgpu_packet_slides_host(const dabgpu_packet_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
+/* FEC frames of packet-mode sub-channels: RS(204,188) correction on the device  */
+/* (EN 300 401 clause 5.3.5; the reference has no FEC code at all).               */
+/* dabgpu_packet_fec_dev runs on the same stream between                          */
+/* dabgpu_decode_ensembles_dev and dabgpu_packet_slides_dev, one entry per        */
+/* sub-channel whose component has fec_scheme 1: it   */
+/* finds the FEC frames in the logical frames, corrects them and writes logical   */
+/* frames that the slides call reads unchanged -- there the caller names d_out as */
+/* d_in and keeps fec non-zero; `superframe` of a slide then counts delayed       */
+/* frames.  The contract and the code are include/dabgpu_packet_fec.h.            */
+/*                                                                            */
+/* Not provided: erasure decoding from packet CRC verdicts (a failed packet CRC   */
+/* is not used as an erasure); correction of the FEC packets' own bytes in the    */
+/* output; FEC schemes other than 1.                                              */
+/*                                                                            */
+/* THE CONTRACT of one entry in one call (every ambiguity decided; where this     */
+/* text and the standard's wording could part, this text governs).                */
+/*                                                                            */
+/* Slots.  Bit rate R: S = R / 8 slots of 24 bytes per logical frame, numbered    */
+/* g = 0, 1, ... from a fresh start, across frames and calls.                     */
+/*                                                                            */
+/* FEC frame.  103 consecutive slots: 94 of application data, A[0..2255] in       */
+/* stream order, then 9 FEC packets.  A slot is MARK c when (h0 >> 6) == 0,       */
+/* (((h0 & 3) << 8) | h1) == 1022 and c = (h0 >> 2) & 15 is at most 8.            */
+/* P[0..197] = bytes 2..23 of the nine FEC packets; P[0..191] is the RS data      */
+/* table, P[192..197] is ignored.  Row r (0..11): cw_r[c] = A[12 c + r], c < 188; */
+/* cw_r[188 + j] = P[12 j + r], j < 16.  GF(2^8), x^8 + x^4 + x^3 + x^2 + 1,      */
+/* alpha = 2; generator prod_{i=0..15} (x + alpha^i); cw_r[0] is the coefficient  */
+/* of x^203 (RS(255,239) shortened by 51 leading zeros);                          */
+/* S_k = sum_c cw_r[c] alpha^(k (203 - c)), k = 0..15.                            */
+/*                                                                            */
+/* Finding frames.  No phase is assumed, no lock is kept.  A frame ENDS at slot q  */
+/* when at least 7 of the slots q - 8 + i (i = 0..8) are mark i (slots before the  */
+/* fresh start are no mark; marks are taken from the bytes as received).           */
+/* Candidates in ascending q: first slot q - 102 below 0: frames_cut++; else first */
+/* slot at or before the end of the last accepted frame: frames_overlapping++;     */
+/* neither is processed.  Else accepted: frames++, processed in the call in which  */
+/* its last slot arrives.                                                          */
+/*                                                                            */
+/* Correction.  Bounded distance, errors only, per row: if a codeword lies within  */
+/* Hamming distance 8 of the received 204 bytes (every differing position inside   */
+/* the 204; it is unique) the row's 188 data bytes become that codeword's:         */
+/* rows_corrected++, bytes_corrected += differing data positions,                  */
+/* parity_bytes_corrected += the others.  A codeword as received: rows_clean++.    */
+/* Otherwise the row stays as received: rows_uncorrectable++.  The FEC packets     */
+/* themselves are written out as received.                                         */
+/*                                                                            */
+/* Delay.  Output lags input by D = ceil(102 / S) frames (102 at 8 kbit/s, 2 at    */
+/* 512): output frame f of a call is stream frame F0 + f - D, F0 the frames seen   */
+/* since the fresh start.  Stream frames below 0 are S copies of the padding       */
+/* packet 0C 00 00, 19 x 00, CRC (address 0, one slot; packets_padding there).     */
+/* The state record is opaque -- F0, the last accepted end, the marks of the last  */
+/* 8 slots, the last D frames, corrected where their frame has ended --            */
+/* dabgpu_packet_fec_state_bytes(bitrate) of it (at most 3664).  NULL, all zero or */
+/* a record this library did not write for this bit rate: a fresh start.  The      */
+/* result of a stream does not depend on where it is cut into calls (n_cifs below  */
+/* D and n_cifs = 0 included).                                                     */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_packet_fec_result {   /* counts of THIS call */
+    int32_t cifs, slots, marks;             /* n_cifs, n_cifs S, the marks among those slots                    */
+    int32_t frames, frames_cut, frames_overlapping;
+    int32_t rows_clean, rows_corrected, rows_uncorrectable;
+    int32_t bytes_corrected;                /* data positions                                                   */
+    int32_t parity_bytes_corrected;
+    int32_t reserved;
+} dabgpu_packet_fec_result;
+
+typedef struct dabgpu_packet_fec_entry {    /* HOST array, one per sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_in;        /* [n_cifs][in_stride] logical frames of 3 * bitrate_kbps bytes, any alignment     */
+    size_t in_stride;           /* >= 3 * bitrate_kbps                                                           */
+    int32_t bitrate_kbps;       /* a multiple of 8 in 8 .. 512                                                   */
+    int32_t reserved;
+    uint8_t *d_out;             /* [n_cifs][out_stride], any alignment, no overlap with d_in                     */
+    size_t out_stride;          /* >= 3 * bitrate_kbps                                                           */
+    const void *d_state_in;     /* dabgpu_packet_fec_state_bytes() on a 16-byte boundary; NULL = fresh start       */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    dabgpu_packet_fec_result *d_result;
+} dabgpu_packet_fec_entry;
+
+/* bytes of the state record of a sub-channel of this bit rate; 0 for a bit rate the call refuses */
+size_t dabgpu_packet_fec_state_bytes(int bitrate_kbps);
+/* D, the frames the output lags the input; -1 for a bit rate the call refuses */
+int dabgpu_packet_fec_delay(int bitrate_kbps);
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Everything is checked before anything is enqueued, so a refused call
+ * leaves every output as it was: DABGPU_ERR_ARG for what dabgpu_packet_slides_dev refuses for the same fields (a NULL context
+ * or table, a negative count, n_cifs outside 0 .. 2^24, a bit rate outside 8 .. 512 or no multiple of 8, in_stride <
+ * 3 * bitrate_kbps, a NULL d_in with n_cifs > 0, a NULL d_state_out or d_result, a state record off a 16-byte boundary,
+ * d_result off a 4-byte boundary), out_stride < 3 * bitrate_kbps, a NULL d_out with n_cifs > 0, d_out overlapping d_in of the
+ * same entry, d_state_out equal to or overlapping d_state_in; DABGPU_ERR_CAPACITY for a table whose largest launch would need
+ * 2^31 or more workgroups. */
+int dabgpu_packet_fec_dev(dabgpu_ctx *ctx, const dabgpu_packet_fec_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_packet_fec_host(const dabgpu_packet_fec_entry *entries, int n_entries, int n_cifs);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

@@ -73,6 +73,7 @@ enum StageSlot {
     STAGE_MP2 = 16,         // dabgpu_mp2_follow_dev: the entry table and the plans of the rate / frame launches
     STAGE_MP2_AUDIO = 17,   // dabgpu_mp2_subbands_dev: the entry table
     STAGE_PACKET = 18,      // dabgpu_packet_slides_dev: the entry table and the scan records of the scan / walk launches
+    STAGE_PACKET_FEC = 19,  // dabgpu_packet_fec_dev: the entry table, the marks, the accepted frames and their counts
     STAGE_SLOTS
 };
 

@@ -58,6 +58,7 @@ EXPORTS = [
     "dabgpu_mp2_subbands_dev", "dabgpu_mp2_subbands_host",
     "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
     "dabgpu_fig_packet_components", "dabgpu_packet_state_bytes", "dabgpu_packet_slides_dev", "dabgpu_packet_slides_host",
+    "dabgpu_packet_fec_state_bytes", "dabgpu_packet_fec_delay", "dabgpu_packet_fec_dev", "dabgpu_packet_fec_host",
 ]
 
 ABI_VERSION = 6
@@ -185,6 +186,11 @@ PACKET_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("scid", np.int32), ("sub
                                    ("packet_address", np.int32), ("dscty", np.int32), ("dg_flag", np.int32), ("fec_scheme", np.int32),
                                    ("primary", np.int32), ("reserved", np.int32, (3,))])
 assert PACKET_COMPONENT_DTYPE.itemsize == 48
+#: dabgpu_packet_fec_result: what one entry of packet_fec_dev / packet_fec_host counted in one call
+PACKET_FEC_COUNTERS = ("cifs", "slots", "marks", "frames", "frames_cut", "frames_overlapping", "rows_clean", "rows_corrected",
+                       "rows_uncorrectable", "bytes_corrected", "parity_bytes_corrected")
+PACKET_FEC_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_FEC_COUNTERS] + [("reserved", np.int32)])
+assert PACKET_FEC_RESULT_DTYPE.itemsize == 48
 DSCTY_MOT = 60
 #: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
 AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
@@ -295,6 +301,15 @@ class PacketEntry(C.Structure):
                 ("fec", C.c_int32), ("reserved", C.c_int32), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
                 ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_slides", C.c_void_p), ("slide_stride", C.c_size_t),
                 ("max_slides", C.c_int32), ("reserved2", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class PacketFecEntry(C.Structure):
+    """dabgpu_packet_fec_entry: one FEC-protected packet sub-channel of Context.packet_fec_dev (device addresses) or
+    packet_fec_host (host addresses): the logical frames the decode call wrote, the corrected frames (delayed by
+    packet_fec_delay(bitrate) frames; what the slides call then names as d_in), the state records, the counters."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("reserved", C.c_int32),
+                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
+                ("d_result", C.c_void_p)]
 
 
 class PacketComponent(C.Structure):
@@ -612,6 +627,11 @@ def load_library(path):
     L.dabgpu_packet_state_bytes.argtypes = []
     L.dabgpu_packet_slides_dev.argtypes = [vp, C.POINTER(PacketEntry), i, i, vp]
     L.dabgpu_packet_slides_host.argtypes = [C.POINTER(PacketEntry), i, i]
+    L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
+    L.dabgpu_packet_fec_state_bytes.argtypes = [i]
+    L.dabgpu_packet_fec_delay.argtypes = [i]
+    L.dabgpu_packet_fec_dev.argtypes = [vp, C.POINTER(PacketFecEntry), i, i, vp]
+    L.dabgpu_packet_fec_host.argtypes = [C.POINTER(PacketFecEntry), i, i]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -842,6 +862,31 @@ def fig_packet_components(fib, crc_ok, max_out=64):
 def packet_state_bytes():
     """Bytes of one state record of Context.packet_slides_dev / packet_slides_host (all zero = a fresh start)."""
     return int(lib().dabgpu_packet_state_bytes())
+
+
+def packet_fec_state_bytes(bitrate):
+    """Bytes of the state record of Context.packet_fec_dev / packet_fec_host for a sub-channel of this bit rate (NULL or all
+    zero = a fresh start)."""
+    n = int(lib().dabgpu_packet_fec_state_bytes(int(bitrate)))
+    if n == 0:
+        raise ValueError("not a packet-mode bit rate: %r" % (bitrate,))
+    return n
+
+
+def packet_fec_delay(bitrate):
+    """D = ceil(102 / (bitrate / 8)): the logical frames the output of packet_fec_dev / packet_fec_host lags its input."""
+    d = int(lib().dabgpu_packet_fec_delay(int(bitrate)))
+    if d < 0:
+        raise ValueError("not a packet-mode bit rate: %r" % (bitrate,))
+    return d
+
+
+def packet_fec_host(entries, n_cifs):
+    """Context.packet_fec_dev on HOST memory (entries: PacketFecEntry with host addresses): the same checks and the same
+    code, include/dabgpu_packet_fec.h; no context, no GPU."""
+    n = len(entries)
+    arr = (PacketFecEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_packet_fec_host(arr, n, n_cifs), "dabgpu_packet_fec_host")
 
 
 def packet_slides_host(entries, n_cifs):
@@ -1490,6 +1535,16 @@ class Context:
         n = len(entries)
         arr = (PacketEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_packet_slides_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_slides_dev")
+
+    def packet_fec_dev(self, entries, n_cifs, stream=None):
+        """RS(204,188) correction of the FEC frames of packet-mode sub-channels, between decode_ensembles_dev and
+        packet_slides_dev on the same stream: entries is a list of PacketFecEntry (device addresses), one per sub-channel;
+        n_cifs logical frames each.  Per entry: d_out, the stream delayed by packet_fec_delay(bitrate) frames and corrected
+        (the slides call names it as d_in and keeps fec non-zero), d_result (PACKET_FEC_RESULT_DTYPE, counts of this call)
+        and d_state_out, to be passed as d_state_in of the next call.  No host synchronisation."""
+        n = len(entries)
+        arr = (PacketFecEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_packet_fec_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_fec_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

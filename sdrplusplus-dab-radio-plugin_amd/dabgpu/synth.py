@@ -1289,6 +1289,87 @@ def packet_frames(bitrate, streams, n_frames=None):
     return np.stack(frames) if frames else np.zeros((0, 3 * bitrate), np.uint8)
 
 
+# FEC for packet mode (EN 300 401 clause 5.3.5): an FEC frame is 94 slots of packets (the application data table, 2256 bytes
+# filled column by column into 12 rows of 188) followed by nine FEC packets: length 0, counter 0..8 (4 bits), address 1022,
+# then 22 bytes of the RS data table (12 rows of 16 parity bytes, read column by column; the last six bytes are padding).
+PACKET_FEC_DATA_SLOTS = 94
+PACKET_FEC_SLOTS = 9
+
+
+def _rs204_generator():
+    g = [1]                                   # g[i] = coefficient of x^i
+    for k in range(16):
+        nx = [0] * (len(g) + 1)
+        for i, c in enumerate(g):
+            nx[i + 1] ^= c
+            nx[i] ^= _gf_mul(c, int(_GF_EXP[k]))
+        g = nx
+    return g
+
+
+_RS204_G = _rs204_generator()
+
+
+def rs204_parity(row188):
+    """RS(204,188) parity, 16 bytes: the remainder of d(x) x^16 by prod_{k=0..15}(x - alpha^k), GF(2^8) / 0x11D, the first
+    byte the highest degree (RS(255,239) shortened by 51 leading zeros)."""
+    assert len(row188) == 188
+    rem = [0] * 16                            # rem[0] = highest degree
+    for d in row188:
+        fb = int(d) ^ rem[0]
+        rem = [rem[j + 1] ^ _gf_mul(fb, _RS204_G[15 - j]) for j in range(15)] + [_gf_mul(fb, _RS204_G[0])]
+    return np.array(rem, np.uint8)
+
+
+def fec_frame(packets):
+    """94 slots of packets (a list of packets, or their 2256 bytes) -> the 103 slots of an FEC frame, as bytes: the packets
+    as they are, then the nine FEC packets with counters 0..8"""
+    data = packets if isinstance(packets, (bytes, bytearray)) else b"".join(bytes(p) for p in packets)
+    assert len(data) == PACKET_SLOT * PACKET_FEC_DATA_SLOTS
+    table = np.frombuffer(bytes(data), np.uint8).reshape(188, 12)         # [column][row]
+    parity = np.stack([rs204_parity(table[:, r]) for r in range(12)])     # [row][16]
+    rs = parity.T.tobytes() + bytes(6)                                     # column by column, 192 bytes, then padding
+    out = bytes(data)
+    for c in range(PACKET_FEC_SLOTS):
+        out += _bits((0, 2), (c, 4), (PACKET_FEC_ADDRESS, 10)) + rs[22 * c:22 * c + 22]
+    return out
+
+
+def packet_fec_frames(bitrate, streams, n_frames=None):
+    """logical frames [n][3 * bitrate] uint8 of an FEC-protected packet-mode sub-channel (FEC scheme 1): streams is a list of
+    packet lists, taken a packet of each in turn; no packet straddles a logical frame or the 94-slot application data table
+    (padding packets fill up to either), and every full table is followed by its nine FEC packets.  The first table begins
+    with the first frame.  n_frames: at least that many frames (padding and FEC packets behind the streams); the last table
+    may be left unfinished"""
+    slots = bitrate // 8
+    assert bitrate % 8 == 0 and 1 <= slots <= 64
+    queues = [list(q) for q in streams]
+    assert all(len(p) % PACKET_SLOT == 0 and len(p) // PACKET_SLOT <= slots for q in queues for p in q)
+    out, table, turn = b"", b"", 0
+
+    def put(p):
+        nonlocal out, table
+        out += p
+        table += p
+        if len(table) == PACKET_SLOT * PACKET_FEC_DATA_SLOTS:
+            out += fec_frame(table)[len(table):]
+            table = b""
+
+    while any(queues) or len(out) % (PACKET_SLOT * slots) or len(out) < (n_frames or 0) * PACKET_SLOT * slots:
+        room = min(slots - len(out) // PACKET_SLOT % slots, PACKET_FEC_DATA_SLOTS - len(table) // PACKET_SLOT)
+        nxt = None
+        if any(queues):
+            while not queues[turn % len(queues)]:
+                turn += 1
+            nxt = queues[turn % len(queues)]
+        if nxt and len(nxt[0]) // PACKET_SLOT <= room:
+            put(nxt.pop(0))
+            turn += 1
+        else:
+            put(padding_packet(min(4, room)))
+    return np.frombuffer(out, np.uint8).reshape(-1, PACKET_SLOT * slots).copy()
+
+
 # What a multiplex says about itself in the FIC: enough for a receiver to find and decode its audio services
 # without being told anything (FIG 0/0 ensemble, 0/1 sub-channel organisation, 0/2 service organisation,
 # 1/0 ensemble label, 1/1 service labels).

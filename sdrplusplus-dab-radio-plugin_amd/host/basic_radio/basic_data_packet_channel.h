@@ -4,7 +4,10 @@
 // include/dabgpu_packet_walk.h, the code the GPU batch call dabgpu_packet_slides_dev runs, here on the host with its copy
 // orders executed by a loop (no export of libdabgpu is called); every completed image object goes to the one slideshow
 // manager, through Basic_Add_Slide as an audio channel's do.  Up to four packet addresses (DSCTy 60, DG flag 0) of the
-// sub-channel are followed, each with a state record and an arena of its own.  FEC packets are counted, not corrected.
+// sub-channel are followed, each with a state record and an arena of its own.  FEC packets are counted; with
+// SetFecCorrection(true) -- BasicRadio switches it on when FIG 0/14 gives the sub-channel FEC scheme 1 -- every logical frame
+// first goes through the host path of include/dabgpu_packet_fec.h, the code dabgpu_packet_fec_dev runs: the FEC frames are
+// corrected by RS(204,188) and the walk sees the stream delayed by ceil(102 / S) frames (padding packets at first).
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -12,6 +15,7 @@
 #include "basic_radio/basic_pad_reader.h"
 #include "basic_radio/basic_slideshow.h"
 #include "dab/database/dab_database_entities.h"
+#include "dabgpu_packet_fec.h"
 #include "dabgpu_packet_walk.h"
 #include "utility/span.h"
 
@@ -27,6 +31,14 @@ public:
     const Subchannel &GetSubchannel() const { return m_subchannel; }
     void SetFecScheme(int fec_scheme) { m_fec = fec_scheme; }
     int GetFecScheme() const { return m_fec; }
+    // RS(204,188) correction in front of the walk, from the next frame on; switching it starts the FEC stream afresh
+    void SetFecCorrection(bool on) {
+        if (on != m_correct) m_fec_slots = 0;
+        m_correct = on;
+    }
+    bool GetFecCorrection() const { return m_correct; }
+    // counts since the correction was switched on (cifs, slots, marks, frames, rows_*, bytes_corrected ...)
+    const dabgpu_packet_fec::Counters &GetFecCounters() const { return m_fec_counts; }
 
     // a packet address (1 .. 1023) to follow from the next frame on: false for one out of range, and for a fifth
     bool FollowAddress(int address) {
@@ -57,7 +69,7 @@ public:
             m_total_ignored++;
             return;
         }
-        const uint8_t *frame = lf.data();
+        const uint8_t *frame = m_correct ? Correct(lf.data(), S) : lf.data();
         uint32_t verdicts[pkt::MAX_SLOTS];                             // one scan for every address
         for (int pos = 0; pos < S; pos++) verdicts[pos] = pkt::slot_verdict(frame, S, pos, m_fec);
         dabgpu_mot::Orders orders;
@@ -88,6 +100,27 @@ public:
     }
 
 private:
+    // one logical frame through dabgpu_packet_fec::process: -> the frame D frames back, corrected
+    const uint8_t *Correct(const uint8_t *lf, int S) {
+        namespace fec = dabgpu_packet_fec;
+        static const fec::Gf gf = fec::make_gf();
+        const size_t nb = size_t(fec::state_bytes(S)), fb = size_t(fec::SLOT_BYTES) * size_t(S);
+        const bool fresh = m_fec_slots != S;
+        if (fresh) {                                                   // (the first frame, or a frame of another size)
+            m_fec_slots = S;
+            m_fec_turn = 0;
+            m_fec_counts = fec::Counters{};
+            for (auto &st : m_fec_state) st.assign(nb, 0);
+            m_fec_out.assign(fb, 0);
+        }
+        fec::Counters c;
+        fec::process(gf, fresh ? nullptr : m_fec_state[m_fec_turn].data(), m_fec_state[m_fec_turn ^ 1].data(), c, lf, fb, 1, S, m_fec_out.data(), fb);
+        m_fec_turn ^= 1;
+        int32_t *sum = reinterpret_cast<int32_t *>(&m_fec_counts);
+        for (size_t i = 0; i < sizeof c / sizeof(int32_t); i++) sum[i] += reinterpret_cast<const int32_t *>(&c)[i];
+        return m_fec_out.data();
+    }
+
     static constexpr int BODY_CAPACITY = 256 * 1024;
     struct Follower {
         int address = 0;
@@ -102,4 +135,8 @@ private:
     std::vector<uint8_t> m_slot;
     Basic_Slideshow_Manager m_slideshows;
     int m_total_frames = 0, m_total_ignored = 0;
+    bool m_correct = false;
+    int m_fec_slots = 0, m_fec_turn = 0;   // S the FEC state is for (0: none yet); which of the two records is current
+    std::vector<uint8_t> m_fec_state[2], m_fec_out;
+    dabgpu_packet_fec::Counters m_fec_counts{};
 };

@@ -162,7 +162,10 @@ int BasicRadio::open_subchannel(const dabgpu_subchannel &sc) {
 void BasicRadio::update_packet_channels() {
     size_t described = 0;
     for (const auto &pc : m_database.packet_components) described += pc.has_service && pc.is_described;
-    for (auto &kv : m_packet_channels) kv.second->SetFecScheme(m_database.fec_scheme[kv.first & 63]);
+    for (auto &kv : m_packet_channels) {
+        kv.second->SetFecScheme(m_database.fec_scheme[kv.first & 63]);
+        kv.second->SetFecCorrection(m_database.fec_scheme[kv.first & 63] == 1);
+    }
     if (described == m_seen_packet_described && !m_pending_packets) return;
     m_pending_packets = false;
     for (const auto &pc : m_database.packet_components) {
@@ -192,6 +195,7 @@ void BasicRadio::update_packet_channels() {
             continue;
         }
         auto ch = std::make_unique<Basic_Data_Packet_Channel>(*sub, m_database.fec_scheme[sub->id & 63]);
+        ch->SetFecCorrection(ch->GetFecScheme() == 1);
         ch->FollowAddress(pc.packet_address);
         m_subchannels[size_t(idx)].packet = ch.get();
         m_packet_channels.emplace(sub->id, std::move(ch));
