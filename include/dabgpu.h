@@ -1972,9 +1972,9 @@ int dabgpu_packet_slides_host(const dabgpu_packet_entry *entries, int n_entries,
 /* d_in and keeps fec non-zero; `superframe` of a slide then counts delayed       */
 /* frames.  The contract and the code are include/dabgpu_packet_fec.h.            */
 /*                                                                            */
-/* Not provided: erasure decoding from packet CRC verdicts (a failed packet CRC   */
-/* is not used as an erasure); correction of the FEC packets' own bytes in the    */
-/* output; FEC schemes other than 1.                                              */
+/* Not provided: correction of the FEC packets' own bytes in the output; FEC      */
+/* schemes other than 1.  This call does not use a failed packet CRC as an        */
+/* erasure: dabgpu_packet_fec_erasures_dev (below) does.                          */
 /*                                                                            */
 /* THE CONTRACT of one entry in one call (every ambiguity decided; where this     */
 /* text and the standard's wording could part, this text governs).                */
@@ -2055,6 +2055,72 @@ int dabgpu_packet_fec_delay(int bitrate_kbps);
 int dabgpu_packet_fec_dev(dabgpu_ctx *ctx, const dabgpu_packet_fec_entry *entries, int n_entries, int n_cifs, void *stream);
 /* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
 int dabgpu_packet_fec_host(const dabgpu_packet_fec_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
+/* ... with failed packet CRCs as erasures.  A second pair of calls beside the    */
+/* one above, which stays as it is; INTEGRATION.md section 21 says which to       */
+/* choose.  The contract is the section "Erasures" of                             */
+/* include/dabgpu_packet_fec.h, the code include/dabgpu_packet_fec_erasures.h.    */
+/*                                                                            */
+/* Suspect slots.  Each logical frame is scanned when it arrives, on its bytes as  */
+/* received, by steps 1-4 of the packet scan (dabgpu_packet_slides_dev above, fec  */
+/* non-zero): a slot that scan counts as slots_bad is SUSPECT; a slot covered by a */
+/* good packet or taken as an FEC packet is not; padding frames below stream       */
+/* frame 0 have none.                                                              */
+/*                                                                            */
+/* Erased columns.  Suspect slot i (0..93) of an accepted frame's data table       */
+/* erases columns 2i and 2i + 1 of every row: the set E, f = |E|.  Parity columns  */
+/* are never erased.                                                               */
+/*                                                                            */
+/* A row: 1. a codeword: rows_clean++.  2. Else the errors-only rule above, with   */
+/* its counters: what the other call corrects, this one corrects identically.      */
+/* 3. Else, if 2 <= f <= 16, the codeword that equals the received row outside E   */
+/* except in at most e positions -- e = 0 whenever f <= 16, e >= 1 only when       */
+/* 2 e + f <= 14 (it is unique): the row's data bytes become that codeword's,      */
+/* rows_erasure_corrected++, erased_bytes_changed += the changed positions in E,   */
+/* erasure_other_bytes_corrected += those outside E, data and parity.  4. Else     */
+/* rows_uncorrectable++ and the row stays as received.                             */
+/*                                                                            */
+/* The state record has the size of the other call's                               */
+/* (dabgpu_packet_fec_state_bytes) and also carries the suspect bits of the        */
+/* carried slots; a record of one call is a fresh start for the other.             */
+/*                                                                            */
+/* Not provided: correction of the FEC packets' own bytes in the output; erasure   */
+/* of parity columns (the FEC packets carry no CRC); FEC schemes other than 1.     */
+/* ------------------------------------------------------------------------ */
+typedef struct dabgpu_packet_fec_erasure_result {   /* counts of THIS call */
+    int32_t cifs, slots, marks;             /* these twelve: as dabgpu_packet_fec_result                        */
+    int32_t frames, frames_cut, frames_overlapping;
+    int32_t rows_clean, rows_corrected, rows_uncorrectable;
+    int32_t bytes_corrected;
+    int32_t parity_bytes_corrected;
+    int32_t reserved;
+    int32_t slots_suspect;                  /* among the call's new slots                                       */
+    int32_t frames_with_suspects;           /* accepted frames with f >= 2                                      */
+    int32_t frames_beyond_erasures;         /* of those, f > 16: step 3 is closed to their rows                 */
+    int32_t rows_erasure_corrected;         /* by step 3                                                        */
+    int32_t erased_bytes_changed;           /* positions in E                                                   */
+    int32_t erasure_other_bytes_corrected;  /* positions outside E, data and parity                             */
+    int32_t reserved2[2];
+} dabgpu_packet_fec_erasure_result;
+
+typedef struct dabgpu_packet_fec_erasure_entry {    /* the fields of dabgpu_packet_fec_entry, one by one */
+    const uint8_t *d_in;
+    size_t in_stride;
+    int32_t bitrate_kbps;
+    int32_t reserved;
+    uint8_t *d_out;
+    size_t out_stride;
+    const void *d_state_in;     /* dabgpu_packet_fec_state_bytes() on a 16-byte boundary; NULL = fresh start       */
+    void *d_state_out;
+    dabgpu_packet_fec_erasure_result *d_result;
+} dabgpu_packet_fec_erasure_entry;
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Refuses what dabgpu_packet_fec_dev refuses, with the same codes,
+ * everything checked before anything is enqueued. */
+int dabgpu_packet_fec_erasures_dev(dabgpu_ctx *ctx, const dabgpu_packet_fec_erasure_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_packet_fec_erasures_host(const dabgpu_packet_fec_erasure_entry *entries, int n_entries, int n_cifs);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

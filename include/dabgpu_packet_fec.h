@@ -50,8 +50,49 @@
  *
  * Counters of a call: cifs = n_cifs, slots = n_cifs S, marks = the marks among them.
  *
- * Not provided: erasure decoding from packet CRC verdicts (a failed packet CRC is not used as an erasure); correction of the
- * FEC packets' own bytes in the output; FEC schemes other than 1.
+ * ERASURES.  A second pair of calls, dabgpu_packet_fec_erasures_dev / _host, beside the pair above, which stays as it is; the
+ * code is include/dabgpu_packet_fec_erasures.h (process_erasures, the twin of process).  Everything above holds for it --
+ * slots, FEC frames, marks, finding frames, delay, padding, the counters of a call -- with these additions.
+ *
+ * Suspect slots.  Each logical frame is scanned once, when it arrives, on its bytes as received, exactly like the marks.  The
+ * scan is that of dabgpu_packet_walk.h, steps 1 - 4, with fec non-zero.  A slot is SUSPECT when that scan counts it as
+ * slots_bad (steps 2 and 3: a length that does not fit the frame, a packet CRC that does not check).  A slot covered by a good
+ * packet is not suspect; a slot taken as an FEC packet is not suspect.  Packets do not straddle logical frames, so the result
+ * does not depend on how the stream is cut into calls.  Padding frames below stream frame 0 have no suspect slot.
+ *
+ * Erased columns.  For an accepted FEC frame, suspect slot i (0..93) of its data table erases columns 2i and 2i + 1 of every
+ * row (the table is filled column by column, 12 bytes a column).  E is that set of columns, f = |E| = 2 x (suspect table slots),
+ * the same for all twelve rows.  The nine FEC packets carry no CRC, so parity columns are never erased.
+ *
+ * A row, in this order:
+ *   1. a codeword: rows_clean++.
+ *   2. else the errors-only rule above (a codeword within distance 8), with its counters: whatever the other call corrects, this
+ *      one corrects identically.
+ *   3. else, if 2 <= f <= 16: the codeword that equals the received row outside E except in at most e positions, where e = 0 is
+ *      allowed whenever f <= 16 and e >= 1 only when 2 e + f <= 14.  (Two such codewords would differ in at most f + 2 e <= 16
+ *      positions, fewer than the minimum distance 17: there is at most one.)  If it exists, the row's data bytes become that
+ *      codeword's: rows_erasure_corrected++, erased_bytes_changed += the positions in E that changed,
+ *      erasure_other_bytes_corrected += the changed positions outside E, data and parity together.
+ *   4. else rows_uncorrectable++ and the row stays as received.
+ *   The margin of two symbols for e >= 1 is a decision of this contract, not a measurement.  With 2 e + f = 16 nothing is left
+ *   to check the error locator against: a row with more real errors than e -- a burst in the CRC-less FEC packets -- would be
+ *   miscorrected with probability about 0.74^e / e!, which spoils bytes of packets whose CRC was good.  Two spare symbols divide
+ *   that by 65 536.  With e = 0 a miscorrection can only change bytes of slots that were bad already.
+ *   (f = 2 adds nothing to rule 2: e <= 6 is at most eight wrong bytes.  Step 3 begins to tell at f = 4.)
+ *   How: one erasure locator per frame, E being shared by the rows.  Per row the modified syndromes, Berlekamp-Massey on those
+ *   above f, the roots of the errata locator among the 204 positions, Forney's values (in E they may be zero) -- and then the
+ *   pattern is held to the definition as pattern_holds does above: its 16 syndromes equal the row's, every position outside E is
+ *   distinct and non-zero, and their count is within the bound.
+ *
+ * State record.  Of the same size, state_bytes(S); a magic of its own; the suspect bits of the D S carried slots (at most 150,
+ * S = 50) in the head's 32 reserved bytes, carried slot i at bit i & 7 of byte i >> 3.  A record of one call is a fresh start
+ * for the other.  head_ok_erasures() holds the bits of unused positions -- beyond D S, and in padding frames -- to zero.
+ *
+ * Counters.  The twelve words above with the same meaning, then slots_suspect (among the call's new slots),
+ * frames_with_suspects (accepted frames with f >= 2), frames_beyond_erasures (of those, f > 16), rows_erasure_corrected,
+ * erased_bytes_changed, erasure_other_bytes_corrected, and padding to 80 bytes.
+ *
+ * Not provided: correction of the FEC packets' own bytes in the output; erasure of parity columns; FEC schemes other than 1.
  */
 #ifndef DABGPU_PACKET_FEC_H
 #define DABGPU_PACKET_FEC_H

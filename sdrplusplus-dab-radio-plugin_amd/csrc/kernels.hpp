@@ -503,6 +503,30 @@ uint64_t packet_fec_blocks(const PacketFecEntry *entries, int n_entries, int n_c
 // every pointer checked by the caller
 hipError_t launch_packet_fec(PacketFecEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
 
+// ---- ... with failed packet CRCs as erasures (packet_fec_erasure_kernels.hip) ------
+// dabgpu_packet_fec_erasures_dev: the same four launches.  Move also scans every arriving frame's slots (packet CRCs) into a
+// word of suspect bits per window frame; accept carries the last D frames' bits on in the new head; correct goes on, for the
+// rows the errors-only rule leaves, to errata decoding over the frame's erased columns; tally writes the wider record.
+// include/dabgpu_packet_fec_erasures.h.
+struct alignas(16) PacketFecErasureEntry {
+    uint64_t in;               // as PacketFecEntry
+    uint64_t in_stride;
+    uint64_t out;
+    uint64_t out_stride;
+    uint64_t state_in;
+    uint64_t state_out;
+    uint64_t result;           // dabgpu_packet_fec::ErasureCounters
+    uint64_t marks;            // [8 + n_cifs s] bytes                                                 (these four: filled in
+    uint64_t accepted;         // [16 + max_frames] words: count, suspect new slots, 2 x 0, Counters; accepted ends   by the launch)
+    uint64_t counts;           // [max_frames][12] words: ErasureFrameCounts, with suspects, beyond erasures, 2 x 0
+    uint64_t suspects;         // [delay(s) + n_cifs] 64-bit words: a suspect bit per slot of every window frame
+    int32_t s;
+    int32_t max_frames;
+};
+size_t packet_fec_erasure_table_bytes(const PacketFecErasureEntry *entries, int n_entries, int n_cifs);
+uint64_t packet_fec_erasure_blocks(const PacketFecErasureEntry *entries, int n_entries, int n_cifs);
+hipError_t launch_packet_fec_erasures(PacketFecErasureEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

@@ -59,6 +59,7 @@ EXPORTS = [
     "dabgpu_mot_state_bytes", "dabgpu_mot_arena_bytes", "dabgpu_mot_slides_dev", "dabgpu_mot_slides_host", "dabgpu_mot_header_parse",
     "dabgpu_fig_packet_components", "dabgpu_packet_state_bytes", "dabgpu_packet_slides_dev", "dabgpu_packet_slides_host",
     "dabgpu_packet_fec_state_bytes", "dabgpu_packet_fec_delay", "dabgpu_packet_fec_dev", "dabgpu_packet_fec_host",
+    "dabgpu_packet_fec_erasures_dev", "dabgpu_packet_fec_erasures_host",
 ]
 
 ABI_VERSION = 6
@@ -191,6 +192,12 @@ PACKET_FEC_COUNTERS = ("cifs", "slots", "marks", "frames", "frames_cut", "frames
                        "rows_uncorrectable", "bytes_corrected", "parity_bytes_corrected")
 PACKET_FEC_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_FEC_COUNTERS] + [("reserved", np.int32)])
 assert PACKET_FEC_RESULT_DTYPE.itemsize == 48
+#: dabgpu_packet_fec_erasure_result: the twelve words above, then what packet_fec_erasures_dev / _host add
+PACKET_FEC_ERASURE_COUNTERS = PACKET_FEC_COUNTERS + ("slots_suspect", "frames_with_suspects", "frames_beyond_erasures", "rows_erasure_corrected",
+                                                     "erased_bytes_changed", "erasure_other_bytes_corrected")
+PACKET_FEC_ERASURE_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_FEC_COUNTERS] + [("reserved", np.int32)] +
+                                           [(n, np.int32) for n in PACKET_FEC_ERASURE_COUNTERS[len(PACKET_FEC_COUNTERS):]] + [("reserved2", np.int32, (2,))])
+assert PACKET_FEC_ERASURE_RESULT_DTYPE.itemsize == 80
 DSCTY_MOT = 60
 #: dabgpu_audio_component: one MSC stream audio component (fig_audio_components)
 AUDIO_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("subchid", np.int32), ("start_address", np.int32), ("ascty", np.int32),
@@ -310,6 +317,13 @@ class PacketFecEntry(C.Structure):
     _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("reserved", C.c_int32),
                 ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
                 ("d_result", C.c_void_p)]
+
+
+class PacketFecErasureEntry(C.Structure):
+    """dabgpu_packet_fec_erasure_entry: the fields of PacketFecEntry for Context.packet_fec_erasures_dev (device addresses) or
+    packet_fec_erasures_host (host addresses); d_result is a PACKET_FEC_ERASURE_RESULT_DTYPE record.  The state record has
+    the size packet_fec_state_bytes(bitrate) gives; one written by the errors-only call is a fresh start here."""
+    _fields_ = list(PacketFecEntry._fields_)
 
 
 class PacketComponent(C.Structure):
@@ -632,6 +646,8 @@ def load_library(path):
     L.dabgpu_packet_fec_delay.argtypes = [i]
     L.dabgpu_packet_fec_dev.argtypes = [vp, C.POINTER(PacketFecEntry), i, i, vp]
     L.dabgpu_packet_fec_host.argtypes = [C.POINTER(PacketFecEntry), i, i]
+    L.dabgpu_packet_fec_erasures_dev.argtypes = [vp, C.POINTER(PacketFecErasureEntry), i, i, vp]
+    L.dabgpu_packet_fec_erasures_host.argtypes = [C.POINTER(PacketFecErasureEntry), i, i]
     L.dabgpu_decode_stream_frames.argtypes = [vp, vp, sz, i, vp, vp, vp, i, vp]
     L.dabgpu_decode_stream_reset.argtypes = [vp]
     L.dabgpu_streams_reset.argtypes = [vp, i]
@@ -887,6 +903,14 @@ def packet_fec_host(entries, n_cifs):
     n = len(entries)
     arr = (PacketFecEntry * max(n, 1))(*entries)
     _check(lib().dabgpu_packet_fec_host(arr, n, n_cifs), "dabgpu_packet_fec_host")
+
+
+def packet_fec_erasures_host(entries, n_cifs):
+    """Context.packet_fec_erasures_dev on HOST memory (entries: PacketFecErasureEntry with host addresses): the same checks
+    and the same code, include/dabgpu_packet_fec_erasures.h; no context, no GPU."""
+    n = len(entries)
+    arr = (PacketFecErasureEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_packet_fec_erasures_host(arr, n, n_cifs), "dabgpu_packet_fec_erasures_host")
 
 
 def packet_slides_host(entries, n_cifs):
@@ -1545,6 +1569,15 @@ class Context:
         n = len(entries)
         arr = (PacketFecEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_packet_fec_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_fec_dev")
+
+    def packet_fec_erasures_dev(self, entries, n_cifs, stream=None):
+        """packet_fec_dev with the failed packet CRCs of the arriving frames as erasures (up to eight lost packets per FEC
+        frame instead of four): entries is a list of PacketFecErasureEntry (device addresses); d_result is a
+        PACKET_FEC_ERASURE_RESULT_DTYPE record.  What packet_fec_dev corrects, this call corrects identically; its state
+        record is its own (one of packet_fec_dev is a fresh start).  No host synchronisation."""
+        n = len(entries)
+        arr = (PacketFecErasureEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_packet_fec_erasures_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_fec_erasures_dev")
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

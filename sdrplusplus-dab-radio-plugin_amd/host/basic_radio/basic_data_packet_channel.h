@@ -7,7 +7,9 @@
 // sub-channel are followed, each with a state record and an arena of its own.  FEC packets are counted; with
 // SetFecCorrection(true) -- BasicRadio switches it on when FIG 0/14 gives the sub-channel FEC scheme 1 -- every logical frame
 // first goes through the host path of include/dabgpu_packet_fec.h, the code dabgpu_packet_fec_dev runs: the FEC frames are
-// corrected by RS(204,188) and the walk sees the stream delayed by ceil(102 / S) frames (padding packets at first).
+// corrected by RS(204,188) and the walk sees the stream delayed by ceil(102 / S) frames (padding packets at first).  With FEC
+// scheme 1 that path is include/dabgpu_packet_fec_erasures.h's, the code dabgpu_packet_fec_erasures_dev runs: the packets whose
+// CRC fails are erasures, so eight lost packets per FEC frame are recovered instead of four.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -16,6 +18,7 @@
 #include "basic_radio/basic_slideshow.h"
 #include "dab/database/dab_database_entities.h"
 #include "dabgpu_packet_fec.h"
+#include "dabgpu_packet_fec_erasures.h"
 #include "dabgpu_packet_walk.h"
 #include "utility/span.h"
 
@@ -38,7 +41,9 @@ public:
     }
     bool GetFecCorrection() const { return m_correct; }
     // counts since the correction was switched on (cifs, slots, marks, frames, rows_*, bytes_corrected ...)
-    const dabgpu_packet_fec::Counters &GetFecCounters() const { return m_fec_counts; }
+    const dabgpu_packet_fec::Counters &GetFecCounters() const { return m_fec_counts.c; }
+    // the same and what the erasure path adds (slots_suspect, rows_erasure_corrected ...; zero without FEC scheme 1)
+    const dabgpu_packet_fec::ErasureCounters &GetFecErasureCounters() const { return m_fec_counts; }
 
     // a packet address (1 .. 1023) to follow from the next frame on: false for one out of range, and for a fifth
     bool FollowAddress(int address) {
@@ -100,7 +105,8 @@ public:
     }
 
 private:
-    // one logical frame through dabgpu_packet_fec::process: -> the frame D frames back, corrected
+    // one logical frame through dabgpu_packet_fec::process_erasures (FEC scheme 1) or process: -> the frame D frames back,
+    // corrected.  The two keep state records of their own kind: a change of scheme starts the FEC stream afresh
     const uint8_t *Correct(const uint8_t *lf, int S) {
         namespace fec = dabgpu_packet_fec;
         static const fec::Gf gf = fec::make_gf();
@@ -109,12 +115,17 @@ private:
         if (fresh) {                                                   // (the first frame, or a frame of another size)
             m_fec_slots = S;
             m_fec_turn = 0;
-            m_fec_counts = fec::Counters{};
+            m_fec_counts = fec::ErasureCounters{};
             for (auto &st : m_fec_state) st.assign(nb, 0);
             m_fec_out.assign(fb, 0);
         }
-        fec::Counters c;
-        fec::process(gf, fresh ? nullptr : m_fec_state[m_fec_turn].data(), m_fec_state[m_fec_turn ^ 1].data(), c, lf, fb, 1, S, m_fec_out.data(), fb);
+        fec::ErasureCounters c{};
+        const uint8_t *state_in = fresh ? nullptr : m_fec_state[m_fec_turn].data();
+        uint8_t *state_out = m_fec_state[m_fec_turn ^ 1].data();
+        if (m_fec == 1)
+            fec::process_erasures(gf, state_in, state_out, c, lf, fb, 1, S, m_fec_out.data(), fb);
+        else
+            fec::process(gf, state_in, state_out, c.c, lf, fb, 1, S, m_fec_out.data(), fb);
         m_fec_turn ^= 1;
         int32_t *sum = reinterpret_cast<int32_t *>(&m_fec_counts);
         for (size_t i = 0; i < sizeof c / sizeof(int32_t); i++) sum[i] += reinterpret_cast<const int32_t *>(&c)[i];
@@ -138,5 +149,5 @@ private:
     bool m_correct = false;
     int m_fec_slots = 0, m_fec_turn = 0;   // S the FEC state is for (0: none yet); which of the two records is current
     std::vector<uint8_t> m_fec_state[2], m_fec_out;
-    dabgpu_packet_fec::Counters m_fec_counts{};
+    dabgpu_packet_fec::ErasureCounters m_fec_counts{};
 };
