@@ -171,12 +171,17 @@ DABGPU_FEC_FN void head_fresh(Head &h, int S) {
     h.last_end = -1;
     for (int i = 0; i < 8; i++) h.tail[i] = MARK_NONE;
 }
-/* a record this code wrote for S slots a frame */
-DABGPU_FEC_FN bool head_ok(const Head &h, int S) {
-    bool ok = h.magic == MAGIC && h.slots == S && h.frames_seen >= 0 && h.frames_seen <= MAX_FRAMES_SEEN;
+/* a record with this magic, written for S slots a frame: everything but what `reserved` may hold */
+DABGPU_FEC_FN bool head_written(const Head &h, int S, uint32_t magic) {
+    bool ok = h.magic == magic && h.slots == S && h.frames_seen >= 0 && h.frames_seen <= MAX_FRAMES_SEEN;
     ok = ok && h.last_end >= -1 && (h.last_end == -1 || (h.last_end >= FRAME_SLOTS - 1 && h.last_end < h.frames_seen * S));
     for (int i = 0; i < 8; i++)
         ok = ok && (h.tail[i] == MARK_NONE || (h.tail[i] <= 8 && h.frames_seen * S - 8 + i >= 0));
+    return ok;
+}
+/* a record this code wrote for S slots a frame */
+DABGPU_FEC_FN bool head_ok(const Head &h, int S) {
+    bool ok = head_written(h, S, MAGIC);
     for (int i = 0; i < 32; i++) ok = ok && h.reserved[i] == 0;
     return ok;
 }
@@ -343,44 +348,50 @@ DABGPU_FEC_FN void count_row(const RowWork &w, bool codeword, bool holds, FrameC
     }
 }
 
-/* ---- the host path: one FEC frame, one call */
+/* ---- a held pattern applied (kernels and host path) */
 
-/* One FEC frame whose slot i (0..102) is the 24 bytes at slot(i): corrected in place */
-template <class Slot> inline void correct_frame(const Gf &g, Slot slot, Counters &c) {
-    uint8_t fr[FRAME_BYTES];
+/* the data bytes of a held pattern (n positions and values) of row r, written where they lie: slot(i) is the 24 bytes of the
+ * frame's slot i, fr the frame as received */
+template <class Slot> DABGPU_FEC_FN void write_back(Slot slot, const uint8_t *fr, int r, const uint8_t *pos, const uint8_t *val, int n) {
+    for (int i = 0; i < n; i++) {
+        if (pos[i] >= K) continue;
+        const int b = frame_index(r, pos[i]);
+        slot(b / SLOT_BYTES)[b % SLOT_BYTES] = uint8_t(fr[b] ^ val[i]);
+    }
+}
+
+/* ---- the host path: the rows of one FEC frame */
+
+/* the 2472 bytes of the frame whose slot i (0..102) is the 24 bytes at slot(i) */
+template <class Slot> inline void load_frame(Slot slot, uint8_t *fr) {
     for (int i = 0; i < FRAME_SLOTS; i++) {
         const uint8_t *p = slot(i);
         for (int b = 0; b < SLOT_BYTES; b++) fr[SLOT_BYTES * i + b] = p[b];
     }
-    FrameCounts f = {};
-    for (int r = 0; r < ROWS; r++) {
-        RowWork w;
-        unsigned S[T2] = {};
-        for (int col = 0; col < N; col++) syndrome_add(g, fr[frame_index(r, col)], col, S);
-        for (int k = 0; k < T2; k++) w.syn[k] = uint8_t(S[k]);
-        w.ll = w.n = 0;
-        const bool codeword = row_is_codeword(w);
-        bool holds = false;
-        if (!codeword && locator(g, w)) {
-            for (int col = 0; col < N; col++) {
-                unsigned v;
-                if (!root_at(g, w, col, v)) continue;
-                if (w.n < T) {
-                    w.pos[w.n] = uint8_t(col);
-                    w.val[w.n] = uint8_t(v);
-                }
-                w.n++;
-            }
-            holds = pattern_holds(g, w);
+}
+
+/* Row r of the frame fr by the errors-only rule: its syndromes into w, and for a row that is no codeword Berlekamp-Massey, the
+ * roots among the 204 positions and pattern_holds.  True: w holds the pattern to apply. */
+inline bool decode_row(const Gf &g, const uint8_t *fr, int r, RowWork &w, bool &codeword) {
+    unsigned S[T2] = {};
+    for (int col = 0; col < N; col++) syndrome_add(g, fr[frame_index(r, col)], col, S);
+    for (int k = 0; k < T2; k++) w.syn[k] = uint8_t(S[k]);
+    w.ll = w.n = 0;
+    codeword = row_is_codeword(w);
+    if (codeword || !locator(g, w)) return false;
+    for (int col = 0; col < N; col++) {
+        unsigned v;
+        if (!root_at(g, w, col, v)) continue;
+        if (w.n < T) {
+            w.pos[w.n] = uint8_t(col);
+            w.val[w.n] = uint8_t(v);
         }
-        count_row(w, codeword, holds, f);
-        if (!holds) continue;
-        for (int i = 0; i < w.n; i++) {
-            if (w.pos[i] >= K) continue;
-            const int b = frame_index(r, w.pos[i]);
-            slot(b / SLOT_BYTES)[b % SLOT_BYTES] = uint8_t(fr[b] ^ w.val[i]);
-        }
+        w.n++;
     }
+    return pattern_holds(g, w);
+}
+
+inline void add_counts(Counters &c, const FrameCounts &f) {
     c.rows_clean += f.rows_clean;
     c.rows_corrected += f.rows_corrected;
     c.rows_uncorrectable += f.rows_uncorrectable;
@@ -388,55 +399,107 @@ template <class Slot> inline void correct_frame(const Gf &g, Slot slot, Counters
     c.parity_bytes_corrected += f.parity_bytes_corrected;
 }
 
-/* One entry of a call on memory the caller can read and write: the twin of the kernels.  state_in: state_bytes(S) or NULL;
- * state_out: state_bytes(S), no overlap with state_in; out: [n][out_stride], no overlap with in.  c: the counts of this call. */
-inline void process(const Gf &g, const uint8_t *state_in, uint8_t *state_out, Counters &c, const uint8_t *in, uint64_t in_stride, int n, int S,
-                    uint8_t *out, uint64_t out_stride) {
-    const int D = delay(S), fb = SLOT_BYTES * S;
-    Head h;
-    bool fresh = state_in == nullptr;
-    if (!fresh) {
-        for (int i = 0; i < HEAD_BYTES; i++) reinterpret_cast<uint8_t *>(&h)[i] = state_in[i];
-        fresh = !head_ok(h, S);
+/* One FEC frame whose slot i (0..102) is the 24 bytes at slot(i): corrected in place */
+template <class Slot> inline void correct_frame(const Gf &g, Slot slot, Counters &c) {
+    uint8_t fr[FRAME_BYTES];
+    load_frame(slot, fr);
+    FrameCounts f = {};
+    for (int r = 0; r < ROWS; r++) {
+        RowWork w;
+        bool codeword;
+        const bool holds = decode_row(g, fr, r, w, codeword);
+        count_row(w, codeword, holds, f);
+        if (holds) write_back(slot, fr, r, w.pos, w.val, w.n);
     }
-    if (fresh) head_fresh(h, S);
-    c = Counters{};
-    c.cifs = n;
-    c.slots = n * S;
-    /* the window: the D carried frames, then the n new ones; its first n frames go out, its last D are carried on */
-    auto dest = [&](int64_t wf) { return wf < n ? out + uint64_t(wf) * out_stride : state_out + HEAD_BYTES + (wf - n) * fb; };
-    for (int64_t wf = 0; wf < int64_t(D) + n; wf++) {
-        uint8_t *d = dest(wf);
+    add_counts(c, f);
+}
+
+/* ---- the host path: the window of one call */
+
+/* One entry of a call on memory the caller can read and write.  state_in: state_bytes(S) or NULL; state_out: state_bytes(S), no
+ * overlap with state_in; out: [n][out_stride], no overlap with in.  The window is the D carried frames, then the n new ones; its
+ * first n frames go out, its last D are carried on. */
+struct Window {
+    const uint8_t *state_in;
+    uint8_t *state_out;
+    const uint8_t *in;
+    uint64_t in_stride;
+    int n, S;
+    uint8_t *out;
+    uint64_t out_stride;
+    /* where window frame wf goes, and window slot w */
+    uint8_t *frame(int64_t wf) const { return wf < n ? out + uint64_t(wf) * out_stride : state_out + HEAD_BYTES + (wf - n) * (SLOT_BYTES * S); }
+    uint8_t *slot(int64_t w) const { return frame(w / S) + SLOT_BYTES * (w % S); }
+    /* the mark of new slot j, j >= -8, from the bytes as received (below 0: the tail of the head the call began with) */
+    uint8_t mark(const Head &h, int64_t j) const {
+        if (j < 0) return h.tail[8 + j];
+        const uint8_t *p = in + uint64_t(j / S) * in_stride + SLOT_BYTES * (j % S);
+        return mark_of(p[0], p[1]);
+    }
+};
+
+/* the head a call begins with: the record's where ok() knows it, else what fresh() makes.  True: a fresh start. */
+inline bool start_head(Head &h, const uint8_t *state_in, int S, bool (*ok)(const Head &, int), void (*fresh)(Head &, int)) {
+    bool is_fresh = state_in == nullptr;
+    if (!is_fresh) {
+        for (int i = 0; i < HEAD_BYTES; i++) reinterpret_cast<uint8_t *>(&h)[i] = state_in[i];
+        is_fresh = !ok(h, S);
+    }
+    if (is_fresh) fresh(h, S);
+    return is_fresh;
+}
+
+/* every frame of the window to where it goes, as received (a fresh start has padding for carried frames); the record's tail
+ * beyond the carried frames zeroed */
+inline void move_window(const Window &w, bool fresh) {
+    const int D = delay(w.S), fb = SLOT_BYTES * w.S;
+    for (int64_t wf = 0; wf < int64_t(D) + w.n; wf++) {
+        uint8_t *d = w.frame(wf);
         if (wf >= D) {
-            const uint8_t *s = in + uint64_t(wf - D) * in_stride;
+            const uint8_t *s = w.in + uint64_t(wf - D) * w.in_stride;
             for (int i = 0; i < fb; i++) d[i] = s[i];
         } else if (fresh) {
             for (int i = 0; i < fb; i++) d[i] = padding_byte(i % SLOT_BYTES);
         } else {
-            const uint8_t *s = state_in + HEAD_BYTES + wf * fb;
+            const uint8_t *s = w.state_in + HEAD_BYTES + wf * fb;
             for (int i = 0; i < fb; i++) d[i] = s[i];
         }
     }
-    for (int i = HEAD_BYTES + D * fb; i < state_bytes(S); i++) state_out[i] = 0;
-    const int64_t slots = int64_t(n) * S;
-    auto mark = [&](int64_t j) {
-        if (j < 0) return h.tail[8 + j];
-        const uint8_t *p = in + uint64_t(j / S) * in_stride + SLOT_BYTES * (j % S);
-        return mark_of(p[0], p[1]);
-    };
-    auto window_slot = [&](int64_t w) { return dest(w / S) + SLOT_BYTES * (w % S); };
-    for (int64_t j = 0; j < slots; j++) {
-        c.marks += mark(j) != MARK_NONE;
-        if (!ends_here(mark, j)) continue;
-        if (judge(h, c, h.frames_seen * S + j) != ACCEPTED) continue;
-        const int64_t first = int64_t(D) * S + j - (FRAME_SLOTS - 1);
-        correct_frame(g, [&](int i) { return window_slot(first + i); }, c);
-    }
+    for (int i = HEAD_BYTES + D * fb; i < state_bytes(w.S); i++) w.state_out[i] = 0;
+}
+
+/* new slot j of the call: its mark is counted; true when an accepted frame ends there, `first` its first slot counted from the
+ * window's */
+inline bool frame_ends(const Window &w, Head &h, Counters &c, int64_t j, int64_t &first) {
+    auto mark = [&](int64_t jj) { return w.mark(h, jj); };
+    c.marks += mark(j) != MARK_NONE;
+    if (!ends_here(mark, j) || judge(h, c, h.frames_seen * w.S + j) != ACCEPTED) return false;
+    first = int64_t(delay(w.S)) * w.S + j - (FRAME_SLOTS - 1);
+    return true;
+}
+
+/* the head moves on by the call's n frames and is stored */
+inline void store_head(Head &h, const Window &w) {
+    const int64_t slots = int64_t(w.n) * w.S;
     uint8_t tail[8];
-    for (int i = 0; i < 8; i++) tail[i] = mark(slots - 8 + i);
+    for (int i = 0; i < 8; i++) tail[i] = w.mark(h, slots - 8 + i);
     for (int i = 0; i < 8; i++) h.tail[i] = tail[i];
-    h.frames_seen += n;
-    for (int i = 0; i < HEAD_BYTES; i++) state_out[i] = reinterpret_cast<const uint8_t *>(&h)[i];
+    h.frames_seen += w.n;
+    for (int i = 0; i < HEAD_BYTES; i++) w.state_out[i] = reinterpret_cast<const uint8_t *>(&h)[i];
+}
+
+/* One entry of a call: the twin of the kernels.  c: the counts of this call. */
+inline void process(const Gf &g, const uint8_t *state_in, uint8_t *state_out, Counters &c, const uint8_t *in, uint64_t in_stride, int n, int S,
+                    uint8_t *out, uint64_t out_stride) {
+    const Window w = {state_in, state_out, in, in_stride, n, S, out, out_stride};
+    Head h;
+    move_window(w, start_head(h, state_in, S, head_ok, head_fresh));
+    c = Counters{};
+    c.cifs = n;
+    c.slots = n * S;
+    for (int64_t j = 0, first; j < int64_t(n) * S; j++)
+        if (frame_ends(w, h, c, j, first)) correct_frame(g, [&](int i) { return w.slot(first + i); }, c);
+    store_head(h, w);
 }
 
 }  /* namespace dabgpu_packet_fec */

@@ -60,10 +60,7 @@ DABGPU_FEC_FN void head_fresh_erasures(Head &h, int S) {
 /* a record the erasure call wrote for S slots a frame: bit i of `reserved` is carried slot i; none beyond D S, none in a
  * padding frame */
 DABGPU_FEC_FN bool head_ok_erasures(const Head &h, int S) {
-    bool ok = h.magic == ERASURE_MAGIC && h.slots == S && h.frames_seen >= 0 && h.frames_seen <= MAX_FRAMES_SEEN;
-    ok = ok && h.last_end >= -1 && (h.last_end == -1 || (h.last_end >= FRAME_SLOTS - 1 && h.last_end < h.frames_seen * S));
-    for (int i = 0; i < 8; i++)
-        ok = ok && (h.tail[i] == MARK_NONE || (h.tail[i] <= 8 && h.frames_seen * S - 8 + i >= 0));
+    bool ok = head_written(h, S, ERASURE_MAGIC);
     if (!ok) return false;
     const int D = delay(S), used = D * S;
     const int padding = h.frames_seen < D ? int(D - h.frames_seen) * S : 0;
@@ -230,50 +227,24 @@ DABGPU_FEC_FN void count_erasure_row(const ErasureSet &es, const ErasureWork &w,
 /* One FEC frame whose slot i (0..102) is the 24 bytes at slot(i), suspect(i) the suspect bit of table slot i (0..93) */
 template <class Slot, class Suspect> inline void correct_frame_erasures(const Gf &g, Slot slot, Suspect suspect, ErasureCounters &c) {
     uint8_t fr[FRAME_BYTES];
-    for (int i = 0; i < FRAME_SLOTS; i++) {
-        const uint8_t *p = slot(i);
-        for (int b = 0; b < SLOT_BYTES; b++) fr[SLOT_BYTES * i + b] = p[b];
-    }
+    load_frame(slot, fr);
     ErasureSet es = {};
     for (int i = 0; i < DATA_SLOTS; i++)
-        if (suspect(i)) es.slots[i >> 6] |= uint64_t(1) << (i & 63);
+        if (suspect(i)) {
+            es.slots[i >> 6] |= uint64_t(1) << (i & 63);
+            es.f += 2;
+        }
     bool located = false;                 /* the locator is made for the first row that needs it */
-    {
-        int n = 0;
-        for (int i = 0; i < DATA_SLOTS; i++) n += suspect(i) ? 1 : 0;
-        es.f = 2 * n;
-    }
     c.frames_with_suspects += es.f >= 2;
     c.frames_beyond_erasures += es.f > MAX_ERASED;
     ErasureFrameCounts f = {};
     for (int r = 0; r < ROWS; r++) {
         RowWork w;
-        unsigned S[T2] = {};
-        for (int col = 0; col < N; col++) syndrome_add(g, fr[frame_index(r, col)], col, S);
-        for (int k = 0; k < T2; k++) w.syn[k] = uint8_t(S[k]);
-        w.ll = w.n = 0;
-        const bool codeword = row_is_codeword(w);
-        bool holds = false;
-        if (!codeword && locator(g, w)) {
-            for (int col = 0; col < N; col++) {
-                unsigned v;
-                if (!root_at(g, w, col, v)) continue;
-                if (w.n < T) {
-                    w.pos[w.n] = uint8_t(col);
-                    w.val[w.n] = uint8_t(v);
-                }
-                w.n++;
-            }
-            holds = pattern_holds(g, w);
-        }
+        bool codeword;
+        const bool holds = decode_row(g, fr, r, w, codeword);
         if (codeword || holds || !erasures_usable(es)) {
             count_row(w, codeword, holds, f.f);
-            if (!holds) continue;
-            for (int i = 0; i < w.n; i++) {
-                if (w.pos[i] >= K) continue;
-                const int b = frame_index(r, w.pos[i]);
-                slot(b / SLOT_BYTES)[b % SLOT_BYTES] = uint8_t(fr[b] ^ w.val[i]);
-            }
+            if (holds) write_back(slot, fr, r, w.pos, w.val, w.n);
             continue;
         }
         if (!located) erasure_locator(g, es);
@@ -293,86 +264,44 @@ template <class Slot, class Suspect> inline void correct_frame_erasures(const Gf
             eholds = errata_holds(g, es, w.syn, ew);
         }
         count_erasure_row(es, ew, eholds, f);
-        if (!eholds) continue;
-        for (int i = 0; i < ew.n; i++) {
-            if (ew.pos[i] >= K) continue;
-            const int b = frame_index(r, ew.pos[i]);
-            slot(b / SLOT_BYTES)[b % SLOT_BYTES] = uint8_t(fr[b] ^ ew.val[i]);
-        }
+        if (eholds) write_back(slot, fr, r, ew.pos, ew.val, ew.n);
     }
-    c.c.rows_clean += f.f.rows_clean;
-    c.c.rows_corrected += f.f.rows_corrected;
-    c.c.rows_uncorrectable += f.f.rows_uncorrectable;
-    c.c.bytes_corrected += f.f.bytes_corrected;
-    c.c.parity_bytes_corrected += f.f.parity_bytes_corrected;
+    add_counts(c.c, f.f);
     c.rows_erasure_corrected += f.rows_erasure_corrected;
     c.erased_bytes_changed += f.erased_bytes_changed;
     c.erasure_other_bytes_corrected += f.erasure_other_bytes_corrected;
 }
 
-/* One entry of a call on memory the caller can read and write: the twin of the erasure kernels, with the arguments of
- * process().  A record process() wrote is a fresh start here, and the other way round. */
+/* One entry of a call: the twin of the erasure kernels, with the arguments of process() and its window functions.  A record
+ * process() wrote is a fresh start here, and the other way round. */
 inline void process_erasures(const Gf &g, const uint8_t *state_in, uint8_t *state_out, ErasureCounters &c, const uint8_t *in, uint64_t in_stride,
                              int n, int S, uint8_t *out, uint64_t out_stride) {
-    const int D = delay(S), fb = SLOT_BYTES * S;
+    const Window w = {state_in, state_out, in, in_stride, n, S, out, out_stride};
+    const int D = delay(S);
     Head h;
-    bool fresh = state_in == nullptr;
-    if (!fresh) {
-        for (int i = 0; i < HEAD_BYTES; i++) reinterpret_cast<uint8_t *>(&h)[i] = state_in[i];
-        fresh = !head_ok_erasures(h, S);
-    }
-    if (fresh) head_fresh_erasures(h, S);
+    move_window(w, start_head(h, state_in, S, head_ok_erasures, head_fresh_erasures));
     c = ErasureCounters{};
     c.c.cifs = n;
     c.c.slots = n * S;
-    auto dest = [&](int64_t wf) { return wf < n ? out + uint64_t(wf) * out_stride : state_out + HEAD_BYTES + (wf - n) * fb; };
-    for (int64_t wf = 0; wf < int64_t(D) + n; wf++) {
-        uint8_t *d = dest(wf);
-        if (wf >= D) {
-            const uint8_t *s = in + uint64_t(wf - D) * in_stride;
-            for (int i = 0; i < fb; i++) d[i] = s[i];
-        } else if (fresh) {
-            for (int i = 0; i < fb; i++) d[i] = padding_byte(i % SLOT_BYTES);
-        } else {
-            const uint8_t *s = state_in + HEAD_BYTES + wf * fb;
-            for (int i = 0; i < fb; i++) d[i] = s[i];
-        }
-    }
-    for (int i = HEAD_BYTES + D * fb; i < state_bytes(S); i++) state_out[i] = 0;
     /* the suspect words of the last D + 1 window frames, window frame wf at wf % (D + 1): a frame that ends in new frame k
      * began at most D frames before it */
     uint64_t ring[FRAME_SLOTS];
     const int R = D + 1;
     for (int wf = 0; wf < D; wf++) ring[wf % R] = get_bits(h.reserved, wf * S, S);
-    const int64_t slots = int64_t(n) * S;
-    auto mark = [&](int64_t j) {
-        if (j < 0) return h.tail[8 + j];
-        const uint8_t *p = in + uint64_t(j / S) * in_stride + SLOT_BYTES * (j % S);
-        return mark_of(p[0], p[1]);
-    };
-    auto window_slot = [&](int64_t w) { return dest(w / S) + SLOT_BYTES * (w % S); };
-    for (int64_t j = 0; j < slots; j++) {
+    for (int64_t j = 0, first; j < int64_t(n) * S; j++) {
         if (j % S == 0) {
             const uint64_t word = suspects_of(in + uint64_t(j / S) * in_stride, S);
             ring[(D + j / S) % R] = word;
             for (int i = 0; i < S; i++) c.slots_suspect += int((word >> i) & 1u);
         }
-        c.c.marks += mark(j) != MARK_NONE;
-        if (!ends_here(mark, j)) continue;
-        if (judge(h, c.c, h.frames_seen * S + j) != ACCEPTED) continue;
-        const int64_t first = int64_t(D) * S + j - (FRAME_SLOTS - 1);
+        if (!frame_ends(w, h, c.c, j, first)) continue;
         correct_frame_erasures(
-            g, [&](int i) { return window_slot(first + i); },
-            [&](int i) { return ((ring[((first + i) / S) % R] >> ((first + i) % S)) & 1u) != 0; }, c);
+            g, [&](int i) { return w.slot(first + i); }, [&](int i) { return ((ring[((first + i) / S) % R] >> ((first + i) % S)) & 1u) != 0; }, c);
     }
-    uint8_t tail[8];
-    for (int i = 0; i < 8; i++) tail[i] = mark(slots - 8 + i);
-    for (int i = 0; i < 8; i++) h.tail[i] = tail[i];
     uint8_t bits[SUSPECT_BYTES] = {};
     for (int k = 0; k < D; k++) put_bits(bits, k * S, S, ring[(int64_t(n) + k) % R]);
     for (int i = 0; i < SUSPECT_BYTES; i++) h.reserved[i] = bits[i];
-    h.frames_seen += n;
-    for (int i = 0; i < HEAD_BYTES; i++) state_out[i] = reinterpret_cast<const uint8_t *>(&h)[i];
+    store_head(h, w);
 }
 
 }  /* namespace dabgpu_packet_fec */

@@ -476,11 +476,15 @@ uint64_t packet_scan_blocks(const PacketEntry *entries, int n_entries, int n_cif
 hipError_t launch_packet_slides(PacketEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
 
 // ---- RS(204,188) correction of packet-mode FEC frames (packet_fec_kernels.hip) ------
-// dabgpu_packet_fec_dev: one entry per sub-channel, uploaded as a table with its scratch records behind it.  Four launches:
-// move (the carried and the new frames to the output and the new state record; a mark per new slot), accept (one wave per
-// entry: candidate ends by ballot, the accept chain in order, the new record's head), correct (one workgroup per accepted
-// frame: 16 syndromes of 12 rows on all lanes, then Berlekamp-Massey / Chien / Forney for the rows that need it, corrected
-// bytes written back) and tally (one wave per entry sums the frames' counts into the result).  include/dabgpu_packet_fec.h.
+// dabgpu_packet_fec_dev and dabgpu_packet_fec_erasures_dev: one entry per sub-channel, uploaded as a table with its scratch
+// records behind it.  Four launches: move (the carried and the new frames to the output and the new state record; a mark per
+// new slot), accept (one wave per entry: candidate ends by ballot, the accept chain in order, the new record's head), correct
+// (one workgroup per accepted frame: 16 syndromes of 12 rows on all lanes, then Berlekamp-Massey / Chien / Forney for the rows
+// that need it, corrected bytes written back) and tally (one wave per entry sums the frames' counts into the result).
+// include/dabgpu_packet_fec.h.
+// With `erasures`, move also scans every arriving frame's slots (packet CRCs) into a word of suspect bits per window frame;
+// accept carries the last D frames' bits on in the new head; correct goes on, for the rows the errors-only rule leaves, to
+// errata decoding over the frame's erased columns; tally writes the wider record.  include/dabgpu_packet_fec_erasures.h.
 struct alignas(16) PacketFecEntry {
     uint64_t in;               // [n_cifs][in_stride] logical frames of 24 s bytes
     uint64_t in_stride;
@@ -488,44 +492,24 @@ struct alignas(16) PacketFecEntry {
     uint64_t out_stride;
     uint64_t state_in;         // dabgpu_packet_fec::state_bytes(s) or 0
     uint64_t state_out;
-    uint64_t result;           // dabgpu_packet_fec::Counters
-    uint64_t marks;            // [8 + n_cifs s] bytes: the record's tail, then a mark per new slot   (these three: filled in
-    uint64_t accepted;         // [16 + max_frames] words: count, 3 x 0, the call's Counters; accepted ends       by the launch)
-    uint64_t counts;           // [max_frames][8] words: dabgpu_packet_fec::FrameCounts, 3 x 0
+    uint64_t result;           // dabgpu_packet_fec::Counters; erasures: ErasureCounters
+    // these four: filled in by the launch
+    uint64_t marks;            // [8 + n_cifs s] bytes: the record's tail, then a mark per new slot
+    uint64_t accepted;         // [16 + max_frames] words: count, 0 (erasures: suspect new slots), 2 x 0, the call's Counters; accepted ends
+    uint64_t counts;           // [max_frames][8] words: FrameCounts, 3 x 0
+                               // (erasures: [max_frames][12] words: ErasureFrameCounts, with suspects, beyond erasures, 2 x 0)
+    uint64_t suspects;         // 0 (erasures: [delay(s) + n_cifs] 64-bit words: a suspect bit per slot of every window frame)
     int32_t s;
     int32_t max_frames;        // dabgpu_packet_fec::max_frames(s, n_cifs)
-    int32_t reserved[2];
 };
-size_t packet_fec_table_bytes(const PacketFecEntry *entries, int n_entries, int n_cifs);
+static_assert(sizeof(PacketFecEntry) == 96, "an entry of the table in the stage area");
+size_t packet_fec_table_bytes(const PacketFecEntry *entries, int n_entries, int n_cifs, bool erasures);
 // workgroups of the largest launch
 uint64_t packet_fec_blocks(const PacketFecEntry *entries, int n_entries, int n_cifs);
 // `entries`: HOST array (its scratch addresses and max_frames are set here; copied to d_table on `stream` before the kernels);
 // every pointer checked by the caller
-hipError_t launch_packet_fec(PacketFecEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
-
-// ---- ... with failed packet CRCs as erasures (packet_fec_erasure_kernels.hip) ------
-// dabgpu_packet_fec_erasures_dev: the same four launches.  Move also scans every arriving frame's slots (packet CRCs) into a
-// word of suspect bits per window frame; accept carries the last D frames' bits on in the new head; correct goes on, for the
-// rows the errors-only rule leaves, to errata decoding over the frame's erased columns; tally writes the wider record.
-// include/dabgpu_packet_fec_erasures.h.
-struct alignas(16) PacketFecErasureEntry {
-    uint64_t in;               // as PacketFecEntry
-    uint64_t in_stride;
-    uint64_t out;
-    uint64_t out_stride;
-    uint64_t state_in;
-    uint64_t state_out;
-    uint64_t result;           // dabgpu_packet_fec::ErasureCounters
-    uint64_t marks;            // [8 + n_cifs s] bytes                                                 (these four: filled in
-    uint64_t accepted;         // [16 + max_frames] words: count, suspect new slots, 2 x 0, Counters; accepted ends   by the launch)
-    uint64_t counts;           // [max_frames][12] words: ErasureFrameCounts, with suspects, beyond erasures, 2 x 0
-    uint64_t suspects;         // [delay(s) + n_cifs] 64-bit words: a suspect bit per slot of every window frame
-    int32_t s;
-    int32_t max_frames;
-};
-size_t packet_fec_erasure_table_bytes(const PacketFecErasureEntry *entries, int n_entries, int n_cifs);
-uint64_t packet_fec_erasure_blocks(const PacketFecErasureEntry *entries, int n_entries, int n_cifs);
-hipError_t launch_packet_fec_erasures(PacketFecErasureEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+hipError_t launch_packet_fec(PacketFecEntry *entries, int n_entries, int n_cifs, bool erasures, void *d_table, size_t table_bytes,
+                             hipStream_t stream);
 
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {

@@ -510,8 +510,11 @@ def test_new_kernels_neither_spill_nor_use_scratch(built, tmp_path):
     subprocess.check_call([hipcc] + flags + ["-S", "--cuda-device-only", os.path.join(CSRC, "packet_fec_kernels.hip"), "-o", str(out)],
                           stderr=subprocess.DEVNULL)
     md = kernel_metadata(out.read_text())
-    assert len(md) == 4 and all(sum(k in name for name in md) == 1 for k in ("packet_fec_move_kernel", "packet_fec_accept_kernel",
-                                                                            "packet_fec_correct_kernel", "packet_fec_tally_kernel"))
+    # the file holds both calls' kernels: this call's four, each once, and the erasure call's four, and no others
+    assert all(sum(k in name for name in md) == 1 for k in ("packet_fec_move_kernel", "packet_fec_accept_kernel",
+                                                            "packet_fec_correct_kernel", "packet_fec_tally_kernel"))
+    assert len(md) == 8 and all(sum(k in name for name in md) == 1 for k in ("packet_fec_erasure_move_kernel", "packet_fec_erasure_accept_kernel",
+                                                                            "packet_fec_erasure_correct_kernel", "packet_fec_erasure_tally_kernel"))
     for k, v in md.items():
         print("%s: vgprs %s, sgprs %s, LDS %s bytes" % (k, v.get("vgpr_count"), v.get("sgpr_count"), v.get("group_segment_fixed_size")))
         assert v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0, (k, v)
