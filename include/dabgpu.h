@@ -1852,8 +1852,9 @@ int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entrie
 /*                                                                            */
 /* Reed-Solomon RS(204,188) correction of FEC frames is a call of its own in      */
 /* front of this one, dabgpu_packet_fec_dev (below): this call recognises and     */
-/* counts FEC packets and reads what that one wrote, unchanged.  Not done: MOT    */
-/* directory mode (data group types 6, 7); non-MOT packet data                   */
+/* counts FEC packets and reads what that one wrote, unchanged.  MOT directory    */
+/* mode (data group type 6) is dabgpu_packet_carousel_dev (below).  Not done:     */
+/* compressed directories (type 7); non-MOT packet data                          */
 /* (TPEG, SPI, Journaline); conditional access; FIG 0/13 user application        */
 /* signalling (the caller chooses DSCTy 60 / DG 0 from the component list).      */
 /*                                                                            */
@@ -2121,6 +2122,169 @@ typedef struct dabgpu_packet_fec_erasure_entry {    /* the fields of dabgpu_pack
 int dabgpu_packet_fec_erasures_dev(dabgpu_ctx *ctx, const dabgpu_packet_fec_erasure_entry *entries, int n_entries, int n_cifs, void *stream);
 /* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
 int dabgpu_packet_fec_erasures_host(const dabgpu_packet_fec_erasure_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
+/* Packet-mode MOT directory carousels of a batch, to their objects, on the     */
+/* device.  Station logos and programme guides (SPI) are sent in MOT directory   */
+/* mode (EN 301 234 clause 7.2): a directory object (data group type 6) lists    */
+/* every object's transport id and MOT header, and only bodies (type 4) follow.  */
+/* A second pair of calls beside dabgpu_packet_slides_*: one entry per            */
+/* (sub-channel, packet address), behind dabgpu_decode_ensembles_dev on the same  */
+/* stream (and behind either FEC call where there is one), on the same logical    */
+/* frames.  Two launches: the scan of                 */
+/* dabgpu_packet_slides_dev, unchanged, and a walk (one wave per entry).  The     */
+/* contract and the code are include/dabgpu_mot_carousel.h.  The counters of      */
+/* either call tell which mode a component speaks: groups_header_mode here,       */
+/* groups_ignored_type there.                                                     */
+/*                                                                              */
+/* Not done: compressed directories (type 7; counted), FIG 0/13, conditional      */
+/* access, decoding of SPI/EPG content, directory extension parameters (their     */
+/* bytes are in d_directory at extension_offset), directory mode in X-PAD.        */
+/* ------------------------------------------------------------------------ */
+/*
+ * THE CONTRACT of one entry (a sub-channel and one packet address) in one call, every ambiguity decided.
+ *
+ * Frames, packets, groups.  The scan of a frame (steps 1-4) and steps a-g of the followed packets are those of
+ * dabgpu_packet_walk.h, word for word, with the same counters in the head of the result (a dabgpu_packet_result; of its
+ * embedded dabgpu_mot_result the fields groups_ok .. groups_repeated, segments_*, objects_completed, objects_mismatched,
+ * objects_too_large and object_bytes count here, the others stay 0).  A closed group goes through "Closing a group" of
+ * dabgpu_mot_slides_dev, word for word, up to the type test, which here is:
+ *   type 4: a body segment; type 6: a directory segment; type 3: groups_header_mode++; type 7:
+ *   groups_compressed_directory++; any other: groups_ignored_type++.
+ * Types 4 and 6 then pass the rest of "Closing a group" (segment flag .. z != end - o; groups_ok++).
+ *
+ * Placing a segment into the directory or into a body assembly follows "Assembly" of dabgpu_mot_slides_dev from
+ * "n >= ..." on, word for word: at most 256 segments for both kinds, at most directory_capacity bytes for the directory and
+ * object_capacity for a body.  A segment that is present is not overwritten, so a part may become full by a repetition:
+ * segment 0 placed as a non-last segment of S bytes and sent again as the last segment with z <= S bytes makes a part of one
+ * segment.  Its length is then what the last-segment group said, z, and its bytes are the first z of those placed first.
+ *
+ * Directory: one buffer.  For a type-6 segment of transport id t, first match wins:
+ *   t equals the current (complete, valid) directory's id -> groups_repeated++, dropped
+ *   there is a current directory, or no directory under assembly, or t differs from the id under assembly: the current
+ *     directory and its index are forgotten, the delivered marks are cleared, the directory assembly is emptied and takes
+ *     t.  Body assemblies are kept.
+ *   the assembly is marked too large -> dropped (until the id changes)
+ *   else the segment is placed.
+ * Directory check: when segments 0 .. last are present, behind the copy that places the last one, the directory of D bytes
+ * is checked.  First match wins:
+ *   1. D < 13, or the low 30 bits of bytes 0-3 (big-endian) != D         -> directories_mismatched++
+ *   2. byte 0 bit 7 (compression) set                                   -> directories_mismatched++
+ *   3. N = bytes 4, 5; period = bytes 6-8; segment size = 13 bits of bytes 9, 10; X = bytes 11, 12; o = 13 + X
+ *   4. o > D                                                             -> directories_mismatched++
+ *   5. N > 256                                                           -> directories_too_large++
+ *   6. for i < N: o + 9 > D -> mismatched.  tid = 2 bytes at o; the 7 bytes behind it are the header core: body_size(28)
+ *      header_size(13) content_type(6) subtype(9).  header_size < 7 or o + 2 + header_size > D -> mismatched.  Index entry
+ *      i = (tid, o + 2, header_size, body_size, type, subtype); o += 2 + header_size.
+ *   7. o != D                                                            -> directories_mismatched++
+ * On a failure the assembly is emptied and there is no current directory.  Else directories_completed++, it is current (the
+ * assembly is emptied, the bytes stay where they are), its D bytes go to d_directory (object_bytes += D), and every body
+ * assembly whose id is not in the index is emptied, objects_stale++ each.  A transport id listed twice means its lowest i.
+ * directory_id, directory_bytes, directory_objects, directory_period and directory_segment_size of the result describe the
+ * directory that is current at the end of the call (also one merely carried in from the state); without one directory_id
+ * is -1 and the others 0.
+ *
+ * Bodies.  A type-4 segment of id t:
+ *   1. with a current directory: t not listed -> groups_unlisted++, dropped; t listed and delivered -> groups_repeated++,
+ *      dropped.  Without one every body is taken (bodies may arrive before their directory).
+ *   2. it goes to the assembly that holds t, else to the lowest-numbered empty one, else the assembly whose stamp is oldest
+ *      (lowest number on a tie) is emptied, objects_evicted++, and takes t.  The stamp: a 32-bit count of placed body
+ *      segments is kept in the state; an assembly that takes an id is stamped with the count, and with the count after
+ *      each of its placed segments; age = (count - stamp) mod 2^32.
+ *   3. the assembly is marked too large -> dropped; else the segment is placed (object_bytes += z).
+ *
+ * Emission: one attempt behind every followed packet, after its orders (and the directory check's) have been executed.
+ * Without a current directory nothing.  Else the lowest-numbered assembly that is full (segments 0 .. last) and whose id the
+ * directory lists, entry e.  First match wins:
+ *   assembled bytes != e's body_size             -> objects_mismatched++, emptied, not marked delivered
+ *   32 + header_size + bytes > object_stride     -> objects_dropped++, marked delivered, emptied (object_stride as the entry
+ *                                                   gives it, also with max_objects == 0)
+ *   objects_written == max_objects               -> objects_deferred++, once per call per assembly; it stays as it is
+ *   else slot objects_written of THIS call receives a dabgpu_mot_carousel_object record -- transport_id, content_type,
+ *     content_subtype, header_bytes, body_bytes, frame = index of the logical frame in this call, slot = slot position of
+ *     the packet this attempt follows, directory_id --, then e's header bytes from the directory, then the body;
+ *     objects_written++, objects_completed++, object_bytes += header + body, marked delivered, emptied.
+ * A call without followed packets emits nothing.
+ *
+ * State and arena.  The state record has a fixed size: the packet state, the directory part, 32 body parts, the index of 256
+ * entries, the delivered bits, the counts.  All zero = a fresh start; a record this code did not write for exactly these
+ * directory_capacity, assemblies and object_capacity is one.  The arena: group buffer [0, 16384) | directory
+ * [16384, + directory_capacity rounded up to 16) | K bodies of object_capacity rounded up to 16 each.  It belongs to the
+ * state; a group, a directory or an object may span any number of calls, cut anywhere.
+ */
+typedef struct dabgpu_mot_carousel_object {  /* in front of every object in its slot */
+    int32_t transport_id;
+    int32_t content_type, content_subtype;  /* of the header core in the directory                                    */
+    int32_t header_bytes, body_bytes;       /* the MOT header follows the record, the body follows the header          */
+    int32_t frame, slot;                    /* where in this call the object was emitted                               */
+    int32_t directory_id;                   /* transport id of the directory that listed it                            */
+} dabgpu_mot_carousel_object;
+
+typedef struct dabgpu_packet_carousel_result {  /* counts of THIS call */
+    dabgpu_packet_result head;              /* the scan, the followed packets, and from the closed group on            */
+    int32_t groups_header_mode, groups_compressed_directory, groups_unlisted;
+    int32_t directories_completed, directories_mismatched, directories_too_large;
+    int32_t objects_stale, objects_evicted, objects_dropped, objects_deferred, objects_written;
+    int32_t directory_id;                   /* of the current directory at the end of the call, -1 = none              */
+    int32_t directory_bytes, directory_objects, directory_period, directory_segment_size;
+} dabgpu_packet_carousel_result;
+
+typedef struct dabgpu_packet_carousel_entry {   /* HOST array, one per (sub-channel, packet address); every pointer DEVICE memory */
+    const uint8_t *d_in;        /* as dabgpu_packet_entry, field by field, down to arena_bytes                    */
+    size_t in_stride;
+    int32_t bitrate_kbps;
+    int32_t address;
+    int32_t fec;
+    int32_t assemblies;         /* K = 1 .. 32 bodies under assembly at once                                     */
+    const void *d_state_in;     /* dabgpu_packet_carousel_state_bytes() on a 16-byte boundary; NULL or all zero = fresh start */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    void *d_arena;              /* 16-byte boundary, updated in place                                            */
+    size_t arena_bytes;         /* >= dabgpu_packet_carousel_arena_bytes(directory_capacity, assemblies, object_capacity) */
+    uint8_t *d_objects;         /* [max_objects] slots, 16-byte boundary; may be NULL with max_objects == 0        */
+    size_t object_stride;       /* a multiple of 16, >= 32                                                       */
+    int32_t max_objects;        /* max_objects * object_stride < 2^31                                            */
+    int32_t object_capacity;    /* bytes of a body, per assembly: 0 .. 256 * 8191                                */
+    uint8_t *d_directory;       /* [directory_capacity], 16-byte boundary: the bytes of every directory that becomes
+                                 * current in this call (the last one wins); else left as it was                 */
+    int32_t directory_capacity; /* 16 .. 2^20                                                                    */
+    int32_t reserved;
+    dabgpu_packet_carousel_result *d_result;
+} dabgpu_packet_carousel_entry;
+
+size_t dabgpu_packet_carousel_state_bytes(void);
+/* the smallest arena for these sizes (0 for sizes outside their ranges) */
+size_t dabgpu_packet_carousel_arena_bytes(int directory_capacity, int assemblies, int object_capacity);
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Everything is checked before anything is enqueued, so a refused call
+ * leaves every output as it was: DABGPU_ERR_ARG for what dabgpu_packet_slides_dev refuses for the same fields (d_objects,
+ * object_stride and max_objects for d_slides, slide_stride and max_slides), for directory_capacity, assemblies or
+ * object_capacity outside their ranges, arena_bytes below dabgpu_packet_carousel_arena_bytes(...), a NULL d_directory or one
+ * off its 16-byte boundary; DABGPU_ERR_CAPACITY as there. */
+int dabgpu_packet_carousel_dev(dabgpu_ctx *ctx, const dabgpu_packet_carousel_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_packet_carousel_host(const dabgpu_packet_carousel_entry *entries, int n_entries, int n_cifs);
+
+typedef struct dabgpu_mot_directory {       /* the fixed part of a MOT directory */
+    int32_t objects;            /* N                                                                             */
+    int32_t period;             /* CarouselPeriod, tenths of a second; 0 = undefined                             */
+    int32_t segment_size;       /* 0 = not fixed                                                                 */
+    int32_t extension_offset, extension_bytes;      /* the directory extension: 13, X                            */
+    int32_t directory_bytes;
+    int32_t reserved[2];
+} dabgpu_mot_directory;
+
+typedef struct dabgpu_mot_directory_object {
+    int32_t transport_id;
+    int32_t header_offset, header_bytes;    /* where its MOT header lies in the directory: for dabgpu_mot_header_parse  */
+    int32_t body_bytes, content_type, content_subtype;      /* of its header core                                       */
+    int32_t reserved[2];
+} dabgpu_mot_directory_object;
+
+/* host only: the directory check of the contract above (rules 1-7) over dir[n], as d_directory holds it.  info and
+ * out[0 .. *n_out) are written on DABGPU_OK alone: DABGPU_ERR_ARG for a NULL pointer (out may be NULL with max == 0), a
+ * negative n or max, or a directory the check refuses; DABGPU_ERR_CAPACITY for more objects than max. */
+int dabgpu_mot_directory_parse(const uint8_t *dir, int n, dabgpu_mot_directory *info, dabgpu_mot_directory_object *out, int max,
+                               int *n_out);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

@@ -164,7 +164,7 @@ DABGPU_MOT_FN bool part_ok(const Part &q, int p, int cap) {
     if (q.last && part_bytes(q) > cap) return false;
     return true;
 }
-DABGPU_MOT_FN void sanitize(State &st, int32_t body_capacity) {
+DABGPU_MOT_FN bool state_ok(const State &st, int32_t body_capacity) {
     bool ok = (st.cont_type == 0 || st.cont_type == 3 || st.cont_type == 13) && st.last_len <= 48 && st.group_open <= 1 &&
               st.armed <= 1 && st.next_length < GROUP_CAP && (st.armed || !st.next_length) && st.asm_valid <= 1 &&
               st.done_valid <= 1 && st.too_large <= 1 && st.core_have <= 0x7F && st.body_capacity == body_capacity &&
@@ -172,10 +172,119 @@ DABGPU_MOT_FN void sanitize(State &st, int32_t body_capacity) {
                              : (st.group_need == 0 && st.group_have == 0 && st.group_crc == 0));
     ok = ok && part_ok(st.part[0], 0, HEADER_CAP) && part_ok(st.part[1], 1, body_capacity);
     for (int w = 1; w < BODY_SEGMENTS / 32; w++) ok = ok && st.part[0].have[w] == 0;
-    if (ok) return;
+    return ok;
+}
+DABGPU_MOT_FN void sanitize(State &st, int32_t body_capacity) {
+    if (state_ok(st, body_capacity)) return;
     uint8_t *b = reinterpret_cast<uint8_t *>(&st);
     for (unsigned i = 0; i < sizeof(State); i++) b[i] = 0;
     st.body_capacity = body_capacity;
+}
+
+DABGPU_MOT_FN void push_order(Orders &ord, int32_t kind, int32_t src, uint32_t dst, int32_t len) {
+    if (len <= 0 && kind != ORDER_RECORD) return;
+    Order &o = ord.o[ord.n++];
+    o.kind = kind;
+    o.src = src;
+    o.dst = dst;
+    o.len = len;
+}
+
+/* "Assembly" from "n >= ..." on: segment n (last or not, z bytes) of a part of at most `segments` segments and `cap` bytes.
+ * -> the offset in the part where the caller places it (it has been noted present: segments_placed++), PLACE_REPEATED (it was
+ * there: segments_repeated++; the part may be full) or PLACE_DROPPED (a rule refused it and counted; the part is as it was,
+ * or too_large is set) */
+constexpr int PLACE_REPEATED = -1, PLACE_DROPPED = -2;
+DABGPU_MOT_FN int place(Part &q, uint8_t &too_large, Counters &c, int segments, int cap, int n, bool last, int z) {
+    if (n >= segments) {
+        c.objects_too_large++;
+        too_large = 1;
+        return PLACE_DROPPED;
+    }
+    int size = q.seg_size;
+    if (!last) {
+        if (z == 0 || (size && z != size) || (q.last && n >= q.last - 1)) {
+            c.groups_malformed++;
+            return PLACE_DROPPED;
+        }
+        size = z;
+    } else {
+        if (n > 0 && !size) {
+            c.segments_early_last++;
+            return PLACE_DROPPED;
+        }
+        if ((q.last && (q.last - 1 != n || q.last_len != z)) || (size && z > size) || top_segment(q) > n) {
+            c.groups_malformed++;
+            return PLACE_DROPPED;
+        }
+    }
+    const int at = n * size;                                           /* (n = 0 when the size is not known) */
+    if (at + z > cap) {
+        c.objects_too_large++;
+        too_large = 1;
+        return PLACE_DROPPED;
+    }
+    if (!last) {
+        q.seg_size = size;
+    } else {
+        q.last = n + 1;
+        q.last_len = z;
+    }
+    if ((q.have[n >> 5] >> (n & 31)) & 1) {
+        c.segments_repeated++;
+        return PLACE_REPEATED;
+    }
+    q.have[n >> 5] |= 1u << (n & 31);
+    c.segments_placed++;
+    return at;
+}
+
+/* "Closing a group" behind the type test: head = the first HEAD_BYTES of a group of `need` bytes whose CRC was good.
+ * -> true: groups_ok++, and the segment is g (z bytes at group offset o); false: a rule refused the group and counted */
+struct GroupSegment {
+    int32_t tid, n, last, o, z;
+};
+DABGPU_MOT_FN bool group_segment(const uint8_t *head, int need, Counters &c, GroupSegment &g) {
+    const uint8_t b0 = head[0];
+    const int end = need - 2;                                          /* end: where the CRC begins */
+    int o = 2;
+    if (b0 & 0x80) o += 2;                                             /* the extension field */
+    if (!(b0 & 0x20) || o + 2 > end) {
+        c.groups_malformed++;
+        return false;
+    }
+    g.last = head[o] >> 7;
+    g.n = ((head[o] & 0x7F) << 8) | head[o + 1];
+    o += 2;
+    if (!(b0 & 0x10)) {
+        c.groups_no_transport_id++;
+        return false;
+    }
+    if (o + 1 > end) {
+        c.groups_malformed++;
+        return false;
+    }
+    const int ua = head[o], li = ua & 0x0F;
+    o += 1;
+    if (!(ua & 0x10)) {
+        c.groups_no_transport_id++;
+        return false;
+    }
+    if (li < 2 || o + li + 2 > end) {
+        c.groups_malformed++;
+        return false;
+    }
+    g.tid = (head[o] << 8) | head[o + 1];
+    o += li;                                                           /* the end-user address behind the transport id */
+    g.z = ((head[o] & 0x1F) << 8) | head[o + 1];                       /* (o + 2 <= 2 + 2 + 2 + 1 + 15 + 2 = 24) */
+    o += 2;
+    if (g.z != end - o) {
+        c.groups_malformed++;
+        return false;
+    }
+    g.o = o;
+    c.groups_ok++;
+    return true;
 }
 
 struct Sink {
@@ -187,14 +296,7 @@ struct Sink {
 
     DABGPU_MOT_FN void drop_context() { dabgpu_mot::drop_context(st); }
 
-    DABGPU_MOT_FN void order(int32_t kind, int32_t src, uint32_t dst, int32_t len) {
-        if (len <= 0 && kind != ORDER_RECORD) return;
-        Order &o = ord.o[ord.n++];
-        o.kind = kind;
-        o.src = src;
-        o.dst = dst;
-        o.len = len;
-    }
+    DABGPU_MOT_FN void order(int32_t kind, int32_t src, uint32_t dst, int32_t len) { push_order(ord, kind, src, dst, len); }
 
     /* header and body are all there */
     DABGPU_MOT_FN void complete() {
@@ -247,47 +349,9 @@ struct Sink {
             st.asm_tid = uint16_t(tid);
         }
         if (st.too_large) return;
-        Part &q = st.part[p];
-        const int cap = part_cap(p, call.body_capacity);
-        if (n >= part_segments(p)) {
-            c.objects_too_large++;
-            st.too_large = 1;
-            return;
-        }
-        int size = q.seg_size;
-        if (!last) {
-            if (z == 0 || (size && z != size) || (q.last && n >= q.last - 1)) {
-                c.groups_malformed++;
-                return;
-            }
-            size = z;
-        } else {
-            if (n > 0 && !size) {
-                c.segments_early_last++;
-                return;
-            }
-            if ((q.last && (q.last - 1 != n || q.last_len != z)) || (size && z > size) || top_segment(q) > n) {
-                c.groups_malformed++;
-                return;
-            }
-        }
-        const int at = n * size;                                       /* (n = 0 when the size is not known) */
-        if (at + z > cap) {
-            c.objects_too_large++;
-            st.too_large = 1;
-            return;
-        }
-        if (!last) {
-            q.seg_size = size;
-        } else {
-            q.last = n + 1;
-            q.last_len = z;
-        }
-        if ((q.have[n >> 5] >> (n & 31)) & 1) {
-            c.segments_repeated++;
-        } else {
-            q.have[n >> 5] |= 1u << (n & 31);
-            c.segments_placed++;
+        const int at = place(st.part[p], st.too_large, c, part_segments(p), part_cap(p, call.body_capacity), n, last, z);
+        if (at == PLACE_DROPPED) return;
+        if (at >= 0) {
             order(ORDER_MOVE, o, uint32_t((p ? BODY_OFF : HEADER_OFF) + at), z);
             c.object_bytes += z;
             if (p == 0)                                                /* what of the header core lies in this segment */
@@ -309,48 +373,13 @@ struct Sink {
             c.groups_crc_failed++;
             return;
         }
-        const int type = b0 & 0x0F, end = need - 2;                    /* end: where the CRC begins */
+        const int type = b0 & 0x0F;
         if (type != 3 && type != 4) {
             c.groups_ignored_type++;
             return;
         }
-        int o = 2;
-        if (b0 & 0x80) o += 2;                                         /* the extension field */
-        if (!(b0 & 0x20) || o + 2 > end) {
-            c.groups_malformed++;
-            return;
-        }
-        const bool last = st.head[o] >> 7;
-        const int n = ((st.head[o] & 0x7F) << 8) | st.head[o + 1];
-        o += 2;
-        if (!(b0 & 0x10)) {
-            c.groups_no_transport_id++;
-            return;
-        }
-        if (o + 1 > end) {
-            c.groups_malformed++;
-            return;
-        }
-        const int ua = st.head[o], li = ua & 0x0F;
-        o += 1;
-        if (!(ua & 0x10)) {
-            c.groups_no_transport_id++;
-            return;
-        }
-        if (li < 2 || o + li + 2 > end) {
-            c.groups_malformed++;
-            return;
-        }
-        const int tid = (st.head[o] << 8) | st.head[o + 1];
-        o += li;                                                       /* the end-user address behind the transport id */
-        const int z = ((st.head[o] & 0x1F) << 8) | st.head[o + 1];      /* (o + 2 <= 2 + 2 + 2 + 1 + 15 + 2 = 24) */
-        o += 2;
-        if (z != end - o) {
-            c.groups_malformed++;
-            return;
-        }
-        c.groups_ok++;
-        segment(type == 4, tid, n, last, o, z);
+        GroupSegment g;
+        if (group_segment(st.head, need, c, g)) segment(type == 4, g.tid, g.n, g.last, g.o, g.z);
     }
 
     DABGPU_MOT_FN void subfield(int type, const uint8_t *xpad_end, int at, int len) {

@@ -93,14 +93,17 @@ DABGPU_MOT_FN void drop_open(State &st, Counters &c) {
     forget_group(st);
 }
 
-DABGPU_MOT_FN void sanitize(State &st, int32_t body_capacity) {
+/* the fields of this record, without the assembly's part */
+DABGPU_MOT_FN bool own_ok(const State &st, int32_t body_capacity) {
     const mot::State &m = st.mot;
     bool ok = st.seen <= 1 && st.prev <= 3 && st.open <= 1 && st.pad == 0 && st.have <= mot::GROUP_CAP &&
               (st.open || (st.have == 0 && st.crc == 0)) && (st.seen || (st.prev == 0 && !st.open));
     for (int i = 0; i < 8; i++) ok = ok && st.reserved[i] == 0;
-    ok = ok && m.cont_type == 0 && m.last_len == 0 && m.group_open == 0 && m.armed == 0 && m.next_length == 0 &&
-         m.body_capacity == body_capacity;
-    if (!ok) {
+    return ok && m.cont_type == 0 && m.last_len == 0 && m.group_open == 0 && m.armed == 0 && m.next_length == 0 &&
+           m.body_capacity == body_capacity;
+}
+DABGPU_MOT_FN void sanitize(State &st, int32_t body_capacity) {
+    if (!own_ok(st, body_capacity)) {
         uint8_t *p = reinterpret_cast<uint8_t *>(&st);
         for (unsigned i = 0; i < sizeof(State); i++) p[i] = 0;
         st.mot.body_capacity = body_capacity;
@@ -161,9 +164,11 @@ DABGPU_MOT_FN int packet_read_bytes(int L, int h2) {
     return udl > SLOT_BYTES * L - 5 ? 3 : 3 + udl;
 }
 
-/* One followed packet of L slots: steps a .. g.  pkt: its first packet_read_bytes() bytes.  Leaves this packet's orders in
- * `ord` (ORDER_PACKET's src counts from pkt; at most one of them, then what close_group() leaves). */
-DABGPU_MOT_FN void follow_packet(State &st, Counters &c, mot::Orders &ord, const mot::Call &call, const uint8_t *pkt, int L) {
+/* One followed packet of L slots: steps a .. f, and of g what comes before the group closes.  pkt: its first
+ * packet_read_bytes() bytes.  Leaves the packet's order in `ord` (ORDER_PACKET's src counts from pkt; at most one).  -> true
+ * when a group is ready to close: its length is in st.mot.group_need, its CRC register in st.mot.group_crc, its first bytes in
+ * st.mot.head, and the caller's sink closes it (its orders follow this one in `ord`). */
+DABGPU_MOT_FN bool take_packet(State &st, Counters &c, mot::Orders &ord, const uint8_t *pkt, int L) {
     ord.n = 0;
     const int h0 = pkt[0], h2 = pkt[2];
     const int ci = (h0 >> 4) & 3, first = (h0 >> 3) & 1, last = (h0 >> 2) & 1, cmd = h2 >> 7, udl = h2 & 0x7F;
@@ -176,11 +181,11 @@ DABGPU_MOT_FN void follow_packet(State &st, Counters &c, mot::Orders &ord, const
     if (udl > SLOT_BYTES * L - 5) {
         c.packets_malformed++;
         drop_open(st, c);
-        return;
+        return false;
     }
     if (cmd) {
         c.packets_command++;
-        return;
+        return false;
     }
     if (first) {
         drop_open(st, c);
@@ -188,13 +193,13 @@ DABGPU_MOT_FN void follow_packet(State &st, Counters &c, mot::Orders &ord, const
         c.groups_opened++;
     } else if (!st.open) {
         c.packets_orphan++;
-        return;
+        return false;
     }
     const int have = st.have;
     if (have + udl > mot::GROUP_CAP) {
         c.groups_too_long++;
         forget_group(st);
-        return;
+        return false;
     }
     uint32_t crc = st.crc ^ 0xFFFFu;
     for (int i = 0; i < udl; i++) {
@@ -202,21 +207,27 @@ DABGPU_MOT_FN void follow_packet(State &st, Counters &c, mot::Orders &ord, const
         crc = pad::crc16_step(crc, v);
         if (have + i < mot::HEAD_BYTES) st.mot.head[have + i] = v;
     }
-    mot::Sink k{st.mot, c.mot, ord, call, pkt};
-    k.order(ORDER_PACKET, 3, uint32_t(have), udl);
+    mot::push_order(ord, ORDER_PACKET, 3, uint32_t(have), udl);
     c.group_bytes += udl;
     st.have = uint16_t(have + udl);
     st.crc = uint16_t(crc ^ 0xFFFFu);
-    if (!last) return;
+    if (!last) return false;
     const int need = st.have;
     const uint16_t reg = st.crc;
     forget_group(st);
     if (need < 4) {
         c.mot.groups_malformed++;
-        return;
+        return false;
     }
     st.mot.group_need = uint16_t(need);
     st.mot.group_crc = reg;
+    return true;
+}
+
+/* One followed packet of L slots: steps a .. g, the closed group into the slideshow call's sink */
+DABGPU_MOT_FN void follow_packet(State &st, Counters &c, mot::Orders &ord, const mot::Call &call, const uint8_t *pkt, int L) {
+    if (!take_packet(st, c, ord, pkt, L)) return;
+    mot::Sink k{st.mot, c.mot, ord, call, pkt};
     k.close_group();
 }
 
@@ -228,21 +239,11 @@ inline void execute_order(const mot::Order &o, const mot::Orders &ord, const uin
         mot::execute(o, ord, pkt, arena, slides);
 }
 
-/* One logical frame (index k of the call) of one entry, on memory the caller can read and write */
-inline void walk_frame(State &st, Counters &c, const mot::Call &entry, const uint8_t *frame, int k, int S, int address, int fec,
-                       uint8_t *arena, uint8_t *slides) {
+/* The scan of one logical frame and its counters: followed(pos, L) takes every followed packet in position order */
+template <class Followed>
+inline void scan_frame(Counters &c, const uint8_t *frame, int S, int address, int fec, Followed followed) {
     FrameTally t = {};
-    mot::Orders ord;
-    mot::Call call = entry;
-    call.superframe = k;
-    resolve_chain(
-        S, address, t, [&](int pos) { return slot_verdict(frame, S, pos, fec); },
-        [&](int pos, int L) {
-            const uint8_t *pkt = frame + SLOT_BYTES * pos;
-            call.au = pos;
-            follow_packet(st, c, ord, call, pkt, L);
-            for (int i = 0; i < ord.n; i++) execute_order(ord.o[i], ord, pkt, arena, slides);
-        });
+    resolve_chain(S, address, t, [&](int pos) { return slot_verdict(frame, S, pos, fec); }, followed);
     c.cifs++;
     c.slots += S;
     c.packets_fec += t.fec;
@@ -250,6 +251,20 @@ inline void walk_frame(State &st, Counters &c, const mot::Call &entry, const uin
     c.packets_padding += t.padding;
     c.packets_other += t.other;
     c.packets_followed += t.followed;
+}
+
+/* One logical frame (index k of the call) of one entry, on memory the caller can read and write */
+inline void walk_frame(State &st, Counters &c, const mot::Call &entry, const uint8_t *frame, int k, int S, int address, int fec,
+                       uint8_t *arena, uint8_t *slides) {
+    mot::Orders ord;
+    mot::Call call = entry;
+    call.superframe = k;
+    scan_frame(c, frame, S, address, fec, [&](int pos, int L) {
+        const uint8_t *pkt = frame + SLOT_BYTES * pos;
+        call.au = pos;
+        follow_packet(st, c, ord, call, pkt, L);
+        for (int i = 0; i < ord.n; i++) execute_order(ord.o[i], ord, pkt, arena, slides);
+    });
 }
 
 /* One entry of a call: the twin of the two kernels */

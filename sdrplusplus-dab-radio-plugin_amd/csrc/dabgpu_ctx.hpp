@@ -75,6 +75,7 @@ enum StageSlot {
     STAGE_PACKET = 18,      // dabgpu_packet_slides_dev: the entry table and the scan records of the scan / walk launches
     STAGE_PACKET_FEC = 19,  // dabgpu_packet_fec_dev: the entry table, the marks, the accepted frames and their counts
     STAGE_PACKET_FEC_ERASURES = 20,  // dabgpu_packet_fec_erasures_dev: the same, and a word of suspect bits per window frame
+    STAGE_PACKET_CAROUSEL = 21,      // dabgpu_packet_carousel_dev: the entry table, what it adds per entry, the scan records
     STAGE_SLOTS
 };
 

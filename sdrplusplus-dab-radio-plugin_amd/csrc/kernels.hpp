@@ -468,12 +468,24 @@ struct alignas(16) PacketEntry {
 // A scan record: word 0 = followed packets n, word 1 = FEC | bad << 8 | padding << 16 | other << 24 (each <= 64), words 2, 3
 // zero, then n words pos | L << 8 | h0 << 16 | h2 << 24 (room for s)
 __host__ __device__ inline int packet_record_words(int s) { return 4 + s; }
-size_t packet_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs);
+// what dabgpu_packet_carousel_dev adds to an entry (its walk is the same kernel body with another sink; PacketEntry's slides,
+// slide_stride, max_slides and body_capacity are then d_objects, object_stride, max_objects and object_capacity, its arena
+// dabgpu_carousel::arena_bytes(...), its state dabgpu_carousel::State, its result dabgpu_carousel::Counters)
+struct alignas(16) CarouselExtra {
+    uint64_t directory;        // [directory_capacity]
+    int32_t directory_capacity;
+    int32_t assemblies;
+};
+// carousel: the table also holds a CarouselExtra per entry, between the entries and the records
+size_t packet_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs, bool carousel);
 // workgroups of the scan launch; 0 = nothing to scan
 uint64_t packet_scan_blocks(const PacketEntry *entries, int n_entries, int n_cifs);
 // `entries`: HOST array (its `records` are set here; copied to d_table on `stream` before the kernels); every pointer checked
-// by the caller
-hipError_t launch_packet_slides(PacketEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+// by the caller.  extras: NULL = the slides walk; else [n_entries] (HOST) and the carousel walk
+hipError_t launch_packet_walk(PacketEntry *entries, const CarouselExtra *extras, int n_entries, int n_cifs, void *d_table,
+                              size_t table_bytes, hipStream_t stream);
+// the carousel's walk launch alone, on the uploaded table (packet_carousel_kernels.hip; called by launch_packet_walk)
+hipError_t launch_carousel_walk(const PacketEntry *d_table, const CarouselExtra *d_extras, int n_entries, int n_cifs, hipStream_t stream);
 
 // ---- RS(204,188) correction of packet-mode FEC frames (packet_fec_kernels.hip) ------
 // dabgpu_packet_fec_dev and dabgpu_packet_fec_erasures_dev: one entry per sub-channel, uploaded as a table with its scratch

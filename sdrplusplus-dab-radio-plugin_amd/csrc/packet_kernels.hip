@@ -14,17 +14,14 @@
 // frames with followed packets by ballot, and per followed packet stages its header and useful bytes into LDS, lane 0 runs
 // steps a .. g and close_group() over LDS and leaves copy orders, and all 64 lanes execute them.  Work is proportional to the
 // followed packets.
-#include <hip/hip_runtime.h>
-
-#include "../../include/dabgpu_packet_walk.h"
-#include "kernels.hpp"
-#include "wave_copy.hpp"
+//
+// The walk's body is a template over its sink (packet_walk_body.hpp): SlidesWalk here is dabgpu_packet_slides_dev (header
+// mode: a closed group goes to the slideshow call's own code); dabgpu_packet_carousel_dev's sink and its instantiation are
+// packet_carousel_kernels.hip.  The scan is the same launch for both.
+#include "packet_walk_body.hpp"
 
 namespace dabk {
 namespace {
-
-namespace mot = dabgpu_mot;
-namespace pkt = dabgpu_packet;
 
 static_assert(sizeof(pkt::State) % 16 == 0 && sizeof(pkt::Counters) % 4 == 0, "copied by words");
 
@@ -84,105 +81,32 @@ __global__ __launch_bounds__(64) void packet_scan_kernel(const PacketEntry *tabl
     }
 }
 
-__global__ __launch_bounds__(64) void packet_walk_kernel(const PacketEntry *table, int n_cifs) {
-    __shared__ pkt::State st;
-    __shared__ pkt::Counters c;
-    __shared__ mot::Orders ord;
-    __shared__ __attribute__((aligned(16))) uint8_t bytes[pkt::MAX_PACKET_BYTES];
-    const PacketEntry e = table[blockIdx.x];
-    const int lane = threadIdx.x, S = e.s, rw = packet_record_words(S);
-    constexpr int STATE_WORDS = int(sizeof(pkt::State) / 16);
-    if (lane < STATE_WORDS)
-        reinterpret_cast<uint4 *>(&st)[lane] = e.state_in ? reinterpret_cast<const uint4 *>(e.state_in)[lane] : make_uint4(0u, 0u, 0u, 0u);
-    if (lane < int(sizeof(pkt::Counters) / 4)) reinterpret_cast<int32_t *>(&c)[lane] = 0;
-    __syncthreads();
-    const uint32_t *records = reinterpret_cast<const uint32_t *>(e.records);
-    // the scan's counters, a lane per frame
-    int followed = 0, fec = 0, bad = 0, padding = 0, other = 0;
-    for (int k = lane; k < n_cifs; k += 64) {
-        const uint32_t n = records[size_t(k) * rw], w = records[size_t(k) * rw + 1];
-        followed += int(n);
-        fec += int(w & 0xFF);
-        bad += int((w >> 8) & 0xFF);
-        padding += int((w >> 16) & 0xFF);
-        other += int(w >> 24);
-    }
-    for (int off = 1; off < 64; off <<= 1) {
-        followed += __shfl_xor(followed, off);
-        fec += __shfl_xor(fec, off);
-        bad += __shfl_xor(bad, off);
-        padding += __shfl_xor(padding, off);
-        other += __shfl_xor(other, off);
-    }
-    if (lane == 0) {
-        pkt::sanitize(st, e.body_capacity);
-        c.cifs = n_cifs;
-        c.slots = n_cifs * S;
-        c.slots_bad = bad;
-        c.packets_fec = fec;
-        c.packets_padding = padding;
-        c.packets_other = other;
-        c.packets_followed = followed;
-    }
-    uint8_t *arena = reinterpret_cast<uint8_t *>(e.arena), *slides = reinterpret_cast<uint8_t *>(e.slides);
+// header mode: dabgpu_packet_walk.h's follow_packet, nothing behind its orders
+struct SlidesWalk {
+    using State = pkt::State;
+    using Counters = pkt::Counters;
     mot::Call call;
-    call.body_capacity = e.body_capacity;
-    call.max_slides = e.max_slides;
-    call.slide_stride = e.slide_stride;
-    for (int k0 = 0; k0 < n_cifs; k0 += 64) {
-        const int mine = k0 + lane;
-        uint64_t busy = __ballot(mine < n_cifs && records[size_t(mine < n_cifs ? mine : 0) * rw] != 0);
-        while (busy) {
-            const int k = k0 + __ffsll(static_cast<unsigned long long>(busy)) - 1;
-            busy &= busy - 1;
-            const uint32_t *rec = records + size_t(k) * rw;
-            const int n = int(rec[0]) < S ? int(rec[0]) : S;
-            const uint8_t *frame = reinterpret_cast<const uint8_t *>(e.in) + size_t(k) * e.in_stride;
-            call.superframe = k;
-            for (int i = 0; i < n; i++) {
-                const uint32_t w = rec[4 + i];
-                int pos = int(w & 0xFF), L = int((w >> 8) & 0xFF);
-                // (what the scan wrote; held inside the frame whatever the record says)
-                L = L < 1 ? 1 : L > 4 ? 4 : L;
-                L = L > S ? S : L;
-                pos = pos + L > S ? S - L : pos;
-                const uint8_t *src = frame + pkt::SLOT_BYTES * pos;
-                __syncthreads();                                       // (the packet before has been read)
-                if (lane < 3) bytes[lane] = src[lane];
-                __syncthreads();
-                const int need = pkt::packet_read_bytes(L, bytes[2]);
-                for (int b = 3 + lane; b < need; b += 64) bytes[b] = src[b];
-                __syncthreads();
-                if (lane == 0) {
-                    call.au = pos;
-                    pkt::follow_packet(st, c, ord, call, bytes, L);
-                }
-                __syncthreads();
-                const int n_orders = ord.n;
-                for (int j = 0; j < n_orders; j++) {
-                    const mot::Order o = ord.o[j];
-                    if (o.kind == pkt::ORDER_PACKET) {
-                        for (int b = lane; b < o.len; b += 64) arena[o.dst + b] = bytes[o.src + b];
-                    } else if (o.kind == mot::ORDER_MOVE) {
-                        wave_copy(arena + o.dst, arena + o.src, o.len, lane);
-                    } else if (o.kind == mot::ORDER_SLIDE) {
-                        wave_copy(slides + o.dst, arena + o.src, o.len, lane);
-                    } else if (lane < mot::RECORD_BYTES / 4) {
-                        reinterpret_cast<int32_t *>(slides + o.dst)[lane] = ord.record[o.src][lane];
-                    }
-                    __syncthreads();                                   // the next order, or the next walk, may read this one's bytes
-                }
-            }
-        }
+    __device__ __forceinline__ SlidesWalk(const PacketEntry &e, const CarouselExtra *) {
+        call.body_capacity = e.body_capacity;
+        call.max_slides = e.max_slides;
+        call.slide_stride = e.slide_stride;
     }
-    __syncthreads();
-    if (lane < STATE_WORDS) reinterpret_cast<uint4 *>(e.state_out)[lane] = reinterpret_cast<const uint4 *>(&st)[lane];
-    if (lane < int(sizeof(pkt::Counters) / 4))
-        reinterpret_cast<int32_t *>(e.result)[lane] = reinterpret_cast<const int32_t *>(&c)[lane];
-}
+    __device__ __forceinline__ static uint8_t *directory(const CarouselExtra *) { return nullptr; }
+    __device__ __forceinline__ static pkt::Counters &head(Counters &c) { return c; }
+    __device__ __forceinline__ void sanitize(State &st) const { pkt::sanitize(st, call.body_capacity); }
+    __device__ __forceinline__ void follow(State &st, Counters &c, mot::Orders &ord, const uint8_t *bytes, int L, int k, int pos) {
+        call.superframe = k;
+        call.au = pos;
+        pkt::follow_packet(st, c, ord, call, bytes, L);
+    }
+    __device__ __forceinline__ void behind(State &, Counters &, mot::Orders &, const uint8_t *, uint8_t *, uint8_t *, uint8_t *, int) {}
+    __device__ __forceinline__ static void finish(const State &, Counters &) {}
+};
 
 size_t records_bytes(const PacketEntry &e, int n_cifs) { return size_t(n_cifs) * size_t(packet_record_words(e.s)) * 4; }
-size_t table_part(int n_entries) { return size_t(n_entries) * sizeof(PacketEntry); }
+size_t table_part(int n_entries, bool carousel) {
+    return size_t(n_entries) * (sizeof(PacketEntry) + (carousel ? sizeof(CarouselExtra) : 0));
+}
 unsigned blocks_per_entry(const PacketEntry *entries, int n_entries, int n_cifs) {
     unsigned most = 0;
     for (int i = 0; i < n_entries; i++) {
@@ -195,8 +119,8 @@ unsigned blocks_per_entry(const PacketEntry *entries, int n_entries, int n_cifs)
 
 }  // namespace
 
-size_t packet_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs) {
-    size_t bytes = table_part(n_entries);
+size_t packet_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs, bool carousel) {
+    size_t bytes = table_part(n_entries, carousel);
     for (int i = 0; i < n_entries; i++) bytes += records_bytes(entries[i], n_cifs);
     return bytes;
 }
@@ -205,7 +129,9 @@ uint64_t packet_scan_blocks(const PacketEntry *entries, int n_entries, int n_cif
     return uint64_t(n_entries) * blocks_per_entry(entries, n_entries, n_cifs);
 }
 
-hipError_t launch_packet_slides(PacketEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream) {
+hipError_t launch_packet_walk(PacketEntry *entries, const CarouselExtra *extras, int n_entries, int n_cifs, void *d_table,
+                              size_t table_bytes, hipStream_t stream) {
+    const bool carousel = extras != nullptr;
     if (n_entries <= 0) return hipSuccess;
     if (!d_table || n_cifs < 0 || n_cifs > pkt::MAX_N_CIFS || (reinterpret_cast<uintptr_t>(d_table) & 15)) return hipErrorInvalidValue;
     for (int i = 0; i < n_entries; i++) {
@@ -213,26 +139,37 @@ hipError_t launch_packet_slides(PacketEntry *entries, int n_entries, int n_cifs,
         if (e.s < 1 || e.s > pkt::MAX_SLOTS || e.in_stride < uint64_t(pkt::SLOT_BYTES) * e.s || e.max_slides < 0 || e.body_capacity < 0 ||
             e.body_capacity > mot::BODY_CAP_MAX || (e.max_slides > 0 && uint64_t(e.max_slides) * e.slide_stride >= (uint64_t(1) << 31)))
             return hipErrorInvalidValue;
+        if (carousel && (!extras[i].directory || !car::sizes_ok(extras[i].directory_capacity, extras[i].assemblies, e.body_capacity)))
+            return hipErrorInvalidValue;
     }
-    if (table_bytes < packet_table_bytes(entries, n_entries, n_cifs)) return hipErrorInvalidValue;
+    if (table_bytes < packet_table_bytes(entries, n_entries, n_cifs, carousel)) return hipErrorInvalidValue;
     const uint64_t blocks = packet_scan_blocks(entries, n_entries, n_cifs);
     if (blocks >= (uint64_t(1) << 31)) return hipErrorInvalidValue;
-    size_t at = table_part(n_entries);
+    size_t at = table_part(n_entries, carousel);
     for (int i = 0; i < n_entries; i++) {
         entries[i].records = uint64_t(reinterpret_cast<uintptr_t>(d_table)) + at;
         at += records_bytes(entries[i], n_cifs);
     }
     // (pageable memory: the copy has left `entries` when the call returns)
-    hipError_t err = hipMemcpyAsync(d_table, entries, table_part(n_entries), hipMemcpyHostToDevice, stream);
+    const size_t entries_bytes = size_t(n_entries) * sizeof(PacketEntry);
+    hipError_t err = hipMemcpyAsync(d_table, entries, entries_bytes, hipMemcpyHostToDevice, stream);
     if (err != hipSuccess) return err;
     const PacketEntry *table = static_cast<const PacketEntry *>(d_table);
+    const CarouselExtra *d_extras = nullptr;
+    if (carousel) {
+        void *at_extras = static_cast<uint8_t *>(d_table) + entries_bytes;
+        err = hipMemcpyAsync(at_extras, extras, size_t(n_entries) * sizeof(CarouselExtra), hipMemcpyHostToDevice, stream);
+        if (err != hipSuccess) return err;
+        d_extras = static_cast<const CarouselExtra *>(at_extras);
+    }
     if (blocks > 0) {
         hipLaunchKernelGGL(packet_scan_kernel, dim3(unsigned(blocks)), dim3(64), 0, stream, table, n_cifs,
                            blocks_per_entry(entries, n_entries, n_cifs));
         err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
-    hipLaunchKernelGGL(packet_walk_kernel, dim3(unsigned(n_entries)), dim3(64), 0, stream, table, n_cifs);
+    if (carousel) return launch_carousel_walk(table, d_extras, n_entries, n_cifs, stream);
+    hipLaunchKernelGGL(packet_walk_kernel<SlidesWalk>, dim3(unsigned(n_entries)), dim3(64), 0, stream, table, d_extras, n_cifs);
     return hipGetLastError();
 }
 

@@ -60,6 +60,8 @@ EXPORTS = [
     "dabgpu_fig_packet_components", "dabgpu_packet_state_bytes", "dabgpu_packet_slides_dev", "dabgpu_packet_slides_host",
     "dabgpu_packet_fec_state_bytes", "dabgpu_packet_fec_delay", "dabgpu_packet_fec_dev", "dabgpu_packet_fec_host",
     "dabgpu_packet_fec_erasures_dev", "dabgpu_packet_fec_erasures_host",
+    "dabgpu_packet_carousel_state_bytes", "dabgpu_packet_carousel_arena_bytes", "dabgpu_packet_carousel_dev",
+    "dabgpu_packet_carousel_host", "dabgpu_mot_directory_parse",
 ]
 
 ABI_VERSION = 6
@@ -182,6 +184,24 @@ PACKET_COUNTERS = ("cifs", "slots", "slots_bad", "packets_fec", "packets_padding
                    "groups_unfinished", "groups_too_long", "group_bytes")
 PACKET_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_COUNTERS] + [("reserved", np.int32), ("mot", MOT_RESULT_DTYPE)])
 assert PACKET_RESULT_DTYPE.itemsize == 192
+#: dabgpu_packet_carousel_result: what one entry of packet_carousel_dev / packet_carousel_host counted in one call; `head` is
+#: a PACKET_RESULT_DTYPE record (the scan, the followed packets, the closed groups)
+PACKET_CAROUSEL_COUNTERS = ("groups_header_mode", "groups_compressed_directory", "groups_unlisted", "directories_completed",
+                            "directories_mismatched", "directories_too_large", "objects_stale", "objects_evicted", "objects_dropped",
+                            "objects_deferred", "objects_written", "directory_id", "directory_bytes", "directory_objects",
+                            "directory_period", "directory_segment_size")
+PACKET_CAROUSEL_RESULT_DTYPE = np.dtype([("head", PACKET_RESULT_DTYPE)] + [(n, np.int32) for n in PACKET_CAROUSEL_COUNTERS])
+assert PACKET_CAROUSEL_RESULT_DTYPE.itemsize == 256
+#: dabgpu_mot_carousel_object: the record in front of every object in its slot (then header_bytes of MOT header, then the body)
+MOT_CAROUSEL_OBJECT_DTYPE = np.dtype([(n, np.int32) for n in (
+    "transport_id", "content_type", "content_subtype", "header_bytes", "body_bytes", "frame", "slot", "directory_id")])
+assert MOT_CAROUSEL_OBJECT_DTYPE.itemsize == 32
+#: dabgpu_mot_directory / dabgpu_mot_directory_object: what mot_directory_parse gives
+MOT_DIRECTORY_DTYPE = np.dtype([(n, np.int32) for n in ("objects", "period", "segment_size", "extension_offset", "extension_bytes",
+                                                        "directory_bytes")] + [("reserved", np.int32, (2,))])
+MOT_DIRECTORY_OBJECT_DTYPE = np.dtype([(n, np.int32) for n in ("transport_id", "header_offset", "header_bytes", "body_bytes",
+                                                               "content_type", "content_subtype")] + [("reserved", np.int32, (2,))])
+assert MOT_DIRECTORY_DTYPE.itemsize == 32 and MOT_DIRECTORY_OBJECT_DTYPE.itemsize == 32
 #: dabgpu_packet_component: one packet-mode service component (fig_packet_components)
 PACKET_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("scid", np.int32), ("subchid", np.int32), ("start_address", np.int32),
                                    ("packet_address", np.int32), ("dscty", np.int32), ("dg_flag", np.int32), ("fec_scheme", np.int32),
@@ -308,6 +328,17 @@ class PacketEntry(C.Structure):
                 ("fec", C.c_int32), ("reserved", C.c_int32), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
                 ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_slides", C.c_void_p), ("slide_stride", C.c_size_t),
                 ("max_slides", C.c_int32), ("reserved2", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class PacketCarouselEntry(C.Structure):
+    """dabgpu_packet_carousel_entry: one (sub-channel, packet address) of Context.packet_carousel_dev (device addresses) or
+    packet_carousel_host (host addresses): the fields of PacketEntry, the three sizes (directory_capacity, assemblies,
+    object_capacity), the object slots and the directory buffer."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("address", C.c_int32),
+                ("fec", C.c_int32), ("assemblies", C.c_int32), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
+                ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_objects", C.c_void_p), ("object_stride", C.c_size_t),
+                ("max_objects", C.c_int32), ("object_capacity", C.c_int32), ("d_directory", C.c_void_p),
+                ("directory_capacity", C.c_int32), ("reserved", C.c_int32), ("d_result", C.c_void_p)]
 
 
 class PacketFecEntry(C.Structure):
@@ -641,6 +672,13 @@ def load_library(path):
     L.dabgpu_packet_state_bytes.argtypes = []
     L.dabgpu_packet_slides_dev.argtypes = [vp, C.POINTER(PacketEntry), i, i, vp]
     L.dabgpu_packet_slides_host.argtypes = [C.POINTER(PacketEntry), i, i]
+    L.dabgpu_packet_carousel_state_bytes.restype = C.c_size_t
+    L.dabgpu_packet_carousel_state_bytes.argtypes = []
+    L.dabgpu_packet_carousel_arena_bytes.restype = C.c_size_t
+    L.dabgpu_packet_carousel_arena_bytes.argtypes = [i, i, i]
+    L.dabgpu_packet_carousel_dev.argtypes = [vp, C.POINTER(PacketCarouselEntry), i, i, vp]
+    L.dabgpu_packet_carousel_host.argtypes = [C.POINTER(PacketCarouselEntry), i, i]
+    L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
     L.dabgpu_packet_fec_state_bytes.argtypes = [i]
     L.dabgpu_packet_fec_delay.argtypes = [i]
@@ -878,6 +916,40 @@ def fig_packet_components(fib, crc_ok, max_out=64):
 def packet_state_bytes():
     """Bytes of one state record of Context.packet_slides_dev / packet_slides_host (all zero = a fresh start)."""
     return int(lib().dabgpu_packet_state_bytes())
+
+
+def packet_carousel_state_bytes():
+    """Bytes of one state record of Context.packet_carousel_dev / packet_carousel_host (all zero = a fresh start)."""
+    return int(lib().dabgpu_packet_carousel_state_bytes())
+
+
+def packet_carousel_arena_bytes(directory_capacity, assemblies, object_capacity):
+    """The smallest arena of Context.packet_carousel_dev / packet_carousel_host for these three sizes."""
+    n = int(lib().dabgpu_packet_carousel_arena_bytes(int(directory_capacity), int(assemblies), int(object_capacity)))
+    if n == 0:
+        raise ValueError("sizes outside their ranges: %r" % ((directory_capacity, assemblies, object_capacity),))
+    return n
+
+
+def packet_carousel_host(entries, n_cifs):
+    """Context.packet_carousel_dev on HOST memory (entries: PacketCarouselEntry with host addresses): the same checks and the
+    same code, include/dabgpu_mot_carousel.h; no context, no GPU."""
+    n = len(entries)
+    arr = (PacketCarouselEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_packet_carousel_host(arr, n, n_cifs), "dabgpu_packet_carousel_host")
+
+
+def mot_directory_parse(directory, max_objects=256):
+    """A MOT directory (the bytes d_directory holds) -> (info, objects): a MOT_DIRECTORY_DTYPE record and a
+    MOT_DIRECTORY_OBJECT_DTYPE array, one per listed object; directory[header_offset:][:header_bytes] is what
+    mot_header_parse takes.  Raises for a directory the check refuses (no GPU needed)."""
+    d = np.ascontiguousarray(np.frombuffer(bytes(directory), np.uint8))
+    info = np.zeros(1, MOT_DIRECTORY_DTYPE)
+    out = np.zeros(max(max_objects, 1), MOT_DIRECTORY_OBJECT_DTYPE)
+    n = C.c_int(0)
+    _check(lib().dabgpu_mot_directory_parse(_p(d) if d.size else _p(np.zeros(1, np.uint8)), d.size, _p(info), _p(out), max_objects,
+                                            C.byref(n)), "dabgpu_mot_directory_parse")
+    return info[0], out[:n.value].copy()
 
 
 def packet_fec_state_bytes(bitrate):
@@ -1559,6 +1631,16 @@ class Context:
         n = len(entries)
         arr = (PacketEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_packet_slides_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_slides_dev")
+
+    def packet_carousel_dev(self, entries, n_cifs, stream=None):
+        """Objects of packet-mode MOT directory carousels, behind decode_ensembles_dev (and either FEC call) on the same
+        stream: entries is a list of PacketCarouselEntry (device addresses), one per (sub-channel, packet address); n_cifs
+        logical frames each.  Per entry: d_objects slots of a MOT_CAROUSEL_OBJECT_DTYPE record, the MOT header from the
+        directory and the body; d_directory, the current directory's bytes; d_result, a PACKET_CAROUSEL_RESULT_DTYPE record.
+        No host synchronisation."""
+        n = len(entries)
+        arr = (PacketCarouselEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_packet_carousel_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_carousel_dev")
 
     def packet_fec_dev(self, entries, n_cifs, stream=None):
         """RS(204,188) correction of the FEC frames of packet-mode sub-channels, between decode_ensembles_dev and

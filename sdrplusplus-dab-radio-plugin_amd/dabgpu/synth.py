@@ -1107,6 +1107,38 @@ def mot_object_groups(tid, header, body, seg_size, header_seg_size=None, **kw):
     return out
 
 
+MOT_DG_DIRECTORY, MOT_DG_DIRECTORY_COMPRESSED = 6, 7
+
+
+def mot_directory(objects, period=0, segment_size=0, extension=b"", compressed=False, size=None, count=None):
+    """a MOT directory (EN 301 234 clause 7.2.2): CompressionFlag(1) Rfu(1) DirectorySize(30), NumberOfObjects(16),
+    CarouselPeriod(24, tenths of a second; 0 = undefined), Rfu(1) Rfa(2) SegmentSize(13; 0 = not fixed),
+    DirectoryExtensionLength(16), the directory extension, then per object its TransportId(16) and its MOT header (core and
+    extension).  objects: [(transport id, header bytes)]; size / count: what the fields say (default: the truth);
+    compressed sets the flag alone"""
+    extension = bytes(extension)
+    entries = b"".join(int(tid).to_bytes(2, "big") + bytes(header) for tid, header in objects)
+    total = 13 + len(extension) + len(entries) if size is None else size
+    n = len(objects) if count is None else count
+    assert total < 1 << 30 and n < 1 << 16 and period < 1 << 24 and segment_size < 1 << 13 and len(extension) < 1 << 16
+    return ((int(compressed) << 31) | total).to_bytes(4, "big") + n.to_bytes(2, "big") + period.to_bytes(3, "big") + \
+        segment_size.to_bytes(2, "big") + len(extension).to_bytes(2, "big") + extension + entries
+
+
+def mot_carousel_groups(dir_tid, objects, seg_size, dir_seg_size=None, period=0, extension=b"", **kw):
+    """one cycle of a MOT directory carousel (EN 301 234 clause 7.2): objects is [(transport id, header, body)].  ->
+    (the directory's data groups (type 6), [the body's data groups (type 4) of each object]); no header groups (type 3) are
+    sent in directory mode: the headers travel in the directory.  dir_seg_size: default the whole directory in one segment"""
+    directory = mot_directory([(tid, header) for tid, header, _ in objects], period, 0, extension)
+    segs = mot_segments(directory, dir_seg_size or len(directory))
+    dir_groups = [mot_group(MOT_DG_DIRECTORY, dir_tid, n, n == len(segs) - 1, seg, continuity=n, **kw) for n, seg in enumerate(segs)]
+    bodies = []
+    for tid, _, body in objects:
+        segs = mot_segments(body, seg_size)
+        bodies.append([mot_group(MOT_DG_BODY, tid, n, n == len(segs) - 1, seg, continuity=n, **kw) for n, seg in enumerate(segs)])
+    return dir_groups, bodies
+
+
 def dgli(length, good=True):
     """the data group length indicator: rfa(2) length(14), the CRC over these two bytes"""
     assert 0 <= length < 1 << 14

@@ -10,8 +10,15 @@
 // corrected by RS(204,188) and the walk sees the stream delayed by ceil(102 / S) frames (padding packets at first).  With FEC
 // scheme 1 that path is include/dabgpu_packet_fec_erasures.h's, the code dabgpu_packet_fec_erasures_dev runs: the packets whose
 // CRC fails are erasures, so eight lost packets per FEC frame are recovered instead of four.
+//
+// Beside that walk, on the same followed packets, runs the control of include/dabgpu_mot_carousel.h, the code
+// dabgpu_packet_carousel_dev runs: a component that speaks MOT directory mode (a directory in data groups of type 6, then
+// bodies alone) yields its current directory and its objects here (GetDirectory, GetCarouselObjects), while the header-mode
+// walk counts its groups as ignored; one that speaks header mode yields slides as before, and the carousel control counts
+// groups_header_mode.  The two share nothing but the frame's scan: the walk, its counters and its slides are untouched.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <vector>
 #include "basic_radio/basic_pad_reader.h"
@@ -19,6 +26,7 @@
 #include "dab/database/dab_database_entities.h"
 #include "dabgpu_packet_fec.h"
 #include "dabgpu_packet_fec_erasures.h"
+#include "dabgpu_mot_carousel.h"
 #include "dabgpu_packet_walk.h"
 #include "utility/span.h"
 
@@ -55,6 +63,7 @@ public:
         f->address = address;
         f->arena.resize(size_t(dabgpu_mot::arena_bytes(BODY_CAPACITY)));
         dabgpu_packet::sanitize(f->state, BODY_CAPACITY);
+        f->carousel = std::make_unique<Carousel>();
         m_followers.push_back(std::move(f));
         if (m_slot.empty()) m_slot.resize(m_call.slide_stride);
         return true;
@@ -63,6 +72,20 @@ public:
     int GetAddress(int i) const { return m_followers[size_t(i)]->address; }
     // counts since the address was added (slides_written: of the last packet alone)
     const dabgpu_packet::Counters &GetCounters(int i) const { return m_followers[size_t(i)]->counts; }
+    // directory mode: counts since the address was added (objects_written: of the last packet alone; directory_*: of the
+    // current directory), the current directory's bytes (empty: none; dabgpu_mot::parse_header reads a listed header) and
+    // the objects delivered so far
+    struct Carousel_Object {
+        dabgpu_carousel::DirectoryObject entry;                        // header_offset: not kept (the header is here)
+        int directory_id;
+        std::vector<uint8_t> header, body;
+    };
+    const dabgpu_carousel::Counters &GetCarouselCounters(int i) const { return m_followers[size_t(i)]->carousel->counts; }
+    tcb::span<const uint8_t> GetDirectory(int i) const {
+        const Carousel &k = *m_followers[size_t(i)]->carousel;
+        return {k.directory.data(), k.state.cur_valid ? size_t(k.state.cur_bytes) : size_t(0)};
+    }
+    const std::vector<Carousel_Object> &GetCarouselObjects(int i) const { return m_followers[size_t(i)]->carousel->objects; }
     int GetTotalFrames() const { return m_total_frames; }
     int GetTotalFramesIgnored() const { return m_total_ignored; }
 
@@ -92,14 +115,17 @@ public:
                     pkt::follow_packet(f->state, c, orders, call, packet, L);
                     for (int i = 0; i < orders.n; i++) pkt::execute_order(orders.o[i], orders, packet, f->arena.data(), m_slot.data());
                     if (c.mot.slides_written) Basic_Add_Slide(m_slideshows, m_slot.data());
+                    f->carousel->Follow(packet, L, m_total_frames, pos);
                 });
-            c.cifs++;
-            c.slots += S;
-            c.packets_fec += t.fec;
-            c.slots_bad += t.bad;
-            c.packets_padding += t.padding;
-            c.packets_other += t.other;
-            c.packets_followed += t.followed;
+            for (pkt::Counters *k : {&c, &f->carousel->counts.head}) {   // (one scan: the same tally for both)
+                k->cifs++;
+                k->slots += S;
+                k->packets_fec += t.fec;
+                k->slots_bad += t.bad;
+                k->packets_padding += t.padding;
+                k->packets_other += t.other;
+                k->packets_followed += t.followed;
+            }
         }
         m_total_frames++;
     }
@@ -133,11 +159,52 @@ private:
     }
 
     static constexpr int BODY_CAPACITY = 256 * 1024;
+    // the directory-mode control of one address: a state record, an arena, the directory buffer and one slot of its own
+    struct Carousel {
+        static constexpr int DIRECTORY_CAPACITY = 64 * 1024, ASSEMBLIES = 8;
+        dabgpu_carousel::State state{};    // all zero: a fresh start
+        dabgpu_carousel::Counters counts{};
+        dabgpu_carousel::Call call{};
+        std::vector<uint8_t> arena, directory, slot;
+        std::vector<Carousel_Object> objects;
+        Carousel() {
+            namespace car = dabgpu_carousel;
+            call.directory_capacity = DIRECTORY_CAPACITY;
+            call.assemblies = ASSEMBLIES;
+            call.object_capacity = BODY_CAPACITY;
+            call.max_objects = 1;                                      // (one emission attempt a packet: one object)
+            call.object_stride = uint32_t(dabgpu_mot::RECORD_BYTES + dabgpu_mot::SEGMENT_MAX + BODY_CAPACITY);
+            arena.resize(size_t(car::arena_bytes(DIRECTORY_CAPACITY, ASSEMBLIES, BODY_CAPACITY)));
+            directory.resize(DIRECTORY_CAPACITY);
+            slot.resize(call.object_stride);
+            car::sanitize(state, DIRECTORY_CAPACITY, ASSEMBLIES, BODY_CAPACITY);
+        }
+        void Follow(const uint8_t *packet, int L, int frame, int pos) {
+            namespace car = dabgpu_carousel;
+            call.frame = frame;
+            call.slot = pos;
+            call.deferred = 0;
+            counts.objects_written = 0;                                // the slot is this packet's
+            car::walk_packet(state, counts, call, packet, L, arena.data(), directory.data(), slot.data());
+            car::finish(state, counts);
+            if (!counts.objects_written) return;
+            int32_t rec[8];
+            std::memcpy(rec, slot.data(), sizeof rec);
+            Carousel_Object o;
+            o.entry = car::DirectoryObject{rec[0], 0, rec[3], rec[4], rec[1], rec[2], {0, 0}};
+            o.directory_id = rec[7];
+            const uint8_t *h = slot.data() + dabgpu_mot::RECORD_BYTES;
+            o.header.assign(h, h + rec[3]);
+            o.body.assign(h + rec[3], h + rec[3] + rec[4]);
+            objects.push_back(std::move(o));
+        }
+    };
     struct Follower {
         int address = 0;
         dabgpu_packet::State state{};      // all zero: a fresh start
         dabgpu_packet::Counters counts{};
         std::vector<uint8_t> arena;
+        std::unique_ptr<Carousel> carousel;
     };
     Subchannel m_subchannel;
     int m_fec;
