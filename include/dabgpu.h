@@ -1853,10 +1853,11 @@ int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entrie
 /* Reed-Solomon RS(204,188) correction of FEC frames is a call of its own in      */
 /* front of this one, dabgpu_packet_fec_dev (below): this call recognises and     */
 /* counts FEC packets and reads what that one wrote, unchanged.  MOT directory    */
-/* mode (data group type 6) is dabgpu_packet_carousel_dev (below).  Not done:     */
-/* compressed directories (type 7); non-MOT packet data                          */
-/* (TPEG, SPI, Journaline); conditional access; FIG 0/13 user application        */
-/* signalling (the caller chooses DSCTy 60 / DG 0 from the component list).      */
+/* mode (data group type 6) is dabgpu_packet_carousel_dev (below); the data      */
+/* groups of non-MOT components (TPEG, SPI, Journaline) and FIG 0/13 user        */
+/* application signalling are dabgpu_packet_groups_dev and                       */
+/* dabgpu_fig_user_applications (below).  Not done: compressed directories       */
+/* (type 7); conditional access.                                                 */
 /*                                                                            */
 /* THE CONTRACT of one entry in one call (EN 300 401 clauses 5.3.2, 5.3.3; every  */
 /* ambiguity decided).                                                           */
@@ -2137,9 +2138,10 @@ int dabgpu_packet_fec_erasures_host(const dabgpu_packet_fec_erasure_entry *entri
 /* either call tell which mode a component speaks: groups_header_mode here,       */
 /* groups_ignored_type there.                                                     */
 /*                                                                              */
-/* Not done: compressed directories (type 7; counted), FIG 0/13, conditional      */
-/* access, decoding of SPI/EPG content, directory extension parameters (their     */
-/* bytes are in d_directory at extension_offset), directory mode in X-PAD.        */
+/* Not done: compressed directories (type 7; counted), conditional access,        */
+/* decoding of SPI/EPG content, directory extension parameters (their bytes are   */
+/* in d_directory at extension_offset), directory mode in X-PAD.  (FIG 0/13:      */
+/* dabgpu_fig_user_applications, below.)                                          */
 /* ------------------------------------------------------------------------ */
 /*
  * THE CONTRACT of one entry (a sub-channel and one packet address) in one call, every ambiguity decided.
@@ -2285,6 +2287,166 @@ typedef struct dabgpu_mot_directory_object {
  * negative n or max, or a directory the check refuses; DABGPU_ERR_CAPACITY for more objects than max. */
 int dabgpu_mot_directory_parse(const uint8_t *dir, int n, dabgpu_mot_directory *info, dabgpu_mot_directory_object *out, int max,
                                int *n_out);
+
+/* ------------------------------------------------------------------------ */
+/* Data groups of ANY packet-mode service component of a batch, on the device:  */
+/* TPEG, SPI/EPG, Journaline, filecasting, transparent data channels.  A third   */
+/* pair of calls beside dabgpu_packet_slides_* and dabgpu_packet_carousel_*: one */
+/* entry per (sub-channel, packet address), behind dabgpu_decode_ensembles_dev   */
+/* on the same stream (and behind either FEC call where there is one), on the    */
+/* same logical frames.  Mode 0 gives every MSC data  */
+/* group (EN 300 401 clause 5.3.3.1) with its header fields read, its CRC         */
+/* checked and repeats recognised; mode 1 (the component's DG flag is 1) gives    */
+/* the packets' useful bytes as one stream.  Two launches: the scan of            */
+/* dabgpu_packet_slides_dev, unchanged, and one workgroup per entry with a lane   */
+/* per followed packet (segmented scans, no serial walk).  The contract and the   */
+/* code are include/dabgpu_data_groups.h.  dabgpu_fig_user_applications (host)    */
+/* says from FIG 0/13 which application a component's data is for.                */
+/*                                                                              */
+/* Not done: interpreting the content of any application; conditional access.    */
+/* ------------------------------------------------------------------------ */
+/*
+ * THE CONTRACT of one entry (a sub-channel and one packet address) in one call, every ambiguity decided.
+ *
+ * The scan of a frame (rules 1-4) and steps a-e of "Followed packets" are dabgpu_packet_walk.h's, word for word, with its
+ * counters: cifs, slots, slots_bad, packets_*, continuity_breaks, groups_opened, groups_unfinished, groups_too_long,
+ * group_bytes.  The cap on a group is 16384 bytes.
+ *
+ * MODE 0 (the component's DG flag is 0: data groups are used).
+ *   f. the udl bytes from offset 3 are appended; group_bytes += udl.
+ *   g. last: the group closes with n = have bytes, groups_closed++, and no group is open.  First match wins:
+ *        n < 4                                              -> groups_malformed++   (as the slides call decides)
+ *        b0 = byte 0: extension flag 0x80, CRC flag 0x40, segment flag 0x20, user access flag 0x10, type = b0 & 0x0F;
+ *        byte 1: continuity = high nibble, repetition = low nibble.
+ *        CRC flag set and the CRC (the packet CRC's polynomial, start and complement) over bytes 0 .. n - 3 is not bytes
+ *          n - 2, n - 1 (big-endian)                        -> groups_crc_failed++  (the CRC is judged before the headers,
+ *                                                              as in "Closing a group" of the slideshow contract)
+ *        end = n - 2 with the CRC flag, else n; o = 2
+ *        extension flag: o + 2 > end -> groups_malformed++; extension = the 16 bits at o; o += 2
+ *        segment flag:   o + 2 > end -> groups_malformed++; segment = the 16 bits at o (last(1) number(15)); o += 2
+ *        user access flag: o + 1 > end -> groups_malformed++; ua = byte at o; o += 1; li = ua & 0x0F;
+ *          transport-id flag (ua & 0x10) set and li < 2 -> groups_malformed++; o + li > end -> groups_malformed++;
+ *          transport id = the 16 bits at o when its flag is set; the end user address is the other li - 2 (or li) bytes;
+ *          o += li
+ *        the group is ACCEPTED: data field = bytes o .. end - 1 (it may be empty).  CRC flag clear: groups_no_crc++.
+ *
+ * Repeats.  An accepted group is a repeat when the latest earlier accepted group of the same type on this entry (this call
+ * or an earlier one, emitted or not) has the same continuity index: groups_repeated++ (whatever keep_repeats says).  With
+ * keep_repeats == 0 it is not emitted; otherwise it is, with DG_REPEAT in its flags.
+ *
+ * Emission.  The groups to emit (accepted, and not a repeat unless repeats are kept) are numbered i = 0, 1, ... in closing
+ * order within THIS call; offset_i = the sum over j < i of length_j rounded up to 16 (held at 2^31 once it reaches it).
+ * Group i is emitted iff i < max_groups and offset_i + length_i <= bytes_capacity: groups_emitted++, bytes_emitted +=
+ * length_i, its n bytes at d_bytes + offset_i and record i at d_groups + i; else groups_no_room++.  The emitted groups are
+ * therefore a prefix of the groups to emit.  Records beyond the emitted ones and bytes outside the emitted groups are not
+ * written.
+ *
+ * MODE 1 (DG flag 1: no data groups).  Steps a, b, c as above, except that nothing is ever open: a break leaves a record
+ * (below) instead of dropping.  A packet that passes them contributes its udl bytes to one stream; first and last are not
+ * looked at.  at = the sum of udl of the contributing packets before it in THIS call.  It is emitted (its bytes at d_bytes +
+ * at, bytes_emitted += udl) iff at + udl <= bytes_capacity; else bytes_no_room += udl.  Every continuity break is numbered
+ * i = 0, 1, ... within this call; with i < max_groups record i is {offset = at of the packet that broke, length 0, cif, slot,
+ * flags = DG_BREAK, every other field 0} and groups_emitted++, else groups_no_room++.  The other groups_* counters stay 0,
+ * group_bytes too.
+ * An open group in the state record is forgotten without a count.
+ *
+ * The state record: seen, prev, open, have, the CRC register over the open group (not complemented), the last continuity
+ * index per type (16 bytes and a mask), and the open group's bytes (16384; zero behind `have`).  All zero = a fresh start; a
+ * record this code did not write is a fresh start, and no value in it makes a call read or write outside the record.  A
+ * stream may be cut into calls anywhere; a group may span any number of calls.
+ */
+#define DABGPU_DG_EXTENSION    1
+#define DABGPU_DG_CRC          2    /* a CRC was present, and it was good */
+#define DABGPU_DG_SEGMENT      4
+#define DABGPU_DG_USER_ACCESS  8
+#define DABGPU_DG_TRANSPORT_ID 16
+#define DABGPU_DG_REPEAT       32
+#define DABGPU_DG_BREAK        64   /* mode 1: a continuity break lies at `offset` of the stream */
+
+typedef struct dabgpu_data_group {          /* 32 bytes */
+    int32_t offset, length;                 /* where the whole group lies in d_bytes, and its bytes                     */
+    int32_t cif;                            /* index in this call of the frame of the closing packet                    */
+    uint8_t slot;                           /* slot position of the closing packet                                      */
+    uint8_t type, continuity, repetition;   /* from bytes 0 and 1                                                       */
+    uint16_t flags;                         /* DABGPU_DG_*; bits 8-11: the bytes of the end user address                */
+    uint16_t extension;                     /* the extension field, 0 without one                                       */
+    int32_t segment;                        /* -1, or the 16-bit segment field: last(1) number(15)                      */
+    int32_t transport_id;                   /* -1, or the id                                                            */
+    uint16_t data_offset, data_length;      /* the data field inside the group                                          */
+} dabgpu_data_group;
+
+typedef struct dabgpu_packet_groups_result {    /* counts of THIS call */
+    int32_t cifs, slots, slots_bad;
+    int32_t packets_fec, packets_padding, packets_other, packets_followed;
+    int32_t continuity_breaks, packets_malformed, packets_command, packets_orphan;
+    int32_t groups_opened, groups_unfinished, groups_too_long;
+    int32_t group_bytes;
+    int32_t groups_closed, groups_malformed, groups_crc_failed, groups_no_crc;
+    int32_t groups_repeated, groups_emitted, groups_no_room;
+    int32_t bytes_emitted, bytes_no_room;
+    int32_t reserved[4];
+} dabgpu_packet_groups_result;
+
+typedef struct dabgpu_packet_groups_entry {    /* HOST array, one per (sub-channel, packet address); every pointer DEVICE memory */
+    const uint8_t *d_in;        /* as dabgpu_packet_entry, field by field, down to fec                           */
+    size_t in_stride;
+    int32_t bitrate_kbps;
+    int32_t address;
+    int32_t fec;
+    int32_t mode;               /* 0: data groups; 1: no data groups, the useful bytes as a stream               */
+    int32_t keep_repeats;       /* mode 0: non-zero = a repeat is emitted, with DABGPU_DG_REPEAT                  */
+    int32_t reserved;
+    const void *d_state_in;     /* dabgpu_packet_groups_state_bytes() on a 16-byte boundary; NULL or all zero = fresh start */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    uint8_t *d_bytes;           /* [bytes_capacity], 16-byte boundary; may be NULL with bytes_capacity == 0       */
+    dabgpu_data_group *d_groups;/* [max_groups], 4-byte boundary; may be NULL with max_groups == 0                */
+    int32_t bytes_capacity;     /* 0 .. 2^31 - 1                                                                 */
+    int32_t max_groups;         /* >= 0                                                                          */
+    dabgpu_packet_groups_result *d_result;
+} dabgpu_packet_groups_entry;
+
+size_t dabgpu_packet_groups_state_bytes(void);
+/* the followed packets the kernel takes at a time (its seams lie at multiples of this; for tests and sizing only) */
+int dabgpu_packet_groups_chunk(void);
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Everything is checked before anything is enqueued, so a refused call
+ * leaves every output as it was: DABGPU_ERR_ARG for what dabgpu_packet_slides_dev refuses for d_in, in_stride, bitrate_kbps,
+ * address, n_cifs, the two state records and d_result; for a mode other than 0 or 1, a negative bytes_capacity or max_groups,
+ * a NULL d_bytes with bytes_capacity > 0 or one off its 16-byte boundary, a NULL d_groups with max_groups > 0 or one off its
+ * 4-byte boundary.  DABGPU_ERR_CAPACITY as there, and for n_cifs * 3 * bitrate_kbps >= 2^31 (the stream offsets of a call are
+ * int32). */
+int dabgpu_packet_groups_dev(dabgpu_ctx *ctx, const dabgpu_packet_groups_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the same code: no context, no GPU */
+int dabgpu_packet_groups_host(const dabgpu_packet_groups_entry *entries, int n_entries, int n_cifs);
+
+typedef struct dabgpu_user_application {
+    uint32_t sid; int32_t scids;            /* FIG 0/13: SId, SCIdS                                          */
+    int32_t ua_type;                        /* user application type, 11 bits.  Registered in TS 101 756:    */
+                                            /*   0x002 MOT slideshow                                         */
+                                            /*   0x004 TPEG                                                  */
+                                            /*   0x007 SPI (programme guide, logos)                          */
+                                            /*   0x00D filecasting                                           */
+                                            /*   0x44A Journaline                                            */
+    int32_t tmid_packet;                    /* 1: FIG 0/8 joins it to a packet-mode component (an SCId); 0: to a sub-channel, or
+                                             * the same FIBs carry no FIG 0/8 for it                         */
+    int32_t subchid, scid, packet_address;  /* -1 where the same FIBs do not say                             */
+    int32_t data_length;                    /* 0 .. 23 bytes of user application data                        */
+    uint8_t data[23];
+    uint8_t reserved;
+} dabgpu_user_application;
+
+/* host only, the sister of dabgpu_fig_packet_components: the user applications (FIG 0/13) of CRC-clean FIBs of ONE ensemble,
+ * current configuration of this ensemble (C/N = 0, OE = 0).  The FIG is a sequence of entries: SId (16 bits with P/D = 0, 32
+ * with P/D = 1), SCIdS(4) number of user applications(4), and per application type(11) data length(5) and that many bytes
+ * (an entry or an application cut off by the FIG's end ends the FIG).  Each (SId, SCIdS, type) is reported once, its first.
+ * It is joined through FIG 0/8 (SId, Ext(1) Rfa(3) SCIdS(4), then L/S(1): 0 = MSC/FIC flag(1) SubChId(6), 1 = Rfa(3) SCId(12);
+ * an Rfa byte behind it with Ext) to its component -- the first FIG 0/8 of that (SId, SCIdS), wherever it lies among the
+ * FIBs; a short-form entry whose MSC/FIC flag is 1 names a FIDC, not a sub-channel, and is passed over as if absent -- and
+ * for a packet-mode component on through FIG 0/3 to its subchid and packet_address.  Sorted by (sid, scids, ua_type).  *n
+ * receives the count; DABGPU_ERR_CAPACITY if max is too small (nothing written).  The types are not interpreted.  At most
+ * 256 applications, 256 FIG 0/8 entries and 256 FIG 0/3 entries are kept, the first ones; what lies beyond is passed over. */
+int dabgpu_fig_user_applications(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_user_application *out, int max,
+                                 int *n);
 
 /* ------------------------------------------------------------------------ */
 /* A9 on its own: batched punctured soft Viterbi (K=7, rate 1/4).             */

@@ -487,6 +487,33 @@ hipError_t launch_packet_walk(PacketEntry *entries, const CarouselExtra *extras,
 // the carousel's walk launch alone, on the uploaded table (packet_carousel_kernels.hip; called by launch_packet_walk)
 hipError_t launch_carousel_walk(const PacketEntry *d_table, const CarouselExtra *d_extras, int n_entries, int n_cifs, hipStream_t stream);
 
+// ---- data groups of any packet-mode component (packet_groups_kernels.hip) -----------
+// dabgpu_packet_groups_dev: the scan launch above as it stands (on a PacketEntry table of which it reads in, in_stride, s,
+// address, fec and records), then one workgroup of PACKET_GROUPS_CHUNK lanes per entry: a lane per followed packet, the
+// steps of include/dabgpu_data_groups.h as segmented scans, chunk by chunk with a carry.
+constexpr int PACKET_GROUPS_CHUNK = 256;   // followed packets a workgroup takes at a time
+struct alignas(16) PacketGroupsEntry {
+    uint64_t state_in;         // dabgpu_groups::State or 0
+    uint64_t state_out;
+    uint64_t bytes;            // [bytes_capacity]
+    uint64_t groups;           // [max_groups] dabgpu_groups::Record
+    uint64_t result;           // dabgpu_groups::Counters
+    int32_t bytes_capacity;
+    int32_t max_groups;
+    int32_t mode;
+    int32_t keep_repeats;
+    int32_t reserved[2];
+};
+static_assert(sizeof(PacketGroupsEntry) == 64, "an entry of the table in the stage area");
+// the scan launch alone on an uploaded table whose `records` are set: what launch_packet_walk enqueues in front of its walk
+// (`entries`: the HOST copy, for the grid)
+hipError_t launch_packet_scan(const PacketEntry *d_table, const PacketEntry *entries, int n_entries, int n_cifs, hipStream_t stream);
+// the table: [n_entries] PacketEntry, [n_entries] PacketGroupsEntry, then the scan records
+size_t packet_groups_table_bytes(const PacketEntry *entries, int n_entries, int n_cifs);
+// `scan`, `entries`: HOST arrays (scan[i].records is set here; both are copied to d_table on `stream` before the two launches)
+hipError_t launch_packet_groups(PacketEntry *scan, const PacketGroupsEntry *entries, int n_entries, int n_cifs, void *d_table,
+                                size_t table_bytes, hipStream_t stream);
+
 // ---- RS(204,188) correction of packet-mode FEC frames (packet_fec_kernels.hip) ------
 // dabgpu_packet_fec_dev and dabgpu_packet_fec_erasures_dev: one entry per sub-channel, uploaded as a table with its scratch
 // records behind it.  Four launches: move (the carried and the new frames to the output and the new state record; a mark per

@@ -129,6 +129,15 @@ uint64_t packet_scan_blocks(const PacketEntry *entries, int n_entries, int n_cif
     return uint64_t(n_entries) * blocks_per_entry(entries, n_entries, n_cifs);
 }
 
+hipError_t launch_packet_scan(const PacketEntry *d_table, const PacketEntry *entries, int n_entries, int n_cifs, hipStream_t stream) {
+    const uint64_t blocks = packet_scan_blocks(entries, n_entries, n_cifs);
+    if (blocks >= (uint64_t(1) << 31)) return hipErrorInvalidValue;
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(packet_scan_kernel, dim3(unsigned(blocks)), dim3(64), 0, stream, d_table, n_cifs,
+                       blocks_per_entry(entries, n_entries, n_cifs));
+    return hipGetLastError();
+}
+
 hipError_t launch_packet_walk(PacketEntry *entries, const CarouselExtra *extras, int n_entries, int n_cifs, void *d_table,
                               size_t table_bytes, hipStream_t stream) {
     const bool carousel = extras != nullptr;

@@ -62,6 +62,8 @@ EXPORTS = [
     "dabgpu_packet_fec_erasures_dev", "dabgpu_packet_fec_erasures_host",
     "dabgpu_packet_carousel_state_bytes", "dabgpu_packet_carousel_arena_bytes", "dabgpu_packet_carousel_dev",
     "dabgpu_packet_carousel_host", "dabgpu_mot_directory_parse",
+    "dabgpu_packet_groups_state_bytes", "dabgpu_packet_groups_chunk", "dabgpu_packet_groups_dev", "dabgpu_packet_groups_host",
+    "dabgpu_fig_user_applications",
 ]
 
 ABI_VERSION = 6
@@ -202,6 +204,24 @@ MOT_DIRECTORY_DTYPE = np.dtype([(n, np.int32) for n in ("objects", "period", "se
 MOT_DIRECTORY_OBJECT_DTYPE = np.dtype([(n, np.int32) for n in ("transport_id", "header_offset", "header_bytes", "body_bytes",
                                                                "content_type", "content_subtype")] + [("reserved", np.int32, (2,))])
 assert MOT_DIRECTORY_DTYPE.itemsize == 32 and MOT_DIRECTORY_OBJECT_DTYPE.itemsize == 32
+#: dabgpu_data_group: one emitted MSC data group of packet_groups_dev / packet_groups_host (mode 1: one continuity break)
+DATA_GROUP_DTYPE = np.dtype([("offset", np.int32), ("length", np.int32), ("cif", np.int32), ("slot", np.uint8), ("type", np.uint8),
+                             ("continuity", np.uint8), ("repetition", np.uint8), ("flags", np.uint16), ("extension", np.uint16),
+                             ("segment", np.int32), ("transport_id", np.int32), ("data_offset", np.uint16), ("data_length", np.uint16)])
+assert DATA_GROUP_DTYPE.itemsize == 32
+DG_EXTENSION, DG_CRC, DG_SEGMENT, DG_USER_ACCESS, DG_TRANSPORT_ID, DG_REPEAT, DG_BREAK = 1, 2, 4, 8, 16, 32, 64
+#: dabgpu_packet_groups_result: what one entry of packet_groups_dev / packet_groups_host counted in one call
+PACKET_GROUPS_COUNTERS = PACKET_COUNTERS + ("groups_closed", "groups_malformed", "groups_crc_failed", "groups_no_crc", "groups_repeated",
+                                            "groups_emitted", "groups_no_room", "bytes_emitted", "bytes_no_room")
+PACKET_GROUPS_RESULT_DTYPE = np.dtype([(n, np.int32) for n in PACKET_GROUPS_COUNTERS] + [("reserved", np.int32, (4,))])
+assert PACKET_GROUPS_RESULT_DTYPE.itemsize == 112
+#: dabgpu_user_application: one (SId, SCIdS, user application type) of FIG 0/13, joined to its component
+USER_APPLICATION_DTYPE = np.dtype([("sid", np.uint32), ("scids", np.int32), ("ua_type", np.int32), ("tmid_packet", np.int32),
+                                   ("subchid", np.int32), ("scid", np.int32), ("packet_address", np.int32), ("data_length", np.int32),
+                                   ("data", np.uint8, (23,)), ("reserved", np.uint8)])
+assert USER_APPLICATION_DTYPE.itemsize == 56
+#: registered user application types it is useful to know (TS 101 756); the library does not interpret them
+UA_SLIDESHOW, UA_TPEG, UA_SPI, UA_FILECASTING, UA_JOURNALINE = 0x002, 0x004, 0x007, 0x00D, 0x44A
 #: dabgpu_packet_component: one packet-mode service component (fig_packet_components)
 PACKET_COMPONENT_DTYPE = np.dtype([("sid", np.uint32), ("scid", np.int32), ("subchid", np.int32), ("start_address", np.int32),
                                    ("packet_address", np.int32), ("dscty", np.int32), ("dg_flag", np.int32), ("fec_scheme", np.int32),
@@ -339,6 +359,16 @@ class PacketCarouselEntry(C.Structure):
                 ("d_arena", C.c_void_p), ("arena_bytes", C.c_size_t), ("d_objects", C.c_void_p), ("object_stride", C.c_size_t),
                 ("max_objects", C.c_int32), ("object_capacity", C.c_int32), ("d_directory", C.c_void_p),
                 ("directory_capacity", C.c_int32), ("reserved", C.c_int32), ("d_result", C.c_void_p)]
+
+
+class PacketGroupsEntry(C.Structure):
+    """dabgpu_packet_groups_entry: one (sub-channel, packet address) of Context.packet_groups_dev (device addresses) or
+    packet_groups_host (host addresses): the logical frames, the address followed, mode (0 data groups, 1 raw bytes),
+    keep_repeats, the state records, the bytes and records that come out, the counters."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("address", C.c_int32),
+                ("fec", C.c_int32), ("mode", C.c_int32), ("keep_repeats", C.c_int32), ("reserved", C.c_int32),
+                ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p), ("d_bytes", C.c_void_p), ("d_groups", C.c_void_p),
+                ("bytes_capacity", C.c_int32), ("max_groups", C.c_int32), ("d_result", C.c_void_p)]
 
 
 class PacketFecEntry(C.Structure):
@@ -678,6 +708,12 @@ def load_library(path):
     L.dabgpu_packet_carousel_arena_bytes.argtypes = [i, i, i]
     L.dabgpu_packet_carousel_dev.argtypes = [vp, C.POINTER(PacketCarouselEntry), i, i, vp]
     L.dabgpu_packet_carousel_host.argtypes = [C.POINTER(PacketCarouselEntry), i, i]
+    L.dabgpu_packet_groups_state_bytes.restype = C.c_size_t
+    L.dabgpu_packet_groups_state_bytes.argtypes = []
+    L.dabgpu_packet_groups_chunk.argtypes = []
+    L.dabgpu_packet_groups_dev.argtypes = [vp, C.POINTER(PacketGroupsEntry), i, i, vp]
+    L.dabgpu_packet_groups_host.argtypes = [C.POINTER(PacketGroupsEntry), i, i]
+    L.dabgpu_fig_user_applications.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
     L.dabgpu_packet_fec_state_bytes.argtypes = [i]
@@ -911,6 +947,39 @@ def fig_packet_components(fib, crc_ok, max_out=64):
     _check(lib().dabgpu_fig_packet_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_packet_components")
     return [PacketComponent(a.sid, a.scid, a.subchid, a.start_address, a.packet_address, a.dscty, a.dg_flag, a.fec_scheme, a.primary)
             for a in arr[:n.value]]
+
+
+def fig_user_applications(fib, crc_ok, max_out=64):
+    """The user applications one ensemble announces (FIG 0/13) in its CRC-clean FIBs, each (SId, SCIdS, type) once, joined
+    through FIG 0/8 (and FIG 0/3 for packet mode) to its component, sorted by (sid, scids, ua_type): fib
+    [n_frames][12][32] uint8, crc_ok [n_frames][12] -> a USER_APPLICATION_DTYPE array (no GPU needed)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    out = np.zeros(max(max_out, 1), USER_APPLICATION_DTYPE)
+    n = C.c_int(0)
+    _check(lib().dabgpu_fig_user_applications(_p(fib), _p(crc_ok), n_frames, _p(out), max_out, C.byref(n)), "dabgpu_fig_user_applications")
+    return out[:n.value].copy()
+
+
+def packet_groups_state_bytes():
+    """Bytes of one state record of Context.packet_groups_dev / packet_groups_host (all zero = a fresh start)."""
+    return int(lib().dabgpu_packet_groups_state_bytes())
+
+
+def packet_groups_chunk():
+    """The followed packets the kernel of Context.packet_groups_dev takes at a time: its seams lie at multiples of this."""
+    return int(lib().dabgpu_packet_groups_chunk())
+
+
+def packet_groups_host(entries, n_cifs):
+    """Context.packet_groups_dev on HOST memory (entries: PacketGroupsEntry with host addresses): the same checks and the same
+    code, include/dabgpu_data_groups.h; no context, no GPU."""
+    n = len(entries)
+    arr = (PacketGroupsEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_packet_groups_host(arr, n, n_cifs), "dabgpu_packet_groups_host")
 
 
 def packet_state_bytes():
@@ -1641,6 +1710,16 @@ class Context:
         n = len(entries)
         arr = (PacketCarouselEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_packet_carousel_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_carousel_dev")
+
+    def packet_groups_dev(self, entries, n_cifs, stream=None):
+        """The MSC data groups (mode 0) or the raw useful bytes (mode 1) of any packet-mode component, behind
+        decode_ensembles_dev (and either FEC call) on the same stream: entries is a list of PacketGroupsEntry (device
+        addresses), one per (sub-channel, packet address); n_cifs logical frames each.  Per entry: the groups' bytes in
+        d_bytes, a DATA_GROUP_DTYPE record each in d_groups, d_result (PACKET_GROUPS_RESULT_DTYPE, counts of this call) and
+        d_state_out, to be passed as d_state_in of the next call.  No host synchronisation."""
+        n = len(entries)
+        arr = (PacketGroupsEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_packet_groups_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_groups_dev")
 
     def packet_fec_dev(self, entries, n_cifs, stream=None):
         """RS(204,188) correction of the FEC frames of packet-mode sub-channels, between decode_ensembles_dev and

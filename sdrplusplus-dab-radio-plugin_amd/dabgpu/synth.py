@@ -1282,6 +1282,45 @@ def packetise(groups, address, sizes=(4,), ci=0):
     return out
 
 
+def wrong_crc(group):
+    """a data group that carries a CRC (msc_data_group(..., crc=True)), with that CRC wrong"""
+    g = bytearray(group)
+    g[-1] ^= 0x01
+    return bytes(g)
+
+
+def packetise_chosen(group, address, plan, ci=0):
+    """one data group in packets of chosen shape: plan is a list of (slots, udl) -- that many slots, the next udl bytes of
+    the group (0 included; less than the room is filled up) -- and of ("command", slots) for a command packet between them;
+    the plan must take the group exactly.  First is set on the first data packet, last on the last.  -> packets (continuity
+    index from `ci`, counting command packets too)"""
+    group, at, out = bytes(group), 0, []
+    data_items = [i for i, p in enumerate(plan) if p[0] != "command"]
+    assert sum(plan[i][1] for i in data_items) == len(group) and data_items
+    for i, p in enumerate(plan):
+        if p[0] == "command":
+            out.append(packet(address, b"\xC3" * 3, p[1], ci=ci + i, first=True, last=True, command=True))
+            continue
+        slots, udl = p
+        out.append(packet(address, group[at:at + udl], slots, ci=ci + i, first=i == data_items[0], last=i == data_items[-1], fill=0xEE))
+        at += udl
+    return out
+
+
+def packetise_raw(data, address, sizes=(4,), ci=0, flags=((True, True), (False, False), (True, False), (False, True))):
+    """a byte string for a component without data groups (DG flag 1): packets of sizes[k % len] slots, each full but the last;
+    first and last take flags[k % len] (a receiver must not look at them)"""
+    data, at, out, k = bytes(data), 0, [], 0
+    while at < len(data) or k == 0:
+        slots = sizes[k % len(sizes)]
+        take = min(PACKET_SLOT * slots - 5, len(data) - at)
+        first, last = flags[k % len(flags)]
+        out.append(packet(address, data[at:at + take], slots, ci=ci + k, first=first, last=last, fill=0xEE))
+        at += take
+        k += 1
+    return out
+
+
 def padding_packet(slots=1, fill=0x55):
     """a padding packet: address 0, no useful data"""
     return packet(0, b"", slots, fill=fill)
@@ -1494,6 +1533,24 @@ def fig0_8(entries, pd=0):
     return fig0(8, b"".join(_bits((sid, w), (0, 1), (0, 3), (scids, 4), (0, 1), (0, 1), (scid, 6)) for sid, scids, scid in entries), pd=pd)
 
 
+def fig0_8_long(entries, pd=0):
+    """Service component global definition, long form (packet mode): [(sid, scids, scid 12 bits), ...] (clause 6.3.5)."""
+    w = 32 if pd else 16
+    return fig0(8, b"".join(_bits((sid, w), (0, 1), (0, 3), (scids, 4), (1, 1), (0, 3), (scid, 12)) for sid, scids, scid in entries), pd=pd)
+
+
+def fig0_13(entries, pd=0):
+    """User application information (clause 6.3.6): [(sid, scids, [(ua_type 11 bits, data bytes), ...]), ...]."""
+    w = 32 if pd else 16
+    body = b""
+    for sid, scids, apps in entries:
+        body += _bits((sid, w), (scids, 4), (len(apps), 4))
+        for ua_type, data in apps:
+            assert len(data) < 32
+            body += _bits((ua_type, 11), (len(data), 5)) + bytes(data)
+    return fig0(13, body, pd=pd)
+
+
 def fig0_9(ecc, lto_half_hours, inter_table=1):
     """Country, LTO and international table (clause 8.1.3.2); lto in half hours, negative = west of UTC."""
     return fig0(9, _bits((0, 1), (0, 1), (1 if lto_half_hours < 0 else 0, 1), (abs(lto_half_hours), 5), (ecc, 8), (inter_table, 8)))
@@ -1596,7 +1653,7 @@ class ServiceEnsemble:
     start_cu), ...].  n_frames must be a multiple of 5 so that whole super-frames (5 logical frames) tile."""
 
     def __init__(self, seed, services, n_frames=5, eid=0xC181, label="Synth Ensemble", dab_services=(), extras=True, bodies=None,
-                 dab_pads=None, packet_services=()):
+                 dab_pads=None, packet_services=(), user_applications=()):
         """dab_services: DAB (MPEG layer II) services on UEP sub-channels, [(label, sid, subchannel_id, uep_index,
         start_cu), ...]; every logical frame of such a sub-channel is one layer-II frame (header + random body).
         extras=False leaves the rotation to the labels alone (FIG 0/0, 0/1, 0/2, 0/10 and one label per CIF): what
@@ -1609,7 +1666,9 @@ class ServiceEnsemble:
         packet_services: packet-mode data services on EEP sub-channels, [(label, sid, subchannel_id, option, level, bitrate,
         start_cu, components, frames, fec_scheme), ...]: components = [(scid, packet address, dscty, dg_flag), ...] (FIG 0/2
         TMId 3 and FIG 0/3; the first is the primary one), frames = 4 * n_frames logical frames (packet_frames), fec_scheme
-        non-zero announces FIG 0/14.  No random draw depends on them."""
+        non-zero announces FIG 0/14.  No random draw depends on them.
+        user_applications: of packet-mode components, [(sid, scids, scid, [(ua_type, data), ...]), ...]: one FIG 0/8 (long form)
+        and one FIG 0/13 for all of them, in rotation with the labels."""
         assert n_frames % 5 == 0
         rng = np.random.default_rng(seed)
         self.n_frames, self.eid, self.label, self.services = n_frames, eid, label, services
@@ -1669,6 +1728,9 @@ class ServiceEnsemble:
         sv += [{"sid": sid, "components": [{"scid": c[0], "primary": k == 0} for k, c in enumerate(comps)]}
                for (lab, sid, _scid, _o, _l, _b, _s, comps, *_rest) in self.packet_services]
         labels += [fig1(1, sid, lab) for (lab, sid, *_rest) in self.packet_services]
+        if user_applications:
+            labels += [fig0_8_long([(sid, scids, scid) for (sid, scids, scid, _a) in user_applications]),
+                       fig0_13([(sid, scids, apps) for (sid, scids, _c, apps) in user_applications])]
         # what else a multiplex says about itself (one of these per CIF, in rotation with the labels): country and
         # local time, component identifiers and labels, programme types, languages, a linkage set with its FM
         # alternative and that station's frequencies, the neighbouring ensemble carrying the first service

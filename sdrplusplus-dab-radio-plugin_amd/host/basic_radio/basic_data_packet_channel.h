@@ -16,6 +16,12 @@
 // bodies alone) yields its current directory and its objects here (GetDirectory, GetCarouselObjects), while the header-mode
 // walk counts its groups as ignored; one that speaks header mode yields slides as before, and the carousel control counts
 // groups_header_mode.  The two share nothing but the frame's scan: the walk, its counters and its slides are untouched.
+//
+// Components that are not MOT in data groups (DSCTy other than 60, or DG flag 1: TPEG, SPI, Journaline, transparent data
+// channels) are followed by FollowDataGroups: every logical frame goes through the serial walk of
+// include/dabgpu_data_groups.h, the code dabgpu_packet_groups_dev and dabgpu_packet_groups_host run, one frame a call with the
+// state record handed on; every data group it emits goes to OnDataGroup (its record and its bytes), the raw bytes of a
+// component without data groups to OnRawData with a record for every continuity break (where in them bytes are missing), the counters add up (GetDataGroupCounters).  MOT components go where they went.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -27,7 +33,9 @@
 #include "dabgpu_packet_fec.h"
 #include "dabgpu_packet_fec_erasures.h"
 #include "dabgpu_mot_carousel.h"
+#include "dabgpu_data_groups.h"
 #include "dabgpu_packet_walk.h"
+#include "utility/observable.h"
 #include "utility/span.h"
 
 class Basic_Data_Packet_Channel {
@@ -86,6 +94,38 @@ public:
         return {k.directory.data(), k.state.cur_valid ? size_t(k.state.cur_bytes) : size_t(0)};
     }
     const std::vector<Carousel_Object> &GetCarouselObjects(int i) const { return m_followers[size_t(i)]->carousel->objects; }
+    // a packet address whose data groups (mode 0) or raw useful bytes (mode 1: the component's DG flag) are handed out as
+    // they are, from the next frame on: false for an address or mode out of range, and for a fifth
+    bool FollowDataGroups(int address, int mode, bool keep_repeats = false) {
+        if (address < 1 || address > 1023 || mode < 0 || mode > 1) return false;
+        for (const auto &f : m_data_followers)
+            if (f->address == address) return f->call.mode == mode;
+        if (int(m_data_followers.size()) >= MAX_ADDRESSES) return false;
+        auto f = std::make_unique<DataFollower>();
+        f->address = address;
+        f->call.mode = mode;
+        f->call.keep_repeats = keep_repeats;
+        // (one frame a call: at most 64 packets close a group or break, one group of up to 16384 bytes among them)
+        f->call.max_groups = dabgpu_packet::MAX_SLOTS;
+        f->call.bytes_capacity = dabgpu_groups::GROUP_CAP + dabgpu_packet::MAX_SLOTS * 96;
+        f->bytes.resize(size_t(f->call.bytes_capacity));
+        f->records.resize(size_t(f->call.max_groups));
+        f->call.bytes = f->bytes.data();
+        f->call.groups = f->records.data();
+        for (auto &st : f->state) st = std::make_unique<dabgpu_groups::State>();   // all zero: a fresh start
+        m_data_followers.push_back(std::move(f));
+        return true;
+    }
+    int GetTotalDataAddresses() const { return int(m_data_followers.size()); }
+    int GetDataAddress(int i) const { return m_data_followers[size_t(i)]->address; }
+    int GetDataMode(int i) const { return m_data_followers[size_t(i)]->call.mode; }
+    // counts since the address was added
+    const dabgpu_groups::Counters &GetDataGroupCounters(int i) const { return m_data_followers[size_t(i)]->counts; }
+    // (packet address, the group's record -- cif counts the channel's frames, offset is 0 --, the whole group)
+    auto &OnDataGroup() { return m_obs_data_group; }
+    // (packet address, the useful bytes one frame added to the stream, one record per continuity break of that frame: flags
+    // DABGPU_DG_BREAK, offset = where in these bytes bytes are missing in front, cif = the channel's frame count, slot)
+    auto &OnRawData() { return m_obs_raw_data; }
     int GetTotalFrames() const { return m_total_frames; }
     int GetTotalFramesIgnored() const { return m_total_ignored; }
 
@@ -127,10 +167,47 @@ public:
                 k->packets_followed += t.followed;
             }
         }
+        for (auto &f : m_data_followers) FollowData(*f, frame, S);
         m_total_frames++;
     }
 
 private:
+    struct DataFollower {
+        int address = 0;
+        dabgpu_groups::Call call{};
+        dabgpu_groups::Counters counts{};
+        std::unique_ptr<dabgpu_groups::State> state[2];
+        int turn = 0;
+        std::vector<uint8_t> bytes;
+        std::vector<dabgpu_groups::Record> records;
+    };
+    // one logical frame of one address through dabgpu_groups::walk_frames, as a call of one frame
+    void FollowData(DataFollower &f, const uint8_t *frame, int S) {
+        namespace dg = dabgpu_groups;
+        dg::Counters c{};
+        dg::walk_frames(f.state[f.turn].get(), f.state[f.turn ^ 1].get(), c, f.call, frame, uint64_t(dabgpu_packet::SLOT_BYTES) * uint64_t(S), 1, S,
+                        f.address, m_fec);
+        f.turn ^= 1;
+        int32_t *sum = reinterpret_cast<int32_t *>(&f.counts);
+        for (size_t i = 0; i < sizeof c / sizeof(int32_t); i++) sum[i] += reinterpret_cast<const int32_t *>(&c)[i];
+        if (f.call.mode) {
+            if (c.bytes_emitted || c.groups_emitted)
+            {
+                for (int i = 0; i < c.groups_emitted; i++) f.records[size_t(i)].cif = m_total_frames;
+                m_obs_raw_data.Notify(f.address, tcb::span<const uint8_t>(f.bytes.data(), size_t(c.bytes_emitted)),
+                                      tcb::span<const dabgpu_groups::Record>(f.records.data(), size_t(c.groups_emitted)));
+            }
+            return;
+        }
+        for (int i = 0; i < c.groups_emitted; i++) {
+            dg::Record r = f.records[size_t(i)];
+            const uint8_t *g = f.bytes.data() + r.offset;
+            r.cif = m_total_frames;
+            r.offset = 0;
+            m_obs_data_group.Notify(f.address, r, tcb::span<const uint8_t>(g, size_t(r.length)));
+        }
+    }
+
     // one logical frame through dabgpu_packet_fec::process_erasures (FEC scheme 1) or process: -> the frame D frames back,
     // corrected.  The two keep state records of their own kind: a change of scheme starts the FEC stream afresh
     const uint8_t *Correct(const uint8_t *lf, int S) {
@@ -210,6 +287,9 @@ private:
     int m_fec;
     dabgpu_mot::Call m_call{};
     std::vector<std::unique_ptr<Follower>> m_followers;
+    std::vector<std::unique_ptr<DataFollower>> m_data_followers;
+    Observable<int, const dabgpu_groups::Record &, tcb::span<const uint8_t>> m_obs_data_group;
+    Observable<int, tcb::span<const uint8_t>, tcb::span<const dabgpu_groups::Record>> m_obs_raw_data;
     std::vector<uint8_t> m_slot;
     Basic_Slideshow_Manager m_slideshows;
     int m_total_frames = 0, m_total_ignored = 0;

@@ -157,7 +157,8 @@ int BasicRadio::open_subchannel(const dabgpu_subchannel &sc) {
     return add_subchannel_locked(sc);
 }
 
-// Open a data packet channel for every packet-mode component that carries MOT in data groups, once FIG 0/2, FIG 0/3 and
+// Open a data packet channel for every packet-mode component (MOT in data groups: slides and carousels; any other: its data
+// groups or raw bytes as they are), once FIG 0/2, FIG 0/3 and
 // FIG 0/1 have all spoken; further addresses of an open sub-channel join its channel (up to four)
 void BasicRadio::update_packet_channels() {
     size_t described = 0;
@@ -169,10 +170,14 @@ void BasicRadio::update_packet_channels() {
     if (described == m_seen_packet_described && !m_pending_packets) return;
     m_pending_packets = false;
     for (const auto &pc : m_database.packet_components) {
-        if (!pc.has_service || !pc.is_described || pc.dscty != 60 || pc.dg_flag) continue;
+        if (!pc.has_service || !pc.is_described) continue;
+        // MOT in data groups goes to the slides and the carousel control; anything else is handed out as data groups or,
+        // without data groups, as raw bytes
+        const bool mot = pc.dscty == 60 && !pc.dg_flag;
         auto open = m_packet_channels.find(pc.subchannel_id);
         if (open != m_packet_channels.end()) {
-            open->second->FollowAddress(pc.packet_address);
+            if (mot) open->second->FollowAddress(pc.packet_address);
+            else open->second->FollowDataGroups(pc.packet_address, pc.dg_flag ? 1 : 0);
             continue;
         }
         if (m_channels.count(pc.subchannel_id)) continue;       // (an audio channel has the sub-channel)
@@ -196,7 +201,8 @@ void BasicRadio::update_packet_channels() {
         }
         auto ch = std::make_unique<Basic_Data_Packet_Channel>(*sub, m_database.fec_scheme[sub->id & 63]);
         ch->SetFecCorrection(ch->GetFecScheme() == 1);
-        ch->FollowAddress(pc.packet_address);
+        if (mot) ch->FollowAddress(pc.packet_address);
+        else ch->FollowDataGroups(pc.packet_address, pc.dg_flag ? 1 : 0);
         m_subchannels[size_t(idx)].packet = ch.get();
         m_packet_channels.emplace(sub->id, std::move(ch));
     }

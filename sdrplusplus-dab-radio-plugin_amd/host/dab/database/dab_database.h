@@ -19,6 +19,23 @@ struct PacketComponent {
     bool dg_flag = false;                  // false: data groups are used
 };
 
+// FIG 0/13: a user application of a service component (SId, SCIdS); kept as sent, not interpreted.  Registered types it is
+// useful to know (TS 101 756): 0x002 slideshow, 0x004 TPEG, 0x007 SPI, 0x00D filecasting, 0x44A Journaline.
+struct UserApplication {
+    uint32_t service_id = 0;
+    bool service_id_32 = false;
+    uint8_t scids = 0;
+    uint16_t type = 0;                     // 11 bits
+    std::vector<uint8_t> data;             // user application data, 0 .. 23 bytes
+};
+// FIG 0/8: which component (SId, SCIdS) is: a sub-channel (short form) or a packet-mode component's SCId (long form)
+struct ComponentGlobal {
+    uint32_t service_id = 0;
+    uint8_t scids = 0;
+    bool is_packet = false;
+    uint16_t id = 0;                       // SubChId (6 bits) or SCId (12 bits)
+};
+
 struct DAB_Database {
     Ensemble ensemble;
     std::vector<Service> services;
@@ -30,6 +47,29 @@ struct DAB_Database {
     std::vector<OtherEnsemble> other_ensembles;
     std::vector<PacketComponent> packet_components;        // render_radio_block.cpp:533 asks for their channels
     uint8_t fec_scheme[64] = {};                           // FIG 0/14, by SubChId; 0 = none announced
+    std::vector<UserApplication> user_applications;        // FIG 0/13, each (SId, SCIdS, type) once
+    std::vector<ComponentGlobal> component_globals;        // FIG 0/8, each (SId, SCIdS) once
+
+    // the user applications of a packet-mode component: FIG 0/13 joined through FIG 0/8's (SId, SCIdS) to its SCId
+    std::vector<const UserApplication *> UserApplicationsOf(const PacketComponent &pc) const {
+        std::vector<const UserApplication *> out;
+        for (const auto &g : component_globals) {
+            if (!g.is_packet || g.id != pc.scid) continue;
+            for (const auto &ua : user_applications)
+                if (ua.service_id == g.service_id && ua.scids == g.scids) out.push_back(&ua);
+        }
+        return out;
+    }
+    // ... and of a stream-mode component, through its SubChId
+    std::vector<const UserApplication *> UserApplicationsOfSubchannel(subchannel_id_t id) const {
+        std::vector<const UserApplication *> out;
+        for (const auto &g : component_globals) {
+            if (g.is_packet || g.id != id) continue;
+            for (const auto &ua : user_applications)
+                if (ua.service_id == g.service_id && ua.scids == g.scids) out.push_back(&ua);
+        }
+        return out;
+    }
 };
 
 struct DAB_Database_Statistics {           // GetDatabaseStatistics(), render_radio_block.cpp:755

@@ -40,9 +40,10 @@ void FIC_Parser::fig0(const uint8_t *d, int n) {
     // packet mode: the current configuration of this ensemble alone (C/N = 0, OE = 0)
     case 3: if (!(d[0] & 0xC0)) fig0_3(d + 1, n - 1); break;
     case 14: if (!(d[0] & 0xC0)) fig0_14(d + 1, n - 1); break;
+    case 13: if (!(d[0] & 0xC0)) fig0_13(d + 1, n - 1, pd); break;
     case 5: fig0_5(d + 1, n - 1); break;
     case 6: fig0_6(d + 1, n - 1, pd); break;
-    case 8: fig0_8(d + 1, n - 1, pd); break;
+    case 8: fig0_8(d + 1, n - 1, pd, !(d[0] & 0xC0)); break;
     case 9: fig0_9(d + 1, n - 1); break;
     case 10: fig0_10(d + 1, n - 1); break;
     case 17: fig0_17(d + 1, n - 1); break;
@@ -118,6 +119,39 @@ void FIC_Parser::fig0_3(const uint8_t *d, int n) {
             c->packet_address = uint16_t(((d[i + 3] & 3) << 8) | d[i + 4]);
         }
         i += size;
+    }
+}
+
+// FIG 0/13 user application information: SId (16 / 32 bits), SCIdS(4) number of user applications(4), then per application
+// type(11) data length(5) and that many bytes.  Each (SId, SCIdS, type) once, its first; an entry cut off ends the FIG.
+void FIC_Parser::fig0_13(const uint8_t *d, int n, bool pd) {
+    const int idlen = pd ? 4 : 2;
+    int i = 0;
+    while (i + idlen + 1 <= n) {
+        uint32_t sid = 0;
+        for (int k = 0; k < idlen; k++) sid = (sid << 8) | d[i + k];
+        const uint8_t scids = d[i + idlen] >> 4;
+        const int count = d[i + idlen] & 0x0F;
+        i += idlen + 1;
+        for (int a = 0; a < count; a++) {
+            if (i + 2 > n) return;
+            const uint16_t type = uint16_t((d[i] << 3) | (d[i + 1] >> 5));
+            const int len = d[i + 1] & 0x1F;
+            if (i + 2 + len > n) return;
+            auto &list = m_updater.UserApplications();
+            bool known = false;
+            for (const auto &u : list) known = known || (u.service_id == sid && u.scids == scids && u.type == type);
+            if (!known && list.size() < DAB_Database_Updater::MAX_ENTITIES) {
+                UserApplication u;
+                u.service_id = sid;
+                u.service_id_32 = pd;
+                u.scids = scids;
+                u.type = type;
+                u.data.assign(d + i + 2, d + i + 2 + len);
+                list.push_back(std::move(u));
+            }
+            i += 2 + len;
+        }
     }
 }
 
@@ -253,7 +287,7 @@ void FIC_Parser::fig0_6(const uint8_t *d, int n, bool pd) {
 
 // FIG 0/8 service component global definition: SId, Ext flag(1) Rfa(3) SCIdS(4), then L/S=0: MSC/FIC(1) SubChId(6)
 // or L/S=1: Rfa(3) SCId(12); one more Rfa byte when the Ext flag is set.
-void FIC_Parser::fig0_8(const uint8_t *d, int n, bool pd) {
+void FIC_Parser::fig0_8(const uint8_t *d, int n, bool pd, bool current) {
     const int idlen = pd ? 4 : 2;
     int i = 0;
     while (i + idlen + 2 <= n) {
@@ -265,7 +299,15 @@ void FIC_Parser::fig0_8(const uint8_t *d, int n, bool pd) {
         const bool long_form = c >> 7;
         const int size = idlen + 2 + (long_form ? 1 : 0) + (ext ? 1 : 0);
         if (i + size > n) return;
+        // (which component (SId, SCIdS) is, for FIG 0/13's join; a list of its own, the statistics stay what they were)
+        const uint16_t ident = long_form ? uint16_t(((c & 0x0F) << 8) | d[i + idlen + 2]) : uint16_t(c & 0x3F);
         i += size;
+        if (current && (long_form || !((c >> 6) & 1))) {             // (this ensemble's current configuration; not FIDC)
+            auto &globals = m_updater.ComponentGlobals();
+            bool known = false;
+            for (const auto &g : globals) known = known || (g.service_id == sid && g.scids == scids);
+            if (!known && globals.size() < DAB_Database_Updater::MAX_ENTITIES) globals.push_back(ComponentGlobal{sid, uint8_t(scids), long_form, ident});
+        }
         if (long_form || ((c >> 6) & 1)) continue;           // packet mode / FIDC: not followed
         for (auto &comp : m_updater.Components())
             if (comp.service_id.value == sid && comp.subchannel_id == (c & 0x3F))

@@ -27,10 +27,11 @@ private:
     void fig0_2(const uint8_t *d, int n, bool pd);
     void fig0_3(const uint8_t *d, int n);
     void fig0_14(const uint8_t *d, int n);
+    void fig0_13(const uint8_t *d, int n, bool pd);
     PacketComponent *packet_component(uint16_t scid);
     void fig0_5(const uint8_t *d, int n);
     void fig0_6(const uint8_t *d, int n, bool pd);
-    void fig0_8(const uint8_t *d, int n, bool pd);
+    void fig0_8(const uint8_t *d, int n, bool pd, bool current);
     void fig0_9(const uint8_t *d, int n);
     void fig0_10(const uint8_t *d, int n);
     void fig0_17(const uint8_t *d, int n);
