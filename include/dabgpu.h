@@ -1273,6 +1273,98 @@ int dabgpu_modulate_eti_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, const 
                             size_t frame_stride, dabgpu_mod_status *d_status, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* ETI(NI) input: ETI(NI) byte streams read back   */
+/* into what the decode call leaves -- FIBs with CRC flags and every            */
+/* sub-channel's logical frames -- so that the FIG functions and every follow   */
+/* call (d_in / in_stride) run on a recording or a multiplexer's output as they  */
+/* do behind the channel decoder.  A batch of entries, each a stream with its    */
+/* own multiplex.  The input is a BYTE STREAM: cut anywhere, bytes missing in    */
+/* the middle.  The contract -- stream, verdicts, candidates, the walk, rows,    */
+/* status, state -- is written out in include/dabgpu_eti_read.h, which the       */
+/* kernels, the host twin and the host mirror all run.  In short, per entry:     */
+/*   S = the state's carried tail (0..6143 bytes) + the n_bytes new bytes; at    */
+/*   most max_frames = (6143 + n_bytes) / 6144 rows.  A position is a CANDIDATE  */
+/*   when FSYNC, its parity against FCT, the header fields and the header CRC    */
+/*   hold.  From p = 0: a candidate gives a row and p += 6144; otherwise the walk */
+/*   resynchronises on the next candidate (skipped, resyncs).  What is left      */
+/*   (at most 6143 bytes) is the new tail and is judged again by the next call.   */
+/*   Row r with verdict 0 is TAKEN: its FIC to d_fib[r], the three FIB CRC flags  */
+/*   (computed here, the FIC decoder's rule) to d_crc_ok[r], stream k's bytes to  */
+/*   d_out[k][r] for every d_out[k] that is not NULL (the caller's order, as      */
+/*   dabgpu_eti_frames_dev takes it through plan->order).  A row whose data CRC    */
+/*   fails (4) or whose NST, FL or STC differ from the plan's                     */
+/*   (DABGPU_ETI_OTHER_PLAN) keeps its place in time with zero FIC, flags and     */
+/*   stream rows: the follow calls see a lost frame.  Rows behind the emitted      */
+/*   count are not written.  plan NULL is the discovery pass: only the FIC is      */
+/*   extracted; dabgpu_eti_streams_from_frame reads the multiplex from a taken     */
+/*   frame, whose offset in S is in its status.                                    */
+/* Frames missing by FCT are NOT replaced by zero rows: after byte loss the         */
+/* entries of a call emit different row counts (status gap says how many frames     */
+/* are missing in front of a row).                                                  */
+/*                                                                                */
+/* dabgpu_eti_read_state_bytes   size of the per-entry state record (a head with    */
+/*            the tail length, the last row's FCT and FP and the running totals,     */
+/*            then the tail).  All zero = a stream that starts.  Written whole.  A    */
+/*            record the library did not write makes no call read outside it (a      */
+/*            tail length above 6143 counts as 6143).                                 */
+/* dabgpu_eti_read_dev   entries: HOST array.  d_bytes 16-byte aligned (NULL with     */
+/*            n_bytes 0), no byte outside [d_bytes, d_bytes + n_bytes) is read.       */
+/*            d_state_in (or NULL) / d_state_out 16-byte aligned and not the same.     */
+/*            d_fib [max_frames][3][32] and d_status 16-byte aligned, d_result 4-,      */
+/*            every d_out[k] 8-byte aligned; d_out is a HOST array of plan->nst DEVICE  */
+/*            pointers or NULL.  plan: what dabgpu_eti_layout gave, or NULL.  Four      */
+/*            launches, no synchronisation, no global atomic.  Everything is checked    */
+/*            before anything is enqueued: a refused call (DABGPU_ERR_ARG) writes       */
+/*            nothing.                                                                  */
+/* dabgpu_eti_read_host   the same on host pointers (no context, no device): the        */
+/*            serial walk of the same header.                                           */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_ETI_OTHER_PLAN     5    /* a verdict beside DABGPU_ETI_BAD_*: a good frame of another multiplex */
+#define DABGPU_ETI_READ_GAP       1    /* status flags: gap != 0                                               */
+#define DABGPU_ETI_READ_FP_BREAK  2    /* FP is not the previous row's FP + 1 modulo 8                          */
+#define DABGPU_ETI_READ_ERR_FIELD 4    /* ERR is not 0xFF (the writer's warm-up frames included)                */
+#define DABGPU_ETI_READ_FIB_CRC   8    /* a taken row with a FIB that failed its CRC                            */
+
+typedef struct dabgpu_eti_read_status { /* per row, 16 bytes */
+    uint32_t offset;                   /* of the frame in S                                          */
+    uint8_t  verdict;                  /* 0, DABGPU_ETI_BAD_DATA_CRC or DABGPU_ETI_OTHER_PLAN         */
+    uint8_t  fct, fp, err;             /* the header's                                               */
+    uint8_t  fib_ok;                   /* bit j = FIB j passed its CRC (0 unless taken)              */
+    uint8_t  gap;                      /* (FCT - (previous row's FCT + 1)) mod 250; 0 for the first  */
+    uint8_t  flags;                    /* DABGPU_ETI_READ_*                                          */
+    uint8_t  reserved;                 /* 0                                                          */
+    uint32_t reserved2;                /* 0                                                          */
+} dabgpu_eti_read_status;
+
+typedef struct dabgpu_eti_read_result { /* per entry and call, 48 bytes */
+    uint32_t rows, taken;              /* rows emitted; of them with verdict 0                       */
+    uint32_t bad_data_crc, other_plan; /* ... with verdict 4, 5                                      */
+    uint32_t skipped, resyncs;         /* bytes stepped over; times the walk had to search           */
+    uint32_t gap_sum;                  /* sum of the rows' gaps                                      */
+    uint32_t fib_errors;               /* FIBs of taken rows that failed their CRC                   */
+    uint32_t tail_bytes;               /* held in the new state                                      */
+    uint32_t reserved[3];              /* 0                                                          */
+} dabgpu_eti_read_result;
+
+typedef struct dabgpu_eti_read_entry {
+    const uint8_t *d_bytes;            /* the new bytes                                              */
+    int32_t n_bytes;                   /* 0 .. 2^30                                                  */
+    int32_t reserved;                  /* 0                                                          */
+    const dabgpu_eti_plan *plan;       /* HOST; NULL = discovery                                     */
+    uint8_t *const *d_out;             /* HOST array [plan->nst] of DEVICE pointers, or NULL         */
+    const void *d_state_in;            /* or NULL                                                    */
+    void *d_state_out;
+    uint8_t *d_fib;                    /* [max_frames][3][32]                                        */
+    uint8_t *d_crc_ok;                 /* [max_frames][3]                                            */
+    dabgpu_eti_read_status *d_status;  /* [max_frames]                                               */
+    dabgpu_eti_read_result *d_result;
+} dabgpu_eti_read_entry;
+
+size_t dabgpu_eti_read_state_bytes(void);
+int dabgpu_eti_read_dev(dabgpu_ctx *ctx, const dabgpu_eti_read_entry *entries, int n_entries, void *stream);
+int dabgpu_eti_read_host(const dabgpu_eti_read_entry *entries, int n_entries);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

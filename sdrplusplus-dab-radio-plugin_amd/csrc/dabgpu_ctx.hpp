@@ -77,6 +77,7 @@ enum StageSlot {
     STAGE_PACKET_FEC_ERASURES = 20,  // dabgpu_packet_fec_erasures_dev: the same, and a word of suspect bits per window frame
     STAGE_PACKET_CAROUSEL = 21,      // dabgpu_packet_carousel_dev: the entry table, what it adds per entry, the scan records
     STAGE_PACKET_GROUPS = 22,        // dabgpu_packet_groups_dev: the scan's table, this call's table, the scan records
+    STAGE_ETI_READ = 23,             // dabgpu_eti_read_dev: the entry table, the candidate bitmaps and the row lists
     STAGE_SLOTS
 };
 

@@ -5,6 +5,9 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <vector>
+
+#include "../../include/dabgpu_eti_read.h"
 
 using namespace dabapi;
 
@@ -227,6 +230,149 @@ int dabgpu_eti_parse(const uint8_t *f, dabgpu_eti_info *info) {
     if (uint32_t(r.header_crc) != crc16(f + 4, size_t(6 + 4 * r.nst))) return done(DABGPU_ETI_BAD_HEADER_CRC);
     if (uint32_t(r.data_crc) != crc16(f + r.fic_offset, size_t(FIC_BYTES + 8 * stl_sum))) return done(DABGPU_ETI_BAD_DATA_CRC);
     return done(DABGPU_OK);
+}
+
+}  // extern "C"
+
+// ---- ETI(NI) input (include/dabgpu.h, "ETI(NI) input"; include/dabgpu_eti_read.h) -------------------------------------------
+namespace er = dabgpu_eti_read;
+
+static_assert(sizeof(dabgpu_eti_read_status) == sizeof(er::Status) && sizeof(dabgpu_eti_read_result) == sizeof(er::Result) &&
+                  sizeof(dabgpu_eti_read_entry) == 80,
+              "ABI structs mirror the header's");
+static_assert(offsetof(dabgpu_eti_read_status, gap) == offsetof(er::Status, gap) &&
+                  offsetof(dabgpu_eti_read_result, tail_bytes) == offsetof(er::Result, tail_bytes),
+              "ABI structs mirror the header's");
+static_assert(DABGPU_ETI_OTHER_PLAN == er::OTHER_PLAN && DABGPU_ETI_BAD_DATA_CRC == er::BAD_DATA_CRC &&
+                  DABGPU_ETI_READ_GAP == er::FLAG_GAP && DABGPU_ETI_READ_FP_BREAK == er::FLAG_FP_BREAK &&
+                  DABGPU_ETI_READ_ERR_FIELD == er::FLAG_ERR_FIELD && DABGPU_ETI_READ_FIB_CRC == er::FLAG_FIB_CRC,
+              "verdicts and flags");
+
+namespace {
+
+constexpr int32_t ETI_READ_MAX_BYTES = 1 << 30;
+
+// everything both calls refuse, before anything is done; fills the kernels' table when there is one
+int eti_read_check(const dabgpu_eti_read_entry *entries, int n_entries, dabk::EtiReadEntry *table) {
+    if (n_entries < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
+    const auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
+    for (int i = 0; i < n_entries; i++) {
+        const dabgpu_eti_read_entry &e = entries[i];
+        if (e.n_bytes < 0 || e.n_bytes > ETI_READ_MAX_BYTES || (e.n_bytes > 0 && !e.d_bytes)) return DABGPU_ERR_ARG;
+        if (!e.d_state_out || !e.d_result) return DABGPU_ERR_ARG;
+        const int max_frames = (e.n_bytes + er::MAX_TAIL) / er::FRAME_BYTES;
+        if (max_frames > 0 && (!e.d_fib || !e.d_crc_ok || !e.d_status)) return DABGPU_ERR_ARG;
+        if ((addr(e.d_bytes) | addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_fib) | addr(e.d_status)) & 15) return DABGPU_ERR_ARG;
+        if (addr(e.d_result) & 3) return DABGPU_ERR_ARG;
+        const uint64_t sb = er::STATE_BYTES;
+        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
+            return DABGPU_ERR_ARG;
+        if (e.plan) {
+            const dabgpu_eti_plan &p = *e.plan;
+            if (!plan_consistent(p)) return DABGPU_ERR_ARG;
+            for (int k = 0; k < p.nst; k++) {
+                // the STC's own length is what a frame is compared with: it must be what the moves are sized by
+                const uint8_t *stc = p.header + 8 + 4 * k;
+                if (8 * (((stc[2] & 3) << 8) | stc[3]) != p.bytes[k]) return DABGPU_ERR_ARG;
+                if (e.d_out && (addr(e.d_out[k]) & 7)) return DABGPU_ERR_ARG;
+            }
+        }
+    }
+    if (!table) return DABGPU_OK;
+    for (int i = 0; i < n_entries; i++) {
+        const dabgpu_eti_read_entry &e = entries[i];
+        dabk::EtiReadEntry &t = table[i];
+        t.bytes = addr(e.d_bytes);
+        t.state_in = addr(e.d_state_in);
+        t.state_out = addr(e.d_state_out);
+        t.fib = addr(e.d_fib);
+        t.crc_ok = addr(e.d_crc_ok);
+        t.status = addr(e.d_status);
+        t.result = addr(e.d_result);
+        t.n_bytes = e.n_bytes;
+        t.max_frames = (e.n_bytes + er::MAX_TAIL) / er::FRAME_BYTES;
+        if (!e.plan) continue;
+        const dabgpu_eti_plan &p = *e.plan;
+        t.has_plan = 1;
+        t.nst = p.nst;
+        t.fl = p.fl;
+        t.data_bytes = FIC_BYTES + p.data_bytes;
+        t.chunk_words = (t.data_bytes / 4 + 63) / 64;
+        for (int k = 0; k < p.nst; k++) {
+            t.out[k] = e.d_out ? addr(e.d_out[p.order[k]]) : 0;
+            t.offset[k] = uint16_t(p.offset[k]);
+            t.nbytes[k] = uint16_t(p.bytes[k]);
+        }
+        std::memcpy(t.stc, p.header + 8, size_t(4 * p.nst));
+        // the constants of the data CRC depend on the length alone: the entries of a batch mostly share them
+        if (i > 0 && table[i - 1].has_plan && table[i - 1].data_bytes == t.data_bytes) {
+            std::memcpy(t.lane_shift, table[i - 1].lane_shift, sizeof t.lane_shift);
+            t.data_init = table[i - 1].data_init;
+            continue;
+        }
+        for (int lane = 0; lane < 64; lane++) t.lane_shift[lane] = uint16_t(gf_xpow(32ull * unsigned(t.chunk_words) * unsigned(63 - lane)));
+        t.data_init = uint16_t(gf_mul(0xFFFFu, gf_xpow(8ull * unsigned(t.data_bytes))));
+    }
+    return DABGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dabgpu_eti_read_state_bytes(void) { return size_t(er::STATE_BYTES); }
+
+int dabgpu_eti_read_dev(dabgpu_ctx *ctx, const dabgpu_eti_read_entry *entries, int n_entries, void *stream) {
+    if (!ctx) return DABGPU_ERR_ARG;
+    // everything is checked before anything is enqueued: a refused call leaves every output as it was
+    std::vector<dabk::EtiReadEntry> table(size_t(n_entries > 0 ? n_entries : 0), dabk::EtiReadEntry{});
+    const int bad = eti_read_check(entries, n_entries, table.data());
+    if (bad) return bad;
+    if (n_entries == 0) return DABGPU_OK;
+    size_t table_bytes = table.size() * sizeof(dabk::EtiReadEntry) + dabk::eti_read_bases_bytes(n_entries);
+    for (const dabk::EtiReadEntry &t : table) table_bytes += dabk::eti_read_scratch_bytes(t.n_bytes);
+    DeviceGuard guard(ctx);
+    hipStream_t s = pick_stream(ctx, stream);
+    // (growing the table must not race with a launch that still reads the old one)
+    if (ctx->stage_bytes[STAGE_ETI_READ] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
+    void *d_table = nullptr;
+    const int rc = stage(ctx, STAGE_ETI_READ, table_bytes, &d_table);
+    if (rc) return rc;
+    HIP_TRY(dabk::launch_eti_read(table.data(), n_entries, d_table, s));
+    return DABGPU_OK;
+}
+
+int dabgpu_eti_read_host(const dabgpu_eti_read_entry *entries, int n_entries) {
+    const int bad = eti_read_check(entries, n_entries, nullptr);
+    if (bad) return bad;
+    std::vector<uint8_t> s;
+    for (int i = 0; i < n_entries; i++) {
+        const dabgpu_eti_read_entry &e = entries[i];
+        er::Head in{};
+        if (e.d_state_in) std::memcpy(&in, e.d_state_in, sizeof in);
+        const size_t tail = er::clamp_tail(in.tail_bytes);
+        s.resize(tail + size_t(e.n_bytes));
+        if (tail) std::memcpy(s.data(), static_cast<const uint8_t *>(e.d_state_in) + er::STATE_HEAD_BYTES, tail);
+        if (e.n_bytes) std::memcpy(s.data() + tail, e.d_bytes, size_t(e.n_bytes));
+        er::PlanKey key{};
+        uint8_t *out[DABGPU_ETI_MAX_STREAMS] = {};
+        if (e.plan) {
+            key.nst = e.plan->nst;
+            key.fl = e.plan->fl;
+            std::memcpy(key.stc, e.plan->header + 8, size_t(4 * key.nst));
+            for (int k = 0; k < key.nst; k++) out[k] = e.d_out ? e.d_out[e.plan->order[k]] : nullptr;
+        }
+        er::HostOut o{};
+        o.fib = e.d_fib;
+        o.crc_ok = e.d_crc_ok;
+        o.status = reinterpret_cast<er::Status *>(e.d_status);
+        o.result = reinterpret_cast<er::Result *>(e.d_result);
+        o.out = out;
+        o.offset = e.plan ? e.plan->offset : nullptr;
+        o.bytes = e.plan ? e.plan->bytes : nullptr;
+        er::read_entry(s.data(), s.size(), in, e.plan ? &key : nullptr, o, static_cast<uint8_t *>(e.d_state_out));
+    }
+    return DABGPU_OK;
 }
 
 }  // extern "C"

@@ -789,6 +789,38 @@ struct EtiAnchorArgs {
 };
 hipError_t launch_eti(const EtiAnchorArgs &p, const EtiArgs &a, hipStream_t s);
 
+// ---- ETI(NI) input (eti_read_kernels.hip) -------------------------------------
+constexpr int ETI_READ_SCAN_SPAN = 8192;       // byte positions a workgroup of the scan judges
+constexpr int ETI_READ_ROW_WAVES = 4;          // rows (waves) per workgroup of the check launch
+constexpr int ETI_READ_LIST_HEAD = 4;          // words in front of a row list: rows, where the tail begins, skipped, resyncs
+// One entry of the table in device memory (addresses as integers; ~1.3 KB)
+struct EtiReadEntry {
+    uint64_t bytes, state_in, state_out, fib, crc_ok, status, result;
+    uint64_t bitmap;                           // scratch: bit q % 64 of word q / 64 = position q of S is a candidate
+    uint64_t rows;                             // scratch: ETI_READ_LIST_HEAD words, then the offset in S of every row
+    uint64_t out[ETI_MAX_STREAMS];             // stream k of the FRAME (plan order): [max_frames][bytes[k]], 0 = not wanted
+    int32_t n_bytes, max_frames, bitmap_words, has_plan;
+    int32_t nst, fl;                           // the plan's
+    int32_t data_bytes;                        // FIC + streams of the plan: what its data CRC covers
+    int32_t chunk_words;                       // 32-bit words of them a lane folds
+    uint32_t row_base, scan_base;              // the entry's first wave of the check launch, first workgroup of the scan
+    uint16_t offset[ETI_MAX_STREAMS], nbytes[ETI_MAX_STREAMS];
+    uint16_t lane_shift[64];                   // x^(32 chunk_words (63 - lane)) mod P
+    uint16_t data_init, pad[3];                // 0xFFFF x^(8 data_bytes) mod P
+    uint8_t stc[4 * ETI_MAX_STREAMS];          // the plan's STC words
+};
+// scratch an entry needs behind the table: its bitmap, then its row list (bytes, a multiple of 8)
+inline size_t eti_read_scratch_bytes(int n_bytes) {
+    const size_t words = (size_t(n_bytes) + 63) / 64, rows = (size_t(n_bytes) + 6143) / 6144;
+    return words * 8 + ((ETI_READ_LIST_HEAD + rows) * 4 + 15) / 16 * 16;
+}
+// behind the entries the table holds their scan_base and row_base once more, packed ([n_entries] words each): a wave finds
+// its entry from one coalesced load of them instead of a chain of dependent loads through the entries
+inline size_t eti_read_bases_bytes(int n_entries) { return (size_t(n_entries) * 8 + 15) / 16 * 16; }
+// entries: the host's table with everything but bitmap, rows, row_base and scan_base filled in (this fills them);
+// d_table: n_entries * sizeof(EtiReadEntry) + eti_read_bases_bytes + the sum of eti_read_scratch_bytes, 16-byte aligned
+hipError_t launch_eti_read(EtiReadEntry *entries, int n_entries, void *d_table, hipStream_t s);
+
 // ---- modulator: ETI(NI) frames to Mode-I IQ (mod_kernels.hip) -----------------
 // One ETI frame's coded bits ("coded record"): the 2304 punctured FIC bits of its three FIBs, then the 55 296 bits of its
 // CIF BEFORE time interleaving (every sub-channel's punctured codeword at 64 SAD, zeros elsewhere), bit i in bit i % 32

@@ -64,6 +64,7 @@ EXPORTS = [
     "dabgpu_packet_carousel_host", "dabgpu_mot_directory_parse",
     "dabgpu_packet_groups_state_bytes", "dabgpu_packet_groups_chunk", "dabgpu_packet_groups_dev", "dabgpu_packet_groups_host",
     "dabgpu_fig_user_applications",
+    "dabgpu_eti_read_state_bytes", "dabgpu_eti_read_dev", "dabgpu_eti_read_host",
 ]
 
 ABI_VERSION = 6
@@ -574,6 +575,54 @@ def eti_history_bytes():
     return int(lib().dabgpu_eti_history_bytes())
 
 
+#: ETI(NI) input (include/dabgpu.h, "ETI(NI) input"): verdicts of a row beside 0 (taken), flags of its status
+ETI_BAD_DATA_CRC, ETI_OTHER_PLAN = 4, 5
+ETI_READ_GAP, ETI_READ_FP_BREAK, ETI_READ_ERR_FIELD, ETI_READ_FIB_CRC = 1, 2, 4, 8
+#: dabgpu_eti_read_status: one emitted row
+ETI_READ_STATUS_DTYPE = np.dtype([("offset", np.uint32), ("verdict", np.uint8), ("fct", np.uint8), ("fp", np.uint8), ("err", np.uint8),
+                                  ("fib_ok", np.uint8), ("gap", np.uint8), ("flags", np.uint8), ("reserved", np.uint8),
+                                  ("reserved2", np.uint32)])
+assert ETI_READ_STATUS_DTYPE.itemsize == 16
+#: dabgpu_eti_read_result: what one entry of eti_read_dev / eti_read_host counted in one call
+ETI_READ_RESULT_DTYPE = np.dtype([(f, np.uint32) for f in ("rows", "taken", "bad_data_crc", "other_plan", "skipped", "resyncs",
+                                                           "gap_sum", "fib_errors", "tail_bytes")] + [("reserved", np.uint32, (3,))])
+assert ETI_READ_RESULT_DTYPE.itemsize == 48
+#: the head of a state record of eti_read_dev / eti_read_host; the tail's bytes follow it
+ETI_READ_HEAD_DTYPE = np.dtype([("tail_bytes", np.uint32), ("have_prev", np.uint8), ("last_fct", np.uint8), ("last_fp", np.uint8),
+                                ("reserved", np.uint8)] + [(f, np.uint64) for f in ("rows", "taken", "bad_data_crc", "other_plan",
+                                                                                    "skipped", "resyncs", "gap_sum", "fib_errors",
+                                                                                    "reserved2")])
+assert ETI_READ_HEAD_DTYPE.itemsize == 80
+
+
+class EtiReadEntry(C.Structure):
+    """dabgpu_eti_read_entry: one byte stream of Context.eti_read_dev (device addresses) or eti_read_host (host addresses).
+    plan: C.pointer(EtiPlan) or None (discovery: only the FIC leaves); d_out: an array of plan.nst addresses (C.c_void_p *
+    nst) in the order the streams were given to eti_layout, 0 = not wanted, or None.  The Python objects behind plan and
+    d_out must stay alive until the call has returned."""
+    _fields_ = [("d_bytes", C.c_void_p), ("n_bytes", C.c_int32), ("reserved", C.c_int32), ("plan", C.POINTER(EtiPlan)),
+                ("d_out", C.POINTER(C.c_void_p)), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p), ("d_fib", C.c_void_p),
+                ("d_crc_ok", C.c_void_p), ("d_status", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+def eti_read_state_bytes():
+    """Bytes of one state record of Context.eti_read_dev / eti_read_host (all zero = a stream that starts)."""
+    return int(lib().dabgpu_eti_read_state_bytes())
+
+
+def eti_read_max_frames(n_bytes):
+    """Rows one entry can emit in one call: its outputs hold this many."""
+    return (6143 + int(n_bytes)) // ETI_FRAME_BYTES
+
+
+def eti_read_host(entries):
+    """Context.eti_read_dev on HOST memory (entries: EtiReadEntry with host addresses): the same checks and the same walk,
+    serially, without a context or a GPU (dabgpu_eti_read_host)."""
+    n = len(entries)
+    arr = (EtiReadEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_eti_read_host(arr, n), "dabgpu_eti_read_host")
+
+
 #: ETI(NI) to IQ (include/dabgpu.h, "ETI(NI) to IQ"): dabgpu_mod_status, one transmission frame's record
 MOD_BAD_INPUT, MOD_MISALIGNED = 1, 2
 MOD_STATUS_DTYPE = np.dtype([("flags", np.uint32), ("refused", np.uint8), ("reserved", np.uint8, (3,))])
@@ -713,6 +762,10 @@ def load_library(path):
     L.dabgpu_packet_groups_chunk.argtypes = []
     L.dabgpu_packet_groups_dev.argtypes = [vp, C.POINTER(PacketGroupsEntry), i, i, vp]
     L.dabgpu_packet_groups_host.argtypes = [C.POINTER(PacketGroupsEntry), i, i]
+    L.dabgpu_eti_read_state_bytes.restype = C.c_size_t
+    L.dabgpu_eti_read_state_bytes.argtypes = []
+    L.dabgpu_eti_read_dev.argtypes = [vp, C.POINTER(EtiReadEntry), i, vp]
+    L.dabgpu_eti_read_host.argtypes = [C.POINTER(EtiReadEntry), i]
     L.dabgpu_fig_user_applications.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
@@ -1622,6 +1675,57 @@ class Context:
                               frame_stride=frame_stride)
         self.sync()
         return out, status, state_out
+
+    def eti_read_dev(self, entries, stream=None):
+        """ETI(NI) byte streams -> FIBs, CRC flags and logical frames on the device (dabgpu_eti_read_dev): entries is a list
+        of EtiReadEntry (device addresses), each a stream with its own plan, byte count and state.  Enqueues only."""
+        n = len(entries)
+        arr = (EtiReadEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_eti_read_dev(self._h, arr, n, stream), "dabgpu_eti_read_dev")
+
+    def eti_read(self, bytes_tensor, streams, state=None):
+        """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams ETI(NI)
+        byte streams of ONE multiplex (n_bytes a multiple of 16 unless there is one stream, so that every row is aligned); streams: [(subchannel_id,
+        Subchannel) or EtiStream, ...], or None for the discovery pass (only the FIC leaves).  state: what an earlier call on
+        the same streams returned (None: the streams start here).
+        -> (fib uint8 [n_streams][max_frames][3][32], crc_ok uint8 [n_streams][max_frames][3], outs: one uint8 tensor
+        [n_streams][max_frames][bitrate * 3] per stream in the order of `streams`, status uint8 [n_streams][max_frames][16]
+        (view as ETI_READ_STATUS_DTYPE on the host), result uint8 [n_streams][48] (ETI_READ_RESULT_DTYPE), state); device
+        tensors, zero behind a stream's emitted rows; the work is finished when the call returns."""
+        import torch
+        if bytes_tensor.dtype != torch.uint8 or bytes_tensor.dim() != 2 or not bytes_tensor.is_contiguous() or \
+                (bytes_tensor.shape[0] > 1 and bytes_tensor.shape[1] % 16) or bytes_tensor.data_ptr() % 16:
+            raise ValueError("bytes_tensor must be a contiguous, 16-byte aligned uint8 tensor [n_streams][n_bytes], n_bytes a multiple of 16 "
+                             "unless there is one stream")
+        plan, items = None, []
+        if streams is not None:
+            items = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+            plan = eti_layout(items)
+        dev = bytes_tensor.device
+        n_streams, n_bytes = bytes_tensor.shape
+        rows = eti_read_max_frames(n_bytes)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        fib = torch.zeros((n_streams, rows, 3, 32), **u8)
+        ok = torch.zeros((n_streams, rows, 3), **u8)
+        outs = [torch.zeros((n_streams, rows, s.sc.bitrate_kbps * 3), **u8) for s in items]
+        status = torch.zeros((n_streams, rows, 16), **u8)
+        result = torch.zeros((n_streams, 48), **u8)
+        state_out = torch.empty((n_streams, eti_read_state_bytes()), **u8)
+        entries, keep = [], []
+        for s in range(n_streams):
+            ptrs = (C.c_void_p * max(len(items), 1))(*[o[s].data_ptr() if rows else 0 for o in outs])
+            keep.append(ptrs)
+            entries.append(EtiReadEntry(bytes_tensor[s].data_ptr() if n_bytes else None, n_bytes, 0,
+                                        C.pointer(plan) if plan is not None else None,
+                                        C.cast(ptrs, C.POINTER(C.c_void_p)) if plan is not None else None,
+                                        None if state is None else state[s].data_ptr(), state_out[s].data_ptr(),
+                                        fib[s].data_ptr() if rows else None, ok[s].data_ptr() if rows else None,
+                                        status[s].data_ptr() if rows else None, result[s].data_ptr()))
+        # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
+        torch.cuda.current_stream(dev).synchronize()
+        self.eti_read_dev(entries)
+        self.sync()
+        return fib, ok, outs, status, result, state_out
 
     def dabplus_superframes(self, sfs, bitrate_kbps, out=None, status=None):
         """sfs: uint8 [n][>=15*bitrate] aligned super-frames -> (data [n][110*s], status [n] SUPERFRAME_STATUS_DTYPE).

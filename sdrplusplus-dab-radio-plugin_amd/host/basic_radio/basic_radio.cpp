@@ -114,15 +114,65 @@ void BasicRadio::Process(tcb::span<const viterbi_bit_t> buf) {
 }
 
 // FIB counters, the On_FIC observers and the FIG parser (mutex held)
-void BasicRadio::process_fibs_locked() {
-    for (uint8_t ok : m_crc) {
+void BasicRadio::process_fibs_locked() { process_fibs_locked(m_fib.data(), m_crc.data(), m_crc.size()); }
+
+void BasicRadio::process_fibs_locked(const uint8_t *fib, const uint8_t *crc, size_t n_fibs) {
+    for (size_t i = 0; i < n_fibs; i++) {
         m_total_fibs++;
-        if (!ok) m_total_fib_errors++;
+        if (!crc[i]) m_total_fib_errors++;
     }
-    m_obs_fic.Notify(tcb::span<const uint8_t>(m_fib.data(), m_fib.size()),
-                     tcb::span<const uint8_t>(m_crc.data(), m_crc.size()));
-    for (size_t i = 0; i < m_crc.size(); i++)
-        if (m_crc[i]) m_fic_parser.ProcessFIB(tcb::span<const uint8_t>(m_fib.data() + 32 * i, 32));
+    m_obs_fic.Notify(tcb::span<const uint8_t>(fib, 32 * n_fibs), tcb::span<const uint8_t>(crc, n_fibs));
+    for (size_t i = 0; i < n_fibs; i++)
+        if (crc[i]) m_fic_parser.ProcessFIB(tcb::span<const uint8_t>(fib + 32 * i, 32));
+}
+
+void BasicRadio::ProcessEti(tcb::span<const uint8_t> bytes) {
+    namespace er = dabgpu_eti_read;
+    std::lock_guard<std::mutex> lock(m_mutex);
+    // S = the tail the last call left + the new bytes
+    m_eti_stream.insert(m_eti_stream.end(), bytes.begin(), bytes.end());
+    er::Result c{};
+    bool have = m_eti_head.have_prev != 0, any = false;
+    uint32_t fct = m_eti_head.last_fct, fp = m_eti_head.last_fp;
+    const size_t p = er::walk(m_eti_stream.data(), m_eti_stream.size(), nullptr, c,
+                              [&](uint32_t, uint32_t at, int verdict, const er::Fields &f, const er::PtrFrame &g) {
+        uint32_t fib_ok = 0;
+        if (verdict == er::TAKEN) {
+            // the FIC: three FIBs, their CRCs judged here
+            const uint8_t *fic = g.p + f.fic_offset;
+            uint8_t ok[3];
+            for (int j = 0; j < 3; j++) {
+                ok[j] = er::fib_crc_ok(g, f, j);
+                fib_ok |= uint32_t(ok[j]) << j;
+            }
+            process_fibs_locked(fic, ok, 3);
+            // the sub-channels: stream k of the frame's own STC goes to the open sub-channel at its start address
+            size_t off = size_t(f.fic_offset) + er::FIC_BYTES;
+            for (int k = 0; k < f.nst; k++) {
+                const uint8_t *stc = g.p + 8 + 4 * k;
+                const int sad = ((stc[0] & 3) << 8) | stc[1], nbytes = 8 * (((stc[2] & 3) << 8) | stc[3]);
+                for (size_t i = 0; i < m_subchannels.size(); i++) {
+                    Subchannel &s = m_subchannels[i];
+                    if (s.desc.start_address != sad || s.nbytes != nbytes) continue;
+                    const tcb::span<const uint8_t> lf(g.p + off, size_t(nbytes));
+                    m_obs_msc.Notify(int(i), lf);
+                    if (s.dab_plus) s.dab_plus->Process(lf);
+                    if (s.dab) s.dab->Process(lf);
+                    if (s.packet) s.packet->Process(lf);
+                }
+                off += size_t(nbytes);
+            }
+            // sub-channels the FIC has announced by now are fed from the next frame on
+            if (m_auto_channels) update_channels_from_database();
+        }
+        const er::Status st = er::make_status(at, verdict, f, fib_ok, have, fct, fp);
+        have = any = true;
+        fct = uint32_t(f.fct);
+        fp = uint32_t(f.fp);
+        return st;
+    });
+    m_eti_head = er::next_head(m_eti_head, c, any, fct, fp);
+    m_eti_stream.erase(m_eti_stream.begin(), m_eti_stream.begin() + std::ptrdiff_t(p));
 }
 
 // what the per-frame call needs to know of a sub-channel the FIC has described; false: a profile it cannot decode

@@ -26,6 +26,7 @@
 #include "dab/database/dab_database_updater.h"
 #include "dab/fic/fic_parser.h"
 #include "dabgpu.h"
+#include "dabgpu_eti_read.h"
 #include "utility/gpu_buffers.h"
 #include "utility/observable.h"
 #include "utility/span.h"
@@ -39,6 +40,14 @@ public:
     BasicRadio &operator=(const BasicRadio &) = delete;
 
     void Process(tcb::span<const viterbi_bit_t> buf);
+    // The contribution side: the next bytes of an ETI(NI) byte stream (raw 6144-byte frames; cut anywhere, bytes may be
+    // missing) instead of soft bits.  The header-only walk of include/dabgpu_eti_read.h runs on the host -- frames found,
+    // both CRCs checked, resynchronised after damage, the unfinished tail kept for the next call -- and every taken frame's
+    // FIBs go where Process sends them and its sub-channels' bytes to the channels Process feeds (the multiplex is read
+    // from the frame's own STC and matched by start address).  No call into libdabgpu.
+    void ProcessEti(tcb::span<const uint8_t> bytes);
+    // running totals of ProcessEti: rows, taken, bad_data_crc, skipped, resyncs, gap_sum, fib_errors; tail_bytes held
+    const dabgpu_eti_read::Head &GetEtiReadTotals() const { return m_eti_head; }
     std::mutex &GetMutex() { return m_mutex; }
     Observable<subchannel_id_t, Basic_Audio_Channel &> &On_Audio_Channel() { return m_obs_audio_channel; }
     // read under GetMutex(), as the GUI does (/root/reference/src/render_radio_block.cpp:124, 158-160, 239, 755)
@@ -88,6 +97,7 @@ private:
     void update_packet_channels();
     void update_channels_from_database();
     void process_fibs_locked();
+    void process_fibs_locked(const uint8_t *fib, const uint8_t *crc, size_t n_fibs);
     int add_subchannel_locked(const dabgpu_subchannel &sc);
     const DAB_Parameters m_params;
     dabgpu_ctx *m_ctx;
@@ -114,4 +124,6 @@ private:
     bool m_auto_channels = true;
     int m_total_unsupported = 0;
     int m_total_frames_lost = 0;
+    dabgpu_eti_read::Head m_eti_head{};                  // ProcessEti: the state between calls, its tail in m_eti_stream
+    std::vector<uint8_t> m_eti_stream;                   // S of the current call; what the walk leaves is the next call's tail
 };
