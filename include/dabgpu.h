@@ -1365,6 +1365,176 @@ int dabgpu_eti_read_dev(dabgpu_ctx *ctx, const dabgpu_eti_read_entry *entries, i
 int dabgpu_eti_read_host(const dabgpu_eti_read_entry *entries, int n_entries);
 
 /* ------------------------------------------------------------------------ */
+/* EDI output: the decode call's buffers written   */
+/* as EDI -- ETSI TS 102 693 over the AF layer of TS 102 821 -- one AF packet    */
+/* per CIF.  The format is stated as known, a line per field, at the top of      */
+/* include/dabgpu_edi.h; parity with other EDI tools is not pinned.  A packet is  */
+/*   10 AF header ("AF", LEN, SEQ, AR = 0x90, PT = 'T')                           */
+/*   16 "*ptr" item naming "DETI";  110 "deti" item: dlfc, STAT, MID = 1, FP,      */
+/*      MNSC = FFFF and the 96 FIC bytes (no time stamp)                          */
+/*   11 + 8 STL per stream: "est" n, SCID / SAD / TPL, its bytes of this CIF,      */
+/*      streams by ascending SAD as in the ETI frame                              */
+/*   zero padding to a payload of a multiple of 8 bytes;  2 CRC (the FIB's rule)   */
+/* so a plan's packet has one size, 12 + 8 k bytes.  Everything the ETI writer     */
+/* decides is decided here by the same device code: the FIC delay of 15 CIFs and   */
+/* dabgpu_eti_history -- a history one writer left continues the other --, warm-up,  */
+/* the FIG 0/0 anchor, d_cif_start, COUNT_MISMATCH, dabgpu_eti_status with length =  */
+/* the packet's bytes); STAT is the byte the ETI writer puts into ERR.  The CIF      */
+/* count travels whole: dlfc = 0 .. 4999.                                          */
+/*                                                                                */
+/* dabgpu_edi_packet_bytes   host only: the size of the plan's packet, or           */
+/*            DABGPU_ERR_ARG for a plan dabgpu_eti_layout did not make.             */
+/* dabgpu_edi_frames_dev   the arguments of dabgpu_eti_frames_dev, and: seq_start    */
+/*            a HOST array [n_streams] or NULL (= 0): packet t of stream s gets SEQ   */
+/*            seq_start[s] + t modulo 65536 (the caller adds 4 frames_per_stream      */
+/*            per call, and may do so as soon as the call has returned, whatever      */
+/*            memory the array lies in: it is copied before the call returns); the    */
+/*            output is a byte stream per ensemble, the call's                        */
+/*            4 frames_per_stream packets back to back from d_edi + s stream_stride   */
+/*            (d_edi and stream_stride 16-byte aligned, stream_stride >=              */
+/*            4 frames_per_stream packet bytes), ready for one write().  Bytes         */
+/*            behind a stream's packets are not touched.  Two launches, no             */
+/*            synchronisation (the first call on a context, or one with more streams   */
+/*            than any before, waits for the stream once while its stage area grows).  */
+/*            A refused call (DABGPU_ERR_ARG) enqueues nothing.                        */
+/* dabgpu_edi_parse   host only.  Checks one AF packet of exactly len bytes -- header, */
+/*            CRC, the TAG items, what makes it a DETI packet -- and gives its parts.   */
+/*            Returns DABGPU_OK, DABGPU_ERR_ARG for a NULL argument, or a positive      */
+/*            DABGPU_EDI_* (info is filled as far as the check that failed).            */
+/* dabgpu_edi_streams_from_packet   host only.  The list dabgpu_eti_layout takes, read   */
+/*            from a DETI packet's est items by dabgpu_eti_streams_from_frame's own      */
+/*            mapping from TPL / STL to a sub-channel.  DABGPU_ERR_ARG for a packet      */
+/*            dabgpu_edi_parse does not pass or a TPL / STL pair that names no profile.  */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_EDI_MAX_PACKET 8192     /* header and CRC included: what the reader takes for a packet */
+#define DABGPU_EDI_BAD_HEADER 1        /* "AF", LEN against len and MAX_PACKET, AR, PT                  */
+#define DABGPU_EDI_BAD_CRC    2
+#define DABGPU_EDI_BAD_TAGS   3        /* malformed: an item overruns, a deti / est / *ptr of a wrong length, a count out of range */
+#define DABGPU_EDI_NOT_DETI   4        /* well formed, but not exactly one deti, est numbers not 1..N once each, or a foreign *ptr */
+
+typedef struct dabgpu_edi_info {
+    int32_t len;                       /* LEN: the payload's bytes                                   */
+    int32_t length;                    /* 12 + len                                                   */
+    int32_t seq, crc;                  /* as stored in the packet                                    */
+    int32_t n_ptr, n_deti, n_other;    /* items of these names (n_other: names stepped over)         */
+    int32_t atstf, ficf, rfudf;        /* the deti item's flags                                      */
+    int32_t dlfc;                      /* 250 FCTH + FCT                                             */
+    int32_t stat, mid, fp, mnsc;
+    int32_t utco, tsta;                /* when atstf (tsta 0xFFFFFF otherwise)                       */
+    uint32_t seconds;
+    int32_t fic_offset;                /* where the 96 FIC bytes begin in the packet, -1 without     */
+    int32_t nst;                       /* est items (of a DETI packet)                               */
+    int32_t reserved[4];
+    int32_t scid[DABGPU_ETI_MAX_STREAMS], sad[DABGPU_ETI_MAX_STREAMS], tpl[DABGPU_ETI_MAX_STREAMS],
+            stl[DABGPU_ETI_MAX_STREAMS];     /* of est k + 1                                          */
+    int32_t offset[DABGPU_ETI_MAX_STREAMS];  /* where its 8 stl bytes begin in the packet             */
+} dabgpu_edi_info;
+
+int dabgpu_edi_packet_bytes(const dabgpu_eti_plan *plan);
+int dabgpu_edi_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_streams, int frames_per_stream,
+                          const uint8_t *d_fib, const uint8_t *d_crc_ok, const uint8_t *const *d_out,
+                          const dabgpu_eti_history *d_history_in, dabgpu_eti_history *d_history_out,
+                          const int32_t *d_cif_start, const uint32_t *seq_start, uint8_t *d_edi, size_t stream_stride,
+                          dabgpu_eti_status *d_status, void *stream);
+int dabgpu_edi_parse(const uint8_t *packet, size_t len, dabgpu_edi_info *info);
+int dabgpu_edi_streams_from_packet(const uint8_t *packet, size_t len, dabgpu_eti_stream *streams, int *n);
+
+/* ------------------------------------------------------------------------ */
+/* EDI input: AF packet byte streams -- a TCP        */
+/* capture, a file -- read back into what the decode call leaves, as the ETI(NI)  */
+/* reader does, on the device or on host memory.  The contract -- stream, H and C, the walk, what   */
+/* is judged how, rows, status, state -- is written out in include/dabgpu_edi.h.   */
+/* In short, per entry: S = the state's carried tail (0..8191 bytes) + the         */
+/* n_bytes new bytes.  A position holds a packet when its ten header bytes are      */
+/* plausible, the packet lies inside S and its CRC holds; the walk steps from       */
+/* packet to packet and searches for the next one where there is none (skipped,     */
+/* resyncs), never trusting the LEN of a packet whose CRC fails.  A CRC-good         */
+/* packet that is malformed (bad_tags), not a DETI packet (not_deti) or of another   */
+/* multiplex than the plan's (other_plan) is counted and gives no row.  Every other  */
+/* is row r: its FIC to d_fib[r] (zero with DABGPU_EDI_READ_NO_FIC), the three FIB    */
+/* CRC flags computed here to d_crc_ok[r], stream k's bytes to d_out[k][r] for every   */
+/* d_out[k] that is not NULL (the caller's order, through plan->order).  plan NULL     */
+/* is the discovery pass: every DETI packet is a row, only FIC and status leave;        */
+/* dabgpu_edi_streams_from_packet reads the multiplex from a row's packet (offset and   */
+/* length in its status).  What is left (below 8192 bytes) is the new tail.  CIFs       */
+/* missing by dlfc are NOT replaced by zero rows: status gap says how many are           */
+/* missing in front of a row, exactly (modulo 5000), and SEQ_BREAK that packets are.     */
+/*                                                                                     */
+/* dabgpu_edi_read_max_rows   rows one entry can emit: (8191 + n_bytes) / m with m the     */
+/*            smallest packet that gives a row, 26 in discovery and                       */
+/*            26 + sum(11 + 8 STL) with a plan.  Its outputs hold this many.  Never 0.     */
+/*            DABGPU_ERR_ARG for n_bytes outside 0 .. 2^30 or a plan dabgpu_eti_layout      */
+/*            did not make.                                                                */
+/* dabgpu_edi_read_state_bytes   size of the per-entry state record (a head of 96 bytes,     */
+/*            then 8192 tail bytes).  All zero = a stream that starts.  Written whole.  A     */
+/*            record the library did not write makes no call read outside it.                */
+/* dabgpu_edi_read_dev   entries: HOST array (at most 65535) with the fields of                  */
+/*            dabgpu_eti_read_entry and the same alignments (d_bytes, the states, d_fib,          */
+/*            d_status 16 bytes; d_result 4; every d_out[k] 8), d_state_in and d_state_out not     */
+/*            overlapping, d_fib / d_crc_ok / d_status never NULL; d_out a HOST array of           */
+/*            plan->nst DEVICE pointers or NULL.  No byte outside [d_bytes, d_bytes + n_bytes)      */
+/*            is read.  Two launches -- every position's header test and the CRCs of the hits,      */
+/*            then a wave per entry that walks, judges and moves -- no synchronisation (but once     */
+/*            while the stage area grows), no global atomic.  Everything is checked before           */
+/*            anything is enqueued: a refused call (DABGPU_ERR_ARG) writes nothing.  A stream that    */
+/*            is header-plausible every 10 bytes costs at most n / 10 CRCs of at most 8 KB each:      */
+/*            the bound is stated, not optimised.                                                     */
+/* dabgpu_edi_read_host   the same on host pointers (no context, no device): the serial walk of        */
+/*            the same header.                                                                        */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_EDI_READ_GAP         1  /* status flags: gap != 0                                               */
+#define DABGPU_EDI_READ_SEQ_BREAK   2  /* SEQ is not the previous CRC-good packet's + 1                         */
+#define DABGPU_EDI_READ_FP_MISMATCH 4  /* FP != dlfc mod 8                                                      */
+#define DABGPU_EDI_READ_STAT_FIELD  8  /* STAT is not 0xFF (the writer's warm-up packets included)              */
+#define DABGPU_EDI_READ_FIB_CRC    16  /* a FIB of the row failed its CRC                                       */
+#define DABGPU_EDI_READ_NO_FIC     32  /* FICF = 0: the row's FIC and flags are zero                            */
+#define DABGPU_EDI_READ_TIME       64  /* ATSTF = 1: utco, seconds and tsta are the packet's                    */
+
+typedef struct dabgpu_edi_read_status { /* per row, 32 bytes */
+    uint32_t offset;                   /* of the packet in S                                         */
+    uint16_t length;                   /* 12 + LEN                                                   */
+    uint16_t dlfc;                     /* 0 .. 4999                                                  */
+    uint16_t seq;
+    uint16_t gap;                      /* (dlfc - (previous row's dlfc + 1)) mod 5000; 0 for the first */
+    uint8_t  fp, stat, mid;            /* the deti item's                                            */
+    uint8_t  fib_ok;                   /* bit j = FIB j passed its CRC                               */
+    uint8_t  flags;                    /* DABGPU_EDI_READ_*                                          */
+    uint8_t  utco;
+    uint8_t  reserved[2];              /* 0                                                          */
+    uint32_t seconds, tsta;            /* 0 / 0xFFFFFF without DABGPU_EDI_READ_TIME                  */
+    uint32_t reserved2;                /* 0                                                          */
+} dabgpu_edi_read_status;
+
+typedef struct dabgpu_edi_read_result { /* per entry and call, 48 bytes */
+    uint32_t rows;                     /* rows emitted                                               */
+    uint32_t not_deti, bad_tags, other_plan; /* CRC-good packets that gave no row                    */
+    uint32_t skipped, resyncs;         /* bytes stepped over; stretches of them                      */
+    uint32_t gap_sum;                  /* sum of the rows' gaps                                      */
+    uint32_t fib_errors;               /* FIBs of rows with a FIC that failed their CRC              */
+    uint32_t tail_bytes;               /* held in the new state                                      */
+    uint32_t reserved[3];              /* 0                                                          */
+} dabgpu_edi_read_result;
+
+typedef struct dabgpu_edi_read_entry {
+    const uint8_t *d_bytes;            /* the new bytes                                              */
+    int32_t n_bytes;                   /* 0 .. 2^30                                                  */
+    int32_t reserved;                  /* 0                                                          */
+    const dabgpu_eti_plan *plan;       /* NULL = discovery                                           */
+    uint8_t *const *d_out;             /* array [plan->nst] of pointers, or NULL                     */
+    const void *d_state_in;            /* or NULL                                                    */
+    void *d_state_out;
+    uint8_t *d_fib;                    /* [max_rows][3][32]                                          */
+    uint8_t *d_crc_ok;                 /* [max_rows][3]                                              */
+    dabgpu_edi_read_status *d_status;  /* [max_rows]                                                 */
+    dabgpu_edi_read_result *d_result;
+} dabgpu_edi_read_entry;
+
+size_t dabgpu_edi_read_state_bytes(void);
+int dabgpu_edi_read_max_rows(int n_bytes, const dabgpu_eti_plan *plan);
+int dabgpu_edi_read_dev(dabgpu_ctx *ctx, const dabgpu_edi_read_entry *entries, int n_entries, void *stream);
+int dabgpu_edi_read_host(const dabgpu_edi_read_entry *entries, int n_entries);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

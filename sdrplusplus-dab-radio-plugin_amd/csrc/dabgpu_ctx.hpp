@@ -78,6 +78,8 @@ enum StageSlot {
     STAGE_PACKET_CAROUSEL = 21,      // dabgpu_packet_carousel_dev: the entry table, what it adds per entry, the scan records
     STAGE_PACKET_GROUPS = 22,        // dabgpu_packet_groups_dev: the scan's table, this call's table, the scan records
     STAGE_ETI_READ = 23,             // dabgpu_eti_read_dev: the entry table, the candidate bitmaps and the row lists
+    STAGE_EDI = 24,                  // dabgpu_edi_frames_dev: per stream the CIF count of the pre-pass and the first sequence number
+    STAGE_EDI_READ = 25,             // dabgpu_edi_read_dev: the entry table and the two bitmaps of every entry
     STAGE_SLOTS
 };
 

@@ -16,7 +16,7 @@
 // cross-lane exchanges.  The start value 0xFFFF contributes 0xFFFF x^(8 L) mod P, one more constant, and the result is
 // inverted.  The header CRC changes from frame to frame only through FCT and FP: the host computes it once with both
 // zero and the kernel adds the two bytes' own remainders.
-#include "kernels.hpp"
+#include "eti_cif.hpp"
 
 namespace dabk {
 
@@ -30,33 +30,6 @@ constexpr int ETI_WAVES = ETI_WG / 64;
 constexpr int ETI_FRAME_WORDS = ETI_FRAME_BYTES / 4;
 constexpr int ETI_FIC_WORDS = ETI_FIC_BYTES / 4;
 constexpr int ETI_MAP_WORDS = 768;             // 8-byte words of sub-channel data a frame can hold (< 6144 / 8)
-constexpr uint32_t ETI_POLY = 0x11021u;
-constexpr int FLAG_WARMUP = 1, FLAG_FIB_CRC = 2, FLAG_NO_ANCHOR = 4, FLAG_COUNT_MISMATCH = 8;
-
-// a(x) b(x) mod P, b's lowest `bits` bits
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b, int bits) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = bits - 1; i >= 0; i--) {
-        r <<= 1;
-        if (r & 0x10000u) r ^= ETI_POLY;
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-
-// the count a valid first FIB that begins with FIG 0/0 carries, or -1 (w0 / w1: its first two little-endian words)
-__device__ __forceinline__ int fig0_0_count(uint32_t w0, uint32_t w1, int crc_ok) {
-    const int upper = int(w1 & 0x1fu), lower = int((w1 >> 8) & 0xffu);
-    if (!crc_ok || (w0 & 0xffffu) != 0x0005u || upper >= 20 || lower >= 250) return -1;
-    return upper * 250 + lower;
-}
-
-__device__ __forceinline__ int history_valid(const EtiHistory *h) {
-    if (!h) return 0;
-    const int v = h->valid;
-    return v < 0 ? 0 : v > ETI_FIC_DELAY ? ETI_FIC_DELAY : v;
-}
 
 __global__ __launch_bounds__(ETI_WG) void eti_anchor_kernel(EtiAnchorArgs p) {
     __shared__ int s_anchor;
@@ -65,12 +38,12 @@ __global__ __launch_bounds__(ETI_WG) void eti_anchor_kernel(EtiAnchorArgs p) {
     const uint8_t *fib = p.fib + size_t(s) * n_cif * ETI_FIC_BYTES;         // [n_cif][96]: 4 groups of 3 FIBs per frame
     const uint8_t *ok = p.crc_ok + size_t(s) * n_cif * 3;
     const EtiHistory *hin = p.history_in ? p.history_in + s : nullptr;
-    const int valid_in = history_valid(hin);
+    const int valid_in = eti_history_valid(hin);
     if (tid == 0) s_anchor = 0x7fffffff;
     __syncthreads();
     for (int c = tid; c < n_cif; c += ETI_WG) {
         const uint32_t *w = reinterpret_cast<const uint32_t *>(fib + size_t(c) * ETI_FIC_BYTES);
-        if (fig0_0_count(w[0], w[1], ok[c * 3]) >= 0) {
+        if (eti_fig0_0_count(w[0], w[1], ok[c * 3]) >= 0) {
             atomicMin(&s_anchor, c);
             break;
         }
@@ -83,7 +56,7 @@ __global__ __launch_bounds__(ETI_WG) void eti_anchor_kernel(EtiAnchorArgs p) {
         base = start % ETI_CIF_COUNTS;
     } else if (anchor < n_cif) {
         const uint32_t *w = reinterpret_cast<const uint32_t *>(fib + size_t(anchor) * ETI_FIC_BYTES);
-        const int count = fig0_0_count(w[0], w[1], 1);
+        const int count = eti_fig0_0_count(w[0], w[1], 1);
         base = (count + ETI_CIF_COUNTS - anchor % ETI_CIF_COUNTS) % ETI_CIF_COUNTS;
     } else {
         no_anchor = 1;
@@ -134,12 +107,7 @@ __global__ __launch_bounds__(ETI_WG) void eti_frame_kernel(EtiArgs a) {
     uint32_t *W = s_frame[wave];
 
     // per workgroup: the byte table of the CRC, the sub-channel of every data word, the sources
-    {
-        uint32_t r = uint32_t(tid) << 8;
-#pragma unroll
-        for (int i = 0; i < 8; i++) r = (r & 0x8000u) ? ((r << 1) ^ ETI_POLY) : (r << 1);
-        s_tab[tid] = uint16_t(r);
-    }
+    s_tab[tid] = eti_crc_table_entry(tid);
     if (tid < a.nst) {
         s_src[tid] = (unsigned long long)(uintptr_t)a.out[tid] - a.offset[tid];
         s_bytes[tid] = a.bytes[tid];
@@ -161,31 +129,17 @@ __global__ __launch_bounds__(ETI_WG) void eti_frame_kernel(EtiArgs a) {
     uint32_t flags = 0, fib_ok = 0;
     int count = 0;
     if (live) {
-        const int c = t - ETI_FIC_DELAY;
-        const EtiHistory *hin = a.history_in ? a.history_in + s : nullptr;
-        const bool warm = c < 0 && t < ETI_FIC_DELAY - history_valid(hin);
-        const uint8_t *fic = c >= 0 ? a.fib + (size_t(s) * n_cif + c) * ETI_FIC_BYTES : warm ? nullptr : hin->fib[t];
-        const uint8_t *ok = c >= 0 ? a.crc_ok + (size_t(s) * n_cif + c) * 3 : warm ? nullptr : hin->crc_ok[t];
-        const int base = a.base[s];
-        count = ((base & 0xffff) + t + ETI_CIF_COUNTS - ETI_FIC_DELAY) % ETI_CIF_COUNTS;
-        int own = -1;
-        if (!warm) {
-            const uint32_t *w = reinterpret_cast<const uint32_t *>(fic);
-            fib_ok = (ok[0] ? 1u : 0u) | (ok[1] ? 2u : 0u) | (ok[2] ? 4u : 0u);
-            own = fig0_0_count(w[0], w[1], int(fib_ok & 1u));
-            if (lane < ETI_FIC_WORDS) W[fic_word + lane] = w[lane];
-        } else if (lane < ETI_FIC_WORDS) {
-            W[fic_word + lane] = 0u;
-        }
-        flags = (warm ? FLAG_WARMUP : fib_ok != 7u ? FLAG_FIB_CRC : 0) | ((base >> 16) & 1 ? FLAG_NO_ANCHOR : 0) |
-                (own >= 0 && own != count ? FLAG_COUNT_MISMATCH : 0);
+        const EtiCif cif = eti_cif(a.fib, a.crc_ok, a.history_in, a.base, s, t, n_cif);
+        count = cif.count;
+        fib_ok = cif.fib_ok;
+        flags = cif.flags;
+        if (lane < ETI_FIC_WORDS) W[fic_word + lane] = cif.fic ? reinterpret_cast<const uint32_t *>(cif.fic)[lane] : 0u;
         const uint32_t fct = uint32_t(count % 250), fp = uint32_t(count & 7) << 5;
         if (lane < a.nst) W[2 + lane] = a.header[2 + lane];
         if (lane == 0) {
-            const uint32_t err = warm ? 0x00u : fib_ok == 7u ? 0xFFu : 0xE1u;
-            W[0] = err | ((fct & 1u) ? 0x49C5F800u : 0xB63A0700u);
+            W[0] = cif.err | ((fct & 1u) ? 0x49C5F800u : 0xB63A0700u);
             W[1] = a.header[1] | fct | (fp << 16);
-            const uint32_t hc = uint32_t(a.header_crc0) ^ gf_mul(a.fct_shift, fct, 8) ^ gf_mul(a.fp_shift, fp, 8);
+            const uint32_t hc = uint32_t(a.header_crc0) ^ eti_gf_mul(a.fct_shift, fct, 8) ^ eti_gf_mul(a.fp_shift, fp, 8);
             W[2 + a.nst] = 0xFFFFu | ((hc >> 8) << 16) | ((hc & 0xffu) << 24);
         }
         // the sub-channels' bytes of this CIF: 8-byte words, four loads in flight per lane
@@ -225,7 +179,7 @@ __global__ __launch_bounds__(ETI_WG) void eti_frame_kernel(EtiArgs a) {
                 crc = ((crc << 8) & 0xffffu) ^ s_tab[(crc >> 8) ^ (v >> 24)];
             }
         }
-        uint32_t r = gf_mul(crc, a.lane_shift[lane], 16);
+        uint32_t r = eti_gf_mul(crc, a.lane_shift[lane], 16);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) r ^= uint32_t(__shfl_xor(int(r), d, 64));
         r = (r ^ a.data_init ^ 0xffffu) & 0xffffu;
@@ -253,11 +207,19 @@ __global__ __launch_bounds__(ETI_WG) void eti_frame_kernel(EtiArgs a) {
 
 }  // namespace
 
+hipError_t launch_eti_anchor(const EtiAnchorArgs &p, hipStream_t s) {
+    if (p.n_streams <= 0 || p.frames_per_stream <= 0) return hipSuccess;
+    if (!p.fib || !p.crc_ok || !p.base) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(eti_anchor_kernel, dim3(unsigned(p.n_streams)), dim3(ETI_WG), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_eti(const EtiAnchorArgs &p, const EtiArgs &a, hipStream_t s) {
     if (a.n_streams <= 0 || a.frames_per_stream <= 0) return hipSuccess;
-    if (!a.fib || !a.crc_ok || !a.base || !a.eti || !a.status || p.base != a.base) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(eti_anchor_kernel, dim3(unsigned(a.n_streams)), dim3(ETI_WG), 0, s, p);
-    hipError_t e = hipGetLastError();
+    if (!a.fib || !a.crc_ok || !a.base || !a.eti || !a.status || p.base != a.base || p.n_streams != a.n_streams ||
+        p.frames_per_stream != a.frames_per_stream)
+        return hipErrorInvalidValue;
+    hipError_t e = launch_eti_anchor(p, s);
     if (e != hipSuccess) return e;
     const long long total = (long long)a.n_streams * a.frames_per_stream * 4;
     hipLaunchKernelGGL(eti_frame_kernel, dim3(unsigned((total + ETI_WAVES - 1) / ETI_WAVES)), dim3(ETI_WG), 0, s, a);

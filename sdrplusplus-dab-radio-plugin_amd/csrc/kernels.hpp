@@ -788,6 +788,53 @@ struct EtiAnchorArgs {
     int n_streams, frames_per_stream;
 };
 hipError_t launch_eti(const EtiAnchorArgs &p, const EtiArgs &a, hipStream_t s);
+// the pre-pass alone (the EDI writer's first launch)
+hipError_t launch_eti_anchor(const EtiAnchorArgs &p, hipStream_t s);
+
+// ---- EDI output (edi_kernels.hip; include/dabgpu_edi.h) ------------------------
+constexpr int EDI_MAX_WRITER_PACKET = 6640;    // what a plan that fits an ETI frame can need (6620), a multiple of 16
+// Everything a call's packets share, by value in the kernel arguments (~1.4 KB)
+struct EdiArgs {
+    const uint8_t *out[ETI_MAX_STREAMS];       // sub-channel k of the PACKET (plan order): [n_streams][n_cif][bytes[k]]
+    uint16_t offset[ETI_MAX_STREAMS];          // byte offset of its data among the sub-channels' data
+    uint16_t bytes[ETI_MAX_STREAMS];
+    uint8_t stc[4 * ETI_MAX_STREAMS];          // the plan's STC words
+    uint16_t lane_shift[64];                   // x^(8 chunk_bytes (63 - lane)) mod P
+    const uint8_t *fib, *crc_ok;
+    const EtiHistory *history_in;
+    const int32_t *base;                       // [n_streams] what the anchor pre-pass left
+    const uint32_t *seq_start;                 // [n_streams] DEVICE, or nullptr = 0
+    uint8_t *edi;
+    EtiStatus *status;
+    unsigned long long stream_stride;
+    int n_streams, frames_per_stream;
+    int nst, data_bytes;
+    int packet_bytes;
+    int chunk_bytes;                           // bytes of the packet in front of its CRC every lane folds
+    uint16_t crc_init;                         // 0xFFFF x^(8 (packet_bytes - 2)) mod P
+};
+hipError_t launch_edi(const EtiAnchorArgs &p, const EdiArgs &a, hipStream_t s);
+
+// ---- EDI input (edi_read_kernels.hip; include/dabgpu_edi.h) --------------------
+constexpr int EDI_READ_SPAN = 4096;            // byte positions a workgroup of the check launch judges
+constexpr int EDI_READ_MAX_ENTRIES = 65535;    // (the check launch's grid has an entry per y)
+// One entry of the table in device memory (addresses as integers)
+struct EdiReadEntry {
+    uint64_t bytes, state_in, state_out, fib, crc_ok, status, result;
+    uint64_t good;                             // scratch: bit q % 64 of word q / 64 = C(q) of the contract
+    uint64_t open;                             // scratch: ... = H(q) and the packet is incomplete
+    uint64_t out[ETI_MAX_STREAMS];             // stream k of the PACKET (plan order): [max_rows][8 STL], 0 = not wanted
+    int32_t n_bytes, max_rows, has_plan, nst;
+    uint8_t stc[4 * ETI_MAX_STREAMS];          // the plan's STC words
+};
+// positions an entry's S can have, whatever its state's tail holds, and the words of one bitmap over them
+inline size_t edi_read_positions(int n_bytes) { return size_t(n_bytes) + 8191u; }
+inline size_t edi_read_bitmap_words(int n_bytes) { return (edi_read_positions(n_bytes) + 63) / 64; }
+// scratch an entry needs behind the table: its two bitmaps (bytes, a multiple of 16)
+inline size_t edi_read_scratch_bytes(int n_bytes) { return (2 * edi_read_bitmap_words(n_bytes) * 8 + 15) / 16 * 16; }
+// entries: the host's table with everything but good and open filled in (this fills them); d_table: n_entries *
+// sizeof(EdiReadEntry) + the sum of edi_read_scratch_bytes, 16-byte aligned
+hipError_t launch_edi_read(EdiReadEntry *entries, int n_entries, void *d_table, hipStream_t s);
 
 // ---- ETI(NI) input (eti_read_kernels.hip) -------------------------------------
 constexpr int ETI_READ_SCAN_SPAN = 8192;       // byte positions a workgroup of the scan judges

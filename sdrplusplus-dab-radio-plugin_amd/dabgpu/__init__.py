@@ -65,6 +65,8 @@ EXPORTS = [
     "dabgpu_packet_groups_state_bytes", "dabgpu_packet_groups_chunk", "dabgpu_packet_groups_dev", "dabgpu_packet_groups_host",
     "dabgpu_fig_user_applications",
     "dabgpu_eti_read_state_bytes", "dabgpu_eti_read_dev", "dabgpu_eti_read_host",
+    "dabgpu_edi_packet_bytes", "dabgpu_edi_frames_dev", "dabgpu_edi_parse", "dabgpu_edi_streams_from_packet",
+    "dabgpu_edi_read_state_bytes", "dabgpu_edi_read_max_rows", "dabgpu_edi_read_dev", "dabgpu_edi_read_host",
 ]
 
 ABI_VERSION = 6
@@ -623,6 +625,107 @@ def eti_read_host(entries):
     _check(lib().dabgpu_eti_read_host(arr, n), "dabgpu_eti_read_host")
 
 
+#: EDI (include/dabgpu.h, "EDI output" / "EDI input"; include/dabgpu_edi.h): AF packets, one per CIF
+EDI_MAX_PACKET = 8192
+EDI_BAD_HEADER, EDI_BAD_CRC, EDI_BAD_TAGS, EDI_NOT_DETI = 1, 2, 3, 4
+EDI_PARSE_ERRORS = {1: "not an AF packet of this length (SYNC, LEN, AR, PT)", 2: "CRC", 3: "malformed TAG items",
+                    4: "not a DETI packet"}
+EDI_READ_GAP, EDI_READ_SEQ_BREAK, EDI_READ_FP_MISMATCH, EDI_READ_STAT_FIELD = 1, 2, 4, 8
+EDI_READ_FIB_CRC, EDI_READ_NO_FIC, EDI_READ_TIME = 16, 32, 64
+#: dabgpu_edi_read_status: one emitted row
+EDI_READ_STATUS_DTYPE = np.dtype([("offset", np.uint32), ("length", np.uint16), ("dlfc", np.uint16), ("seq", np.uint16),
+                                  ("gap", np.uint16), ("fp", np.uint8), ("stat", np.uint8), ("mid", np.uint8), ("fib_ok", np.uint8),
+                                  ("flags", np.uint8), ("utco", np.uint8), ("reserved", np.uint8, (2,)), ("seconds", np.uint32),
+                                  ("tsta", np.uint32), ("reserved2", np.uint32)])
+assert EDI_READ_STATUS_DTYPE.itemsize == 32
+#: dabgpu_edi_read_result: what one entry of edi_read_host counted in one call
+EDI_READ_RESULT_DTYPE = np.dtype([(f, np.uint32) for f in ("rows", "not_deti", "bad_tags", "other_plan", "skipped", "resyncs",
+                                                           "gap_sum", "fib_errors", "tail_bytes")] + [("reserved", np.uint32, (3,))])
+assert EDI_READ_RESULT_DTYPE.itemsize == 48
+#: the head of a state record of edi_read_host; the tail's 8192 bytes follow it
+EDI_READ_HEAD_DTYPE = np.dtype([("tail_bytes", np.uint32), ("have_prev", np.uint8), ("have_seq", np.uint8), ("in_skip", np.uint8),
+                                ("reserved", np.uint8), ("last_dlfc", np.uint16), ("last_seq", np.uint16), ("reserved1", np.uint32)] +
+                               [(f, np.uint64) for f in ("rows", "not_deti", "bad_tags", "other_plan", "skipped", "resyncs", "gap_sum",
+                                                         "fib_errors")] + [("reserved2", np.uint64, (2,))])
+assert EDI_READ_HEAD_DTYPE.itemsize == 96
+
+
+class EdiInfo(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("len", "length", "seq", "crc", "n_ptr", "n_deti", "n_other", "atstf", "ficf", "rfudf", "dlfc",
+                                         "stat", "mid", "fp", "mnsc", "utco", "tsta")] + \
+               [("seconds", C.c_uint32), ("fic_offset", C.c_int32), ("nst", C.c_int32), ("reserved", C.c_int32 * 4),
+                ("scid", C.c_int32 * 64), ("sad", C.c_int32 * 64), ("tpl", C.c_int32 * 64), ("stl", C.c_int32 * 64),
+                ("offset", C.c_int32 * 64)]
+
+
+class EdiReadEntry(EtiReadEntry):
+    """dabgpu_edi_read_entry: one byte stream of edi_read_host (host addresses); the fields of EtiReadEntry, d_fib / d_crc_ok /
+    d_status sized by edi_read_max_rows.  The Python objects behind plan and d_out must stay alive until the call has
+    returned."""
+
+
+def _edi_bytes(packet):
+    return np.ascontiguousarray(np.frombuffer(bytes(packet), np.uint8) if isinstance(packet, (bytes, bytearray)) else packet,
+                                np.uint8).reshape(-1)
+
+
+def edi_packet_bytes(plan):
+    """Bytes of the one AF packet size a plan's CIFs are written as (dabgpu_edi_packet_bytes: host only)."""
+    n = lib().dabgpu_edi_packet_bytes(C.byref(plan))
+    _check(min(n, 0), "dabgpu_edi_packet_bytes")
+    return n
+
+
+def edi_parse(packet):
+    """Check one AF packet (header, CRC, TAG items, what makes it a DETI packet; dabgpu_edi_parse: host only) and give its
+    parts: dict with len, length, seq, crc, dlfc, stat, mid, fp, mnsc, atstf, ficf, rfudf, utco, seconds, tsta, nst, streams
+    [{scid, sad, tpl, stl, data}], fic (96 bytes or None).  ValueError for anything else; its args[1] is the DABGPU_EDI_* code."""
+    f = _edi_bytes(packet)
+    info = EdiInfo()
+    rc = lib().dabgpu_edi_parse(_p(f), f.size, C.byref(info))
+    if rc < 0:
+        raise DabGpuError(rc, "dabgpu_edi_parse")
+    if rc > 0:
+        raise ValueError("not a DETI packet: " + EDI_PARSE_ERRORS.get(rc, str(rc)), rc)
+    streams = [{"scid": info.scid[k], "sad": info.sad[k], "tpl": info.tpl[k], "stl": info.stl[k],
+                "data": f[info.offset[k]:info.offset[k] + 8 * info.stl[k]].copy()} for k in range(info.nst)]
+    out = {k: getattr(info, k) for k in ("len", "length", "seq", "crc", "n_ptr", "n_deti", "n_other", "atstf", "ficf", "rfudf", "dlfc",
+                                         "stat", "mid", "fp", "mnsc", "utco", "tsta", "seconds", "nst")}
+    out["fic"] = f[info.fic_offset:info.fic_offset + 96].copy() if info.fic_offset >= 0 else None
+    out["streams"] = streams
+    return out
+
+
+def edi_streams(packet):
+    """The stream list of one DETI packet, read back from its est items (dabgpu_edi_streams_from_packet: host only):
+    [EtiStream, ...] in the packet's order, what eti_layout takes."""
+    f = _edi_bytes(packet)
+    arr = (EtiStream * ETI_MAX_STREAMS)()
+    n = C.c_int(0)
+    _check(lib().dabgpu_edi_streams_from_packet(_p(f), f.size, arr, C.byref(n)), "dabgpu_edi_streams_from_packet")
+    return [EtiStream(arr[k].subchannel_id, arr[k].sc) for k in range(n.value)]
+
+
+def edi_read_state_bytes():
+    """Bytes of one state record of edi_read_host (all zero = a stream that starts)."""
+    return int(lib().dabgpu_edi_read_state_bytes())
+
+
+def edi_read_max_rows(n_bytes, plan=None):
+    """Rows one entry of edi_read_host can emit in one call: its outputs hold this many (plan None: discovery)."""
+    n = lib().dabgpu_edi_read_max_rows(int(n_bytes), None if plan is None else C.byref(plan))
+    _check(min(n, 0), "dabgpu_edi_read_max_rows")
+    return n
+
+
+def edi_read_host(entries):
+    """AF packet byte streams -> FIBs, CRC flags and logical frames on HOST memory (entries: EdiReadEntry with host
+    addresses), serially, without a context or a GPU (dabgpu_edi_read_host)."""
+    n = len(entries)
+    arr = (EtiReadEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_edi_read_host(arr, n), "dabgpu_edi_read_host")
+
+
 #: ETI(NI) to IQ (include/dabgpu.h, "ETI(NI) to IQ"): dabgpu_mod_status, one transmission frame's record
 MOD_BAD_INPUT, MOD_MISALIGNED = 1, 2
 MOD_STATUS_DTYPE = np.dtype([("flags", np.uint32), ("refused", np.uint8), ("reserved", np.uint8, (3,))])
@@ -766,6 +869,15 @@ def load_library(path):
     L.dabgpu_eti_read_state_bytes.argtypes = []
     L.dabgpu_eti_read_dev.argtypes = [vp, C.POINTER(EtiReadEntry), i, vp]
     L.dabgpu_eti_read_host.argtypes = [C.POINTER(EtiReadEntry), i]
+    L.dabgpu_edi_packet_bytes.argtypes = [C.POINTER(EtiPlan)]
+    L.dabgpu_edi_frames_dev.argtypes = [vp, C.POINTER(EtiPlan), i, i, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    L.dabgpu_edi_parse.argtypes = [vp, sz, C.POINTER(EdiInfo)]
+    L.dabgpu_edi_streams_from_packet.argtypes = [vp, sz, vp, C.POINTER(C.c_int)]
+    L.dabgpu_edi_read_state_bytes.restype = C.c_size_t
+    L.dabgpu_edi_read_state_bytes.argtypes = []
+    L.dabgpu_edi_read_max_rows.argtypes = [i, C.POINTER(EtiPlan)]
+    L.dabgpu_edi_read_host.argtypes = [C.POINTER(EtiReadEntry), i]
+    L.dabgpu_edi_read_dev.argtypes = [vp, C.POINTER(EtiReadEntry), i, vp]
     L.dabgpu_fig_user_applications.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
@@ -1591,12 +1703,27 @@ class Context:
                                                d_history_in, d_history_out, d_cif_start, d_eti, d_status, stream),
                "dabgpu_eti_frames_dev")
 
-    def decode_frames_eti(self, soft, n_streams, streams, history=None):
-        """Soft bits (torch int8 tensor on this context's device, [n_streams*frames_per_stream][>= 230400]) -> ETI(NI):
-        decode_frames_dev + eti_frames_dev on device tensors.  streams: [(subchannel_id, Subchannel), ...].
-        history: what an earlier call on the same streams returned (None: the streams start here).
-        -> (eti uint8 [n_streams, n_cif, 6144], status uint8 [n_streams, n_cif, 8] (view as ETI_STATUS_DTYPE on the host),
-        history); all device tensors, the work is finished when the call returns."""
+    def edi_frames_dev(self, plan, n_streams, frames_per_stream, d_fib, d_crc_ok, d_out, d_edi, stream_stride, d_status,
+                       seq_start=None, d_history_in=None, d_history_out=None, d_cif_start=None, stream=None):
+        """EDI from what a decode call left on the device (dabgpu_edi_frames_dev): the arguments of eti_frames_dev -> one AF
+        packet per CIF, the 4 * frames_per_stream packets of stream s back to back from d_edi + s * stream_stride (both
+        16-byte aligned), d_status (ETI_STATUS_DTYPE, length = edi_packet_bytes(plan)).  seq_start: the first packet's SEQ per
+        stream (a sequence of n_streams numbers, None: 0).  Enqueues only."""
+        n = plan.nst
+        ptrs = (C.c_void_p * n)(*[C.c_void_p(x) for x in d_out]) if n else None
+        if n and len(d_out) != n:
+            raise ValueError("the plan has %d streams, d_out %d" % (n, len(d_out)))
+        seq = None
+        if seq_start is not None:
+            if len(seq_start) != n_streams:
+                raise ValueError("seq_start has %d entries for %d streams" % (len(seq_start), n_streams))
+            seq = (C.c_uint32 * max(n_streams, 1))(*[int(x) & 0xFFFFFFFF for x in seq_start])
+        _check(self._lib.dabgpu_edi_frames_dev(self._h, C.byref(plan), n_streams, frames_per_stream, d_fib, d_crc_ok, ptrs,
+                                               d_history_in, d_history_out, d_cif_start, seq, d_edi, stream_stride, d_status,
+                                               stream), "dabgpu_edi_frames_dev")
+
+    def _decode_for_contribution(self, soft, n_streams, streams, history):
+        """decode_frames_dev on device tensors, for decode_frames_eti / decode_frames_edi -> what their writer call takes"""
         import torch
         streams = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
         plan = eti_layout(streams)
@@ -1620,18 +1747,44 @@ class Context:
             msc_in, eti_in = history
         msc_out = [torch.empty((n_streams, 15, sc.length * 64), dtype=torch.int8, device=dev) for sc in scs]
         eti_out = torch.empty((n_streams, eti_history_bytes()), **u8)
-        eti = torch.empty((n_streams, n_cif, ETI_FRAME_BYTES), **u8)
         status = torch.empty((n_streams, n_cif, 8), **u8)
         # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
         torch.cuda.current_stream(dev).synchronize()
         self.decode_frames_dev(soft.data_ptr(), soft.stride(0), n_streams, fps, fib.data_ptr(), ok.data_ptr(), scs,
                                None if msc_in is None else [t.data_ptr() for t in msc_in], [t.data_ptr() for t in msc_out],
                                [t.data_ptr() for t in outs])
+        return plan, fps, n_cif, fib, ok, outs, status, eti_in, (msc_out, eti_out)
+
+    def decode_frames_eti(self, soft, n_streams, streams, history=None):
+        """Soft bits (torch int8 tensor on this context's device, [n_streams*frames_per_stream][>= 230400]) -> ETI(NI):
+        decode_frames_dev + eti_frames_dev on device tensors.  streams: [(subchannel_id, Subchannel), ...].
+        history: what an earlier call on the same streams returned (None: the streams start here).
+        -> (eti uint8 [n_streams, n_cif, 6144], status uint8 [n_streams, n_cif, 8] (view as ETI_STATUS_DTYPE on the host),
+        history); all device tensors, the work is finished when the call returns."""
+        import torch
+        plan, fps, n_cif, fib, ok, outs, status, eti_in, hist = self._decode_for_contribution(soft, n_streams, streams, history)
+        eti = torch.empty((n_streams, n_cif, ETI_FRAME_BYTES), dtype=torch.uint8, device=soft.device)
         self.eti_frames_dev(plan, n_streams, fps, fib.data_ptr(), ok.data_ptr(), [t.data_ptr() for t in outs], eti.data_ptr(),
                             status.data_ptr(), d_history_in=None if eti_in is None else eti_in.data_ptr(),
-                            d_history_out=eti_out.data_ptr())
+                            d_history_out=hist[1].data_ptr())
         self.sync()
-        return eti, status, (msc_out, eti_out)
+        return eti, status, hist
+
+    def decode_frames_edi(self, soft, n_streams, streams, history=None, seq_start=None):
+        """decode_frames_eti with EDI out: decode_frames_dev + edi_frames_dev on device tensors.  seq_start: the first packet's
+        SEQ per stream (None: 0); the caller adds n_cif per call.
+        -> (edi uint8 [n_streams, n_cif * edi_packet_bytes(plan)], every stream's AF packets back to back, status uint8
+        [n_streams, n_cif, 8] (ETI_STATUS_DTYPE), history -- the record of decode_frames_eti: either call continues the other)."""
+        import torch
+        plan, fps, n_cif, fib, ok, outs, status, eti_in, hist = self._decode_for_contribution(soft, n_streams, streams, history)
+        stride = (n_cif * edi_packet_bytes(plan) + 15) // 16 * 16
+        edi = torch.zeros((n_streams, stride), dtype=torch.uint8, device=soft.device)
+        torch.cuda.current_stream(soft.device).synchronize()
+        self.edi_frames_dev(plan, n_streams, fps, fib.data_ptr(), ok.data_ptr(), [t.data_ptr() for t in outs], edi.data_ptr(), stride,
+                            status.data_ptr(), seq_start=seq_start, d_history_in=None if eti_in is None else eti_in.data_ptr(),
+                            d_history_out=hist[1].data_ptr())
+        self.sync()
+        return edi[:, :n_cif * edi_packet_bytes(plan)], status, hist
 
     def modulate_eti_dev(self, plan, streams, n_streams, frames_per_stream, d_eti, d_iq, d_status, cfg=None, d_state_in=None,
                          d_state_out=None, frame_stride=NB_FRAME_SAMPLES, stream=None):
@@ -1682,6 +1835,56 @@ class Context:
         n = len(entries)
         arr = (EtiReadEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_eti_read_dev(self._h, arr, n, stream), "dabgpu_eti_read_dev")
+
+    def edi_read_dev(self, entries, stream=None):
+        """AF packet byte streams -> FIBs, CRC flags and logical frames on the device (dabgpu_edi_read_dev): entries is a list
+        of EdiReadEntry (device addresses), each a stream with its own plan, byte count and state.  Enqueues only."""
+        n = len(entries)
+        arr = (EtiReadEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_edi_read_dev(self._h, arr, n, stream), "dabgpu_edi_read_dev")
+
+    def edi_read(self, bytes_tensor, streams, state=None):
+        """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams AF
+        packet byte streams of ONE multiplex (n_bytes a multiple of 16 unless there is one stream, so that every row is
+        aligned); streams: [(subchannel_id, Subchannel) or EtiStream, ...], or None for the discovery pass (only the FIC
+        leaves).  state: what an earlier call on the same streams returned (None: the streams start here).
+        -> (fib uint8 [n_streams][max_rows][3][32], crc_ok uint8 [n_streams][max_rows][3], outs: one uint8 tensor [n_streams]
+        [max_rows][bitrate * 3] per stream in the order of `streams`, status uint8 [n_streams][max_rows][32] (view as
+        EDI_READ_STATUS_DTYPE on the host), result uint8 [n_streams][48] (EDI_READ_RESULT_DTYPE), state); device tensors, zero
+        behind a stream's emitted rows; the work is finished when the call returns."""
+        import torch
+        if bytes_tensor.dtype != torch.uint8 or bytes_tensor.dim() != 2 or not bytes_tensor.is_contiguous() or \
+                (bytes_tensor.shape[0] > 1 and bytes_tensor.shape[1] % 16) or bytes_tensor.data_ptr() % 16:
+            raise ValueError("bytes_tensor must be a contiguous, 16-byte aligned uint8 tensor [n_streams][n_bytes], n_bytes a multiple of 16 "
+                             "unless there is one stream")
+        plan, items = None, []
+        if streams is not None:
+            items = [s if isinstance(s, EtiStream) else EtiStream(int(s[0]), s[1]) for s in streams]
+            plan = eti_layout(items)
+        dev = bytes_tensor.device
+        n_streams, n_bytes = bytes_tensor.shape
+        rows = edi_read_max_rows(n_bytes, plan)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        fib = torch.zeros((n_streams, rows, 3, 32), **u8)
+        ok = torch.zeros((n_streams, rows, 3), **u8)
+        outs = [torch.zeros((n_streams, rows, s.sc.bitrate_kbps * 3), **u8) for s in items]
+        status = torch.zeros((n_streams, rows, 32), **u8)
+        result = torch.zeros((n_streams, 48), **u8)
+        state_out = torch.empty((n_streams, edi_read_state_bytes()), **u8)
+        entries, keep = [], []
+        for s in range(n_streams):
+            ptrs = (C.c_void_p * max(len(items), 1))(*[o[s].data_ptr() for o in outs])
+            keep.append(ptrs)
+            entries.append(EdiReadEntry(bytes_tensor[s].data_ptr() if n_bytes else None, n_bytes, 0,
+                                        C.pointer(plan) if plan is not None else None,
+                                        C.cast(ptrs, C.POINTER(C.c_void_p)) if plan is not None else None,
+                                        None if state is None else state[s].data_ptr(), state_out[s].data_ptr(),
+                                        fib[s].data_ptr(), ok[s].data_ptr(), status[s].data_ptr(), result[s].data_ptr()))
+        # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
+        torch.cuda.current_stream(dev).synchronize()
+        self.edi_read_dev(entries)
+        self.sync()
+        return fib, ok, outs, status, result, state_out
 
     def eti_read(self, bytes_tensor, streams, state=None):
         """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams ETI(NI)

@@ -151,15 +151,7 @@ void BasicRadio::ProcessEti(tcb::span<const uint8_t> bytes) {
             for (int k = 0; k < f.nst; k++) {
                 const uint8_t *stc = g.p + 8 + 4 * k;
                 const int sad = ((stc[0] & 3) << 8) | stc[1], nbytes = 8 * (((stc[2] & 3) << 8) | stc[3]);
-                for (size_t i = 0; i < m_subchannels.size(); i++) {
-                    Subchannel &s = m_subchannels[i];
-                    if (s.desc.start_address != sad || s.nbytes != nbytes) continue;
-                    const tcb::span<const uint8_t> lf(g.p + off, size_t(nbytes));
-                    m_obs_msc.Notify(int(i), lf);
-                    if (s.dab_plus) s.dab_plus->Process(lf);
-                    if (s.dab) s.dab->Process(lf);
-                    if (s.packet) s.packet->Process(lf);
-                }
+                route_stream_locked(sad, nbytes, g.p + off);
                 off += size_t(nbytes);
             }
             // sub-channels the FIC has announced by now are fed from the next frame on
@@ -173,6 +165,50 @@ void BasicRadio::ProcessEti(tcb::span<const uint8_t> bytes) {
     });
     m_eti_head = er::next_head(m_eti_head, c, any, fct, fp);
     m_eti_stream.erase(m_eti_stream.begin(), m_eti_stream.begin() + std::ptrdiff_t(p));
+}
+
+// one stream of a contribution frame or packet: its bytes of this CIF go to the open sub-channel at its start address
+void BasicRadio::route_stream_locked(int start_address, int nbytes, const uint8_t *data) {
+    for (size_t i = 0; i < m_subchannels.size(); i++) {
+        Subchannel &s = m_subchannels[i];
+        if (s.desc.start_address != start_address || s.nbytes != nbytes) continue;
+        const tcb::span<const uint8_t> lf(data, size_t(nbytes));
+        m_obs_msc.Notify(int(i), lf);
+        if (s.dab_plus) s.dab_plus->Process(lf);
+        if (s.dab) s.dab->Process(lf);
+        if (s.packet) s.packet->Process(lf);
+    }
+}
+
+void BasicRadio::ProcessEdi(tcb::span<const uint8_t> bytes) {
+    namespace ed = dabgpu_edi;
+    std::lock_guard<std::mutex> lock(m_mutex);
+    // S = the tail the last call left + the new bytes
+    m_edi_stream.insert(m_edi_stream.end(), bytes.begin(), bytes.end());
+    ed::Result c{};
+    ed::Carry k = ed::carry_of(m_edi_head);
+    ed::Fields fields;
+    const size_t p = ed::walk(m_edi_stream.data(), m_edi_stream.size(), nullptr, k, c, fields,
+                              [&](uint32_t, uint32_t at, int total, const ed::Fields &f, bool seq_break, const ed::Carry &before, const ed::PtrPacket &g) {
+        uint32_t fib_ok = 0;
+        if (f.ficf) {
+            // the FIC: three FIBs, their CRCs judged here
+            uint8_t ok[3];
+            for (int j = 0; j < 3; j++) {
+                ok[j] = ed::fib_crc_ok(g, f.fic_at, j);
+                fib_ok |= uint32_t(ok[j]) << j;
+            }
+            process_fibs_locked(g.p + f.fic_at, ok, 3);
+        }
+        // the sub-channels: est n of the packet goes to the open sub-channel at its start address
+        for (int n = 0; n < f.n_est; n++)
+            route_stream_locked(((f.sstc[n][0] & 3) << 8) | f.sstc[n][1], 8 * int(f.stl[n]), g.p + f.data_at[n]);
+        // sub-channels the FIC has announced by now are fed from the next packet on
+        if (m_auto_channels) update_channels_from_database();
+        return ed::make_status(at, total, f, fib_ok, seq_break, before);
+    });
+    m_edi_head = ed::next_head(m_edi_head, c, k);
+    m_edi_stream.erase(m_edi_stream.begin(), m_edi_stream.begin() + std::ptrdiff_t(p));
 }
 
 // what the per-frame call needs to know of a sub-channel the FIC has described; false: a profile it cannot decode

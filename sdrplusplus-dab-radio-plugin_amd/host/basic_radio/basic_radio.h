@@ -26,6 +26,7 @@
 #include "dab/database/dab_database_updater.h"
 #include "dab/fic/fic_parser.h"
 #include "dabgpu.h"
+#include "dabgpu_edi.h"
 #include "dabgpu_eti_read.h"
 #include "utility/gpu_buffers.h"
 #include "utility/observable.h"
@@ -48,6 +49,12 @@ public:
     void ProcessEti(tcb::span<const uint8_t> bytes);
     // running totals of ProcessEti: rows, taken, bad_data_crc, skipped, resyncs, gap_sum, fib_errors; tail_bytes held
     const dabgpu_eti_read::Head &GetEtiReadTotals() const { return m_eti_head; }
+    // The same for an EDI byte stream (AF packets back to back, as a TCP capture is): the serial walk of
+    // include/dabgpu_edi.h -- packets found by header and CRC, resynchronised after damage, the unfinished tail kept for the
+    // next call -- and every DETI packet's FIBs and est items routed as ProcessEti routes a frame's.  No call into libdabgpu.
+    void ProcessEdi(tcb::span<const uint8_t> bytes);
+    // running totals of ProcessEdi: rows, not_deti, bad_tags, skipped, resyncs, gap_sum, fib_errors; tail_bytes held
+    const dabgpu_edi::Head &GetEdiReadTotals() const { return m_edi_head; }
     std::mutex &GetMutex() { return m_mutex; }
     Observable<subchannel_id_t, Basic_Audio_Channel &> &On_Audio_Channel() { return m_obs_audio_channel; }
     // read under GetMutex(), as the GUI does (/root/reference/src/render_radio_block.cpp:124, 158-160, 239, 755)
@@ -98,6 +105,7 @@ private:
     void update_channels_from_database();
     void process_fibs_locked();
     void process_fibs_locked(const uint8_t *fib, const uint8_t *crc, size_t n_fibs);
+    void route_stream_locked(int start_address, int nbytes, const uint8_t *data);
     int add_subchannel_locked(const dabgpu_subchannel &sc);
     const DAB_Parameters m_params;
     dabgpu_ctx *m_ctx;
@@ -126,4 +134,6 @@ private:
     int m_total_frames_lost = 0;
     dabgpu_eti_read::Head m_eti_head{};                  // ProcessEti: the state between calls, its tail in m_eti_stream
     std::vector<uint8_t> m_eti_stream;                   // S of the current call; what the walk leaves is the next call's tail
+    dabgpu_edi::Head m_edi_head{};                       // ProcessEdi: the same
+    std::vector<uint8_t> m_edi_stream;
 };
