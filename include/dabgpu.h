@@ -1535,6 +1535,120 @@ int dabgpu_edi_read_dev(dabgpu_ctx *ctx, const dabgpu_edi_read_entry *entries, i
 int dabgpu_edi_read_host(const dabgpu_edi_read_entry *entries, int n_entries);
 
 /* ------------------------------------------------------------------------ */
+/* EDI PFT layer: EDI over UDP or multicast.  Every    */
+/* AF packet travels as PF fragments (TS 102 821), usually with Reed-Solomon        */
+/* RS(255,207) parity over interleaved chunks so that whole datagrams may be lost.   */
+/* The writer cuts the AF packets dabgpu_edi_frames_dev leaves into fragments; the    */
+/* reader puts fragment byte streams (datagram payloads concatenated by the caller,    */
+/* or a file) back together into the AF packet byte streams dabgpu_edi_read_dev         */
+/* takes.  The format as known, the layout rule and the reader's whole contract --       */
+/* stream, walk, groups and the horizon, closing, records, state -- are written out in   */
+/* include/dabgpu_pft.h; parity with other EDI tools is not pinned.                        */
+/*                                                                                        */
+/* dabgpu_pft_layout   host only.  How packets of packet_bytes (12 .. 8192) are cut:       */
+/*            with fec, fragments sized so that any m of a packet's may be lost            */
+/*            (s0 = min(48 c / (m + 1), max_payload), f = ceil(B / s0), s = ceil(B / f));     */
+/*            without, fragments of max_payload bytes.  addr: fragments carry Source and       */
+/*            Dest.  guaranteed_losses is exact.  DABGPU_ERR_ARG for what the rule refuses      */
+/*            (info is not written).                                                           */
+/* dabgpu_pft_fragments_dev   d_af: n_packets AF packets of layout->packet_bytes back to         */
+/*            back per stream, stream s at d_af + s * in_stride (what dabgpu_edi_frames_dev        */
+/*            leaves); pseq_start: HOST array [n_streams] or NULL (= 0), the first packet's         */
+/*            Pseq per stream -- the caller adds n_packets to it after the call, the kernel           */
+/*            wraps modulo 65536.  Stream s's fragments leave back to back from d_pf +                */
+/*            s * out_stride, layout->stream_bytes per packet.  A workgroup per packet: parity         */
+/*            with a lane per (chunk, parity byte), fragments by the interleave rule.  d_af and         */
+/*            d_pf 16-byte aligned, strides multiples of 16, in_stride >= n_packets *                    */
+/*            packet_bytes, out_stride >= n_packets * stream_bytes, no overlap; a layout                  */
+/*            dabgpu_pft_layout did not make, or anything else here, is DABGPU_ERR_ARG and                 */
+/*            nothing is enqueued or written.  One launch, no synchronisation (but once while the           */
+/*            stage area grows).                                                                            */
+/* dabgpu_pft_fragments_host   the same on host pointers, serially (no context, no device).                   */
+/* dabgpu_pft_read_state_bytes / _out_bytes / _max_records   sizes of an entry's state record                  */
+/*            (a head, the two open groups, the tail; all zero = a stream that starts), its output              */
+/*            (29216 + n_bytes: nothing can run out of room) and its records                                    */
+/*            (2 + (8211 + n_bytes) / 15).  The latter two are 0 for n_bytes outside 0 .. 2^30.                  */
+/* dabgpu_pft_read_dev   entries: HOST array (at most 65535).  Per entry, in short: S = the carried               */
+/*            tail + the new bytes; fragments are taken where a plausible header (HCRC) and its                    */
+/*            payload lie inside S, bytes between them are skipped and counted; fragments join                      */
+/*            the group of their Pseq, open only at 1 and 2 above the horizon; a complete group                     */
+/*            is emitted, in Pseq order; a group that the horizon passes, or FLUSH closes, is                       */
+/*            filled by erasure-only RS decoding where every chunk misses at most 48 bytes, and                      */
+/*            LOST otherwise.  Packets leave back to back in d_out, a record per closed group in                      */
+/*            d_records.  d_bytes, the states and d_out 16-byte aligned, d_records and d_result 4;                    */
+/*            d_state_in and d_state_out not overlapping.  Three launches -- every position's header                  */
+/*            test, a wave per entry that walks and moves, a workgroup per emitted packet that                         */
+/*            fills and checks -- no synchronisation (but once while the stage area grows), no                          */
+/*            global atomic.  Everything is checked before anything is enqueued: a refused call                         */
+/*            (DABGPU_ERR_ARG) writes nothing.  The walk is one serial step per fragment and entry:                      */
+/*            stated, not optimised.                                                                                    */
+/* dabgpu_pft_read_host   the same on host pointers (no context, no device): the serial reader of                        */
+/*            the same header.                                                                                          */
+/* To chain into dabgpu_edi_read_dev, result.out_bytes has to reach the host in between (one 4-byte                        */
+/* copy): the EDI entry's n_bytes is a host field.                                                                         */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_PFT_FEC          1      /* record flags: the group's fragments carry RSk / RSz                 */
+#define DABGPU_PFT_ADDR         2      /* ... Source / Dest                                                    */
+#define DABGPU_PFT_RECOVERED    4      /* fragments were missing and every chunk was filled                     */
+#define DABGPU_PFT_INCONSISTENT 8      /* a filled chunk fails one of its 48 syndromes: a received byte was wrong */
+#define DABGPU_PFT_LOST        16      /* nothing emitted, length 0                                             */
+#define DABGPU_PFT_AF_OK       32      /* the emitted bytes are one AF packet whose CRC holds                   */
+#define DABGPU_PFT_FLUSHED     64      /* closed by DABGPU_PFT_READ_FLUSH                                       */
+#define DABGPU_PFT_READ_FLUSH   1      /* entry flag: close every open group at the call's end                  */
+
+typedef struct dabgpu_pft_layout_info { /* 64 bytes */
+    int32_t packet_bytes, fec, m, max_payload, addr;   /* as given                                   */
+    int32_t chunks, rs_k, rs_z, block_bytes;           /* c, k, z, B (0 without fec)                 */
+    int32_t fcount, plen;                              /* f, s                                       */
+    int32_t header_bytes;                              /* 14 + 2 fec + 4 addr                        */
+    int32_t stream_bytes;                              /* all fragments of one packet                */
+    int32_t guaranteed_losses;
+    int32_t reserved[2];                               /* 0                                          */
+} dabgpu_pft_layout_info;
+
+typedef struct dabgpu_pft_read_record { /* per closed group that held a fragment, 32 bytes */
+    uint32_t offset;                   /* of the packet in the call's output                         */
+    uint16_t length;                   /* l; 0 = LOST                                                */
+    uint16_t pseq, fcount, received;
+    uint16_t plen;                     /* s                                                          */
+    uint8_t  rs_k, rs_z, chunks;       /* 0 without FEC                                              */
+    uint8_t  max_erasures;             /* the worst chunk's erased positions (255 = that or more)    */
+    uint16_t flags;                    /* DABGPU_PFT_*                                               */
+    uint16_t source, dest;
+    uint32_t reserved[2];              /* 0                                                          */
+} dabgpu_pft_read_record;
+
+typedef struct dabgpu_pft_read_result { /* per entry and call, 64 bytes */
+    uint32_t records, packets, lost, recovered;
+    uint32_t fragments, duplicates, mismatched, late;
+    uint32_t unsupported, missing, skipped, resyncs;
+    uint32_t out_bytes, tail_bytes, chunks_filled, bytes_filled;
+} dabgpu_pft_read_result;
+
+typedef struct dabgpu_pft_read_entry {
+    const uint8_t *d_bytes;            /* the new bytes                                              */
+    int32_t n_bytes;                   /* 0 .. 2^30                                                  */
+    int32_t flags;                     /* DABGPU_PFT_READ_FLUSH or 0                                 */
+    const void *d_state_in;            /* or NULL                                                    */
+    void *d_state_out;
+    uint8_t *d_out;                    /* [dabgpu_pft_read_out_bytes(n_bytes)]                       */
+    dabgpu_pft_read_record *d_records; /* [dabgpu_pft_read_max_records(n_bytes)]                     */
+    dabgpu_pft_read_result *d_result;
+} dabgpu_pft_read_entry;
+
+int dabgpu_pft_layout(int packet_bytes, int fec, int m, int max_payload, int addr, dabgpu_pft_layout_info *info);
+int dabgpu_pft_fragments_dev(dabgpu_ctx *ctx, const dabgpu_pft_layout_info *layout, int n_streams, int n_packets, const uint8_t *d_af,
+                             size_t in_stride, const uint32_t *pseq_start, uint32_t source, uint32_t dest, uint8_t *d_pf, size_t out_stride,
+                             void *stream);
+int dabgpu_pft_fragments_host(const dabgpu_pft_layout_info *layout, int n_streams, int n_packets, const uint8_t *af, size_t in_stride,
+                              const uint32_t *pseq_start, uint32_t source, uint32_t dest, uint8_t *pf, size_t out_stride);
+size_t dabgpu_pft_read_state_bytes(void);
+size_t dabgpu_pft_read_out_bytes(int n_bytes);
+int dabgpu_pft_read_max_records(int n_bytes);
+int dabgpu_pft_read_dev(dabgpu_ctx *ctx, const dabgpu_pft_read_entry *entries, int n_entries, void *stream);
+int dabgpu_pft_read_host(const dabgpu_pft_read_entry *entries, int n_entries);
+
+/* ------------------------------------------------------------------------ */
 /* The host-fed ring: dabgpu_ofdm_demod_frames + dabgpu_decode_frames for a    */
 /* caller whose samples start in HOST memory (files, a network), pipelined.    */
 /* The reference runs these two stages on two threads with a 2-frame ring       */

@@ -80,6 +80,8 @@ enum StageSlot {
     STAGE_ETI_READ = 23,             // dabgpu_eti_read_dev: the entry table, the candidate bitmaps and the row lists
     STAGE_EDI = 24,                  // dabgpu_edi_frames_dev: per stream the CIF count of the pre-pass and the first sequence number
     STAGE_EDI_READ = 25,             // dabgpu_edi_read_dev: the entry table and the two bitmaps of every entry
+    STAGE_PFT = 26,                  // dabgpu_pft_fragments_dev: the first Pseq of every stream
+    STAGE_PFT_READ = 27,             // dabgpu_pft_read_dev: the entry table, the two bitmaps and the fill launch's arena of every entry
     STAGE_SLOTS
 };
 

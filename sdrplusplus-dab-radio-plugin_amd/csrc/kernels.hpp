@@ -836,6 +836,43 @@ inline size_t edi_read_scratch_bytes(int n_bytes) { return (2 * edi_read_bitmap_
 // sizeof(EdiReadEntry) + the sum of edi_read_scratch_bytes, 16-byte aligned
 hipError_t launch_edi_read(EdiReadEntry *entries, int n_entries, void *d_table, hipStream_t s);
 
+// ---- EDI PFT layer, writer (pft_kernels.hip; include/dabgpu_pft.h) --------------
+// Everything a call's packets share, by value in the kernel arguments: the fields of dabgpu_pft::Layout the kernel reads
+struct PftArgs {
+    const uint8_t *af;                         // [n_streams] at in_stride: n_packets AF packets of packet_bytes back to back
+    uint8_t *pf;                               // [n_streams] at out_stride: n_packets * stream_bytes
+    unsigned long long in_stride, out_stride;
+    const uint32_t *pseq_start;                // [n_streams] DEVICE
+    int32_t packet_bytes, fec, addr, chunks, rs_k, rs_z, block_bytes, fcount, plen, header_bytes, stream_bytes;
+    uint32_t source, dest;
+};
+hipError_t launch_pft(const PftArgs &a, int n_streams, int n_packets, hipStream_t s);
+
+// ---- EDI PFT layer, reader (pft_read_kernels.hip; include/dabgpu_pft.h) ---------
+constexpr int PFT_READ_SPAN = 4096;            // byte positions a workgroup of the check launch judges
+constexpr int PFT_READ_MAX_ENTRIES = 65535;    // (the check and fill launches' grids have an entry per y)
+constexpr int PFT_READ_MAX_TAIL = 8211;        // == dabgpu_pft::MAX_TAIL
+constexpr int PFT_READ_MAX_BLOCK = 10496;      // == dabgpu_pft::MAX_BLOCK
+// One entry of the table in device memory (addresses as integers)
+struct PftReadEntry {
+    uint64_t bytes, state_in, state_out, out, records, result;
+    uint64_t good;                             // scratch: bit q % 64 of word q / 64 = T(q) of the contract
+    uint64_t stop;                             // scratch: H(q) with an incomplete fragment, or U(q): the walk ends there
+    uint64_t arena;                            // scratch: per group the fill launch works on, its received map and fragments
+    int32_t n_bytes, flags;
+    uint32_t max_records, arena_bytes;
+};
+inline size_t pft_read_positions(int n_bytes) { return size_t(n_bytes) + size_t(PFT_READ_MAX_TAIL); }
+inline size_t pft_read_bitmap_words(int n_bytes) { return (pft_read_positions(n_bytes) + 63) / 64; }
+// A group the fill launch works on holds a fragment with FEC (16 header bytes and its payload) in S, or is one of the two
+// carried: 32 map bytes and its payload are at most twice its bytes in S, or 32 + PFT_READ_MAX_BLOCK
+inline size_t pft_read_arena_bytes(int n_bytes) { return (2 * (32 + size_t(PFT_READ_MAX_BLOCK)) + 2 * pft_read_positions(n_bytes) + 15) / 16 * 16; }
+// scratch an entry needs behind the table: its two bitmaps and its arena (bytes, a multiple of 16)
+inline size_t pft_read_scratch_bytes(int n_bytes) { return (2 * pft_read_bitmap_words(n_bytes) * 8 + 15) / 16 * 16 + pft_read_arena_bytes(n_bytes); }
+// entries: the host's table with everything but good, stop, arena and arena_bytes filled in (this fills them); d_table:
+// n_entries * sizeof(PftReadEntry) + the sum of pft_read_scratch_bytes, 16-byte aligned
+hipError_t launch_pft_read(PftReadEntry *entries, int n_entries, void *d_table, hipStream_t s);
+
 // ---- ETI(NI) input (eti_read_kernels.hip) -------------------------------------
 constexpr int ETI_READ_SCAN_SPAN = 8192;       // byte positions a workgroup of the scan judges
 constexpr int ETI_READ_ROW_WAVES = 4;          // rows (waves) per workgroup of the check launch

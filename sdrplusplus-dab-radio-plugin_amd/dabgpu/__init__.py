@@ -67,6 +67,8 @@ EXPORTS = [
     "dabgpu_eti_read_state_bytes", "dabgpu_eti_read_dev", "dabgpu_eti_read_host",
     "dabgpu_edi_packet_bytes", "dabgpu_edi_frames_dev", "dabgpu_edi_parse", "dabgpu_edi_streams_from_packet",
     "dabgpu_edi_read_state_bytes", "dabgpu_edi_read_max_rows", "dabgpu_edi_read_dev", "dabgpu_edi_read_host",
+    "dabgpu_pft_layout", "dabgpu_pft_fragments_dev", "dabgpu_pft_fragments_host", "dabgpu_pft_read_state_bytes",
+    "dabgpu_pft_read_out_bytes", "dabgpu_pft_read_max_records", "dabgpu_pft_read_dev", "dabgpu_pft_read_host",
 ]
 
 ABI_VERSION = 6
@@ -726,6 +728,101 @@ def edi_read_host(entries):
     _check(lib().dabgpu_edi_read_host(arr, n), "dabgpu_edi_read_host")
 
 
+#: EDI PFT layer (include/dabgpu.h, "EDI PFT layer"; include/dabgpu_pft.h): PF fragments with RS(255,207), EDI over UDP
+PFT_FEC, PFT_ADDR, PFT_RECOVERED, PFT_INCONSISTENT, PFT_LOST, PFT_AF_OK, PFT_FLUSHED = 1, 2, 4, 8, 16, 32, 64
+PFT_READ_FLUSH = 1
+#: dabgpu_pft_read_record: one closed group that held a fragment
+PFT_READ_RECORD_DTYPE = np.dtype([("offset", np.uint32), ("length", np.uint16), ("pseq", np.uint16), ("fcount", np.uint16),
+                                  ("received", np.uint16), ("plen", np.uint16), ("rs_k", np.uint8), ("rs_z", np.uint8),
+                                  ("chunks", np.uint8), ("max_erasures", np.uint8), ("flags", np.uint16), ("source", np.uint16),
+                                  ("dest", np.uint16), ("reserved", np.uint32, (2,))])
+assert PFT_READ_RECORD_DTYPE.itemsize == 32
+#: dabgpu_pft_read_result: what one entry of pft_read_dev / pft_read_host counted in one call
+PFT_READ_RESULT_DTYPE = np.dtype([(f, np.uint32) for f in ("records", "packets", "lost", "recovered", "fragments", "duplicates",
+                                                           "mismatched", "late", "unsupported", "missing", "skipped", "resyncs",
+                                                           "out_bytes", "tail_bytes", "chunks_filled", "bytes_filled")])
+assert PFT_READ_RESULT_DTYPE.itemsize == 64
+#: the head of a state record of pft_read_dev / pft_read_host; the two open groups and the tail follow it
+PFT_READ_HEAD_DTYPE = np.dtype([("tail_bytes", np.uint32), ("have_horizon", np.uint8), ("in_skip", np.uint8), ("late_run", np.uint8),
+                                ("reserved", np.uint8), ("horizon", np.uint16), ("reserved1", np.uint16), ("reserved2", np.uint32)] +
+                               [(f, np.uint64) for f in ("records", "packets", "lost", "recovered", "fragments", "duplicates",
+                                                         "mismatched", "late", "unsupported", "missing", "skipped", "resyncs",
+                                                         "out_bytes", "chunks_filled", "bytes_filled", "reserved3")])
+assert PFT_READ_HEAD_DTYPE.itemsize == 144
+
+
+class PftLayout(C.Structure):
+    """dabgpu_pft_layout_info: how AF packets of one size are cut into PF fragments (pft_layout)"""
+    _fields_ = [(f, C.c_int32) for f in ("packet_bytes", "fec", "m", "max_payload", "addr", "chunks", "rs_k", "rs_z", "block_bytes",
+                                         "fcount", "plen", "header_bytes", "stream_bytes", "guaranteed_losses")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
+class PftReadEntry(C.Structure):
+    """dabgpu_pft_read_entry: one PF fragment byte stream of Context.pft_read_dev (device addresses) or pft_read_host (host
+    addresses).  d_out holds pft_read_out_bytes(n_bytes), d_records pft_read_max_records(n_bytes) records."""
+    _fields_ = [("d_bytes", C.c_void_p), ("n_bytes", C.c_int32), ("flags", C.c_int32), ("d_state_in", C.c_void_p),
+                ("d_state_out", C.c_void_p), ("d_out", C.c_void_p), ("d_records", C.c_void_p), ("d_result", C.c_void_p)]
+
+
+def pft_layout(packet_bytes, fec=True, m=2, max_payload=1400, addr=False):
+    """How AF packets of packet_bytes are cut into PF fragments (dabgpu_pft_layout: host only): with fec, so that any m
+    fragments of a packet may be lost, no fragment's payload above max_payload.  -> PftLayout (chunks, rs_k, rs_z, fcount,
+    plen, stream_bytes, guaranteed_losses, ...).  DabGpuError for what the rule refuses."""
+    info = PftLayout()
+    _check(lib().dabgpu_pft_layout(int(packet_bytes), int(bool(fec)), int(m), int(max_payload), int(bool(addr)), C.byref(info)),
+           "dabgpu_pft_layout")
+    return info
+
+
+def pft_fragments_host(layout, af, pseq_start=None, source=0, dest=0):
+    """AF packets -> PF fragments on HOST memory, serially (dabgpu_pft_fragments_host).  af: uint8 [n_streams][n_packets *
+    layout.packet_bytes]; pseq_start: the first packet's Pseq per stream (None: 0).  -> uint8 [n_streams][n_packets *
+    layout.stream_bytes]."""
+    af = np.ascontiguousarray(af, np.uint8)
+    n_streams, n_in = af.shape
+    n_packets = n_in // layout.packet_bytes
+    if n_packets * layout.packet_bytes != n_in:
+        raise ValueError("af must hold whole packets of layout.packet_bytes")
+    in_stride, out_stride = (n_in + 15) // 16 * 16, (n_packets * layout.stream_bytes + 15) // 16 * 16
+    src, dst = _aligned_bytes(max(n_streams * in_stride, 16)), _aligned_bytes(max(n_streams * out_stride, 16))
+    src[:n_streams * in_stride].reshape(n_streams, in_stride)[:, :n_in] = af
+    seq = None if pseq_start is None else (C.c_uint32 * max(n_streams, 1))(*[int(v) & 0xFFFFFFFF for v in pseq_start])
+    _check(lib().dabgpu_pft_fragments_host(C.byref(layout), n_streams, n_packets, _p(src), in_stride, seq, int(source), int(dest), _p(dst),
+                                           out_stride), "dabgpu_pft_fragments_host")
+    return dst[:n_streams * out_stride].reshape(n_streams, out_stride)[:, :n_packets * layout.stream_bytes].copy()
+
+
+def _aligned_bytes(n, fill=0):
+    """a uint8 array of n bytes on a 16-byte boundary"""
+    raw = np.full(n + 16, fill, np.uint8)
+    at = (-raw.ctypes.data) % 16
+    return raw[at:at + n]
+
+
+def pft_read_state_bytes():
+    """Bytes of one state record of Context.pft_read_dev / pft_read_host (all zero = a stream that starts)."""
+    return int(lib().dabgpu_pft_read_state_bytes())
+
+
+def pft_read_out_bytes(n_bytes):
+    """Bytes one entry can emit in one call: its d_out holds this many."""
+    return int(lib().dabgpu_pft_read_out_bytes(int(n_bytes)))
+
+
+def pft_read_max_records(n_bytes):
+    """Records one entry can leave in one call: its d_records holds this many."""
+    return int(lib().dabgpu_pft_read_max_records(int(n_bytes)))
+
+
+def pft_read_host(entries):
+    """Context.pft_read_dev on HOST memory (entries: PftReadEntry with host addresses): the same checks and the header's
+    serial reader, without a context or a GPU (dabgpu_pft_read_host)."""
+    n = len(entries)
+    arr = (PftReadEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_pft_read_host(arr, n), "dabgpu_pft_read_host")
+
+
 #: ETI(NI) to IQ (include/dabgpu.h, "ETI(NI) to IQ"): dabgpu_mod_status, one transmission frame's record
 MOD_BAD_INPUT, MOD_MISALIGNED = 1, 2
 MOD_STATUS_DTYPE = np.dtype([("flags", np.uint32), ("refused", np.uint8), ("reserved", np.uint8, (3,))])
@@ -878,6 +975,16 @@ def load_library(path):
     L.dabgpu_edi_read_max_rows.argtypes = [i, C.POINTER(EtiPlan)]
     L.dabgpu_edi_read_host.argtypes = [C.POINTER(EtiReadEntry), i]
     L.dabgpu_edi_read_dev.argtypes = [vp, C.POINTER(EtiReadEntry), i, vp]
+    L.dabgpu_pft_layout.argtypes = [i, i, i, i, i, C.POINTER(PftLayout)]
+    L.dabgpu_pft_fragments_dev.argtypes = [vp, C.POINTER(PftLayout), i, i, vp, sz, vp, C.c_uint32, C.c_uint32, vp, sz, vp]
+    L.dabgpu_pft_fragments_host.argtypes = [C.POINTER(PftLayout), i, i, vp, sz, vp, C.c_uint32, C.c_uint32, vp, sz]
+    for fn in (L.dabgpu_pft_read_state_bytes, L.dabgpu_pft_read_out_bytes):
+        fn.restype = C.c_size_t
+    L.dabgpu_pft_read_state_bytes.argtypes = []
+    L.dabgpu_pft_read_out_bytes.argtypes = [i]
+    L.dabgpu_pft_read_max_records.argtypes = [i]
+    L.dabgpu_pft_read_host.argtypes = [C.POINTER(PftReadEntry), i]
+    L.dabgpu_pft_read_dev.argtypes = [vp, C.POINTER(PftReadEntry), i, vp]
     L.dabgpu_fig_user_applications.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
@@ -1885,6 +1992,69 @@ class Context:
         self.edi_read_dev(entries)
         self.sync()
         return fib, ok, outs, status, result, state_out
+
+    def pft_fragments_dev(self, layout, n_streams, n_packets, d_af, in_stride, d_pf, out_stride, pseq_start=None, source=0, dest=0,
+                          stream=None):
+        """AF packets -> PF fragments on the device (dabgpu_pft_fragments_dev): n_packets packets of layout.packet_bytes back
+        to back per stream from d_af + s * in_stride (what edi_frames_dev leaves) -> layout.stream_bytes per packet, back to
+        back per stream from d_pf + s * out_stride (all 16-byte aligned).  pseq_start: the first packet's Pseq per stream, a
+        HOST sequence (None: 0); the caller adds n_packets to it.  Enqueues only."""
+        seq = None if pseq_start is None else (C.c_uint32 * max(n_streams, 1))(*[int(v) & 0xFFFFFFFF for v in pseq_start])
+        _check(self._lib.dabgpu_pft_fragments_dev(self._h, C.byref(layout), n_streams, n_packets, d_af, in_stride, seq, int(source),
+                                                  int(dest), d_pf, out_stride, stream), "dabgpu_pft_fragments_dev")
+
+    def pft_fragments(self, layout, af, pseq_start=None, source=0, dest=0):
+        """pft_fragments_dev on a torch uint8 tensor [n_streams][n_packets * layout.packet_bytes] (row stride a multiple of 16
+        unless there is one stream) -> uint8 tensor [n_streams][n_packets * layout.stream_bytes]; finished on return."""
+        import torch
+        n_streams, n_in = af.shape
+        n_packets = n_in // layout.packet_bytes
+        if af.dtype != torch.uint8 or n_packets * layout.packet_bytes != n_in or af.stride(1) != 1 or af.data_ptr() % 16 or \
+                (n_streams > 1 and af.stride(0) % 16):
+            raise ValueError("af must be a 16-byte aligned uint8 tensor of whole packets, its row stride a multiple of 16")
+        out_stride = (n_packets * layout.stream_bytes + 15) // 16 * 16
+        out = torch.zeros((n_streams, out_stride), dtype=torch.uint8, device=af.device)
+        in_stride = af.stride(0) if n_streams > 1 else (n_in + 15) // 16 * 16
+        torch.cuda.current_stream(af.device).synchronize()
+        self.pft_fragments_dev(layout, n_streams, n_packets, af.data_ptr(), in_stride, out.data_ptr(), out_stride, pseq_start, source, dest)
+        self.sync()
+        return out[:, :n_packets * layout.stream_bytes]
+
+    def pft_read_dev(self, entries, stream=None):
+        """PF fragment byte streams -> AF packet byte streams on the device (dabgpu_pft_read_dev): entries is a list of
+        PftReadEntry (device addresses), each a stream with its own byte count, flags and state.  Enqueues only."""
+        n = len(entries)
+        arr = (PftReadEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_pft_read_dev(self._h, arr, n, stream), "dabgpu_pft_read_dev")
+
+    def pft_read(self, bytes_tensor, state=None, flush=False):
+        """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams PF
+        fragment byte streams (n_bytes a multiple of 16 unless there is one stream).  state: what an earlier call on the same
+        streams returned (None: the streams start here); flush: close every open group at the end.
+        -> (out uint8 [n_streams][pft_read_out_bytes(n_bytes)], the AF packets of stream s back to back in its first
+        result["out_bytes"] bytes; records uint8 [n_streams][max_records][32] (view as PFT_READ_RECORD_DTYPE on the host),
+        result uint8 [n_streams][64] (PFT_READ_RESULT_DTYPE), state); device tensors; the work is finished when the call
+        returns.  To hand a stream on to edi_read its out_bytes has to come to the host first."""
+        import torch
+        if bytes_tensor.dtype != torch.uint8 or bytes_tensor.dim() != 2 or not bytes_tensor.is_contiguous() or \
+                (bytes_tensor.shape[0] > 1 and bytes_tensor.shape[1] % 16) or bytes_tensor.data_ptr() % 16:
+            raise ValueError("bytes_tensor must be a contiguous, 16-byte aligned uint8 tensor [n_streams][n_bytes], n_bytes a multiple of 16 "
+                             "unless there is one stream")
+        dev = bytes_tensor.device
+        n_streams, n_bytes = bytes_tensor.shape
+        u8 = dict(dtype=torch.uint8, device=dev)
+        out = torch.zeros((n_streams, pft_read_out_bytes(n_bytes)), **u8)
+        records = torch.zeros((n_streams, pft_read_max_records(n_bytes), 32), **u8)
+        result = torch.zeros((n_streams, 64), **u8)
+        state_out = torch.empty((n_streams, pft_read_state_bytes()), **u8)
+        entries = [PftReadEntry(bytes_tensor[s].data_ptr() if n_bytes else None, n_bytes, PFT_READ_FLUSH if flush else 0,
+                                None if state is None else state[s].data_ptr(), state_out[s].data_ptr(), out[s].data_ptr(),
+                                records[s].data_ptr(), result[s].data_ptr()) for s in range(n_streams)]
+        # the library's stream is not ordered behind torch's: what torch has enqueued for these tensors comes first
+        torch.cuda.current_stream(dev).synchronize()
+        self.pft_read_dev(entries)
+        self.sync()
+        return out, records, result, state_out
 
     def eti_read(self, bytes_tensor, streams, state=None):
         """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams ETI(NI)

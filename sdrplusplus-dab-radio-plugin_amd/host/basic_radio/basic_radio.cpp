@@ -211,6 +211,40 @@ void BasicRadio::ProcessEdi(tcb::span<const uint8_t> bytes) {
     m_edi_stream.erase(m_edi_stream.begin(), m_edi_stream.begin() + std::ptrdiff_t(p));
 }
 
+void BasicRadio::ProcessPft(tcb::span<const uint8_t> bytes, bool flush) {
+    namespace pf = dabgpu_pft;
+    static const pf::Gf gf = pf::make_gf();
+    std::vector<uint8_t> out;
+    pf::Result result{};
+    {
+        std::lock_guard<std::mutex> lock(m_pft_mutex);
+        const uint8_t *state_in = m_pft_state.empty() ? nullptr : m_pft_state.data();
+        pf::Head in{};
+        if (state_in) std::memcpy(&in, state_in, sizeof in);
+        // S = the tail the last call left + the new bytes
+        const size_t tail = pf::clamp_tail(in.tail_bytes);
+        std::vector<uint8_t> s(tail + bytes.size());
+        if (tail) std::memcpy(s.data(), state_in + pf::STATE_TAIL_AT, tail);
+        if (!bytes.empty()) std::memcpy(s.data() + tail, bytes.data(), bytes.size());
+        out.resize(size_t(pf::read_out_bytes(uint32_t(bytes.size()))));
+        std::vector<pf::Record> records(pf::read_max_records(uint32_t(bytes.size())));
+        std::vector<uint8_t> scratch(static_cast<size_t>(pf::MAX_BLOCK), 0);
+        m_pft_next.assign(size_t(pf::STATE_BYTES), 0);
+        pf::read_entry(gf, s.data(), s.size(), state_in, flush ? uint32_t(pf::READ_FLUSH) : 0u, out.data(), records.data(), uint32_t(records.size()),
+                       &result, m_pft_next.data(), scratch.data());
+        m_pft_state.swap(m_pft_next);
+    }
+    // (packets that are no AF packets go along: ProcessEdi resynchronises over them and counts them)
+    if (result.out_bytes) ProcessEdi({out.data(), size_t(result.out_bytes)});
+}
+
+dabgpu_pft::Head BasicRadio::GetPftReadTotals() const {
+    dabgpu_pft::Head h{};
+    std::lock_guard<std::mutex> lock(m_pft_mutex);
+    if (!m_pft_state.empty()) std::memcpy(&h, m_pft_state.data(), sizeof h);
+    return h;
+}
+
 // what the per-frame call needs to know of a sub-channel the FIC has described; false: a profile it cannot decode
 bool BasicRadio::describe_subchannel(::Subchannel &sub, dabgpu_subchannel &sc) {
     sc = dabgpu_subchannel{};

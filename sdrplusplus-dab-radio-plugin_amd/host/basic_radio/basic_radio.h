@@ -28,6 +28,7 @@
 #include "dabgpu.h"
 #include "dabgpu_edi.h"
 #include "dabgpu_eti_read.h"
+#include "dabgpu_pft.h"
 #include "utility/gpu_buffers.h"
 #include "utility/observable.h"
 #include "utility/span.h"
@@ -55,6 +56,13 @@ public:
     void ProcessEdi(tcb::span<const uint8_t> bytes);
     // running totals of ProcessEdi: rows, not_deti, bad_tags, skipped, resyncs, gap_sum, fib_errors; tail_bytes held
     const dabgpu_edi::Head &GetEdiReadTotals() const { return m_edi_head; }
+    // The same for EDI as it travels over UDP: a byte stream of PF fragments (datagram payloads one after the other).  The
+    // serial reader of include/dabgpu_pft.h puts the AF packets back together -- fragments in any order, missing ones filled by
+    // RS(255,207) erasure decoding where they can be -- and hands them to ProcessEdi.  flush: close every open group at the
+    // end (the stream ends here).  No call into libdabgpu.
+    void ProcessPft(tcb::span<const uint8_t> bytes, bool flush = false);
+    // running totals of ProcessPft (records, packets, lost, recovered, fragments, ...)
+    dabgpu_pft::Head GetPftReadTotals() const;
     std::mutex &GetMutex() { return m_mutex; }
     Observable<subchannel_id_t, Basic_Audio_Channel &> &On_Audio_Channel() { return m_obs_audio_channel; }
     // read under GetMutex(), as the GUI does (/root/reference/src/render_radio_block.cpp:124, 158-160, 239, 755)
@@ -136,4 +144,6 @@ private:
     std::vector<uint8_t> m_eti_stream;                   // S of the current call; what the walk leaves is the next call's tail
     dabgpu_edi::Head m_edi_head{};                       // ProcessEdi: the same
     std::vector<uint8_t> m_edi_stream;
+    mutable std::mutex m_pft_mutex;                      // ProcessPft's own (ProcessEdi takes m_mutex itself); GetPftReadTotals takes it too
+    std::vector<uint8_t> m_pft_state, m_pft_next;        // ProcessPft: the state record between calls (empty: a stream that starts)
 };
