@@ -2847,6 +2847,148 @@ int dabgpu_viterbi(dabgpu_ctx *ctx, const int8_t *punct, int n_codewords, const 
                    int nsteps, uint8_t *out_bytes);
 
 /* ------------------------------------------------------------------------ */
+/* T-DMB: stream-mode data sub-channels (FIG 0/2, TMId 1, DSCTy 24) to checked  */
+/* MPEG-2 TS packets, on the device (ETSI TS 102 427).  One entry per (stream,   */
+/* stream-mode sub-channel), behind dabgpu_decode_ensembles_dev,                 */
+/* dabgpu_eti_read_dev or dabgpu_edi_read_dev on the same stream, on the logical  */
+/* frames those calls leave.  Three launches whatever */
+/* the number of entries: sync (a workgroup per entry, a lane per phase), gather  */
+/* and RS(204,188) (a workgroup per packet), continuity (a workgroup per entry).  */
+/* The contract, every ambiguity decided, and the code are include/dabgpu_dmb.h:  */
+/* sync search over all 204 phases (lock after 5 sync bytes 204 apart, loss after */
+/* 8 misses), the 12-branch convolutional de-interleaver as a gather              */
+/* x[i] = y[s + 204 (i mod 12) + i], the outer code of dabgpu_packet_fec_dev,     */
+/* continuity counters of all 8192 PIDs and a census of the first 32.  The output */
+/* of a stream does not depend on where it is cut into calls.                     */
+/*                                                                              */
+/* With less room than dabgpu_dmb_max_packets the packets that do not fit wait in   */
+/* the state record (up to 64) and come out first in the next call.                */
+/*                                                                              */
+/* Not provided: anything inside the TS; erasure decoding.                         */
+/* ------------------------------------------------------------------------ */
+#define DABGPU_DSCTY_MPEG2_TS 24            /* TS 101 756 table 2: MPEG-2 transport stream (T-DMB) */
+#define DABGPU_DMB_TS_BYTES 188
+#define DABGPU_DMB_CENSUS 32
+#define DABGPU_DMB_DEFER_ROOM 64
+enum { DABGPU_DMB_AS_RECEIVED = 0, DABGPU_DMB_CORRECTED = 1, DABGPU_DMB_UNCORRECTABLE = 2 };
+#define DABGPU_DMB_EXEMPT 1                 /* record flag: discontinuity_indicator set in an adaptation field of length >= 1 */
+
+typedef struct dabgpu_dmb_record {          /* one emitted TS packet */
+    uint8_t status;                         /* DABGPU_DMB_AS_RECEIVED / _CORRECTED / _UNCORRECTABLE (then byte 1 |= 0x80 in d_ts) */
+    uint8_t corrected_data, corrected_parity;
+    uint8_t byte3;                          /* transport_scrambling_control << 6 | adaptation_field_control << 4 | continuity_counter */
+    uint16_t pid;
+    uint8_t flags;                          /* DABGPU_DMB_EXEMPT */
+    uint8_t reserved;
+    uint32_t position;                      /* of the packet's first byte in the sub-channel's byte stream, modulo 2^32 */
+    uint32_t reserved2;
+} dabgpu_dmb_record;
+
+typedef struct dabgpu_dmb_result {          /* counts of THIS call, then where the stream stands */
+    int32_t cifs, bytes;
+    int32_t sync_hits;                      /* sync bytes found where the lock looked for them */
+    int32_t locks, lock_losses;
+    int32_t packets_emitted, packets_clean, packets_corrected, packets_uncorrectable;
+    int32_t packets_dropped;                /* of a lock that was lost before they were complete */
+    int32_t bytes_corrected, parity_bytes_corrected;
+    int32_t discontinuities, duplicates;
+    int32_t locked, phase;                  /* at the end of the call; phase = lock position mod 204, -1 unlocked */
+    int32_t pids, pids_overflowed;          /* cumulative: census entries in use; distinct PIDs that found it full */
+    int32_t packets_deferred;               /* waiting in d_state_out: the next call emits them first                */
+    int32_t packets_lost;                   /* of this call: beyond max_packets and beyond the 64 the record holds   */
+} dabgpu_dmb_result;
+
+typedef struct dabgpu_dmb_census_entry {    /* cumulative, since the fresh start */
+    uint16_t pid, reserved;
+    uint32_t packets, discontinuities, duplicates, scrambled;
+} dabgpu_dmb_census_entry;
+
+typedef struct dabgpu_dmb_entry {           /* HOST array, one per sub-channel; every pointer DEVICE memory */
+    const uint8_t *d_in;        /* [n_cifs][in_stride] logical frames of 3 * bitrate_kbps bytes, any alignment     */
+    size_t in_stride;           /* >= 3 * bitrate_kbps                                                           */
+    int32_t bitrate_kbps;       /* a multiple of 8 in 8 .. 1824                                                  */
+    int32_t max_packets;        /* room in d_ts and d_records, >= 0; dabgpu_dmb_max_packets() holds everything   */
+    uint8_t *d_ts;              /* [max_packets][188], 16-byte boundary: the emitted packets back to back         */
+    dabgpu_dmb_record *d_records; /* [max_packets], 16-byte boundary                                             */
+    const void *d_state_in;     /* dabgpu_dmb_state_bytes() on a 16-byte boundary; NULL = fresh start            */
+    void *d_state_out;          /* same size and alignment; != d_state_in, no overlap                            */
+    dabgpu_dmb_result *d_result;
+} dabgpu_dmb_entry;
+
+/* bytes of a state record (any bit rate) */
+size_t dabgpu_dmb_state_bytes(void);
+/* the most packets a call of n_cifs frames can emit: ceil(3 * bitrate_kbps * n_cifs / 204) that it completes and the
+ * DABGPU_DMB_DEFER_ROOM an earlier call may have deferred; -1 for what the call refuses.  With less room only the first
+ * max_packets are emitted (packets, records, counts by status, continuity and census: all at emission); the next up to
+ * DABGPU_DMB_DEFER_ROOM wait in d_state_out and are emitted first by the next call (packets_deferred); the rest are
+ * packets_lost.  While nothing is lost the output of a stream does not depend on the room given either. */
+int dabgpu_dmb_max_packets(int bitrate_kbps, int n_cifs);
+/* the census of a state record on HOST memory (NULL, all zero or foreign: none): up to DABGPU_DMB_CENSUS entries into
+ * `census`, in the order the PIDs first appeared; returns how many, or DABGPU_ERR_ARG */
+int dabgpu_dmb_state_census(const void *state, int bitrate_kbps, dabgpu_dmb_census_entry *census);
+
+/* host only, the sister of dabgpu_fig_audio_components and dabgpu_fig_packet_components: the stream-mode data components
+ * (FIG 0/2 TMId = 1, both P/D forms: DSCTy(6), SubChId(6), P/S(1), CA flag(1)) of CRC-clean FIBs of ONE ensemble, current
+ * configuration of this ensemble (C/N = 0, OE = 0), joined through the SubChId to FIG 0/1 for the start address -- which is
+ * also what joins a component to its dabgpu_subchannel among the entries of dabgpu_fig_subchannels.  Sorted by start
+ * address; each SubChId once (its first component); a component whose sub-channel the same FIBs have not announced is left
+ * out.  Components are reported, not judged: dscty == DABGPU_DSCTY_MPEG2_TS is what dabgpu_dmb_follow_dev is for, whether
+ * another DSCTy is followed is the caller's choice.  *n receives the count; DABGPU_ERR_CAPACITY if max is too small (nothing
+ * written). */
+typedef struct dabgpu_stream_component {
+    uint32_t sid;               /* 16-bit (P/D = 0) or 32-bit (P/D = 1) service identifier */
+    int32_t subchid;
+    int32_t start_address;      /* CU, as dabgpu_subchannel.start_address                 */
+    int32_t dscty;              /* TS 101 756 table 2; 24 = MPEG-2 transport stream        */
+    int32_t primary;            /* P/S flag                                                */
+    int32_t ca;                 /* CA flag                                                 */
+    int32_t reserved[2];
+} dabgpu_stream_component;
+int dabgpu_fig_stream_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_stream_component *out, int max,
+                                 int *n);
+
+/* host only: the programmes of a buffer of TS packets [n_packets][188] (ISO/IEC 13818-1 clauses 2.4.4.3 and 2.4.4.8), as
+ * dabgpu_dmb_follow_dev leaves them in d_ts.  PAT sections (PID 0, table_id 0) and the PMT sections (table_id 2) of the PIDs the
+ * PAT names are assembled through pointer_field and continuation packets (adaptation fields skipped; a packet with the
+ * transport_error_indicator set, or a continuity counter out of order, ends the section being assembled), checked with
+ * CRC-32/MPEG-2 (a section that fails counts in crc_errors and is ignored) and taken when current_next_indicator is set.
+ * Listed: programme numbers with their PMT PID in PAT order (programme 0 names the network PID and is no programme), and per
+ * programme whose PMT was seen: PCR PID, whether an IOD descriptor (tag 0x1D) stands in its programme info, and the
+ * elementary streams (stream_type, PID) in PMT order.  A later section of the same table replaces the earlier one.  Nothing
+ * of SL, OD, BIFS or the video is interpreted.  Programmes beyond DABGPU_TS_MAX_PROGRAMS and streams beyond
+ * DABGPU_TS_MAX_STREAMS are counted in n_programs / n_streams but not stored.  DABGPU_ERR_ARG for a NULL pointer or a
+ * negative count. */
+#define DABGPU_TS_MAX_PROGRAMS 16
+#define DABGPU_TS_MAX_STREAMS 16
+typedef struct dabgpu_ts_program {
+    int32_t program_number, pmt_pid;
+    int32_t pmt_seen;                       /* a PMT section of this programme checked; the fields below are valid  */
+    int32_t pcr_pid, iod_present, n_streams;
+    int32_t stream_type[DABGPU_TS_MAX_STREAMS], stream_pid[DABGPU_TS_MAX_STREAMS];
+} dabgpu_ts_program;
+typedef struct dabgpu_ts_info {
+    int32_t transport_stream_id;            /* -1: no PAT seen                                                      */
+    int32_t network_pid;                    /* -1: none named                                                       */
+    int32_t n_programs;
+    int32_t pat_sections, pmt_sections;     /* sections that checked                                                */
+    int32_t crc_errors;
+    int32_t reserved[2];
+    dabgpu_ts_program programs[DABGPU_TS_MAX_PROGRAMS];
+} dabgpu_ts_info;
+int dabgpu_ts_programs(const uint8_t *ts, int n_packets, dabgpu_ts_info *info);
+
+/* entries [n_entries] (HOST).  No host synchronisation.  Everything is checked before anything is enqueued, so a refused call
+ * leaves every output as it was: DABGPU_ERR_ARG for a NULL context or table, a negative count, n_cifs outside 0 .. 2^16, a bit
+ * rate outside 8 .. 1824 or no multiple of 8, in_stride < 3 * bitrate_kbps, a NULL d_in with n_cifs > 0, a negative
+ * max_packets, a NULL d_ts or d_records with max_packets > 0, a NULL d_state_out or d_result, d_ts, d_records or
+ * a state record off a 16-byte boundary, d_result off a 4-byte boundary, d_state_out equal to or overlapping d_state_in;
+ * DABGPU_ERR_CAPACITY for more than 65535 entries, or when n_entries times the largest entry's ceil(3 * bitrate_kbps * n_cifs /
+ * 204) reaches 2^24 (a workgroup of 256 lanes per packet: the launch's thread count stays below 2^32). */
+int dabgpu_dmb_follow_dev(dabgpu_ctx *ctx, const dabgpu_dmb_entry *entries, int n_entries, int n_cifs, void *stream);
+/* the same table with HOST pointers, the same checks, the serial code of include/dabgpu_dmb.h: no context, no GPU */
+int dabgpu_dmb_follow_host(const dabgpu_dmb_entry *entries, int n_entries, int n_cifs);
+
+/* ------------------------------------------------------------------------ */
 /* Timing helper: duration (ms) of the launches of each kernel family,         */
 /* measured with hipEvents on the launch stream, around the kernel launch       */
 /* alone, while dabgpu_set_timing(ctx,1) is on (every call to it starts a new   */

@@ -82,6 +82,7 @@ enum StageSlot {
     STAGE_EDI_READ = 25,             // dabgpu_edi_read_dev: the entry table and the two bitmaps of every entry
     STAGE_PFT = 26,                  // dabgpu_pft_fragments_dev: the first Pseq of every stream
     STAGE_PFT_READ = 27,             // dabgpu_pft_read_dev: the entry table, the two bitmaps and the fill launch's arena of every entry
+    STAGE_DMB = 28,                  // dabgpu_dmb_follow_dev: the entry table, the sync launch's words and packet starts of every entry
     STAGE_SLOTS
 };
 

@@ -550,6 +550,37 @@ uint64_t packet_fec_blocks(const PacketFecEntry *entries, int n_entries, int n_c
 hipError_t launch_packet_fec(PacketFecEntry *entries, int n_entries, int n_cifs, bool erasures, void *d_table, size_t table_bytes,
                              hipStream_t stream);
 
+// ---- T-DMB stream-mode sub-channels to TS packets (dmb_kernels.hip) -----------------
+// dabgpu_dmb_follow_dev: one entry per sub-channel, uploaded as a table with its scratch behind it.  Three launches: sync (a
+// workgroup per entry, a lane per phase: run counters, the locks of the call, the start of every packet the call emits, the
+// new record's head, run counters and carried bytes), packets (a workgroup per emitted packet: the de-interleaving gather,
+// 16 syndromes across the lanes, Berlekamp-Massey / Chien / Forney where needed, 188 bytes and a record out) and continuity
+// (a workgroup per entry: a lane per packet in chunks of 256, the counter table and the census in LDS, the result and the
+// rest of the new record).  include/dabgpu_dmb.h.
+constexpr int DMB_SYNC_WORDS = 16;   // count, dropped, sync_hits, locks, lock_losses, locked, phase, 0 ...
+struct alignas(16) DmbEntry {
+    uint64_t in;               // [n_cifs][in_stride] logical frames of 3 kbps bytes
+    uint64_t in_stride;
+    uint64_t ts;               // [capacity][188]
+    uint64_t records;          // [capacity] dabgpu_dmb::Record
+    uint64_t state_in;         // dabgpu_dmb::STATE_BYTES or 0
+    uint64_t state_out;
+    uint64_t result;           // dabgpu_dmb::Result
+    uint64_t sync;             // filled in by the launch: [DMB_SYNC_WORDS + max_packets] words: the sync launch's counts, then
+                               // every emitted packet's start, counted from 2448 bytes before the call's first byte
+    int32_t kbps;
+    int32_t max_packets;       // dabgpu_dmb::new_packets(kbps, n_cifs): the most the call completes
+    int32_t capacity;          // room in ts / records, packets; what does not fit is deferred into the new state record
+};
+static_assert(sizeof(DmbEntry) == 80, "an entry of the table in the stage area");
+constexpr int DMB_MAX_ENTRIES = 65535;
+size_t dmb_table_bytes(const DmbEntry *entries, int n_entries);
+// workgroups of the largest launch (256 lanes each: DMB_MAX_BLOCKS keeps the launch's thread count below 2^32)
+constexpr uint64_t DMB_MAX_BLOCKS = (uint64_t(1) << 24) - 1;
+uint64_t dmb_blocks(const DmbEntry *entries, int n_entries);
+// `entries`: HOST array (sync is set here; copied to d_table on `stream` before the kernels); every pointer checked by the caller
+hipError_t launch_dmb(DmbEntry *entries, int n_entries, int n_cifs, void *d_table, size_t table_bytes, hipStream_t stream);
+
 // ---- channel decoder (viterbi_kernels.hip) ---------------------------------
 struct CodeTables {
     const uint16_t *mother_pos;  // [n_punct] mother-bit position of punctured bit i

@@ -69,6 +69,8 @@ EXPORTS = [
     "dabgpu_edi_read_state_bytes", "dabgpu_edi_read_max_rows", "dabgpu_edi_read_dev", "dabgpu_edi_read_host",
     "dabgpu_pft_layout", "dabgpu_pft_fragments_dev", "dabgpu_pft_fragments_host", "dabgpu_pft_read_state_bytes",
     "dabgpu_pft_read_out_bytes", "dabgpu_pft_read_max_records", "dabgpu_pft_read_dev", "dabgpu_pft_read_host",
+    "dabgpu_dmb_state_bytes", "dabgpu_dmb_max_packets", "dabgpu_dmb_state_census", "dabgpu_dmb_follow_dev", "dabgpu_dmb_follow_host",
+    "dabgpu_fig_stream_components", "dabgpu_ts_programs",
 ]
 
 ABI_VERSION = 6
@@ -390,6 +392,38 @@ class PacketFecErasureEntry(C.Structure):
     packet_fec_erasures_host (host addresses); d_result is a PACKET_FEC_ERASURE_RESULT_DTYPE record.  The state record has
     the size packet_fec_state_bytes(bitrate) gives; one written by the errors-only call is a fresh start here."""
     _fields_ = list(PacketFecEntry._fields_)
+
+
+class StreamComponent(C.Structure):
+    """dabgpu_stream_component: a stream-mode data component (FIG 0/2 TMId 1) joined to FIG 0/1"""
+    _fields_ = [("sid", C.c_uint32), ("subchid", C.c_int32), ("start_address", C.c_int32), ("dscty", C.c_int32),
+                ("primary", C.c_int32), ("ca", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+TS_MAX_PROGRAMS, TS_MAX_STREAMS = 16, 16
+
+
+class TsProgram(C.Structure):
+    """dabgpu_ts_program: a programme of the PAT and, when pmt_seen, of its PMT"""
+    _fields_ = [("program_number", C.c_int32), ("pmt_pid", C.c_int32), ("pmt_seen", C.c_int32), ("pcr_pid", C.c_int32),
+                ("iod_present", C.c_int32), ("n_streams", C.c_int32), ("stream_type", C.c_int32 * TS_MAX_STREAMS),
+                ("stream_pid", C.c_int32 * TS_MAX_STREAMS)]
+
+
+class TsInfo(C.Structure):
+    """dabgpu_ts_info: what dabgpu_ts_programs found in a buffer of TS packets"""
+    _fields_ = [("transport_stream_id", C.c_int32), ("network_pid", C.c_int32), ("n_programs", C.c_int32),
+                ("pat_sections", C.c_int32), ("pmt_sections", C.c_int32), ("crc_errors", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("programs", TsProgram * TS_MAX_PROGRAMS)]
+
+
+class DmbEntry(C.Structure):
+    """dabgpu_dmb_entry: one T-DMB stream-mode sub-channel of Context.dmb_follow_dev (device addresses) or dmb_follow_host
+    (host addresses): the logical frames, room for max_packets TS packets of 188 bytes and as many DMB_RECORD_DTYPE records
+    (dmb_max_packets(bitrate, n_cifs) holds everything; with less, up to DMB_DEFER_ROOM packets wait in the state record), the state records (dmb_state_bytes()), a DMB_RESULT_DTYPE record."""
+    _fields_ = [("d_in", C.c_void_p), ("in_stride", C.c_size_t), ("bitrate_kbps", C.c_int32), ("max_packets", C.c_int32),
+                ("d_ts", C.c_void_p), ("d_records", C.c_void_p), ("d_state_in", C.c_void_p), ("d_state_out", C.c_void_p),
+                ("d_result", C.c_void_p)]
 
 
 class PacketComponent(C.Structure):
@@ -987,6 +1021,14 @@ def load_library(path):
     L.dabgpu_pft_read_dev.argtypes = [vp, C.POINTER(PftReadEntry), i, vp]
     L.dabgpu_fig_user_applications.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
     L.dabgpu_mot_directory_parse.argtypes = [vp, i, vp, vp, i, C.POINTER(C.c_int)]
+    L.dabgpu_fig_stream_components.argtypes = [vp, vp, i, vp, i, C.POINTER(C.c_int)]
+    L.dabgpu_ts_programs.argtypes = [vp, i, C.POINTER(TsInfo)]
+    L.dabgpu_dmb_state_bytes.restype = C.c_size_t
+    L.dabgpu_dmb_state_bytes.argtypes = []
+    L.dabgpu_dmb_max_packets.argtypes = [i, i]
+    L.dabgpu_dmb_state_census.argtypes = [vp, i, vp]
+    L.dabgpu_dmb_follow_dev.argtypes = [vp, C.POINTER(DmbEntry), i, i, vp]
+    L.dabgpu_dmb_follow_host.argtypes = [C.POINTER(DmbEntry), i, i]
     L.dabgpu_packet_fec_state_bytes.restype = C.c_size_t
     L.dabgpu_packet_fec_state_bytes.argtypes = [i]
     L.dabgpu_packet_fec_delay.argtypes = [i]
@@ -1291,6 +1333,90 @@ def mot_directory_parse(directory, max_objects=256):
     _check(lib().dabgpu_mot_directory_parse(_p(d) if d.size else _p(np.zeros(1, np.uint8)), d.size, _p(info), _p(out), max_objects,
                                             C.byref(n)), "dabgpu_mot_directory_parse")
     return info[0], out[:n.value].copy()
+
+
+#: T-DMB stream-mode sub-channels (include/dabgpu.h, "T-DMB"; include/dabgpu_dmb.h)
+DSCTY_MPEG2_TS = 24
+DMB_TS_BYTES, DMB_CENSUS = 188, 32
+DMB_AS_RECEIVED, DMB_CORRECTED, DMB_UNCORRECTABLE = 0, 1, 2
+DMB_EXEMPT = 1
+#: dabgpu_dmb_record: one emitted TS packet
+DMB_RECORD_DTYPE = np.dtype([("status", np.uint8), ("corrected_data", np.uint8), ("corrected_parity", np.uint8), ("byte3", np.uint8),
+                             ("pid", np.uint16), ("flags", np.uint8), ("reserved", np.uint8), ("position", np.uint32),
+                             ("reserved2", np.uint32)])
+assert DMB_RECORD_DTYPE.itemsize == 16
+#: dabgpu_dmb_result: what one entry of dmb_follow_dev / dmb_follow_host counted in one call, and where the stream stands
+DMB_COUNTERS = ("cifs", "bytes", "sync_hits", "locks", "lock_losses", "packets_emitted", "packets_clean", "packets_corrected",
+                "packets_uncorrectable", "packets_dropped", "bytes_corrected", "parity_bytes_corrected", "discontinuities",
+                "duplicates")
+DMB_RESULT_DTYPE = np.dtype([(n, np.int32) for n in DMB_COUNTERS + ("locked", "phase", "pids", "pids_overflowed", "packets_deferred",
+                                                                   "packets_lost")])
+DMB_DEFER_ROOM = 64
+assert DMB_RESULT_DTYPE.itemsize == 80
+#: dabgpu_dmb_census_entry
+DMB_CENSUS_DTYPE = np.dtype([("pid", np.uint16), ("reserved", np.uint16), ("packets", np.uint32), ("discontinuities", np.uint32),
+                             ("duplicates", np.uint32), ("scrambled", np.uint32)])
+assert DMB_CENSUS_DTYPE.itemsize == 20
+
+
+def dmb_state_bytes():
+    """Bytes of one state record of Context.dmb_follow_dev / dmb_follow_host (NULL or all zero = a fresh start)."""
+    return int(lib().dabgpu_dmb_state_bytes())
+
+
+def dmb_max_packets(bitrate, n_cifs):
+    """ceil(3 * bitrate * n_cifs / 204) + DMB_DEFER_ROOM: the most TS packets a call of n_cifs frames can emit -- what it completes and
+    what an earlier call deferred; with this much room in d_ts / d_records nothing is ever deferred."""
+    n = int(lib().dabgpu_dmb_max_packets(int(bitrate), int(n_cifs)))
+    if n < 0:
+        raise ValueError("not a stream-mode bit rate or frame count: %r, %r" % (bitrate, n_cifs))
+    return n
+
+
+def dmb_state_census(state, bitrate):
+    """The PID census of a state record on the host (uint8 array of dmb_state_bytes(), or None) -> DMB_CENSUS_DTYPE array,
+    the first 32 distinct PIDs in the order they appeared, cumulative counts (dabgpu_dmb_state_census)."""
+    out = np.zeros(DMB_CENSUS, DMB_CENSUS_DTYPE)
+    st = None if state is None else np.ascontiguousarray(state, np.uint8)
+    if st is not None and st.size != dmb_state_bytes():
+        raise ValueError("a state record has dmb_state_bytes() bytes")
+    n = lib().dabgpu_dmb_state_census(None if st is None else _p(st), int(bitrate), _p(out))
+    _check(min(n, 0), "dabgpu_dmb_state_census")
+    return out[:n].copy()
+
+
+def fig_stream_components(fib, crc_ok, max_out=64):
+    """The stream-mode data components one ensemble announces (FIG 0/2 TMId 1 joined to FIG 0/1) in its CRC-clean FIBs, each
+    sub-channel once, sorted by start address: fib [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of
+    StreamComponent (dscty DSCTY_MPEG2_TS = T-DMB; no GPU needed)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    arr = (StreamComponent * max(max_out, 1))()
+    n = C.c_int(0)
+    _check(lib().dabgpu_fig_stream_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_stream_components")
+    return [StreamComponent(a.sid, a.subchid, a.start_address, a.dscty, a.primary, a.ca) for a in arr[:n.value]]
+
+
+def ts_programs(ts):
+    """The programmes of TS packets (uint8 [n][188], e.g. what dmb_follow leaves in d_ts): PAT and PMT sections assembled and
+    checked (dabgpu_ts_programs: host only) -> TsInfo."""
+    ts = np.ascontiguousarray(ts, np.uint8)
+    if ts.size % 188:
+        raise ValueError("TS packets are 188 bytes")
+    info = TsInfo()
+    _check(lib().dabgpu_ts_programs(_p(ts) if ts.size else None, ts.size // 188, C.byref(info)), "dabgpu_ts_programs")
+    return info
+
+
+def dmb_follow_host(entries, n_cifs):
+    """Context.dmb_follow_dev on HOST memory (entries: DmbEntry with host addresses): the same checks and the serial code of
+    include/dabgpu_dmb.h; no context, no GPU."""
+    n = len(entries)
+    arr = (DmbEntry * max(n, 1))(*entries)
+    _check(lib().dabgpu_dmb_follow_host(arr, n, n_cifs), "dabgpu_dmb_follow_host")
 
 
 def packet_fec_state_bytes(bitrate):
@@ -2197,6 +2323,43 @@ class Context:
         n = len(entries)
         arr = (PacketGroupsEntry * max(n, 1))(*entries)
         _check(self._lib.dabgpu_packet_groups_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_groups_dev")
+
+    def dmb_follow_dev(self, entries, n_cifs, stream=None):
+        """T-DMB stream-mode sub-channels to checked TS packets on the device (dabgpu_dmb_follow_dev): entries is a list of
+        DmbEntry (device addresses), one per (stream, sub-channel), n_cifs logical frames each.  Per entry: d_ts, the
+        emitted 188-byte packets back to back; d_records (DMB_RECORD_DTYPE); d_result (DMB_RESULT_DTYPE, counts of this
+        call); d_state_out, which the next call takes as d_state_in.  Three launches whatever the number of entries, no
+        host synchronisation."""
+        n = len(entries)
+        arr = (DmbEntry * max(n, 1))(*entries)
+        _check(self._lib.dabgpu_dmb_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dmb_follow_dev")
+
+    def dmb_follow(self, frames, bitrate, state=None):
+        """frames: torch uint8 tensor [n_streams][n_cifs][row] on this context's device, row >= 3 * bitrate, the last dimension
+        contiguous: the next logical frames of n_streams T-DMB sub-channels of one bit rate (what the decode call or the ETI /
+        EDI readers wrote).  state: what an earlier call on the same streams returned (None: the streams start here).
+        -> (ts uint8 [n_streams][max_packets][188], records uint8 [n_streams][max_packets][16] (view as DMB_RECORD_DTYPE on
+        the host), result uint8 [n_streams][80] (DMB_RESULT_DTYPE; packets_emitted says how many of ts are packets), state
+        uint8 [n_streams][dmb_state_bytes()]); device tensors; the work is finished when the call returns."""
+        import torch
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or frames.shape[2] < 3 * bitrate or (frames.numel() and frames.stride(2) != 1):
+            raise ValueError("frames must be a uint8 tensor [n_streams][n_cifs][>= 3 * bitrate] with contiguous rows")
+        n_streams, n_cifs = frames.shape[0], frames.shape[1]
+        m = dmb_max_packets(bitrate, n_cifs)
+        u8 = dict(dtype=torch.uint8, device=frames.device)
+        ts = torch.zeros((n_streams, (max(m, 1) * DMB_TS_BYTES + 15) // 16 * 16), **u8)    # (every stream's packets on a 16-byte boundary)
+        records = torch.zeros((n_streams, max(m, 1), 16), **u8)
+        result = torch.zeros((n_streams, 80), **u8)
+        state_out = torch.empty((n_streams, dmb_state_bytes()), **u8)
+        if n_cifs > 1 and n_streams and frames.stride(1) < 3 * bitrate:
+            raise ValueError("rows overlap")
+        entries = [DmbEntry(frames[s].data_ptr() if n_cifs else None, frames.stride(1) if n_cifs > 1 else max(frames.shape[2], 3 * bitrate),
+                            bitrate, m, ts[s].data_ptr(), records[s].data_ptr(), None if state is None else state[s].data_ptr(),
+                            state_out[s].data_ptr(), result[s].data_ptr()) for s in range(n_streams)]
+        torch.cuda.current_stream(frames.device).synchronize()
+        self.dmb_follow_dev(entries, n_cifs)
+        self.sync()
+        return ts[:, :m * DMB_TS_BYTES].unflatten(1, (m, DMB_TS_BYTES)), records[:, :m], result, state_out
 
     def packet_fec_dev(self, entries, n_cifs, stream=None):
         """RS(204,188) correction of the FEC frames of packet-mode sub-channels, between decode_ensembles_dev and

@@ -105,6 +105,7 @@ void BasicRadio::Process(tcb::span<const viterbi_bit_t> buf) {
             if (s.dab_plus) s.dab_plus->Process(lf);
             if (s.dab) s.dab->Process(lf);
             if (s.packet) s.packet->Process(lf);
+            if (s.dmb) s.dmb->Process(lf);
         }
     }
     LAP(3);
@@ -177,6 +178,7 @@ void BasicRadio::route_stream_locked(int start_address, int nbytes, const uint8_
         if (s.dab_plus) s.dab_plus->Process(lf);
         if (s.dab) s.dab->Process(lf);
         if (s.packet) s.packet->Process(lf);
+        if (s.dmb) s.dmb->Process(lf);
     }
 }
 
@@ -271,7 +273,7 @@ int BasicRadio::open_subchannel(const dabgpu_subchannel &sc) {
         const dabgpu_subchannel &d = m_subchannels[k].desc;
         if (d.start_address == sc.start_address && d.length == sc.length && d.bitrate_kbps == sc.bitrate_kbps &&
             d.is_uep == sc.is_uep && d.eep_type == sc.eep_type && d.protection_level == sc.protection_level && !m_subchannels[k].dab_plus &&
-            !m_subchannels[k].dab && !m_subchannels[k].packet)
+            !m_subchannels[k].dab && !m_subchannels[k].packet && !m_subchannels[k].dmb)
             return int(k);
     }
     return add_subchannel_locked(sc);
@@ -333,6 +335,39 @@ void BasicRadio::update_packet_channels() {
 void BasicRadio::update_channels_from_database() {
     update_audio_channels();
     update_packet_channels();
+    update_dmb_channels();
+}
+
+// Open a DMB channel for every stream-mode data component whose DSCTy says MPEG-2 transport stream, once FIG 0/2 and
+// FIG 0/1 have both spoken.  Components of another DSCTy stay in the database and are not followed.
+void BasicRadio::update_dmb_channels() {
+    if (m_database.stream_components.size() == m_seen_stream_components && !m_pending_streams) return;
+    m_pending_streams = false;
+    for (const auto &comp : m_database.stream_components) {
+        if (comp.dscty != uint8_t(DataServiceType::MPEG2)) continue;
+        if (m_dmb_channels.count(comp.subchannel_id) || m_channels.count(comp.subchannel_id) || m_packet_channels.count(comp.subchannel_id)) continue;
+        bool rejected = false;
+        for (auto id : m_rejected) rejected |= (id == comp.subchannel_id);
+        if (rejected) continue;
+        ::Subchannel *sub = nullptr;
+        for (auto &s : m_database.subchannels)
+            if (s.id == comp.subchannel_id) sub = &s;
+        if (!sub) {                                          // FIG 0/1 for it has not arrived yet
+            m_pending_streams = true;
+            continue;
+        }
+        dabgpu_subchannel sc{};
+        const int idx = describe_subchannel(*sub, sc) && dabgpu_dmb::bitrate_ok(sc.bitrate_kbps) ? open_subchannel(sc) : -1;
+        if (idx < 0) {
+            m_rejected.push_back(sub->id);
+            m_total_unsupported++;
+            continue;
+        }
+        auto ch = std::make_unique<Basic_DMB_Channel>(*sub, sc.bitrate_kbps);
+        m_subchannels[size_t(idx)].dmb = ch.get();
+        m_dmb_channels.emplace(sub->id, std::move(ch));
+    }
+    m_seen_stream_components = m_database.stream_components.size();
 }
 
 void BasicRadio::update_audio_channels() {

@@ -21,6 +21,7 @@
 #include "basic_radio/basic_dab_channel.h"
 #include "basic_radio/basic_dab_plus_channel.h"
 #include "basic_radio/basic_data_packet_channel.h"
+#include "basic_radio/basic_dmb_channel.h"
 #include "dab/constants/dab_parameters.h"
 #include "dab/database/dab_database.h"
 #include "dab/database/dab_database_updater.h"
@@ -78,6 +79,11 @@ public:
         auto it = m_packet_channels.find(id);
         return it == m_packet_channels.end() ? nullptr : it->second.get();
     }
+    // the channel of a stream-mode data sub-channel whose DSCTy says MPEG-2 transport stream (T-DMB), nullptr for any other
+    Basic_DMB_Channel *Get_DMB_Channel(subchannel_id_t id) {
+        auto it = m_dmb_channels.find(id);
+        return it == m_dmb_channels.end() ? nullptr : it->second.get();
+    }
     // sub-channels listed in the FIC that cannot be decoded here (invalid profile, does not fit the CIF)
     int GetTotalUnsupportedSubchannels() const { return m_total_unsupported; }
     void SetAutoChannels(bool v) { m_auto_channels = v; }
@@ -105,11 +111,13 @@ private:
         Basic_DAB_Plus_Channel *dab_plus = nullptr;   // set for sub-channels opened from the database
         Basic_DAB_Channel *dab = nullptr;
         Basic_Data_Packet_Channel *packet = nullptr;
+        Basic_DMB_Channel *dmb = nullptr;
     };
     bool describe_subchannel(::Subchannel &sub, dabgpu_subchannel &sc);
     int open_subchannel(const dabgpu_subchannel &sc);
     void update_audio_channels();
     void update_packet_channels();
+    void update_dmb_channels();
     void update_channels_from_database();
     void process_fibs_locked();
     void process_fibs_locked(const uint8_t *fib, const uint8_t *crc, size_t n_fibs);
@@ -132,6 +140,9 @@ private:
     FIC_Parser m_fic_parser{m_updater};
     std::map<subchannel_id_t, std::unique_ptr<Basic_Audio_Channel>> m_channels;
     std::map<subchannel_id_t, std::unique_ptr<Basic_Data_Packet_Channel>> m_packet_channels;
+    std::map<subchannel_id_t, std::unique_ptr<Basic_DMB_Channel>> m_dmb_channels;
+    size_t m_seen_stream_components = 0;
+    bool m_pending_streams = false;                      // ... a stream-mode data component
     std::vector<subchannel_id_t> m_rejected;             // sub-channels we looked at and cannot open
     size_t m_seen_components = 0;
     size_t m_seen_packet_described = 0;                  // packet components FIG 0/2 has named and FIG 0/3 described

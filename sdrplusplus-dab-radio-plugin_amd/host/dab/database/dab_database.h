@@ -19,6 +19,17 @@ struct PacketComponent {
     bool dg_flag = false;                  // false: data groups are used
 };
 
+// A stream-mode data component (FIG 0/2 TMId = 1); kept in a list of its own, as the packet-mode components are: the audio
+// components, their statistics and the text dump are what they were without it.
+struct StreamDataComponent {
+    uint32_t service_id = 0;
+    bool service_id_32 = false;
+    subchannel_id_t subchannel_id = 0;
+    uint8_t dscty = 0;                     // data service component type; 24 = MPEG-2 transport stream (T-DMB)
+    bool is_primary = false;
+    bool ca_flag = false;
+};
+
 // FIG 0/13: a user application of a service component (SId, SCIdS); kept as sent, not interpreted.  Registered types it is
 // useful to know (TS 101 756): 0x002 slideshow, 0x004 TPEG, 0x007 SPI, 0x00D filecasting, 0x44A Journaline.
 struct UserApplication {
@@ -46,6 +57,7 @@ struct DAB_Database {
     std::vector<DRM_Service> drm_services;         // :667
     std::vector<OtherEnsemble> other_ensembles;
     std::vector<PacketComponent> packet_components;        // render_radio_block.cpp:533 asks for their channels
+    std::vector<StreamDataComponent> stream_components;    // FIG 0/2 TMId 1, each SubChId once (its first component)
     uint8_t fec_scheme[64] = {};                           // FIG 0/14, by SubChId; 0 = none announced
     std::vector<UserApplication> user_applications;        // FIG 0/13, each (SId, SCIdS, type) once
     std::vector<ComponentGlobal> component_globals;        // FIG 0/8, each (SId, SCIdS) once

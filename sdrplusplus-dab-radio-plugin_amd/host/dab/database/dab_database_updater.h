@@ -131,6 +131,7 @@ public:
     void SetComponentLabel(ServiceComponent &c, const std::string &label) { set_string(c.label, label); }
     std::vector<ServiceComponent> &Components() { return m_db.service_components; }
     std::vector<PacketComponent> &PacketComponents() { return m_db.packet_components; }
+    std::vector<StreamDataComponent> &StreamComponents() { return m_db.stream_components; }
     std::vector<UserApplication> &UserApplications() { return m_db.user_applications; }
     std::vector<ComponentGlobal> &ComponentGlobals() { return m_db.component_globals; }
     void SetFecScheme(subchannel_id_t id, uint8_t scheme) {

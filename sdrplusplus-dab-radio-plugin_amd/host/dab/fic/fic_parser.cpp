@@ -182,7 +182,14 @@ void FIC_Parser::fig0_2(const uint8_t *d, int n, bool pd) {
                 }
                 continue;
             }
-            if ((b0 >> 6) != 0) continue;                   // stream data and FIDC are not followed
+            if ((b0 >> 6) == 1) {                           // stream-mode data: DSCTy(6) SubChId(6) P/S(1) CA(1)
+                auto &list = m_updater.StreamComponents();
+                bool known = list.size() >= DAB_Database_Updater::MAX_ENTITIES;
+                for (const auto &c : list) known = known || c.subchannel_id == (b1 >> 2);
+                if (!known) list.push_back(StreamDataComponent{sid, pd, subchannel_id_t(b1 >> 2), uint8_t(b0 & 0x3F), (b1 & 2) != 0, (b1 & 1) != 0});
+                continue;
+            }
+            if ((b0 >> 6) != 0) continue;                   // FIDC is not followed
             bool is_new;
             ServiceComponent &sc = m_updater.GetServiceComponent(sid, b1 >> 2, &is_new);
             const auto ascty = static_cast<AudioServiceType>(b0 & 0x3F);     // 0 = DAB, 63 = DAB+, others kept as sent
