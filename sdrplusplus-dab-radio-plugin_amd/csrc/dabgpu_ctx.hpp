@@ -390,6 +390,38 @@ struct HostCall {
     }
 };
 
+// The device table of an entry-table call -- the `_dev` calls that take a list of entries, check all of it, build the kernels'
+// table on the host and launch over it -- in the staging slot of its family, at least `bytes` long, for launches on `s`.
+// stage() frees a slot that has to grow, and growing the table must not race with a launch that still reads the old one: a
+// slot that is too small waits for `s` first (one caller stream at a time per context: dabgpu.h, conventions).
+struct DeviceTable {
+    void *d = nullptr;
+    size_t bytes = 0;                    // the slot's size: what a launch may use behind its own tables
+};
+inline int stage_table(dabgpu_ctx *ctx, StageSlot slot, size_t bytes, hipStream_t s, DeviceTable *out) {
+    if (ctx->stage_bytes[slot] < bytes) HIP_TRY(hipStreamSynchronize(s));
+    const int rc = stage(ctx, slot, bytes, &out->d);
+    out->bytes = ctx->stage_bytes[slot];
+    return rc;
+}
+// ... and the end of such a call, behind its checks (argument errors, no entries, DABGPU_ERR_CAPACITY: nothing before here
+// touches HIP): the context's device, the caller's stream, the table, then launch(d_table, slot_bytes, s) -> hipError_t.
+template <class Launch> int launch_entry_table(dabgpu_ctx *ctx, StageSlot slot, size_t bytes, void *stream, Launch launch) {
+    DeviceGuard guard(ctx);
+    hipStream_t s = pick_stream(ctx, stream);
+    DeviceTable t;
+    const int rc = stage_table(ctx, slot, bytes, s, &t);
+    if (rc) return rc;
+    HIP_TRY(launch(t.d, t.bytes, s));
+    return DABGPU_OK;
+}
+
+// what every *_check compares: an address as a number, and whether [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline uint64_t addr(const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); }
+inline bool overlaps(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
+    return addr(a) < addr(b) + b_bytes && addr(b) < addr(a) + a_bytes;
+}
+
 // No capacity unit of the CIF used twice (and none outside it): the state-keeping entry points (dabgpu_decode_stream_frames,
 // dabgpu_pipe_submit) key their de-interleaver rings by (start, size), so a sub-channel listed twice would share one ring --
 // both entries reading and writing the same pair of buffers, the ring flipped twice -- and the NEXT call would continue from

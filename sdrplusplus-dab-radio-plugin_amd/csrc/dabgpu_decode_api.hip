@@ -6,6 +6,7 @@
 #include <cstring>
 #include <optional>
 
+#include "../../include/dabgpu_fig.h"
 #include "lane_plan.hpp"
 
 using namespace dab;
@@ -76,11 +77,12 @@ int decode_lane(dabgpu_ctx *ctx, const std::vector<dabk::LaneItem> &items, bool 
         return rc ? rc : (single && policy == 2) ? DABGPU_ERR_NOMEM : 1;
     dabk::LaneScratch lsc{ctx->d_lane_scratch, ctx->lane_scratch_bytes, ctx->lane_unfused};
     if (by_table) {
-        const size_t table_bytes = dabk::lane_table_bytes(items.data(), n);
-        // (growing the table must not race with a launch that still reads the old one)
-        if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-        if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &lsc.table)) return 1;
-        lsc.table_bytes = ctx->stage_bytes[STAGE_ENSEMBLES];
+        // (a table that cannot be had falls back, as scratch that cannot; a stream that cannot be waited for is an error)
+        DeviceTable t;
+        const int trc = stage_table(ctx, STAGE_ENSEMBLES, dabk::lane_table_bytes(items.data(), n), s, &t);
+        if (trc) return trc == DABGPU_ERR_HIP ? trc : 1;
+        lsc.table = t.d;
+        lsc.table_bytes = t.bytes;
     }
     std::optional<ScopedTimer> tm;
     if (timer >= 0) tm.emplace(ctx, timer, s);
@@ -479,127 +481,23 @@ int dabgpu_decode_ensembles_dev(dabgpu_ctx *ctx, const int8_t *d_soft, size_t so
 
 int dabgpu_fig_subchannels(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_subchannel *out, int max, int *n) {
     if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
-    // FIG 0/1 (ETSI EN 300 401 clause 6.2.1): SubChId (6), start address (10), then the short form -- 0, table switch (1),
-    // table index (6) -- or the long form -- 1, option (3), protection level (2), size (10)
-    dabgpu_subchannel found[64];
-    bool seen[64] = {};
-    int count = 0;
-    for (int k = 0; k < n_frames * NB_FIBS; k++) {
-        if (!crc_ok[k]) continue;
-        const uint8_t *d = fib + size_t(k) * 32;
-        for (int i = 0; i < 30;) {
-            if (d[i] == 0xFF) break;
-            const int type = d[i] >> 5, len = d[i] & 0x1F;
-            if (len == 0 || i + 1 + len > 30) break;
-            const uint8_t *b = d + i + 1;
-            i += 1 + len;
-            // type 0, extension 1, current configuration (C/N = 0)
-            if (type != 0 || (b[0] & 0x1F) != 1 || (b[0] & 0x80)) continue;
-            for (int j = 1; j + 3 <= len;) {
-                const int id = b[j] >> 2, start = ((b[j] & 3) << 8) | b[j + 1];
-                dabgpu_subchannel sc{};
-                if (b[j + 2] & 0x80) {
-                    if (j + 4 > len) break;
-                    const int option = (b[j + 2] >> 4) & 7, level = ((b[j + 2] >> 2) & 3) + 1, size = ((b[j + 2] & 3) << 8) | b[j + 3];
-                    j += 4;
-                    if (option > 1) continue;                  // reserved option: not an entry a receiver can use
-                    if (seen[id]) continue;
-                    // the bit rate the size implies: n times the level's capacity units, 8 n (A) or 32 n (B) kbit/s
-                    static const int CU_A[4] = {12, 8, 6, 4}, CU_B[4] = {27, 21, 18, 15};
-                    const int unit = option ? CU_B[level - 1] : CU_A[level - 1];
-                    if (size == 0 || size % unit) return DABGPU_ERR_PROFILE;
-                    sc = dabgpu_subchannel{start, size, 0, option, level, (option ? 32 : 8) * (size / unit)};
-                    dab::PunctureProfile prof;
-                    const int rc = subchannel_profile(&sc, prof);
-                    if (rc) return rc;
-                } else {
-                    const int table_switch = (b[j + 2] >> 6) & 1, index = b[j + 2] & 0x3F;
-                    j += 3;
-                    if (seen[id]) continue;
-                    if (table_switch) return DABGPU_ERR_PROFILE;
-                    const int rc = dabgpu_uep_subchannel(index, start, &sc);
-                    if (rc) return rc;
-                }
-                seen[id] = true;
-                found[count++] = sc;
-            }
-        }
-    }
-    std::stable_sort(found, found + count, [](const dabgpu_subchannel &a, const dabgpu_subchannel &b) { return a.start_address < b.start_address; });
-    *n = count;
-    if (count > max) return DABGPU_ERR_CAPACITY;
-    for (int i = 0; i < count; i++) out[i] = found[i];
-    return DABGPU_OK;
+    // the walk: include/dabgpu_fig.h; the profile an entry names: here, where the puncture tables are
+    return dabgpu_fig::subchannels(fib, crc_ok, n_frames, [](const dabgpu_fig::Organisation &e, dabgpu_subchannel &sc) {
+        if (!e.long_form) return e.table_switch ? int(DABGPU_ERR_PROFILE) : dabgpu_uep_subchannel(e.index, e.start, &sc);
+        // the bit rate the size implies: n times the level's capacity units, 8 n (A) or 32 n (B) kbit/s
+        static const int CU_A[4] = {12, 8, 6, 4}, CU_B[4] = {27, 21, 18, 15};
+        const int unit = e.option ? CU_B[e.level - 1] : CU_A[e.level - 1];
+        if (e.size == 0 || e.size % unit) return int(DABGPU_ERR_PROFILE);
+        sc = dabgpu_subchannel{e.start, e.size, 0, e.option, e.level, (e.option ? 32 : 8) * (e.size / unit)};
+        dab::PunctureProfile prof;
+        return subchannel_profile(&sc, prof);
+    }, out, max, n);
 }
 
 int dabgpu_fig_audio_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_audio_component *out, int max,
                                 int *n) {
     if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
-    // FIG 0/1 gives SubChId -> start address (the entries dabgpu_fig_subchannels lists); FIG 0/2 (EN 300 401 clause 6.3.1)
-    // gives per service: SId (16 bits, or 32 with P/D = 1), Rfa (1) CAId (3) NumComponents (4), then two bytes per component --
-    // TMId (2), and for TMId = 0: ASCTy (6), SubChId (6), P/S (1), CA flag (1)
-    int start_of[64];
-    for (int i = 0; i < 64; i++) start_of[i] = -1;
-    dabgpu_audio_component found[64];
-    bool seen[64] = {};
-    int count = 0;
-    for (int pass = 0; pass < 2; pass++) {                      // 0: the sub-channel organisation; 1: the services
-        for (int k = 0; k < n_frames * NB_FIBS; k++) {
-            if (!crc_ok[k]) continue;
-            const uint8_t *d = fib + size_t(k) * 32;
-            for (int i = 0; i < 30;) {
-                if (d[i] == 0xFF) break;
-                const int type = d[i] >> 5, len = d[i] & 0x1F;
-                if (len == 0 || i + 1 + len > 30) break;
-                const uint8_t *b = d + i + 1;
-                i += 1 + len;
-                // type 0, current configuration (C/N = 0), this ensemble (OE = 0)
-                if (type != 0 || (b[0] & 0xC0)) continue;
-                const int ext = b[0] & 0x1F, pd = (b[0] >> 5) & 1;
-                if (pass == 0 && ext == 1) {
-                    for (int j = 1; j + 3 <= len;) {
-                        const int id = b[j] >> 2, start = ((b[j] & 3) << 8) | b[j + 1];
-                        if (b[j + 2] & 0x80) {
-                            if (j + 4 > len) break;
-                            const int option = (b[j + 2] >> 4) & 7;
-                            j += 4;
-                            if (option > 1) continue;          // (passed over by dabgpu_fig_subchannels as well)
-                        } else {
-                            j += 3;
-                        }
-                        if (start_of[id] < 0) start_of[id] = start;
-                    }
-                } else if (pass == 1 && ext == 2) {
-                    const int sid_bytes = pd ? 4 : 2;
-                    for (int j = 1; j + sid_bytes + 1 <= len;) {
-                        uint32_t sid = 0;
-                        for (int q = 0; q < sid_bytes; q++) sid = (sid << 8) | b[j + q];
-                        const int ncomp = b[j + sid_bytes] & 0x0F;
-                        j += sid_bytes + 1;
-                        if (j + 2 * ncomp > len) break;
-                        for (int c = 0; c < ncomp; c++, j += 2) {
-                            if (b[j] >> 6) continue;           // TMId != 0: data, FIDC or packet mode
-                            const int id = b[j + 1] >> 2;
-                            if (seen[id] || start_of[id] < 0) continue;
-                            seen[id] = true;
-                            dabgpu_audio_component a{};
-                            a.sid = sid;
-                            a.subchid = id;
-                            a.start_address = start_of[id];
-                            a.ascty = b[j] & 0x3F;
-                            a.primary = (b[j + 1] >> 1) & 1;
-                            found[count++] = a;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    std::stable_sort(found, found + count, [](const dabgpu_audio_component &a, const dabgpu_audio_component &b) { return a.start_address < b.start_address; });
-    *n = count;
-    if (count > max) return DABGPU_ERR_CAPACITY;
-    for (int i = 0; i < count; i++) out[i] = found[i];
-    return DABGPU_OK;
+    return dabgpu_fig::audio_components(fib, crc_ok, n_frames, out, max, n);
 }
 
 int dabgpu_decode_frames(dabgpu_ctx *ctx, const int8_t *soft, size_t soft_stride, int n_streams, int frames_per_stream,
@@ -772,7 +670,6 @@ size_t dabgpu_dabplus_carry_bytes(int bitrate_kbps) {
 int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entries, int n_entries, int n_cifs, void *stream) {
     if (!ctx || n_entries < 0 || n_cifs < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
     // everything is checked before anything is enqueued: a refused call leaves every output as it was
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     const int max_sf = (n_cifs + 4) / 5;
     std::vector<dabk::FollowEntry> table(size_t(n_entries), dabk::FollowEntry{});
     for (int i = 0; i < n_entries; i++) {
@@ -786,8 +683,7 @@ int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entri
         if ((addr(e.d_carry_in) | addr(e.d_carry_out)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_status) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
         const uint64_t cb = dabk::follow_carry_bytes(s);
-        if (e.d_carry_in && addr(e.d_carry_in) < addr(e.d_carry_out) + cb && addr(e.d_carry_out) < addr(e.d_carry_in) + cb)
-            return DABGPU_ERR_ARG;
+        if (e.d_carry_in && overlaps(e.d_carry_in, cb, e.d_carry_out, cb)) return DABGPU_ERR_ARG;
         dabk::FollowEntry &t = table[size_t(i)];
         t.in = addr(e.d_in);
         t.carry_in = addr(e.d_carry_in);
@@ -799,16 +695,10 @@ int dabgpu_dabplus_follow_dev(dabgpu_ctx *ctx, const dabgpu_dabplus_entry *entri
         t.s = s;
     }
     if (n_entries == 0) return DABGPU_OK;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::follow_table_bytes(n_entries);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_DABPLUS] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_DABPLUS, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_dabplus_follow(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_DABPLUS], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_DABPLUS, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_dabplus_follow(table.data(), n_entries, n_cifs, d_table, slot_bytes, s);
+    });
 }
 
 // ---------------------------------------------------------------------------- plain Viterbi

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/dabgpu_dmb.h"
+#include "../../include/dabgpu_fig.h"
 
 using namespace dabapi;
 namespace dmb = dabgpu_dmb;
@@ -27,8 +28,6 @@ static_assert(DABGPU_DMB_AS_RECEIVED == dmb::AS_RECEIVED && DABGPU_DMB_CORRECTED
 
 namespace {
 
-uint64_t addr(const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); }
-
 // everything both calls refuse, before anything is done; fills the kernels' table when there is one
 int dmb_check(const dabgpu_dmb_entry *entries, int n_entries, int n_cifs, dabk::DmbEntry *table) {
     if (n_entries < 0 || n_cifs < 0 || n_cifs > dmb::MAX_N_CIFS || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
@@ -41,7 +40,7 @@ int dmb_check(const dabgpu_dmb_entry *entries, int n_entries, int n_cifs, dabk::
         if ((addr(e.d_ts) | addr(e.d_records) | addr(e.d_state_in) | addr(e.d_state_out)) & 15) return DABGPU_ERR_ARG;
         if (addr(e.d_result) & 3) return DABGPU_ERR_ARG;
         const uint64_t sb = dmb::STATE_BYTES;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb) return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (!table) continue;
         dabk::DmbEntry &t = table[i];
         t.in = addr(e.d_in);
@@ -216,71 +215,7 @@ int dabgpu_dmb_state_census(const void *state, int bitrate_kbps, dabgpu_dmb_cens
 
 int dabgpu_fig_stream_components(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_stream_component *out, int max, int *n) {
     if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
-    // pass 0: FIG 0/1 SubChId -> start address (as dabgpu_fig_audio_components); pass 1: FIG 0/2 (EN 300 401 clause 6.3.1), the
-    // components with TMId = 1: DSCTy (6), SubChId (6), P/S (1), CA flag (1)
-    int start_of[64];
-    for (int i = 0; i < 64; i++) start_of[i] = -1;
-    dabgpu_stream_component found[64];
-    bool seen[64] = {};
-    int count = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int k = 0; k < n_frames * dab::NB_FIBS; k++) {
-            if (!crc_ok[k]) continue;
-            const uint8_t *d = fib + size_t(k) * 32;
-            for (int i = 0; i < 30;) {
-                if (d[i] == 0xFF) break;
-                const int type = d[i] >> 5, len = d[i] & 0x1F;
-                if (len == 0 || i + 1 + len > 30) break;
-                const uint8_t *b = d + i + 1;
-                i += 1 + len;
-                // type 0, current configuration (C/N = 0), this ensemble (OE = 0)
-                if (type != 0 || (b[0] & 0xC0)) continue;
-                const int ext = b[0] & 0x1F, pd = (b[0] >> 5) & 1;
-                if (pass == 0 && ext == 1) {
-                    for (int j = 1; j + 3 <= len;) {
-                        const int id = b[j] >> 2, start = ((b[j] & 3) << 8) | b[j + 1];
-                        if (b[j + 2] & 0x80) {
-                            if (j + 4 > len) break;
-                            const int option = (b[j + 2] >> 4) & 7;
-                            j += 4;
-                            if (option > 1) continue;          // (passed over by dabgpu_fig_subchannels as well)
-                        } else {
-                            j += 3;
-                        }
-                        if (start_of[id] < 0) start_of[id] = start;
-                    }
-                } else if (pass == 1 && ext == 2) {
-                    const int sid_bytes = pd ? 4 : 2;
-                    for (int j = 1; j + sid_bytes + 1 <= len;) {
-                        uint32_t sid = 0;
-                        for (int q = 0; q < sid_bytes; q++) sid = (sid << 8) | b[j + q];
-                        const int ncomp = b[j + sid_bytes] & 0x0F;
-                        j += sid_bytes + 1;
-                        if (j + 2 * ncomp > len) break;
-                        for (int c = 0; c < ncomp; c++, j += 2) {
-                            if ((b[j] >> 6) != 1) continue;    // TMId != 1: audio, FIDC or packet mode
-                            const int id = b[j + 1] >> 2;
-                            if (seen[id] || start_of[id] < 0) continue;
-                            seen[id] = true;
-                            dabgpu_stream_component a{};
-                            a.sid = sid;
-                            a.subchid = id;
-                            a.start_address = start_of[id];
-                            a.dscty = b[j] & 0x3F;
-                            a.primary = (b[j + 1] >> 1) & 1;
-                            a.ca = b[j + 1] & 1;
-                            found[count++] = a;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    std::stable_sort(found, found + count, [](const dabgpu_stream_component &a, const dabgpu_stream_component &b) { return a.start_address < b.start_address; });
-    *n = count;
-    if (count > max) return DABGPU_ERR_CAPACITY;
-    for (int i = 0; i < count; i++) out[i] = found[i];
-    return DABGPU_OK;
+    return dabgpu_fig::stream_components(fib, crc_ok, n_frames, out, max, n);
 }
 
 int dabgpu_dmb_follow_dev(dabgpu_ctx *ctx, const dabgpu_dmb_entry *entries, int n_entries, int n_cifs, void *stream) {
@@ -291,16 +226,10 @@ int dabgpu_dmb_follow_dev(dabgpu_ctx *ctx, const dabgpu_dmb_entry *entries, int 
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
     if (n_entries > dabk::DMB_MAX_ENTRIES || dabk::dmb_blocks(table.data(), n_entries) > dabk::DMB_MAX_BLOCKS) return DABGPU_ERR_CAPACITY;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::dmb_table_bytes(table.data(), n_entries);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_DMB] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_DMB, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_dmb(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_DMB], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_DMB, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_dmb(table.data(), n_entries, n_cifs, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_dmb_follow_host(const dabgpu_dmb_entry *entries, int n_entries, int n_cifs) {

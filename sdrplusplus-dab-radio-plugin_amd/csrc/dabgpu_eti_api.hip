@@ -133,7 +133,6 @@ int dabgpu_eti_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_st
                           const int32_t *d_cif_start, uint8_t *d_eti, dabgpu_eti_status *d_status, void *stream) {
     if (!ctx || !plan || !d_fib || !d_crc_ok || !d_eti || !d_status || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;
     if (!plan_consistent(*plan) || (plan->nst > 0 && !d_out)) return DABGPU_ERR_ARG;
-    const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
     if ((addr(d_fib) & 3u) || (addr(d_eti) & 15u) || (addr(d_status) & 7u) || (addr(d_history_in) & 7u) ||
         (addr(d_history_out) & 7u) || (addr(d_cif_start) & 3u))
         return DABGPU_ERR_ARG;
@@ -258,7 +257,6 @@ constexpr int32_t ETI_READ_MAX_BYTES = 1 << 30;
 // everything both calls refuse, before anything is done; fills the kernels' table when there is one
 int eti_read_check(const dabgpu_eti_read_entry *entries, int n_entries, dabk::EtiReadEntry *table) {
     if (n_entries < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    const auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_eti_read_entry &e = entries[i];
         if (e.n_bytes < 0 || e.n_bytes > ETI_READ_MAX_BYTES || (e.n_bytes > 0 && !e.d_bytes)) return DABGPU_ERR_ARG;
@@ -268,8 +266,7 @@ int eti_read_check(const dabgpu_eti_read_entry *entries, int n_entries, dabk::Et
         if ((addr(e.d_bytes) | addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_fib) | addr(e.d_status)) & 15) return DABGPU_ERR_ARG;
         if (addr(e.d_result) & 3) return DABGPU_ERR_ARG;
         const uint64_t sb = er::STATE_BYTES;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
-            return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (e.plan) {
             const dabgpu_eti_plan &p = *e.plan;
             if (!plan_consistent(p)) return DABGPU_ERR_ARG;
@@ -334,15 +331,9 @@ int dabgpu_eti_read_dev(dabgpu_ctx *ctx, const dabgpu_eti_read_entry *entries, i
     if (n_entries == 0) return DABGPU_OK;
     size_t table_bytes = table.size() * sizeof(dabk::EtiReadEntry) + dabk::eti_read_bases_bytes(n_entries);
     for (const dabk::EtiReadEntry &t : table) table_bytes += dabk::eti_read_scratch_bytes(t.n_bytes);
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_ETI_READ] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_ETI_READ, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_eti_read(table.data(), n_entries, d_table, s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_ETI_READ, table_bytes, stream, [&](void *d_table, size_t, hipStream_t s) {
+        return dabk::launch_eti_read(table.data(), n_entries, d_table, s);
+    });
 }
 
 int dabgpu_eti_read_host(const dabgpu_eti_read_entry *entries, int n_entries) {
@@ -422,7 +413,6 @@ ed::PlanKey plan_key(const dabgpu_eti_plan &p) {
 // everything both calls refuse, before anything is done; fills the kernels' table when there is one
 int edi_read_check(const dabgpu_edi_read_entry *entries, int n_entries, dabk::EdiReadEntry *table) {
     if (n_entries < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    const auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_edi_read_entry &e = entries[i];
         if (e.n_bytes < 0 || e.n_bytes > EDI_READ_MAX_BYTES || (e.n_bytes > 0 && !e.d_bytes)) return DABGPU_ERR_ARG;
@@ -432,8 +422,7 @@ int edi_read_check(const dabgpu_edi_read_entry *entries, int n_entries, dabk::Ed
         if ((addr(e.d_bytes) | addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_fib) | addr(e.d_status)) & 15) return DABGPU_ERR_ARG;
         if (addr(e.d_result) & 3) return DABGPU_ERR_ARG;
         const uint64_t sb = ed::STATE_BYTES;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
-            return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (e.plan && e.d_out)
             for (int k = 0; k < e.plan->nst; k++)
                 if (addr(e.d_out[k]) & 7) return DABGPU_ERR_ARG;
@@ -476,7 +465,6 @@ int dabgpu_edi_frames_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, int n_st
                           dabgpu_eti_status *d_status, void *stream) {
     if (!ctx || !plan || !d_fib || !d_crc_ok || !d_edi || !d_status || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;
     if (!plan_stc_consistent(*plan) || (plan->nst > 0 && !d_out)) return DABGPU_ERR_ARG;
-    const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
     if ((addr(d_fib) & 3u) || (addr(d_edi) & 15u) || (addr(d_status) & 7u) || (addr(d_history_in) & 7u) ||
         (addr(d_history_out) & 7u) || (addr(d_cif_start) & 3u) || (stream_stride & 15u))
         return DABGPU_ERR_ARG;
@@ -624,15 +612,9 @@ int dabgpu_edi_read_dev(dabgpu_ctx *ctx, const dabgpu_edi_read_entry *entries, i
     if (n_entries == 0) return DABGPU_OK;
     size_t table_bytes = (table.size() * sizeof(dabk::EdiReadEntry) + 15) / 16 * 16;
     for (const dabk::EdiReadEntry &t : table) table_bytes += dabk::edi_read_scratch_bytes(t.n_bytes);
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_EDI_READ] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_EDI_READ, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_edi_read(table.data(), n_entries, d_table, s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_EDI_READ, table_bytes, stream, [&](void *d_table, size_t, hipStream_t s) {
+        return dabk::launch_edi_read(table.data(), n_entries, d_table, s);
+    });
 }
 
 int dabgpu_edi_read_host(const dabgpu_edi_read_entry *entries, int n_entries) {

@@ -125,7 +125,6 @@ int dabgpu_modulate_eti_dev(dabgpu_ctx *ctx, const dabgpu_eti_plan *plan, const 
             : (c.tii_main != -1 || c.tii_sub != -1))
         return DABGPU_ERR_ARG;
     if (!(c.gain == c.gain)) return DABGPU_ERR_ARG;
-    const auto addr = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
     if ((addr(d_eti) & 15u) || (addr(d_iq) & 15u) || (addr(d_status) & 7u) || (addr(d_state_in) & 15u) || (addr(d_state_out) & 15u))
         return DABGPU_ERR_ARG;
     if (frame_stride < size_t(dab::NB_FRAME_SAMPLES) || (frame_stride & 1u)) return DABGPU_ERR_ARG;

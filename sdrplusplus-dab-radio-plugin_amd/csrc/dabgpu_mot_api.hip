@@ -23,7 +23,6 @@ size_t dabgpu_mot_arena_bytes(size_t body_capacity) {
 // everything both calls refuse, before anything is done; fills the kernel's table when there is one
 static int mot_check(const dabgpu_mot_entry *entries, int n_entries, dabk::MotEntry *table) {
     if (n_entries < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     const uint64_t sb = sizeof(mot::State);
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_mot_entry &e = entries[i];
@@ -33,8 +32,7 @@ static int mot_check(const dabgpu_mot_entry *entries, int n_entries, dabk::MotEn
         if (!e.d_data || !e.d_status || !e.d_follow || !e.d_state_out || !e.d_arena || !e.d_result) return DABGPU_ERR_ARG;
         if ((addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_arena) | addr(e.d_slides)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_status) | addr(e.d_follow) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
-            return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (e.arena_bytes < mot::arena_bytes(0) || e.max_slides < 0) return DABGPU_ERR_ARG;
         if (e.max_slides > 0 && (!e.d_slides || e.slide_stride < size_t(mot::RECORD_BYTES) || e.slide_stride % 16 ||
                                  e.slide_stride >= (uint64_t(1) << 31) || uint64_t(e.max_slides) * e.slide_stride >= (uint64_t(1) << 31)))
@@ -66,16 +64,10 @@ int dabgpu_mot_slides_dev(dabgpu_ctx *ctx, const dabgpu_mot_entry *entries, int 
     const int bad = mot_check(entries, n_entries, table.data());
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = table.size() * sizeof(dabk::MotEntry);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_MOT] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_MOT, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_mot_slides(table.data(), n_entries, d_table, ctx->stage_bytes[STAGE_MOT], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_MOT, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_mot_slides(table.data(), n_entries, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_mot_slides_host(const dabgpu_mot_entry *entries, int n_entries) {

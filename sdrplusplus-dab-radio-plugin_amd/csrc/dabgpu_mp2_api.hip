@@ -21,7 +21,6 @@ size_t dabgpu_mp2_carry_bytes(int bitrate_kbps) { return mp2::bitrate_ok(bitrate
 // everything both calls refuse, before anything is done; fills the kernels' table when there is one
 static int mp2_check(const dabgpu_mp2_entry *entries, int n_entries, int n_cifs, dabk::Mp2Entry *table) {
     if (n_entries < 0 || n_cifs < 0 || n_cifs > (1 << 28) || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_mp2_entry &e = entries[i];
         if (!mp2::bitrate_ok(e.bitrate_kbps)) return DABGPU_ERR_ARG;
@@ -31,8 +30,7 @@ static int mp2_check(const dabgpu_mp2_entry *entries, int n_entries, int n_cifs,
         if ((addr(e.d_carry_in) | addr(e.d_carry_out)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_status) | addr(e.d_follow) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
         const uint64_t cb = uint64_t(mp2::carry_bytes(e.bitrate_kbps));
-        if (e.d_carry_in && addr(e.d_carry_in) < addr(e.d_carry_out) + cb && addr(e.d_carry_out) < addr(e.d_carry_in) + cb)
-            return DABGPU_ERR_ARG;
+        if (e.d_carry_in && overlaps(e.d_carry_in, cb, e.d_carry_out, cb)) return DABGPU_ERR_ARG;
         if (!table) continue;
         dabk::Mp2Entry &t = table[i];
         t.in = addr(e.d_in);
@@ -55,16 +53,10 @@ int dabgpu_mp2_follow_dev(dabgpu_ctx *ctx, const dabgpu_mp2_entry *entries, int 
     const int bad = mp2_check(entries, n_entries, n_cifs, table.data());
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::mp2_table_bytes(n_entries);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_MP2] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_MP2, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_mp2_follow(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_MP2], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_MP2, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_mp2_follow(table.data(), n_entries, n_cifs, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_mp2_follow_host(const dabgpu_mp2_entry *entries, int n_entries, int n_cifs) {
@@ -137,7 +129,6 @@ static_assert(sizeof(dabgpu_mp2_level) == sizeof(mp2::Level) && sizeof(dabgpu_mp
 // everything both calls refuse, before anything is done; fills the kernels' table when there is one
 static int mp2_audio_check(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs, dabk::Mp2AudioEntry *table) {
     if (n_entries < 0 || n_cifs < 0 || n_cifs > (1 << 28) || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_mp2_audio_entry &e = entries[i];
         if (!mp2::bitrate_ok(e.bitrate_kbps)) return DABGPU_ERR_ARG;
@@ -168,16 +159,10 @@ int dabgpu_mp2_subbands_dev(dabgpu_ctx *ctx, const dabgpu_mp2_audio_entry *entri
     const int bad = mp2_audio_check(entries, n_entries, n_cifs, table.data());
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::mp2_audio_table_bytes(n_entries);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_MP2_AUDIO] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_MP2_AUDIO, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_mp2_subbands(table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_MP2_AUDIO], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_MP2_AUDIO, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_mp2_subbands(table.data(), n_entries, n_cifs, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_mp2_subbands_host(const dabgpu_mp2_audio_entry *entries, int n_entries, int n_cifs) {

@@ -38,7 +38,6 @@ int dabgpu_packet_fec_delay(int bitrate_kbps) { return fec::bitrate_ok(bitrate_k
 // everything the calls refuse, before anything is done; fills the kernels' table when there is one
 template <class Entry> static int packet_fec_check(const Entry *entries, int n_entries, int n_cifs, dabk::PacketFecEntry *table) {
     if (n_entries < 0 || n_cifs < 0 || n_cifs > fec::MAX_N_CIFS || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     for (int i = 0; i < n_entries; i++) {
         const Entry &e = entries[i];
         if (!fec::bitrate_ok(e.bitrate_kbps)) return DABGPU_ERR_ARG;
@@ -48,10 +47,10 @@ template <class Entry> static int packet_fec_check(const Entry *entries, int n_e
         if (!e.d_state_out || !e.d_result) return DABGPU_ERR_ARG;
         if ((addr(e.d_state_in) | addr(e.d_state_out)) & 15) return DABGPU_ERR_ARG;
         if (addr(e.d_result) & 3) return DABGPU_ERR_ARG;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb) return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (n_cifs > 0) {
             const uint64_t in_span = uint64_t(n_cifs - 1) * e.in_stride + fb, out_span = uint64_t(n_cifs - 1) * e.out_stride + fb;
-            if (addr(e.d_in) < addr(e.d_out) + out_span && addr(e.d_out) < addr(e.d_in) + in_span) return DABGPU_ERR_ARG;
+            if (overlaps(e.d_in, in_span, e.d_out, out_span)) return DABGPU_ERR_ARG;
         }
         if (!table) continue;
         dabk::PacketFecEntry &t = table[i];
@@ -77,16 +76,10 @@ template <class Entry> static int packet_fec_dev(dabgpu_ctx *ctx, const Entry *e
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
     if (dabk::packet_fec_blocks(table.data(), n_entries, n_cifs) >= (uint64_t(1) << 31)) return DABGPU_ERR_CAPACITY;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::packet_fec_table_bytes(table.data(), n_entries, n_cifs, erasures);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[slot] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, slot, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_packet_fec(table.data(), n_entries, n_cifs, erasures, d_table, ctx->stage_bytes[slot], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, slot, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_packet_fec(table.data(), n_entries, n_cifs, erasures, d_table, slot_bytes, s);
+    });
 }
 
 template <class Entry> static int packet_fec_host(const Entry *entries, int n_entries, int n_cifs) {

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/dabgpu_data_groups.h"
+#include "../../include/dabgpu_fig.h"
 
 using namespace dabapi;
 namespace dg = dabgpu_groups;
@@ -28,7 +29,6 @@ int dabgpu_packet_groups_chunk(void) { return dabk::PACKET_GROUPS_CHUNK; }
 static int groups_check(const dabgpu_packet_groups_entry *entries, int n_entries, int n_cifs, dabk::PacketEntry *scan,
                         dabk::PacketGroupsEntry *table) {
     if (n_entries < 0 || n_cifs < 0 || n_cifs > pkt::MAX_N_CIFS || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     const uint64_t sb = sizeof(dg::State);
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_packet_groups_entry &e = entries[i];
@@ -40,8 +40,7 @@ static int groups_check(const dabgpu_packet_groups_entry *entries, int n_entries
         if (!e.d_state_out || !e.d_result) return DABGPU_ERR_ARG;
         if ((addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_bytes)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_result) | addr(e.d_groups)) & 3) return DABGPU_ERR_ARG;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
-            return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (e.bytes_capacity < 0 || e.max_groups < 0) return DABGPU_ERR_ARG;
         if ((e.bytes_capacity > 0 && !e.d_bytes) || (e.max_groups > 0 && !e.d_groups)) return DABGPU_ERR_ARG;
     }
@@ -79,16 +78,10 @@ int dabgpu_packet_groups_dev(dabgpu_ctx *ctx, const dabgpu_packet_groups_entry *
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
     if (dabk::packet_scan_blocks(scan.data(), n_entries, n_cifs) >= (uint64_t(1) << 31)) return DABGPU_ERR_CAPACITY;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = dabk::packet_groups_table_bytes(scan.data(), n_entries, n_cifs);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_PACKET_GROUPS] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_PACKET_GROUPS, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_packet_groups(scan.data(), table.data(), n_entries, n_cifs, d_table, ctx->stage_bytes[STAGE_PACKET_GROUPS], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_PACKET_GROUPS, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_packet_groups(scan.data(), table.data(), n_entries, n_cifs, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_packet_groups_host(const dabgpu_packet_groups_entry *entries, int n_entries, int n_cifs) {
@@ -115,122 +108,5 @@ int dabgpu_packet_groups_host(const dabgpu_packet_groups_entry *entries, int n_e
 int dabgpu_fig_user_applications(const uint8_t *fib, const uint8_t *crc_ok, int n_frames, dabgpu_user_application *out, int max,
                                  int *n) {
     if (!fib || !crc_ok || !n || n_frames < 0 || max < 0 || (max > 0 && !out)) return DABGPU_ERR_ARG;
-    // pass 0: FIG 0/8 (SId, SCIdS) -> SubChId or SCId, FIG 0/3 SCId -> (SubChId, packet address); pass 1: FIG 0/13.  Each list
-    // keeps its first MAX_FOUND entries, as dabgpu_fig_packet_components does: far more than 12 FIBs a frame announce
-    struct Global {
-        uint32_t sid;
-        int scids, ls, id;
-    };
-    struct Described {
-        int scid, subchid, address;
-    };
-    constexpr int MAX_FOUND = 256;
-    std::vector<Global> globals;
-    std::vector<Described> described;
-    std::vector<dabgpu_user_application> found;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int k = 0; k < n_frames * dab::NB_FIBS; k++) {
-            if (!crc_ok[k]) continue;
-            const uint8_t *d = fib + size_t(k) * 32;
-            for (int i = 0; i < 30;) {
-                if (d[i] == 0xFF) break;
-                const int type = d[i] >> 5, len = d[i] & 0x1F;
-                if (len == 0 || i + 1 + len > 30) break;
-                const uint8_t *b = d + i + 1;
-                i += 1 + len;
-                // type 0, current configuration (C/N = 0), this ensemble (OE = 0)
-                if (type != 0 || (b[0] & 0xC0)) continue;
-                const int ext = b[0] & 0x1F, pd = (b[0] >> 5) & 1, sid_bytes = pd ? 4 : 2;
-                auto sid_at = [&](int j) {
-                    uint32_t sid = 0;
-                    for (int q = 0; q < sid_bytes; q++) sid = (sid << 8) | b[j + q];
-                    return sid;
-                };
-                if (pass == 0 && ext == 3) {
-                    for (int j = 1; j + 5 <= len;) {
-                        const int scid = (b[j] << 4) | (b[j + 1] >> 4), caorg = b[j + 1] & 1;
-                        const Described q = {scid, b[j + 3] >> 2, ((b[j + 3] & 3) << 8) | b[j + 4]};
-                        j += 5 + 2 * caorg;
-                        if (j > len) break;
-                        bool known = false;
-                        for (const Described &o : described) known = known || o.scid == scid;
-                        if (!known && described.size() < size_t(MAX_FOUND)) described.push_back(q);
-                    }
-                } else if (pass == 0 && ext == 8) {
-                    for (int j = 1; j + sid_bytes + 2 <= len;) {
-                        const uint32_t sid = sid_at(j);
-                        const int extended = b[j + sid_bytes] >> 7, scids = b[j + sid_bytes] & 0x0F, ls = b[j + sid_bytes + 1] >> 7;
-                        j += sid_bytes + 1;
-                        if (j + (ls ? 2 : 1) + extended > len) break;
-                        const int id = ls ? ((b[j] & 0x0F) << 8) | b[j + 1] : b[j] & 0x3F;
-                        const bool fidc = !ls && (b[j] & 0x40);        // short form, MSC/FIC flag 1: a FIDC, not a sub-channel
-                        j += (ls ? 2 : 1) + extended;
-                        if (fidc) continue;
-                        bool known = false;
-                        for (const Global &g : globals) known = known || (g.sid == sid && g.scids == scids);
-                        if (!known && globals.size() < size_t(MAX_FOUND)) globals.push_back(Global{sid, scids, ls, id});
-                    }
-                } else if (pass == 1 && ext == 13) {
-                    for (int j = 1; j + sid_bytes + 1 <= len;) {
-                        const uint32_t sid = sid_at(j);
-                        const int scids = b[j + sid_bytes] >> 4, count = b[j + sid_bytes] & 0x0F;
-                        j += sid_bytes + 1;
-                        bool cut = false;
-                        for (int a = 0; a < count && !cut; a++) {
-                            if (j + 2 > len) {
-                                cut = true;
-                                break;
-                            }
-                            const int ua_type = (b[j] << 3) | (b[j + 1] >> 5), data_length = b[j + 1] & 0x1F;
-                            if (j + 2 + data_length > len) {
-                                cut = true;
-                                break;
-                            }
-                            bool seen = false;
-                            for (const dabgpu_user_application &f : found)
-                                seen = seen || (f.sid == sid && f.scids == scids && f.ua_type == ua_type);
-                            if (!seen && found.size() < size_t(MAX_FOUND)) {
-                                dabgpu_user_application u{};
-                                u.sid = sid;
-                                u.scids = scids;
-                                u.ua_type = ua_type;
-                                u.subchid = u.scid = u.packet_address = -1;
-                                u.data_length = data_length > 23 ? 23 : data_length;
-                                for (int q = 0; q < u.data_length; q++) u.data[q] = b[j + 2 + q];
-                                for (const Global &g : globals) {
-                                    if (g.sid != sid || g.scids != scids) continue;
-                                    if (!g.ls) {
-                                        u.subchid = g.id;
-                                    } else {
-                                        u.tmid_packet = 1;
-                                        u.scid = g.id;
-                                        for (const Described &o : described)
-                                            if (o.scid == g.id) {
-                                                u.subchid = o.subchid;
-                                                u.packet_address = o.address;
-                                                break;
-                                            }
-                                    }
-                                    break;
-                                }
-                                found.push_back(u);
-                            }
-                            j += 2 + data_length;
-                        }
-                        if (cut) break;
-                    }
-                }
-            }
-        }
-    }
-    std::stable_sort(found.begin(), found.end(), [](const dabgpu_user_application &a, const dabgpu_user_application &b) {
-        if (a.sid != b.sid) return a.sid < b.sid;
-        if (a.scids != b.scids) return a.scids < b.scids;
-        return a.ua_type < b.ua_type;
-    });
-    const int count = int(found.size());
-    *n = count;
-    if (count > max) return DABGPU_ERR_CAPACITY;
-    for (int i = 0; i < count; i++) out[i] = found[i];
-    return DABGPU_OK;
+    return dabgpu_fig::user_applications(fib, crc_ok, n_frames, out, max, n);
 }

@@ -18,7 +18,6 @@ size_t dabgpu_pad_state_bytes(void) { return sizeof(pad::State); }
 // everything both calls refuse, before anything is done; fills the kernel's table when there is one
 static int pad_check(const dabgpu_pad_entry *entries, int n_entries, dabk::PadEntry *table) {
     if (n_entries < 0 || (n_entries > 0 && !entries)) return DABGPU_ERR_ARG;
-    auto addr = [](const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); };
     const uint64_t sb = sizeof(pad::State);
     for (int i = 0; i < n_entries; i++) {
         const dabgpu_pad_entry &e = entries[i];
@@ -28,8 +27,7 @@ static int pad_check(const dabgpu_pad_entry *entries, int n_entries, dabk::PadEn
         if (!e.d_data || !e.d_status || !e.d_follow || !e.d_state_out || !e.d_label || !e.d_result) return DABGPU_ERR_ARG;
         if ((addr(e.d_state_in) | addr(e.d_state_out)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_status) | addr(e.d_follow) | addr(e.d_label) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb)
-            return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
         if (!table) continue;
         dabk::PadEntry &t = table[i];
         t.data = addr(e.d_data);
@@ -53,16 +51,10 @@ int dabgpu_pad_labels_dev(dabgpu_ctx *ctx, const dabgpu_pad_entry *entries, int 
     const int bad = pad_check(entries, n_entries, table.data());
     if (bad) return bad;
     if (n_entries == 0) return DABGPU_OK;
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
     const size_t table_bytes = table.size() * sizeof(dabk::PadEntry);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_PAD] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_PAD, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_pad_labels(table.data(), n_entries, d_table, ctx->stage_bytes[STAGE_PAD], s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_PAD, table_bytes, stream, [&](void *d_table, size_t slot_bytes, hipStream_t s) {
+        return dabk::launch_pad_labels(table.data(), n_entries, d_table, slot_bytes, s);
+    });
 }
 
 int dabgpu_pad_labels_host(const dabgpu_pad_entry *entries, int n_entries) {

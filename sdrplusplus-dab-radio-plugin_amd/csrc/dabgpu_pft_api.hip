@@ -32,8 +32,6 @@ constexpr int32_t PFT_READ_MAX_BYTES = 1 << 30;
 const pf::Gf GF = pf::make_gf();
 const pf::ParityTable PARITY_TABLE = pf::make_parity_table();
 
-uint64_t addr(const void *p) { return uint64_t(reinterpret_cast<uintptr_t>(p)); }
-
 // a layout is taken only as dabgpu_pft_layout makes it from its first five fields
 bool layout_consistent(const dabgpu_pft_layout_info *given, pf::Layout &a) {
     return given && pf::layout(given->packet_bytes, given->fec, given->m, given->max_payload, given->addr, a) &&
@@ -49,7 +47,7 @@ int fragments_check(const dabgpu_pft_layout_info *layout, int n_streams, int n_p
     const uint64_t in_bytes = uint64_t(n_packets) * uint64_t(a.packet_bytes), out_bytes = uint64_t(n_packets) * uint64_t(a.stream_bytes);
     if (!af || !out || ((addr(af) | addr(out) | in_stride | out_stride) & 15u) || in_stride < in_bytes || out_stride < out_bytes) return DABGPU_ERR_ARG;
     const uint64_t in_span = uint64_t(n_streams - 1) * in_stride + in_bytes, out_span = uint64_t(n_streams - 1) * out_stride + out_bytes;
-    if (addr(af) < addr(out) + out_span && addr(out) < addr(af) + in_span) return DABGPU_ERR_ARG;
+    if (overlaps(af, in_span, out, out_span)) return DABGPU_ERR_ARG;
     return DABGPU_OK;
 }
 
@@ -63,7 +61,7 @@ int read_check(const dabgpu_pft_read_entry *entries, int n_entries, dabk::PftRea
         if ((addr(e.d_bytes) | addr(e.d_state_in) | addr(e.d_state_out) | addr(e.d_out)) & 15) return DABGPU_ERR_ARG;
         if ((addr(e.d_records) | addr(e.d_result)) & 3) return DABGPU_ERR_ARG;
         const uint64_t sb = pf::STATE_BYTES;
-        if (e.d_state_in && addr(e.d_state_in) < addr(e.d_state_out) + sb && addr(e.d_state_out) < addr(e.d_state_in) + sb) return DABGPU_ERR_ARG;
+        if (e.d_state_in && overlaps(e.d_state_in, sb, e.d_state_out, sb)) return DABGPU_ERR_ARG;
     }
     if (!table) return DABGPU_OK;
     for (int i = 0; i < n_entries; i++) {
@@ -174,15 +172,9 @@ int dabgpu_pft_read_dev(dabgpu_ctx *ctx, const dabgpu_pft_read_entry *entries, i
     if (n_entries == 0) return DABGPU_OK;
     size_t table_bytes = (table.size() * sizeof(dabk::PftReadEntry) + 15) / 16 * 16;
     for (const dabk::PftReadEntry &t : table) table_bytes += dabk::pft_read_scratch_bytes(t.n_bytes);
-    DeviceGuard guard(ctx);
-    hipStream_t s = pick_stream(ctx, stream);
-    // (growing the table must not race with a launch that still reads the old one)
-    if (ctx->stage_bytes[STAGE_PFT_READ] < table_bytes) HIP_TRY(hipStreamSynchronize(s));
-    void *d_table = nullptr;
-    const int rc = stage(ctx, STAGE_PFT_READ, table_bytes, &d_table);
-    if (rc) return rc;
-    HIP_TRY(dabk::launch_pft_read(table.data(), n_entries, d_table, s));
-    return DABGPU_OK;
+    return launch_entry_table(ctx, STAGE_PFT_READ, table_bytes, stream, [&](void *d_table, size_t, hipStream_t s) {
+        return dabk::launch_pft_read(table.data(), n_entries, d_table, s);
+    });
 }
 
 int dabgpu_pft_read_host(const dabgpu_pft_read_entry *entries, int n_entries) {

@@ -656,9 +656,7 @@ def eti_read_max_frames(n_bytes):
 def eti_read_host(entries):
     """Context.eti_read_dev on HOST memory (entries: EtiReadEntry with host addresses): the same checks and the same walk,
     serially, without a context or a GPU (dabgpu_eti_read_host)."""
-    n = len(entries)
-    arr = (EtiReadEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_eti_read_host(arr, n), "dabgpu_eti_read_host")
+    _entries_call("dabgpu_eti_read_host", EtiReadEntry, entries)
 
 
 #: EDI (include/dabgpu.h, "EDI output" / "EDI input"; include/dabgpu_edi.h): AF packets, one per CIF
@@ -757,9 +755,7 @@ def edi_read_max_rows(n_bytes, plan=None):
 def edi_read_host(entries):
     """AF packet byte streams -> FIBs, CRC flags and logical frames on HOST memory (entries: EdiReadEntry with host
     addresses), serially, without a context or a GPU (dabgpu_edi_read_host)."""
-    n = len(entries)
-    arr = (EtiReadEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_edi_read_host(arr, n), "dabgpu_edi_read_host")
+    _entries_call("dabgpu_edi_read_host", EtiReadEntry, entries)
 
 
 #: EDI PFT layer (include/dabgpu.h, "EDI PFT layer"; include/dabgpu_pft.h): PF fragments with RS(255,207), EDI over UDP
@@ -852,9 +848,7 @@ def pft_read_max_records(n_bytes):
 def pft_read_host(entries):
     """Context.pft_read_dev on HOST memory (entries: PftReadEntry with host addresses): the same checks and the header's
     serial reader, without a context or a GPU (dabgpu_pft_read_host)."""
-    n = len(entries)
-    arr = (PftReadEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_pft_read_host(arr, n), "dabgpu_pft_read_host")
+    _entries_call("dabgpu_pft_read_host", PftReadEntry, entries)
 
 
 #: ETI(NI) to IQ (include/dabgpu.h, "ETI(NI) to IQ"): dabgpu_mod_status, one transmission frame's record
@@ -1137,6 +1131,30 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _entries_call(name, kind, entries, *args, ctx=None):
+    """The library's call `name` on a list of entries: name(entries, n, *args), or with a Context name(handle, entries, n, *args) of
+    the library that context loaded.  `entries` goes as an array of `kind`, at least one element long (an empty list still passes
+    an address); raises DabGpuError for a status other than DABGPU_OK."""
+    n = len(entries)
+    arr = (kind * max(n, 1))(*entries)
+    if ctx is None:
+        rc = getattr(lib(), name)(arr, n, *args)
+    else:
+        rc = getattr(ctx._lib, name)(ctx._h, arr, n, *args)
+    _check(rc, name)
+
+
+def _fib_batch(fib, crc_ok):
+    """The arguments of the dabgpu_fig_* calls: fib [n_frames][12][32] and crc_ok [n_frames][12] as contiguous uint8 ->
+    (fib, crc_ok, n_frames)."""
+    fib = np.ascontiguousarray(fib, np.uint8)
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
+    n_frames = fib.size // (12 * 32)
+    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
+        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    return fib, crc_ok, n_frames
+
+
 # ------------------------------------------------------------------ tables (no GPU needed)
 def get_ofdm_params(mode=1):
     p = OfdmParams()
@@ -1221,11 +1239,7 @@ def uep_subchannel(table_index, start_address):
 def fig_subchannels(fib, crc_ok, max_out=64):
     """The sub-channel list one ensemble announces (FIG 0/1) in its CRC-clean FIBs, sorted by start address: fib
     [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of Subchannel (no GPU needed)."""
-    fib = np.ascontiguousarray(fib, np.uint8)
-    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
-    n_frames = fib.size // (12 * 32)
-    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
-        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    fib, crc_ok, n_frames = _fib_batch(fib, crc_ok)
     arr = (Subchannel * max(max_out, 1))()
     n = C.c_int(0)
     _check(lib().dabgpu_fig_subchannels(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_subchannels")
@@ -1236,11 +1250,7 @@ def fig_audio_components(fib, crc_ok, max_out=64):
     """The MSC stream audio components one ensemble announces (FIG 0/2 joined to FIG 0/1) in its CRC-clean FIBs, each
     sub-channel once, sorted by start address: fib [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of
     AudioComponent (ascty 0 = DAB, 63 = DAB+; no GPU needed)."""
-    fib = np.ascontiguousarray(fib, np.uint8)
-    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
-    n_frames = fib.size // (12 * 32)
-    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
-        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    fib, crc_ok, n_frames = _fib_batch(fib, crc_ok)
     arr = (AudioComponent * max(max_out, 1))()
     n = C.c_int(0)
     _check(lib().dabgpu_fig_audio_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_audio_components")
@@ -1251,11 +1261,7 @@ def fig_packet_components(fib, crc_ok, max_out=64):
     """The packet-mode service components one ensemble announces (FIG 0/2 TMId 3 joined to FIG 0/3, FIG 0/1 and FIG 0/14) in
     its CRC-clean FIBs, each (sub-channel, packet address) once, sorted by (start address, packet address): fib
     [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of PacketComponent (dscty 60 = MOT; no GPU needed)."""
-    fib = np.ascontiguousarray(fib, np.uint8)
-    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
-    n_frames = fib.size // (12 * 32)
-    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
-        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    fib, crc_ok, n_frames = _fib_batch(fib, crc_ok)
     arr = (PacketComponent * max(max_out, 1))()
     n = C.c_int(0)
     _check(lib().dabgpu_fig_packet_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_packet_components")
@@ -1267,11 +1273,7 @@ def fig_user_applications(fib, crc_ok, max_out=64):
     """The user applications one ensemble announces (FIG 0/13) in its CRC-clean FIBs, each (SId, SCIdS, type) once, joined
     through FIG 0/8 (and FIG 0/3 for packet mode) to its component, sorted by (sid, scids, ua_type): fib
     [n_frames][12][32] uint8, crc_ok [n_frames][12] -> a USER_APPLICATION_DTYPE array (no GPU needed)."""
-    fib = np.ascontiguousarray(fib, np.uint8)
-    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
-    n_frames = fib.size // (12 * 32)
-    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
-        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    fib, crc_ok, n_frames = _fib_batch(fib, crc_ok)
     out = np.zeros(max(max_out, 1), USER_APPLICATION_DTYPE)
     n = C.c_int(0)
     _check(lib().dabgpu_fig_user_applications(_p(fib), _p(crc_ok), n_frames, _p(out), max_out, C.byref(n)), "dabgpu_fig_user_applications")
@@ -1291,9 +1293,7 @@ def packet_groups_chunk():
 def packet_groups_host(entries, n_cifs):
     """Context.packet_groups_dev on HOST memory (entries: PacketGroupsEntry with host addresses): the same checks and the same
     code, include/dabgpu_data_groups.h; no context, no GPU."""
-    n = len(entries)
-    arr = (PacketGroupsEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_packet_groups_host(arr, n, n_cifs), "dabgpu_packet_groups_host")
+    _entries_call("dabgpu_packet_groups_host", PacketGroupsEntry, entries, n_cifs)
 
 
 def packet_state_bytes():
@@ -1317,9 +1317,7 @@ def packet_carousel_arena_bytes(directory_capacity, assemblies, object_capacity)
 def packet_carousel_host(entries, n_cifs):
     """Context.packet_carousel_dev on HOST memory (entries: PacketCarouselEntry with host addresses): the same checks and the
     same code, include/dabgpu_mot_carousel.h; no context, no GPU."""
-    n = len(entries)
-    arr = (PacketCarouselEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_packet_carousel_host(arr, n, n_cifs), "dabgpu_packet_carousel_host")
+    _entries_call("dabgpu_packet_carousel_host", PacketCarouselEntry, entries, n_cifs)
 
 
 def mot_directory_parse(directory, max_objects=256):
@@ -1389,11 +1387,7 @@ def fig_stream_components(fib, crc_ok, max_out=64):
     """The stream-mode data components one ensemble announces (FIG 0/2 TMId 1 joined to FIG 0/1) in its CRC-clean FIBs, each
     sub-channel once, sorted by start address: fib [n_frames][12][32] uint8, crc_ok [n_frames][12] -> list of
     StreamComponent (dscty DSCTY_MPEG2_TS = T-DMB; no GPU needed)."""
-    fib = np.ascontiguousarray(fib, np.uint8)
-    crc_ok = np.ascontiguousarray(crc_ok, np.uint8)
-    n_frames = fib.size // (12 * 32)
-    if fib.size != n_frames * 12 * 32 or crc_ok.size != n_frames * 12:
-        raise ValueError("fib must be [n_frames][12][32] and crc_ok [n_frames][12]")
+    fib, crc_ok, n_frames = _fib_batch(fib, crc_ok)
     arr = (StreamComponent * max(max_out, 1))()
     n = C.c_int(0)
     _check(lib().dabgpu_fig_stream_components(_p(fib), _p(crc_ok), n_frames, arr, max_out, C.byref(n)), "dabgpu_fig_stream_components")
@@ -1414,9 +1408,7 @@ def ts_programs(ts):
 def dmb_follow_host(entries, n_cifs):
     """Context.dmb_follow_dev on HOST memory (entries: DmbEntry with host addresses): the same checks and the serial code of
     include/dabgpu_dmb.h; no context, no GPU."""
-    n = len(entries)
-    arr = (DmbEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_dmb_follow_host(arr, n, n_cifs), "dabgpu_dmb_follow_host")
+    _entries_call("dabgpu_dmb_follow_host", DmbEntry, entries, n_cifs)
 
 
 def packet_fec_state_bytes(bitrate):
@@ -1439,25 +1431,19 @@ def packet_fec_delay(bitrate):
 def packet_fec_host(entries, n_cifs):
     """Context.packet_fec_dev on HOST memory (entries: PacketFecEntry with host addresses): the same checks and the same
     code, include/dabgpu_packet_fec.h; no context, no GPU."""
-    n = len(entries)
-    arr = (PacketFecEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_packet_fec_host(arr, n, n_cifs), "dabgpu_packet_fec_host")
+    _entries_call("dabgpu_packet_fec_host", PacketFecEntry, entries, n_cifs)
 
 
 def packet_fec_erasures_host(entries, n_cifs):
     """Context.packet_fec_erasures_dev on HOST memory (entries: PacketFecErasureEntry with host addresses): the same checks
     and the same code, include/dabgpu_packet_fec_erasures.h; no context, no GPU."""
-    n = len(entries)
-    arr = (PacketFecErasureEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_packet_fec_erasures_host(arr, n, n_cifs), "dabgpu_packet_fec_erasures_host")
+    _entries_call("dabgpu_packet_fec_erasures_host", PacketFecErasureEntry, entries, n_cifs)
 
 
 def packet_slides_host(entries, n_cifs):
     """Context.packet_slides_dev on HOST memory (entries: PacketEntry with host addresses): the same checks and the same
     code, include/dabgpu_packet_walk.h; no context, no GPU."""
-    n = len(entries)
-    arr = (PacketEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_packet_slides_host(arr, n, n_cifs), "dabgpu_packet_slides_host")
+    _entries_call("dabgpu_packet_slides_host", PacketEntry, entries, n_cifs)
 
 
 def dabplus_carry_bytes(bitrate_kbps):
@@ -1473,9 +1459,7 @@ def pad_state_bytes():
 def pad_labels_host(entries):
     """Context.pad_labels_dev on HOST memory (entries: PadEntry with host addresses): the same checks and the same walk,
     no context and no GPU."""
-    n = len(entries)
-    arr = (PadEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_pad_labels_host(arr, n), "dabgpu_pad_labels_host")
+    _entries_call("dabgpu_pad_labels_host", PadEntry, entries)
 
 
 def mp2_carry_bytes(bitrate_kbps):
@@ -1486,17 +1470,13 @@ def mp2_carry_bytes(bitrate_kbps):
 def mp2_follow_host(entries, n_cifs):
     """Context.mp2_follow_dev on HOST memory (entries: Mp2Entry with host addresses): the same checks and the same code,
     include/dabgpu_mp2_frame.h; no context, no GPU."""
-    n = len(entries)
-    arr = (Mp2Entry * max(n, 1))(*entries)
-    _check(lib().dabgpu_mp2_follow_host(arr, n, n_cifs), "dabgpu_mp2_follow_host")
+    _entries_call("dabgpu_mp2_follow_host", Mp2Entry, entries, n_cifs)
 
 
 def mp2_subbands_host(entries, n_cifs):
     """Context.mp2_subbands_dev on HOST memory (entries: Mp2AudioEntry with host addresses): the same checks and the same
     code, include/dabgpu_mp2_audio.h; no context, no GPU."""
-    n = len(entries)
-    arr = (Mp2AudioEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_mp2_subbands_host(arr, n, n_cifs), "dabgpu_mp2_subbands_host")
+    _entries_call("dabgpu_mp2_subbands_host", Mp2AudioEntry, entries, n_cifs)
 
 
 def pad_label_utf8(label):
@@ -1523,9 +1503,7 @@ def mot_arena_bytes(body_capacity):
 def mot_slides_host(entries):
     """Context.mot_slides_dev on HOST memory (entries: MotEntry with host addresses): the same checks and the same walk,
     no context and no GPU."""
-    n = len(entries)
-    arr = (MotEntry * max(n, 1))(*entries)
-    _check(lib().dabgpu_mot_slides_host(arr, n), "dabgpu_mot_slides_host")
+    _entries_call("dabgpu_mot_slides_host", MotEntry, entries)
 
 
 def mot_header_parse(header):
@@ -2065,16 +2043,12 @@ class Context:
     def eti_read_dev(self, entries, stream=None):
         """ETI(NI) byte streams -> FIBs, CRC flags and logical frames on the device (dabgpu_eti_read_dev): entries is a list
         of EtiReadEntry (device addresses), each a stream with its own plan, byte count and state.  Enqueues only."""
-        n = len(entries)
-        arr = (EtiReadEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_eti_read_dev(self._h, arr, n, stream), "dabgpu_eti_read_dev")
+        _entries_call("dabgpu_eti_read_dev", EtiReadEntry, entries, stream, ctx=self)
 
     def edi_read_dev(self, entries, stream=None):
         """AF packet byte streams -> FIBs, CRC flags and logical frames on the device (dabgpu_edi_read_dev): entries is a list
         of EdiReadEntry (device addresses), each a stream with its own plan, byte count and state.  Enqueues only."""
-        n = len(entries)
-        arr = (EtiReadEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_edi_read_dev(self._h, arr, n, stream), "dabgpu_edi_read_dev")
+        _entries_call("dabgpu_edi_read_dev", EtiReadEntry, entries, stream, ctx=self)
 
     def edi_read(self, bytes_tensor, streams, state=None):
         """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams AF
@@ -2149,9 +2123,7 @@ class Context:
     def pft_read_dev(self, entries, stream=None):
         """PF fragment byte streams -> AF packet byte streams on the device (dabgpu_pft_read_dev): entries is a list of
         PftReadEntry (device addresses), each a stream with its own byte count, flags and state.  Enqueues only."""
-        n = len(entries)
-        arr = (PftReadEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_pft_read_dev(self._h, arr, n, stream), "dabgpu_pft_read_dev")
+        _entries_call("dabgpu_pft_read_dev", PftReadEntry, entries, stream, ctx=self)
 
     def pft_read(self, bytes_tensor, state=None, flush=False):
         """bytes_tensor: torch uint8 tensor [n_streams][n_bytes] on this context's device, the next n_bytes of n_streams PF
@@ -2254,18 +2226,14 @@ class Context:
         """Follow DAB+ sub-channels to super-frames on the device: entries is a list of DabplusEntry (device addresses; any
         mix of bit rates), each with n_cifs new logical frames.  Per entry: d_data / d_status rows [0, n_superframes),
         d_result (DABPLUS_FOLLOW_RESULT_DTYPE) and d_carry_out, to be passed as d_carry_in of the next call."""
-        n = len(entries)
-        arr = (DabplusEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_dabplus_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dabplus_follow_dev")
+        _entries_call("dabgpu_dabplus_follow_dev", DabplusEntry, entries, n_cifs, stream, ctx=self)
 
     def mp2_follow_dev(self, entries, n_cifs, stream=None):
         """Follows DAB (MPEG layer II) sub-channels to checked frames and PAD rows on the device: entries is a list of Mp2Entry
         (device addresses), n_cifs the logical frames every entry's d_in holds.  Per entry: d_rows [n_cifs + 1][MP2_ROW_BYTES],
         d_status (SUPERFRAME_STATUS_DTYPE), d_follow (DABPLUS_FOLLOW_RESULT_DTYPE: what PadEntry / MotEntry.d_follow point at,
         with bitrate_kbps = MP2_PAD_KBPS), d_result (MP2_RESULT_DTYPE).  No host synchronisation."""
-        n = len(entries)
-        arr = (Mp2Entry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_mp2_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_mp2_follow_dev")
+        _entries_call("dabgpu_mp2_follow_dev", Mp2Entry, entries, n_cifs, stream, ctx=self)
 
     def mp2_subbands_dev(self, entries, n_cifs, stream=None):
         """Behind mp2_follow_dev on the same stream: decodes every checked frame of every entry (a list of Mp2AudioEntry, device
@@ -2273,26 +2241,20 @@ class Context:
         entry: d_levels [n_cifs + 1] (MP2_LEVEL_DTYPE; rows at or beyond the follow call's `frames` are not written),
         d_subbands NULL or [n_cifs + 1] + MP2_SUBBANDS_SHAPE float32, d_audio (MP2_AUDIO_RESULT_DTYPE).  No host
         synchronisation."""
-        n = len(entries)
-        arr = (Mp2AudioEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_mp2_subbands_dev(self._h, arr, n, n_cifs, stream), "dabgpu_mp2_subbands_dev")
+        _entries_call("dabgpu_mp2_subbands_dev", Mp2AudioEntry, entries, n_cifs, stream, ctx=self)
 
     def pad_labels_dev(self, entries, stream=None):
         """Dynamic labels of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list of
         PadEntry (device addresses).  Per entry: d_label (PAD_LABEL_DTYPE), d_result (PAD_RESULT_DTYPE, counts of this call)
         and d_state_out, to be passed as d_state_in of the next call."""
-        n = len(entries)
-        arr = (PadEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_pad_labels_dev(self._h, arr, n, stream), "dabgpu_pad_labels_dev")
+        _entries_call("dabgpu_pad_labels_dev", PadEntry, entries, stream, ctx=self)
 
     def mot_slides_dev(self, entries, stream=None):
         """Slideshow objects of followed DAB+ sub-channels, behind dabplus_follow_dev on the same stream: entries is a list
         of MotEntry (device addresses).  Per entry: completed objects in the slots of d_slides (MOT_SLIDE_DTYPE, the MOT
         header, the body), d_result (MOT_RESULT_DTYPE, counts of this call), d_state_out, to be passed as d_state_in of the
         next call, and d_arena, which goes into the next call as it is."""
-        n = len(entries)
-        arr = (MotEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_mot_slides_dev(self._h, arr, n, stream), "dabgpu_mot_slides_dev")
+        _entries_call("dabgpu_mot_slides_dev", MotEntry, entries, stream, ctx=self)
 
     def packet_slides_dev(self, entries, n_cifs, stream=None):
         """Slideshow objects of packet-mode MOT components, behind decode_ensembles_dev on the same stream: entries is a list
@@ -2300,9 +2262,7 @@ class Context:
         completed objects in the slots of d_slides (MOT_SLIDE_DTYPE, the MOT header, the body), d_result
         (PACKET_RESULT_DTYPE, counts of this call), d_state_out, to be passed as d_state_in of the next call, and d_arena,
         which goes into the next call as it is.  No host synchronisation."""
-        n = len(entries)
-        arr = (PacketEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_packet_slides_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_slides_dev")
+        _entries_call("dabgpu_packet_slides_dev", PacketEntry, entries, n_cifs, stream, ctx=self)
 
     def packet_carousel_dev(self, entries, n_cifs, stream=None):
         """Objects of packet-mode MOT directory carousels, behind decode_ensembles_dev (and either FEC call) on the same
@@ -2310,9 +2270,7 @@ class Context:
         logical frames each.  Per entry: d_objects slots of a MOT_CAROUSEL_OBJECT_DTYPE record, the MOT header from the
         directory and the body; d_directory, the current directory's bytes; d_result, a PACKET_CAROUSEL_RESULT_DTYPE record.
         No host synchronisation."""
-        n = len(entries)
-        arr = (PacketCarouselEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_packet_carousel_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_carousel_dev")
+        _entries_call("dabgpu_packet_carousel_dev", PacketCarouselEntry, entries, n_cifs, stream, ctx=self)
 
     def packet_groups_dev(self, entries, n_cifs, stream=None):
         """The MSC data groups (mode 0) or the raw useful bytes (mode 1) of any packet-mode component, behind
@@ -2320,9 +2278,7 @@ class Context:
         addresses), one per (sub-channel, packet address); n_cifs logical frames each.  Per entry: the groups' bytes in
         d_bytes, a DATA_GROUP_DTYPE record each in d_groups, d_result (PACKET_GROUPS_RESULT_DTYPE, counts of this call) and
         d_state_out, to be passed as d_state_in of the next call.  No host synchronisation."""
-        n = len(entries)
-        arr = (PacketGroupsEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_packet_groups_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_groups_dev")
+        _entries_call("dabgpu_packet_groups_dev", PacketGroupsEntry, entries, n_cifs, stream, ctx=self)
 
     def dmb_follow_dev(self, entries, n_cifs, stream=None):
         """T-DMB stream-mode sub-channels to checked TS packets on the device (dabgpu_dmb_follow_dev): entries is a list of
@@ -2330,9 +2286,7 @@ class Context:
         emitted 188-byte packets back to back; d_records (DMB_RECORD_DTYPE); d_result (DMB_RESULT_DTYPE, counts of this
         call); d_state_out, which the next call takes as d_state_in.  Three launches whatever the number of entries, no
         host synchronisation."""
-        n = len(entries)
-        arr = (DmbEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_dmb_follow_dev(self._h, arr, n, n_cifs, stream), "dabgpu_dmb_follow_dev")
+        _entries_call("dabgpu_dmb_follow_dev", DmbEntry, entries, n_cifs, stream, ctx=self)
 
     def dmb_follow(self, frames, bitrate, state=None):
         """frames: torch uint8 tensor [n_streams][n_cifs][row] on this context's device, row >= 3 * bitrate, the last dimension
@@ -2367,18 +2321,14 @@ class Context:
         n_cifs logical frames each.  Per entry: d_out, the stream delayed by packet_fec_delay(bitrate) frames and corrected
         (the slides call names it as d_in and keeps fec non-zero), d_result (PACKET_FEC_RESULT_DTYPE, counts of this call)
         and d_state_out, to be passed as d_state_in of the next call.  No host synchronisation."""
-        n = len(entries)
-        arr = (PacketFecEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_packet_fec_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_fec_dev")
+        _entries_call("dabgpu_packet_fec_dev", PacketFecEntry, entries, n_cifs, stream, ctx=self)
 
     def packet_fec_erasures_dev(self, entries, n_cifs, stream=None):
         """packet_fec_dev with the failed packet CRCs of the arriving frames as erasures (up to eight lost packets per FEC
         frame instead of four): entries is a list of PacketFecErasureEntry (device addresses); d_result is a
         PACKET_FEC_ERASURE_RESULT_DTYPE record.  What packet_fec_dev corrects, this call corrects identically; its state
         record is its own (one of packet_fec_dev is a fresh start).  No host synchronisation."""
-        n = len(entries)
-        arr = (PacketFecErasureEntry * max(n, 1))(*entries)
-        _check(self._lib.dabgpu_packet_fec_erasures_dev(self._h, arr, n, n_cifs, stream), "dabgpu_packet_fec_erasures_dev")
+        _entries_call("dabgpu_packet_fec_erasures_dev", PacketFecErasureEntry, entries, n_cifs, stream, ctx=self)
 
     def fic_decode(self, soft):
         """soft: int8 [n_frames][>=9216]."""

@@ -204,7 +204,8 @@ ROT_LAYOUT_EXTREMES = {8: (1, 32, True), 24: (2, 48, True), 504: (32, 63, True),
 
 _FUNCTIONS = {"launch_wave": "viterbi_kernels.hip", "launch_msc_decode_group": "viterbi_kernels.hip", "launch_lane": "viterbi_lane_kernels.hip",
               "decode_lane": "dabgpu_decode_api.hip", "decode_subchannels": "dabgpu_decode_api.hip", "msc_decode_one": "dabgpu_decode_api.hip",
-              "plan_lane_launch": "lane_plan.hpp", "lane_item_fusable": "lane_plan.hpp", "plan_wave_launch": "wave_plan.hpp"}
+              "plan_lane_launch": "lane_plan.hpp", "lane_item_fusable": "lane_plan.hpp", "plan_wave_launch": "wave_plan.hpp",
+              "stage_table": "dabgpu_ctx.hpp"}          # (decode_lane's device table: the size comparison of every entry-table call)
 _DS, _LO, _GL, _DP, _LC, _EN = ("test_decoder_status.py::", "test_lane_one_path.py::", "test_gpu_lane.py::", "test_decoder_profiles.py::",
                                 "test_long_codewords.py::", "test_ensembles.py::")
 _ENTRIES = "the entry count: 1 (msc_decode_dev), 3 (the pairs with the FIC), 16 | 17, 24 | 25"
@@ -227,7 +228,7 @@ CHECKED_ELSEWHERE = {
     "if (n_streams == 0 || frames_per_stream == 0) return DABGPU_OK;": _LC + "test_every_entry_point_accepts_empty_batches",
     "if (plan.fused && n == 1 && one.kind != LaneItem::SUBCHANNEL) {": _LO + "test_plain_codewords_as_a_pack_of_one",
     "if (!dabk::lane_item_fusable(it)) return 1;": _EN + "test_shapes_that_do_not_qualify_give_the_same_bytes",
-    "if (ctx->stage_bytes[STAGE_ENSEMBLES] < table_bytes) HIP_TRY(hipStreamSynchronize(s));": _EN + "test_one_call_decodes_every_ensembles_own_plan",
+    "if (ctx->stage_bytes[slot] < bytes) HIP_TRY(hipStreamSynchronize(s));": _EN + "test_one_call_decodes_every_ensembles_own_plan",
     "bool group = plan.n >= 1 && plan.n + (d_fib ? 1 : 0) >= 2 && lane_policy(ctx, cw_each, false) == 0 && d_soft && n_streams > 0 &&":
         _GL + "test_decode_frames_equals_separate_calls",
     "if (!ctx || !d_soft || !d_out || n_streams < 0 || frames_per_stream < 0) return DABGPU_ERR_ARG;": _DS + "test_single_fault_status",
@@ -260,7 +261,7 @@ NOT_A_SIZE = [
     "if (ev && mid_recorded) *mid_recorded = true;", "if (!sc.table)", "if (items[i].kind == LaneItem::SUBCHANNEL) {",
     "if (policy == 0) return 1;", "if (!single) {", "if (ctx->lane_unfused) return 1;",
     "if (!lane_scratch(ctx, dabk::lane_scratch_bytes(items.data(), n, ctx->lane_unfused), s, &rc))",
-    "return rc ? rc : (single && policy == 2) ? DABGPU_ERR_NOMEM : 1;", "if (by_table) {", "if (stage(ctx, STAGE_ENSEMBLES, table_bytes, &lsc.table)) return 1;",
+    "return rc ? rc : (single && policy == 2) ? DABGPU_ERR_NOMEM : 1;", "if (by_table) {", "if (trc) return trc == DABGPU_ERR_HIP ? trc : 1;",
     "if (timer >= 0) tm.emplace(ctx, timer, s);", "const hipError_t e = dabk::launch_lane(items.data(), n, lsc, s, (tm && !single) ? tm->mids() : nullptr, &parts);", "if (tm && parts) tm->mids_recorded();",
     "return e == hipSuccess ? 0 : DABGPU_ERR_HIP;", "it.args = msc_args(plan.sc[i], d_soft, soft_stride, n_streams, frames_per_stream, d_history_in ? d_history_in[i] : nullptr,",
     "d_history_out ? d_history_out[i] : nullptr, d_out[i]);", "d_history_in ? d_history_in[i] : nullptr, d_history_out ? d_history_out[i] : nullptr,",
